@@ -229,6 +229,31 @@ def _stats(x):
             "argmax": int(np.argmax(raw))}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+DUMP_SEED = 12345
+
+
+def dump_frame(out_dir, frame, name="frame", budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: the [H, W, C] RGBA8 frame the caller of the timed path receives, as <out_dir>/<name>.npy in float32 (the
+    byte values, exact).  A frame larger than `budget` bytes in float32 is written as a fixed sample instead: the pixels of a seeded
+    random choice (ascending flat index y * W + x), <name>.npy [K, C] float32, and their flat indices, <name>_pixel_index.npy [K]
+    float64.  Same frame shape -> same sample, so that two builds' dumps compare element by element.  Returns the paths written."""
+    frame = np.asarray(frame)
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128   # .npy header of a 1-D / 2-D array
+    if frame.size * 4 + header <= budget:
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, frame.astype(np.float32))
+        return [path]
+    h, w, c = frame.shape
+    k = min(h * w, (budget - 2 * header) // (c * 4 + 8))
+    idx = np.sort(np.random.default_rng(seed).choice(h * w, size=k, replace=False))
+    paths = [os.path.join(out_dir, name + ".npy"), os.path.join(out_dir, name + "_pixel_index.npy")]
+    np.save(paths[0], frame.reshape(h * w, c)[idx].astype(np.float32))
+    np.save(paths[1], idx.astype(np.float64))
+    return paths
+
+
 def roofline(kernel, pmc_key, ms_launch, algorithmic_bytes, world):
     """Roofline of the dominant kernel (north_star: "achieved fraction of the HBM roofline").
 
@@ -417,6 +442,8 @@ def main_one_process(args):
     ctx.stats()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs:
+        dump_frame(args.dump_outputs, out.cpu().numpy())
     deal = ctx.deal()
     per_rank = [ctx.rank_stats(r) for r in range(args.gpus)]
     multi = {"ranks_observed": int(ctx.num_ranks), "transport": args.transport,
@@ -585,6 +612,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--save-frame", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed frame of the headline workload (RGBA8 as float32) to DIR/frame.npy; "
+                         "a frame over 64 MB is written as a fixed seeded pixel sample (DIR/frame.npy + DIR/frame_pixel_index.npy)")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--dry-run", action="store_true", help="no GPU: gloo + CPU tensors + a stand-in renderer (collective sequence only)")
     ap.add_argument("--one-process", action="store_true",
@@ -598,6 +628,8 @@ def main():
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="extra renderer setting (SettingsMap key), e.g. --set intersection_form=literal; noted in config.workload")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -730,8 +762,9 @@ def main():
     if os.environ.get("LV_FRAMES_IN_FLIGHT"):   # measurement knob (tools/probe_shard.py explores it per world size)
         frames_in_flight = max(1, int(os.environ["LV_FRAMES_IN_FLIGHT"]))
 
-    def measure(w, wkey):
-        """Instrumented frame (counters), warm-up, K timed frames; returns everything rank 0 reports for this workload."""
+    def measure(w, wkey, dump=False):
+        """Instrumented frame (counters), warm-up, K timed frames; returns everything rank 0 reports for this workload (dump: with a
+        host copy of the last timed frame)."""
         ctx, render_fn = make_context(w, wait_for_consumer=(frames_in_flight == 1))
         if dry:
             render_fn = dry_render
@@ -852,6 +885,8 @@ def main():
         sync_all()
         elapsed = time.perf_counter() - t0
         gc.enable()
+        # the last timed frame, copied before the untimed passes below render into the same buffers again
+        last_frame = frame.cpu().numpy() if dump and frame is not None else None
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         if dist_on:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -949,14 +984,14 @@ def main():
         del extra
         return dict(ctx=ctx, frame=frame, host=host, elapsed=elapsed, rays_per_frame=rays_per_frame, counters=counters, local=local,
                     kernel_bytes=kernel_bytes, frame_bytes=frame_bytes, kernels=kernels, frame_ms=_stats(frame_ms),
-                    build_ms=build_ms, build_first_ms=build_first_ms, st=st, wkey=wkey, diag=diag)
+                    build_ms=build_ms, build_first_ms=build_first_ms, st=st, wkey=wkey, diag=diag, last_frame=last_frame)
 
     if not dry and world == 1 and device_geometry and wl.get("mesh") and not os.environ.get("LV_BENCH_SKIP_HOST_UPLOAD"):
         # for the record only: what the host-built arrays of the same scene cost to upload (the path of rounds 1-5), in a throw-away context
         c0, _ = make_context(wl, host_geometry=True)
         del c0
         gc.collect()
-    head = measure(wl, args.workload)
+    head = measure(wl, args.workload, dump=bool(args.dump_outputs))
     also = None
     if wl.get("also") and not dry:
         del head["ctx"]   # frees the triangle scene before the capsule context builds
@@ -1039,6 +1074,8 @@ def main():
         if args.save_frame and head["frame"] is not None and not dry:
             from PIL import Image
             Image.fromarray(head["frame"].cpu().numpy()).save(args.save_frame)
+        if args.dump_outputs:
+            dump_frame(args.dump_outputs, head["last_frame"])
         if world == 1 and not args.no_cpu_baseline and not dry:
             cpu_wl = wl.get("cpu", {"c3": "c3t"}.get(args.workload, args.workload))   # the oracle leg this workload's frame corresponds to
             result["cpu_baseline"] = cpu_baseline(W, H, pts, seg, tf, attr_range, view, proj, fovy, near, far,

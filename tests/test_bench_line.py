@@ -46,6 +46,23 @@ def test_roofline_degrades_without_counters():
     assert r["frac"] is None
 
 
+def test_dump_frame_whole_or_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: a frame that fits is written whole in float32; a larger one as the same seeded pixel sample every time."""
+    import numpy as np
+    small = np.random.default_rng(1).integers(0, 256, (1080, 1920, 4), dtype=np.uint8)
+    (p,) = bench.dump_frame(str(tmp_path / "a"), small)
+    got = np.load(p)
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = np.random.default_rng(2).integers(0, 256, (2160, 3840, 4), dtype=np.uint8)
+    pa = bench.dump_frame(str(tmp_path / "b"), big)
+    pb = bench.dump_frame(str(tmp_path / "c"), big[::-1].copy())
+    assert sum(os.path.getsize(x) for x in pa) <= bench.DUMP_BUDGET_BYTES
+    vals, idx = np.load(pa[0]), np.load(pa[1])
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(vals, big.reshape(-1, 4)[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(np.load(pb[1]), idx)
+
+
 def test_workload_table_names_the_baseline_configs():
     names = {k: w["name"] for k, w in bench.WORKLOADS.items()}
     assert names["c3"].startswith("C3: 1M-segment") and "64 spp" in names["c3"] and "1920x1080" in names["c3"]
