@@ -464,7 +464,6 @@ template <uint32_t G, uint32_t DOWN>
 __device__ void lv_treelet_group_build(const float (*s_box)[6], uint32_t* s_idx, const uint32_t* s_items, uint32_t numItems,
                                        uint32_t* s_gstack, uint32_t a, uint32_t* __restrict__ childL, uint32_t* __restrict__ childR,
                                        uint32_t* s_out, uint32_t& outCount) {
-    constexpr uint32_t NG = 64u / G;
     const uint32_t lane = threadIdx.x, gi = lane % G, g = lane / G, gbase = g * G;
     uint32_t* stk = s_gstack + g * 3u * LV_TREELET_LANE_STACK;
     uint32_t nextItem = 0u;                 // wave-uniform

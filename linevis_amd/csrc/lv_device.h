@@ -30,9 +30,6 @@
 #ifndef LV_GATHER_MIN_WAVES
 #define LV_GATHER_MIN_WAVES 1
 #endif
-#ifndef LV_NODE_MIX
-#define LV_NODE_MIX 0            // node step: child planes as binary16 halves through v_perm_b32 + v_fma_mix_f32 (lv_slab_h)
-#endif
 #ifndef LV_PRISM_MIN_WAVES
 #define LV_PRISM_MIN_WAVES 3    // k_ppll_gather<LV_PRIM_PRISM>: waves per SIMD the register allocator leaves room for
 #endif
@@ -57,20 +54,8 @@
 #ifndef LV_AO_SMALL_CHUNKS
 #define LV_AO_SMALL_CHUNKS 12u
 #endif
-#ifndef LV_AO_STAY
-#define LV_AO_STAY 1            // k_ao_rays descend loop: stay while at least this many lanes descend (tools/variants.py experiment)
-#endif
-#ifndef LV_AO_ORDERED
-#define LV_AO_ORDERED 1         // k_ao_rays: 1 = nearest hit child first, 0 = children as stored (tools/variants.py experiment)
-#endif
-#ifndef LV_SORT_CHILDREN
-#define LV_SORT_CHILDREN 0       // 1: fully sort the hit children of a node; 0: nearest first, rest unordered
-#endif
 #ifndef LV_AO_STACK_LDS
 #define LV_AO_STACK_LDS 15      // LDS-staged stack entries per thread in k_ao_rays (deeper entries: HBM overflow slab)
-#endif
-#ifndef LV_PRECOMP_AXIS
-#define LV_PRECOMP_AXIS 1
 #endif
 #ifndef LV_AO_MIN_WAVES
 #define LV_AO_MIN_WAVES 5         // waves per SIMD k_ao_rays is compiled for (95 VGPRs; 6 would need <= 85 and 26 KB of LDS)
@@ -450,11 +435,7 @@ __device__ __forceinline__ float lv_rsqrt_shade(float x) {
 __device__ __forceinline__ float lv_rsqrt_shade_reference(float x) {
     return 1.0f / sqrtf(fminf(fmaxf(x, LV_RSQRT_LO), LV_RSQRT_HI));
 }
-#ifdef LV_RSQRT_PLAIN   // measurement variant (tools/variants.py): the compiler's division and square root
-__device__ __forceinline__ f3 norm3s(f3 a) { const float r = lv_rsqrt_shade_reference(dot3(a, a)); return mk3(a.x * r, a.y * r, a.z * r); }
-#else
 __device__ __forceinline__ f3 norm3s(f3 a) { const float r = lv_rsqrt_shade(dot3(a, a)); return mk3(a.x * r, a.y * r, a.z * r); }
-#endif
 
 // shading_numerics = fast (round 6): the hardware's approximate reciprocal square root / reciprocal / log2 / exp2 (v_rsq_f32, v_rcp_f32,
 // v_log_f32, v_exp_f32: <= 1 ulp each) in arithmetic that only ever reaches a COLOUR -- the lighting's normalisations, pow() and

@@ -159,28 +159,6 @@ __device__ __forceinline__ LvPrismTri lv_prism_tri_setup(const float* ringTab, u
     }
     return T;
 }
-// edge functions of a triangle for the ray (o, D) (any length); returns the coverage decision
-__device__ __forceinline__ bool lv_prism_tri_edges(const LvPrismDev& R, const LvPrismPoint pt[2], const LvPrismTri& T, float radius, f3 o,
-                                                   f3 D, float e[3]) {
-    f3 P, Q;
-    lv_prism_basis(R, D, P, Q);
-    const LvPrismProj pj0 = lv_prism_point_proj(pt[0], o, P, Q), pj1 = lv_prism_point_proj(pt[1], o, P, Q);
-    float x[3], y[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        float x0, y0, x1, y1;
-        lv_prism_vertex_xy(pj0, T.c[i], T.s[i], radius, x0, y0);
-        lv_prism_vertex_xy(pj1, T.c[i], T.s[i], radius, x1, y1);
-        x[i] = T.second[i] ? x1 : x0;
-        y[i] = T.second[i] ? y1 : y0;
-    }
-    e[0] = lv_prism_edge(x[1], y[1], x[2], y[2]);
-    e[1] = lv_prism_edge(x[2], y[2], x[0], y[0]);
-    e[2] = lv_prism_edge(x[0], y[0], x[1], y[1]);
-    const bool in = lv_prism_inside(e[0], T.id[1] < T.id[2]) && lv_prism_inside(e[1], T.id[2] < T.id[0]) &&
-                    lv_prism_inside(e[2], T.id[0] < T.id[1]);
-    return in && (e[0] + e[1]) + e[2] > 0.0f;
-}
 template <bool FASTN = false>
 __device__ __forceinline__ void lv_prism_weights(const float e[3], float b[3]) {
     const float rs = FASTN ? __builtin_amdgcn_rcpf((e[0] + e[1]) + e[2]) : 1.0f / ((e[0] + e[1]) + e[2]);

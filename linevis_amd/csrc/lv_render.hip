@@ -427,52 +427,6 @@ __device__ __forceinline__ size_t lv_ao_slot(const uint32_t* __restrict__ tileBa
     return lv_ao_group_base(tileCapacity, lo) + (ordinal - tileBase[lo]);
 }
 
-#ifdef LV_AO_OCTANT_PERM
-// tools/variants.py experiment (EXPERIMENTS.md 12.2): an UPPER BOUND for "ray binning at generation".  A pre-pass
-// (not charged to k_ao_rays) orders the rays of every block of LV_AO_OCTANT_PERM pixels by the octant of their direction; k_ao_rays then
-// takes ray perm[i] where it took ray i, so that the 128-ray chunks a wave pulls hold rays of one or two octants.  Never in the product build.
-__device__ uint32_t* g_aoPerm;
-__global__ __launch_bounds__(256) void k_ao_octant_perm(const LvUniforms U, const float4* __restrict__ gbuf, uint32_t* __restrict__ perm,
-                                                        const LvDevCounters* dc, const uint32_t* __restrict__ tileBase, uint32_t numTiles,
-                                                        const LvAoLayout tileCapacity) {
-    __shared__ unsigned s_cnt[8], s_cur[8];
-    const uint32_t spp = U.aoSamplesPerFrame;
-    const unsigned long long total = (unsigned long long)(dc->aoCount) * spp;
-    const unsigned long long per = (unsigned long long)LV_AO_OCTANT_PERM * spp;
-    for (unsigned long long base = blockIdx.x * per; base < total; base += gridDim.x * per) {
-        if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0u;
-        __syncthreads();
-        const unsigned long long end = base + per < total ? base + per : total;
-        for (int pass = 0; pass < 2; pass++) {
-            for (unsigned long long rr = base + threadIdx.x; rr < end; rr += blockDim.x) {
-                const uint32_t smpIdx = uint32_t(rr % spp);
-                const size_t slot = lv_ao_slot(tileBase, numTiles, tileCapacity, uint32_t(rr / spp));
-                const float4 g1 = gbuf[3 * slot + 1], g2 = gbuf[3 * slot + 2];
-                const f3 T = mk3(g1.x, g1.y, g1.z), N = mk3(g2.x, g2.y, g2.z);
-                const f3 B = cross3(N, T);
-                uint32_t seed = lv_tea(__float_as_uint(g1.w), U.aoGlobalFrameNumber * spp + smpIdx);
-                const float xi0 = lv_rnd(seed), xi1 = lv_rnd(seed);
-                float sn, cs;
-                lv_sincos2pi(xi1, sn, cs);
-                const float rs = sqrtf(1.0f - xi0 * xi0);
-                const f3 smp = mk3(cs * rs, sn * rs, xi0);
-                const f3 d = mk3((T.x * smp.x + B.x * smp.y) + N.x * smp.z, (T.y * smp.x + B.y * smp.y) + N.y * smp.z,
-                                 (T.z * smp.x + B.z * smp.y) + N.z * smp.z);
-                const unsigned oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-                if (pass == 0) atomicAdd(&s_cnt[oct], 1u);
-                else perm[base + atomicAdd(&s_cur[oct], 1u)] = uint32_t(rr);
-            }
-            __syncthreads();
-            if (pass == 0 && threadIdx.x == 0) { unsigned run = 0; for (int k = 0; k < 8; k++) { s_cur[k] = run; run += s_cnt[k]; } }
-            __syncthreads();
-        }
-    }
-}
-#define LV_AO_RAY_INDEX(i) ((unsigned long long)g_aoPerm[i])
-#else
-#define LV_AO_RAY_INDEX(i) (i)
-#endif
-
 // AO sample rays: PERSISTENT waves that keep three kinds of work apart and run each of them with (nearly) all
 // 64 lanes busy.  AO ray r belongs to compacted pixel r / spp, sample r % spp.
 //
@@ -611,7 +565,6 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                         if (STATS) primHits++;
                     }
                 }
-#ifndef LV_AO_IDLE_PROBE
                 if (STATS && PRIM == LV_PRIM_CAPSULE) {
                     const float4 sa = S.segs[2 * size_t(leaf)], sb = S.segs[2 * size_t(leaf) + 1];
                     const f3 ro = mk3(r0.x, r0.y, r1.x), rd = mk3(r1.y, r2.x, r2.y);
@@ -620,7 +573,6 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                     mayAxis += ma ? 1u : 0u;
                     mayBoth += (ma && mb) ? 1u : 0u;
                 }
-#endif
             }
             head += n;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -685,7 +637,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                 const unsigned n = left < LV_WAVE ? unsigned(left) : LV_WAVE;
                 if (STATS && lane == 0 && n) { phIt[0]++; phLn[0] += n; }
                 if (lane < n) {
-                    const unsigned long long rr = LV_AO_RAY_INDEX(chunkNext + lane);
+                    const unsigned long long rr = chunkNext + lane;
                     const uint32_t smpIdx = uint32_t(rr % spp);
                     const size_t slot = lv_ao_slot(tileBase, numTiles, tileCapacity, uint32_t(rr / spp));
                     const float4 g0 = gbuf[3 * slot + 0], g1 = gbuf[3 * slot + 1], g2 = gbuf[3 * slot + 2];
@@ -733,7 +685,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                     inv = mk3(1.0f / r1.y, 1.0f / r2.x, 1.0f / r2.y);
                     oi = mk3(r0.x * inv.x, r0.y * inv.y, r1.x * inv.z);
                     best = U.aoRadius;
-                    r = LV_AO_RAY_INDEX(genBase + gs);
+                    r = genBase + gs;
                     owner = lane;
                     cur = 0;
                     st.sp = 0;
@@ -750,18 +702,11 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             // ---- descend phase: tight loop of node steps; leaves met on the way join the FIFO.  Leave it only when a
             // full batch of leaf tests waits or nobody descends any more (leaving earlier for a retire/refill pass
             // was measured slower: the per-pass bookkeeping outweighs the idle lanes).
-            const int stay = LV_AO_STAY;
             int nNow;
             do {
                 if (STATS && lane == 0) { phIt[1]++; }
                 if (STATS && !(cur & LV_LEAF_BIT)) phLn[1]++;
-#ifdef LV_AO_IDLE_PROBE // tools/variants.py: why lanes idle in the descend loop -- (a) their ray waits for queued leaf tests, (b) no ray
-                if (STATS) {
-                    const unsigned long long mW = __ballot(hasRay && cur == LV_INVALID), mE = __ballot(!hasRay);
-                    if (lane == 0) { mayAxis += unsigned(__popcll(mW)); mayBoth += unsigned(__popcll(mE)); }
-                }
-#endif
-                if (!(cur & LV_LEAF_BIT)) cur = lv_node_step<STATS, LV_AO_ORDERED>(S, cur, oi, inv, 0.0f - litSlack, best + litSlack, st, cnt);
+                if (!(cur & LV_LEAF_BIT)) cur = lv_node_step<STATS>(S, cur, oi, inv, 0.0f - litSlack, best + litSlack, st, cnt);
                 const bool isLeaf = cur != LV_INVALID && (cur & LV_LEAF_BIT);
                 const unsigned long long mL = __ballot(isLeaf);
                 if (mL) {
@@ -775,7 +720,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                     tail += unsigned(__popcll(mL));
                 }
                 nNow = __popcll(__ballot(!(cur & LV_LEAF_BIT)));
-            } while (tail - head < TB && nNow >= (drain ? LV_HANDOVER_MAX_BUSY + 1 : stay));
+            } while (tail - head < TB && nNow >= (drain ? LV_HANDOVER_MAX_BUSY + 1 : 1));
             continue;
         }
         if (nIdle == LV_WAVE && !canRefill) break; // nothing alive, nothing left to fetch
@@ -974,11 +919,6 @@ __global__ __launch_bounds__(LV_BLOCK) void k_bake_setup(const lv_line_point* __
     gbuf[3 * size_t(slot) + 0] = make_float4(rayOrigin.x, rayOrigin.y, rayOrigin.z, 0.0f);
     gbuf[3 * size_t(slot) + 1] = make_float4(tangent.x, tangent.y, tangent.z, __uint_as_float(vertex));
     gbuf[3 * size_t(slot) + 2] = make_float4(surfaceNormal.x, surfaceNormal.y, surfaceNormal.z, __uint_as_float(sub));
-}
-
-__global__ __launch_bounds__(LV_BLOCK) void k_fill_f32(float* p, float v, size_t n) {
-    size_t i = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
-    if (i < n) p[i] = v;
 }
 
 // ================================================================ PPLL
@@ -2706,16 +2646,6 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         else { if (tri) LV_LAUNCH_AOP(false, LV_PRIM_TRIANGLE); else if (ell) LV_LAUNCH_AOP(false, LV_PRIM_ELLIPTIC); else LV_LAUNCH_AOP(false, LV_PRIM_CAPSULE); }
         k_ao_tile_scan<<<1, LV_BLOCK, 0, st>>>(tileCount, numGroups, tileBase, dc);
         const bool anyHit = !U.aoUseDistance;
-#ifdef LV_AO_OCTANT_PERM
-        {   // experiment only: the permutation is built by a pre-pass outside the timed kernel
-            static uint32_t* permBuf = nullptr;
-            static size_t permCap = 0;
-            const size_t need = size_t(maxPixels) * spp;
-            if (need > permCap) { if (permBuf) (void)hipFree(permBuf); LV_HIP(ctx, hipMalloc(&permBuf, need * 4)); permCap = need; }
-            LV_HIP(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_aoPerm), &permBuf, sizeof(permBuf), 0, hipMemcpyHostToDevice, st));
-            k_ao_octant_perm<<<4096, 256, 0, st>>>(U, g, permBuf, dc, tileBase, numGroups, tileCap);
-        }
-#endif
         if (stats) { if (anyHit) LV_LAUNCH_AO2(true, true); else LV_LAUNCH_AO2(true, false); }
         else { if (anyHit) LV_LAUNCH_AO2(false, true); else LV_LAUNCH_AO2(false, false); }
 #undef LV_LAUNCH_AO2
@@ -2930,24 +2860,6 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     }
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[5], st));
 
-#ifdef LV_PROBE_OVERLAP
-    // tools/variants.py probe (EXPERIMENTS.md 12.4): what overlapping the colour pass' traversal with the RTAO pass could win at most --
-    // the WHOLE colour pass is launched on a second stream before the RTAO pass (it reads the previous frame's AO image: the picture is
-    // wrong, the timing is an upper bound of the gain).  Never in the product build.
-    static hipStream_t st2 = nullptr;
-    static hipEvent_t evA = nullptr, evB = nullptr;
-    if (!st2) {
-        LV_HIP(ctx, hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-        LV_HIP(ctx, hipEventCreateWithFlags(&evA, hipEventDisableTiming));
-        LV_HIP(ctx, hipEventCreateWithFlags(&evB, hipEventDisableTiming));
-    }
-    if (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER) {
-        LV_HIP(ctx, hipEventRecord(evA, st));
-        LV_HIP(ctx, hipStreamWaitEvent(st2, evA, 0));
-        k_render_rt<false, LV_PRIM_CAPSULE, LV_SHADE_PLAIN><<<gridTiles, LV_BLOCK, 0, st2>>>(U, S, T, (uint32_t*)outDevice, dc);
-        LV_HIP(ctx, hipEventRecord(evB, st2));
-    }
-#endif
     // ambientOcclusionBaker->updateIterative(), LineRenderer.cpp:257-264
     ctx->aoNumGroups = 0;
     bool firstHitsTraced = false;
@@ -3037,11 +2949,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     } while (0)
         // shading_numerics = fast: the capsule colour pass of plain flow lines (lighting through the approximate operations, FAST = 1)
         const bool fastPlain = ctx->opt.fastShading && !stats && !tri && !U.useHelicityBands && !U.useEllipticTubes && !U.useBands;
-#ifdef LV_PROBE_OVERLAP
-        LV_HIP(ctx, hipStreamWaitEvent(st, evB, 0));
-#else
         if (stats) LV_LAUNCH_RT2(true); else LV_LAUNCH_RT2(false);
-#endif
 #undef LV_LAUNCH_RT2
 #undef LV_LAUNCH_RT_PRE
 #undef LV_LAUNCH_RT

@@ -35,7 +35,7 @@ __device__ __forceinline__ bool lv_ray_sphere(f3 o, f3 d, f3 ctr, float radius, 
     return true;
 }
 
-// td = normalize(tubeEnd - tubeStart): per test (lv_ray_tube) or precomputed per segment with the same norm3 (S.segAxis)
+// td = normalize(tubeEnd - tubeStart): per test (lv_intersect_capsule) or precomputed per segment with the same norm3 (S.segAxis)
 __device__ __forceinline__ bool lv_ray_tube_td(f3 o, f3 d, f3 tubeStart, f3 tubeEnd, f3 td, float radius, float& hitT) {
     f3 deltaP = o - tubeStart;
     f3 av = d - dot3(d, td) * td;
@@ -57,10 +57,6 @@ __device__ __forceinline__ bool lv_ray_tube_td(f3 o, f3 d, f3 tubeStart, f3 tube
         if (dot3(td, ip - tubeStart) > 0.0f && dot3(td, ip - tubeEnd) < 0.0f) { hitT = t1; return true; }
     }
     return false;
-}
-
-__device__ __forceinline__ bool lv_ray_tube(f3 o, f3 d, f3 tubeStart, f3 tubeEnd, float radius, float& hitT) {
-    return lv_ray_tube_td(o, d, tubeStart, tubeEnd, norm3(tubeEnd - tubeStart), radius, hitT);
 }
 
 // IntersectionTube main(): nearest of {cylinder, sphere(p0), sphere(p1)}; kind 0/1/2
@@ -267,20 +263,6 @@ __device__ __forceinline__ LvStackMem lv_stack_mem(unsigned* sStack, unsigned* o
     return m;
 }
 
-// Slab test of one child box against the ray.  Box culling only has to be conservative (boxes are padded at build
-// time and the acceptance test carries a relative + absolute margin), it never decides a hit, so it is the one place
-// that uses fused multiply-adds: t = b * (1/d) - o * (1/d) with oi = o * (1/d) precomputed per ray.
-__device__ __forceinline__ bool lv_slab(float bx0, float by0, float bz0, float bx1, float by1, float bz1, f3 oi, f3 inv,
-                                        float tMin, float tMax, float& tNear) {
-    float tx0 = __builtin_fmaf(bx0, inv.x, -oi.x), tx1 = __builtin_fmaf(bx1, inv.x, -oi.x);
-    float ty0 = __builtin_fmaf(by0, inv.y, -oi.y), ty1 = __builtin_fmaf(by1, inv.y, -oi.y);
-    float tz0 = __builtin_fmaf(bz0, inv.z, -oi.z), tz1 = __builtin_fmaf(bz1, inv.z, -oi.z);
-    float tn = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tMin));
-    float tf = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fminf(fmaxf(tz0, tz1), tMax));
-    tNear = tn;
-    return tn <= __builtin_fmaf(tf, 1.000001f, 2e-7f);
-}
-
 struct LvHit {
     float t;
     uint32_t leaf; // capsules: leaf position (Morton order); triangles: original triangle index
@@ -288,21 +270,9 @@ struct LvHit {
     bool found;
 };
 
-// Traversal is organised as "while-while" with postponed leaves (Aila & Laine, "Understanding the Efficiency of Ray
-// Traversal on GPUs", HPG 2009) for wave64: a lane that reaches a leaf parks it in `pending` and keeps descending;
-// the wave leaves the node loop only when every still-descending lane has parked a leaf, so the expensive capsule test
-// (8 IEEE divisions + 4 square roots) runs with most lanes active instead of once per node step for a handful of lanes.
 // Child references: index | LV_LEAF_BIT for leaves, LV_INVALID (which has the leaf bit set) = finished.
 template <class STACK>
 __device__ __forceinline__ unsigned lv_pop_or_done(STACK& st) { return st.sp == 0 ? LV_INVALID : st.pop(); }
-
-// Evaluated by the lanes still inside the node loop: leave it when every one of them has parked a leaf, or when
-// fewer than LV_NODE_MIN_ACTIVE lanes are still descending (the others wait with a parked leaf and a second one in
-// hand; testing those now keeps both loops above ~50 % lane utilisation).
-__device__ __forceinline__ bool lv_leave_node_loop(unsigned pending) {
-    const unsigned long long descending = __ballot(1);
-    return !__any(pending == LV_INVALID) || __popcll(descending) < LV_NODE_MIN_ACTIVE;
-}
 
 // One node step on the compressed 4-wide LBVH: fetch the 64-byte node (4 x dwordx4), decode + slab-test the four child
 // boxes, continue with the nearest hit child and push the others.  Children may be leaves; the caller looks at the
@@ -317,30 +287,6 @@ __device__ __forceinline__ void lv_cswap(float& ka, unsigned& ca, float& kb, uns
 // slab test on decoded planes: t = plane * (1/d) - o/d with plane = origin + q * scale, folded into
 // t = q * (scale/d) + (origin/d - o/d): one fma per plane after the byte -> float conversion.  The words handed in
 // are already ordered by the ray's direction signs (near planes / far planes), so no per-plane min/max is needed.
-#if LV_NODE_MIX
-// The same test with the plane bytes read as binary16: v_perm_b32 builds {0x6400 | q_k, 0x6400 | q_k+1} = the halves 1024 + q of two
-// children at once (binary16 has ulp 1 on [1024, 2048)), and t = (1024 + q) * A + (B - 1024 A) is ONE v_fma_mix_f32 per plane (the
-// binary16 operand is widened inside the instruction, the arithmetic is float32): 1.5 instructions per plane instead of the
-// v_cvt_f32_ubyte + v_fma_f32 pair.  B2 = B - 1024 A is computed once per node step (lv_node_step).
-typedef _Float16 lv_h2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ lv_h2 lv_plane_pair(uint32_t word, int pair) {
-    const uint32_t w = __builtin_amdgcn_perm(word, 0x64006400u, pair == 0 ? 0x03050104u : 0x03070106u);
-    return __builtin_bit_cast(lv_h2, w);
-}
-__device__ __forceinline__ bool lv_slab_h(_Float16 nx, _Float16 ny, _Float16 nz, _Float16 fx, _Float16 fy, _Float16 fz, f3 A, f3 B2,
-                                          float tMin, float tMax, float& tNear) {
-    const float tx0 = __builtin_fmaf(float(nx), A.x, B2.x);
-    const float ty0 = __builtin_fmaf(float(ny), A.y, B2.y);
-    const float tz0 = __builtin_fmaf(float(nz), A.z, B2.z);
-    const float tx1 = __builtin_fmaf(float(fx), A.x, B2.x);
-    const float ty1 = __builtin_fmaf(float(fy), A.y, B2.y);
-    const float tz1 = __builtin_fmaf(float(fz), A.z, B2.z);
-    const float tn = fmaxf(fmaxf(tx0, ty0), fmaxf(tz0, tMin));
-    const float tf = fminf(fminf(tx1, ty1), fminf(tz1, tMax));
-    tNear = tn;
-    return tn <= __builtin_fmaf(tf, 1.00001f, 4e-7f);
-}
-#endif
 __device__ __forceinline__ bool lv_slab_q(uint32_t nearX, uint32_t nearY, uint32_t nearZ, uint32_t farX, uint32_t farY,
                                           uint32_t farZ, int k, f3 A, f3 B, float tMin, float tMax, float& tNear) {
     const float tx0 = __builtin_fmaf(float((nearX >> (8 * k)) & 0xFFu), A.x, B.x);
@@ -364,9 +310,6 @@ __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned n
     const float4* p = S.nodes + 4 * size_t(node);
     const float4 q0 = p[0], q1 = p[1], q2 = p[2], cf = p[3];
     if (STATS) cnt.nodes++;
-#ifdef LV_NODE_STEP_PROBE // sensitivity probes live in tools/variants_inc/probes.h (tools/variants.py force-includes it); never in the product
-    LV_NODE_STEP_PROBE(p, q0, inv, tMax, S);
-#endif
     unsigned c0 = __float_as_uint(cf.x), c1 = __float_as_uint(cf.y), c2 = __float_as_uint(cf.z), c3 = __float_as_uint(cf.w);
     const f3 A = mk3(q0.w * inv.x, q1.x * inv.y, q1.y * inv.z);
     const f3 B = mk3(__builtin_fmaf(q0.x, inv.x, -oi.x), __builtin_fmaf(q0.y, inv.y, -oi.y), __builtin_fmaf(q0.z, inv.z, -oi.z));
@@ -380,56 +323,15 @@ __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned n
     float k0, k1, k2, k3;
     // empty slots carry an inverted box (lv_write_wide_node) and fail the slab test by themselves; should one slip through,
     // its reference is LV_INVALID and it is neither descended nor pushed
-#if LV_NODE_MIX
-    const f3 B2 = mk3(__builtin_fmaf(-1024.0f, A.x, B.x), __builtin_fmaf(-1024.0f, A.y, B.y), __builtin_fmaf(-1024.0f, A.z, B.z));
-    const lv_h2 nx01 = lv_plane_pair(nearX, 0), nx23 = lv_plane_pair(nearX, 1), ny01 = lv_plane_pair(nearY, 0), ny23 = lv_plane_pair(nearY, 1);
-    const lv_h2 nz01 = lv_plane_pair(nearZ, 0), nz23 = lv_plane_pair(nearZ, 1), fx01 = lv_plane_pair(farX, 0), fx23 = lv_plane_pair(farX, 1);
-    const lv_h2 fy01 = lv_plane_pair(farY, 0), fy23 = lv_plane_pair(farY, 1), fz01 = lv_plane_pair(farZ, 0), fz23 = lv_plane_pair(farZ, 1);
-    const bool h0 = lv_slab_h(nx01.x, ny01.x, nz01.x, fx01.x, fy01.x, fz01.x, A, B2, tMin, tMax, k0);
-    const bool h1 = lv_slab_h(nx01.y, ny01.y, nz01.y, fx01.y, fy01.y, fz01.y, A, B2, tMin, tMax, k1);
-    const bool h2 = lv_slab_h(nx23.x, ny23.x, nz23.x, fx23.x, fy23.x, fz23.x, A, B2, tMin, tMax, k2);
-    const bool h3 = lv_slab_h(nx23.y, ny23.y, nz23.y, fx23.y, fy23.y, fz23.y, A, B2, tMin, tMax, k3);
-#else
     const bool h0 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 0, A, B, tMin, tMax, k0);
     const bool h1 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 1, A, B, tMin, tMax, k1);
     const bool h2 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 2, A, B, tMin, tMax, k2);
     const bool h3 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 3, A, B, tMin, tMax, k3);
-#endif
     const float INF = __builtin_inff();
-    if (ORDERED == 3) {
-        // nearest hit child WITHOUT a sorting network: the minimum of the masked keys (min3 + min), the first slot that holds it
-        // (exact compare: the minimum IS one of the four), the other hit children pushed in stored order.  The hit / selected flags
-        // are lane masks (scalar registers, combined on the scalar unit), so the children themselves are never moved or masked.
-        k0 = h0 ? k0 : INF; k1 = h1 ? k1 : INF; k2 = h2 ? k2 : INF; k3 = h3 ? k3 : INF;
-        const float km = fminf(fminf(k0, k1), fminf(k2, k3));
-        const bool s0 = h0 && k0 == km;
-        const bool s1 = h1 && !s0 && k1 == km;
-        const bool s2 = h2 && !s0 && !s1 && k2 == km;
-        const bool s3 = h3 && !s0 && !s1 && !s2;
-        unsigned sel = LV_INVALID;
-        sel = s3 ? c3 : sel; sel = s2 ? c2 : sel; sel = s1 ? c1 : sel; sel = s0 ? c0 : sel;
-        const bool p0 = h0 && !s0, p1 = h1 && !s1, p2 = h2 && !s2, p3 = h3 && !s3;
-        if (st.sp + 4 <= STACK::kLds) { // four unconditional writes, at most three of them kept
-            st.lds[st.sp * STACK::kStride] = c3; st.sp += p3 ? 1 : 0;
-            st.lds[st.sp * STACK::kStride] = c2; st.sp += p2 ? 1 : 0;
-            st.lds[st.sp * STACK::kStride] = c1; st.sp += p1 ? 1 : 0;
-            st.lds[st.sp * STACK::kStride] = c0; st.sp += p0 ? 1 : 0;
-        } else {
-            if (p3) st.push(c3);
-            if (p2) st.push(c2);
-            if (p1) st.push(c1);
-            if (p0) st.push(c0);
-        }
-        if (sel != LV_INVALID) return sel;
-        return lv_pop_or_done(st);
-    }
     // a missed child keeps its reference and gets the key +inf: the key travels with the reference through the network and
     // decides below whether the reference is pushed / descended (empty slots never hit: inverted boxes, lv_write_wide_node)
     k0 = h0 ? k0 : INF; k1 = h1 ? k1 : INF; k2 = h2 ? k2 : INF; k3 = h3 ? k3 : INF;
-#ifdef LV_NODE_STEP_MASK_REFS
-    c0 = h0 ? c0 : LV_INVALID; c1 = h1 ? c1 : LV_INVALID; c2 = h2 ? c2 : LV_INVALID; c3 = h3 ? c3 : LV_INVALID;
-#endif
-    if (ORDERED == 2 || (ORDERED == 1 && LV_SORT_CHILDREN)) { // 5-comparator sorting network, misses (key = +inf) sink to the end
+    if (ORDERED == 2) { // 5-comparator sorting network, misses (key = +inf) sink to the end
         lv_cswap(k0, c0, k1, c1);
         lv_cswap(k2, c2, k3, c3);
         lv_cswap(k0, c0, k2, c2);
@@ -675,12 +577,8 @@ __device__ __forceinline__ bool lv_leaf_test(const LvSceneDev& S, unsigned leaf,
         if (LIT == 1 || (LIT == -1 && S.literalIntersection)) {
             hit = lv_intersect_capsule_literal(o, d, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), radius, capped, t, kind);
         } else {
-#if LV_PRECOMP_AXIS
             const float4 ax = S.segAxis[leaf];
             hit = lv_intersect_capsule_td(o, d, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(ax.x, ax.y, ax.z), radius, capped, t, kind);
-#else
-            hit = lv_intersect_capsule(o, d, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), radius, capped, t, kind);
-#endif
         }
         if (hit) low = (S.leafSeg[leaf] << 2) | unsigned(kind);
         return hit;
