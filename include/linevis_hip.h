@@ -146,7 +146,7 @@ int lv_set_tube_triangle_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uin
                               const lv_tube_vertex* vertices, uint32_t num_vertices,
                               const lv_line_point* line_points, uint32_t num_line_points);
 
-/* The same two inputs WITHOUT the host in between (round 6; plain flow lines -- no band data, no rotating helicity bands):
+/* The same two inputs WITHOUT the host in between (round 6; band data and helicity: lv_set_trajectories_with_bands):
  * LineDataFlow::setTrajectoryData's arrays (LineDataFlow.cpp:468-578: positions, the selected attribute, one offset per line) are
  * copied to HBM (16 bytes per point) and the device writes what lv_set_lines and lv_set_tube_triangle_mesh would have been handed:
  * the 48-byte line points + index pairs of LineDataFlow::getLinePassTubeAabbRenderData (LineDataFlow.cpp:2112-2277) at once, and the
@@ -158,6 +158,20 @@ int lv_set_tube_triangle_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uin
  * [0] = 0.  Replaces the lines and the mesh of earlier lv_set_lines / lv_set_tube_triangle_mesh calls; a later lv_set_lines drops the
  * trajectories, a later lv_set_tube_triangle_mesh overrides the device tessellation until the next lv_set_trajectories. */
 int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attribute, const uint32_t* line_offsets, uint32_t num_lines);
+/* The per-point arrays of band data and of the rotating helicity bands that go to HBM with the trajectories (lv_set_trajectories is
+ * lv_set_trajectories_with_bands with bands = NULL).  The records then follow use_ribbons + use_analytic_elliptic_tubes (lineNormal =
+ * cross(ribbon direction, tangent), not normalised, LineDataFlow.cpp:2166-2168) and rotating_helicity_bands (lineRotation, a running sum
+ * per line, :2188-2197) whenever these options change, and the device mesh follows use_ribbons (the elliptic tubes of band data with
+ * semi-axes band_width / 2 * min_band_thickness and band_width / 2) and rotating_helicity_bands (the mesh table's rotation runs on
+ * across all lines, :1994,2014-2028).  use_ribbons without ribbon directions, or rotating_helicity_bands without a helicity array,
+ * is LV_E_STATE when the geometry is needed. */
+typedef struct lv_trajectory_bands {
+    const float* ribbon_directions; /* 3 floats per point (LineDataFlow::ribbonsDirections), or NULL */
+    const float* helicity;          /* 1 float per point: the helicity attribute (LineDataFlow.cpp:535-550), or NULL */
+    float max_helicity;             /* > 0: used as given (LineDataFlow::maxHelicity); <= 0: max |helicity| over all points, reduced on the device */
+} lv_trajectory_bands;
+int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const float* attribute, const uint32_t* line_offsets,
+                                   uint32_t num_lines, const lv_trajectory_bands* bands);
 /* Read-backs of the current line points / index pairs and of the current tube mesh (tessellating it first if lv_set_trajectories'
  * lines have none for the current settings).  Any output pointer may be NULL (query the counts). */
 int lv_get_lines(lv_ctx* ctx, lv_line_point* out_points, uint32_t max_points, uint32_t* out_segment_point_indices, uint32_t max_segments,

@@ -87,6 +87,11 @@ KERNEL_NAMES = ["k_ao_primary", "k_ao_rays", "k_render_rt", "k_ppll_gather", "k_
                 "k_ppll_raster_prism"]
 
 
+class TrajectoryBands(C.Structure):
+    """lv_trajectory_bands"""
+    _fields_ = [("ribbon_directions", C.c_void_p), ("helicity", C.c_void_p), ("max_helicity", C.c_float)]
+
+
 class LineVisError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("linevis_hip error %d: %s" % (code, message))
@@ -100,7 +105,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt",
-           "lv_set_trajectories", "lv_get_lines", "lv_get_tube_triangle_mesh",
+           "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
            "lv_create_multi", "lv_multi_ranks", "lv_multi_rank_stats", "lv_multi_rebalance", "lv_multi_deal", "lv_tile_deal", "lv_make_tiles"]
 
 _lib = None
@@ -170,6 +175,7 @@ def load():
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
         ("lv_set_trajectories", [vp, vp, vp, vp, u32]),
+        ("lv_set_trajectories_with_bands", [vp, vp, vp, vp, u32, C.POINTER(TrajectoryBands)]),
         ("lv_get_lines", [vp, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
         ("lv_get_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         ("lv_trace_rays_triangles", [vp, vp, vp, f32, f32, u32, vp, vp, vp]),
@@ -288,14 +294,27 @@ class Context:
         pts = np.ascontiguousarray(line_points, dtype=LINE_POINT_DTYPE)
         self._ck(self.L.lv_set_tube_triangle_mesh(self.h, _p(idx), len(idx), _p(v), len(v), _p(pts), len(pts)))
 
-    def set_trajectories(self, positions, attribute, line_offsets):
-        """lv_set_trajectories: the trajectories go to HBM, line points / index pairs / tube mesh are written by kernels."""
+    def set_trajectories(self, positions, attribute, line_offsets, ribbon_directions=None, helicity=None, max_helicity=0.0):
+        """lv_set_trajectories: the trajectories go to HBM, line points / index pairs / tube mesh are written by kernels.
+        ribbon_directions (one vec3 per point: band data) and / or helicity (one float per point; max_helicity <= 0: max |helicity|,
+        reduced on the device) go along through lv_set_trajectories_with_bands."""
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         off = np.ascontiguousarray(line_offsets, dtype=np.uint32)
         att = None if attribute is None else np.ascontiguousarray(attribute, dtype=np.float32).reshape(-1)
         if len(off) < 1 or int(off[-1]) != len(pos) or (att is not None and len(att) != len(pos)):
             raise ValueError("line_offsets[-1] must equal the number of points (and of attribute values)")
-        self._ck(self.L.lv_set_trajectories(self.h, _p(pos), None if att is None else _p(att), _p(off), len(off) - 1))
+        if ribbon_directions is None and helicity is None:
+            self._ck(self.L.lv_set_trajectories(self.h, _p(pos), None if att is None else _p(att), _p(off), len(off) - 1))
+            return
+        rib = None if ribbon_directions is None else np.ascontiguousarray(ribbon_directions, dtype=np.float32)
+        hel = None if helicity is None else np.ascontiguousarray(helicity, dtype=np.float32)
+        if rib is not None and (rib.size != 3 * len(pos) or (rib.ndim == 2 and rib.shape[1] != 3)):
+            raise ValueError("ribbon_directions must hold one vec3 per point (%d points, got shape %s)" % (len(pos), rib.shape))
+        if hel is not None and hel.size != len(pos):
+            raise ValueError("helicity must hold one float per point (%d points, got %d)" % (len(pos), hel.size))
+        bands = TrajectoryBands(None if rib is None else _p(rib), None if hel is None else _p(hel), float(max_helicity))
+        self._ck(self.L.lv_set_trajectories_with_bands(self.h, _p(pos), None if att is None else _p(att), _p(off), len(off) - 1,
+                                                       C.byref(bands)))
 
     def get_lines(self):
         """(points, segment index pairs) as they sit in HBM (lv_set_lines' input or lv_set_trajectories' device output)."""

@@ -149,9 +149,17 @@ struct lv_ctx {
     LvDeviceBuffer trajLineValid, trajLineRef, trajRecLine, trajTess; // per line: valid points, LvLineRef; per record: its line; tessellation offsets + tables
     uint32_t trajNumLines = 0, trajNumPoints = 0;
     bool trajHasAttr = false, trajSet = false;
+    // lv_set_trajectories_with_bands: ribbon directions (3 floats per point) and the helicity attribute (1 float per point, max |h| in
+    // trajMaxHelicity's one float); per record: its trajectory point and the mesh table's rotation, which runs on across all lines
+    // (computed once per data set).  trajPoints*: what the records in `points` carry (lv_ensure_line_points rewrites them on change)
+    LvDeviceBuffer trajRibbon, trajHelicity, trajMaxHelicity, trajRecPoint, trajMeshRot;
+    bool trajHasRibbons = false, trajHasHelicity = false;
+    bool trajPointsRibbon = false, trajPointsHelicity = false;
     bool triMeshFromTraj = false;             // the mesh in triIdx / triVerts / triPoints was tessellated here (not passed by the caller)
     float triMeshLineWidth = -1.0f;
     uint32_t triMeshSubdivisions = 0;
+    bool triMeshRibbons = false, triMeshHelicity = false;   // the rest of the device mesh's cache key (host/LineData.cpp:633-636)
+    float triMeshBandWidth = -1.0f, triMeshMinBandThickness = -1.0f;
     float triAccelLineWidth = -1.0f, triPad = 0.0f;
     uint32_t triLeafSize = 1;                 // triangles per leaf of the triangle LBVH as built (opt.triLeafSize at build time)
 
@@ -304,8 +312,12 @@ void lv_buf_free(LvDeviceBuffer& b);
 // lv_bvh.hip
 int lv_bvh_build(lv_ctx* ctx);
 int lv_bvh_build_triangles(lv_ctx* ctx);
-// lv_lines.hip: (re)tessellates the tube mesh of lv_set_trajectories' lines if the line width / subdivision count changed; no-op otherwise
+// lv_lines.hip: (re)tessellates the tube mesh of lv_set_trajectories' lines if the line width / subdivision count / band settings
+// changed; no-op otherwise
 int lv_ensure_tube_mesh(lv_ctx* ctx);
+// lv_lines.hip: rewrites lv_set_trajectories' line points if use_ribbons + use_analytic_elliptic_tubes (ribbon normals) or
+// rotating_helicity_bands (lineRotation) changed since they were written; no-op otherwise
+int lv_ensure_line_points(lv_ctx* ctx);
 // lv_multi.hip: one frame over the GPUs of a node behind the same handle
 int lv_multi_create(lv_ctx* handle, const int* devices, int numDevices, const char* transport);
 void lv_multi_destroy(lv_ctx* handle);

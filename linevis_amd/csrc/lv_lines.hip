@@ -7,21 +7,29 @@
 // radius is baked into the vertices.  Here the trajectories themselves live in HBM (lv_set_trajectories: 16 bytes per point) and both
 // products are written by kernels, byte for byte what linevis_amd/host/LineData.cpp and host/Tubes.cpp produce:
 //
-//   a2   k_lp_tangents   one lane per point: central-difference tangent, its length, the "keep" flag (|t| >= 1e-4, :2160)
+//   a2   k_lp_tangents   one lane per point: central-difference tangent, its length, the "keep" flag (|t| >= 1e-4, :2160); with the
+//                        rotating helicity bands also the lineRotation increment (step to the RAW next point)
 //        rocPRIM scan    rank of every kept point; per line: kept points (a line that keeps fewer than two keeps none, :2209-2221)
-//        k_lp_normals    the only recurrence -- the line normal is carried from kept point to kept point (Gram-Schmidt against the
-//                        tangent with the fallback axes of :2171-2177): one wave per line stages the tangents in LDS, lane 0 walks them
+//        k_lp_normals    the line normal is carried from kept point to kept point (Gram-Schmidt against the tangent with the
+//                        fallback axes of :2171-2177): one wave per line stages the tangents in LDS, lane 0 walks them (not for
+//                        band data with elliptic tubes: their normal is cross(ribbon direction, tangent), data parallel)
+//        k_lp_rotation   helicity bands: the per-line running sum of the increments over the kept points, the same LDS walk
 //        k_lp_records    one lane per point: 48-byte record, index pair
+//        The records follow use_ribbons + use_analytic_elliptic_tubes and rotating_helicity_bands: lv_ensure_line_points rewrites them
+//        when those change.
 //   a14  k_tess_counts   vertices / indices per line incl. the reference's quirks for lines with < 2 valid points, two scans
 //        k_tess_body     one lane per (line point, ring vertex): Tubes.cpp:53-85 (circle table from the host, incremental rotation as
 //                        Tubes.cpp:34-51) + the two triangles of the side towards the next point
 //        k_tess_caps     one lane per cap vertex / cap triangle: CappedTriangleTubesCPU.cpp:33-211
 //        k_tess_points   the mesh's line-point table (LineDataFlow.cpp:1996-2020)
+//        band data (use_ribbons): the elliptic tubes (CappedTriangleTubesCPU.cpp:387-745): ellipse offsets / normals from the host's libm,
+//        normal = cross(ribbon direction, tangent), caps through the inverse-transposed frame
+//        helicity bands: the table's rotation runs on across ALL lines (LineDataFlow.cpp:1994,2014-2028) -- k_mesh_rot_inc (parallel
+//        increments, step to the next table entry of the same line), k_mesh_rot_scan (one lane adds them in order), once per data set
 // Every formula has the host layer's evaluation order (-ffp-contract=off on both sides; + - * / sqrt are IEEE-exact on gfx950); the
 // trigonometric tables (circle, cap rings) come from the host's libm once per tessellation, as the reference computes them on the CPU.
-// Plain flow lines only: band data (elliptic tubes) and the rotating helicity bands (whose rotation is a running float sum across ALL
-// lines, LineDataFlow.cpp:1994,2014-2028) stay on the host path (lv_set_lines + lv_set_tube_triangle_mesh).
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -34,6 +42,7 @@ namespace {
 
 const float kTwoPi = 6.28318530717958647692f;
 const float kHalfPi = 1.57079632679489661923f;
+const float kPi = 3.1415926535897932f;   // the literal of LineDataFlow.cpp:2194,2026
 
 __host__ __device__ inline uint32_t nblk(uint64_t n) { return uint32_t((n + LV_BLOCK - 1) / LV_BLOCK); }
 
@@ -50,9 +59,12 @@ __device__ __forceinline__ uint32_t lv_line_of(const uint32_t* __restrict__ off,
 }
 
 // ---- a2, pass 1: tangents + keep flags.  tang[i] = {unit tangent, keep}; flags[i] = keep (scanned into ranks afterwards)
+// helicity != null: inc[i] = the per-line lineRotation increment of point i (LineData.cpp:590-594): the step goes to the RAW next point
 __global__ __launch_bounds__(LV_BLOCK) void k_lp_tangents(const float* __restrict__ pos, const uint32_t* __restrict__ off,
                                                           uint32_t numLines, uint32_t numPoints, float4* __restrict__ tang,
-                                                          uint32_t* __restrict__ flags, uint32_t* __restrict__ lineOf) {
+                                                          uint32_t* __restrict__ flags, uint32_t* __restrict__ lineOf,
+                                                          const float* __restrict__ helicity, const float* __restrict__ maxHelicity,
+                                                          float* __restrict__ inc) {
     const uint32_t i = blockIdx.x * LV_BLOCK + threadIdx.x;
     if (i > numPoints) return;
     if (i == numPoints) { flags[i] = 0u; return; } // the scan's last element: rank[numPoints] = number of kept points
@@ -70,6 +82,24 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lp_tangents(const float* __restric
     }
     tang[i] = make_float4(t.x, t.y, t.z, keep ? 1.0f : 0.0f);
     flags[i] = keep;
+    if (helicity) {
+        const float step = j + 1u < n ? len3(ld3(pos + 3 * size_t(i + 1u)) - ld3(pos + 3 * size_t(i))) : 0.0f;
+        inc[i] = helicity[i] / *maxHelicity * kPi * step / 0.005f;
+    }
+}
+
+// max |helicity| over all points (LineDataFlow.cpp:543-548: max(|min|, |max|)); |h| >= 0 orders like its bit pattern
+__global__ __launch_bounds__(LV_BLOCK) void k_abs_max(const float* __restrict__ h, uint32_t n, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s[LV_BLOCK / LV_WAVE];
+    const uint32_t i = blockIdx.x * LV_BLOCK + threadIdx.x;
+    uint32_t v = i < n ? __float_as_uint(fabsf(h[i])) : 0u;
+    for (int o = LV_WAVE / 2; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    if ((threadIdx.x & (LV_WAVE - 1)) == 0u) s[threadIdx.x / LV_WAVE] = v;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        for (uint32_t w = 1; w < LV_BLOCK / LV_WAVE; w++) v = max(v, s[w]);
+        atomicMax(out, v);
+    }
 }
 
 // per line: valid points m (the tessellation's count), kept records (m if >= 2) and segments, packed as (segments << 32) | records
@@ -119,6 +149,34 @@ __global__ __launch_bounds__(LV_WAVE) void k_lp_normals(const float4* __restrict
     }
 }
 
+// ---- a2, pass 2 of the rotating helicity bands: the per-line running sum of the increments over the kept points, in point order (one
+// wave per line as k_lp_normals; lane 0 adds)
+__global__ __launch_bounds__(LV_WAVE) void k_lp_rotation(const float4* __restrict__ tang, const float* __restrict__ inc,
+                                                         const uint32_t* __restrict__ off, const uint32_t* __restrict__ lineValid,
+                                                         float* __restrict__ rotOut) {
+    __shared__ float2 s[LV_LP_CHUNK];
+    const uint32_t li = blockIdx.x;
+    if (lineValid[li] < 2u) return;
+    const uint32_t b = off[li], n = off[li + 1] - b, lane = threadIdx.x;
+    float rotation = 0.0f;
+    for (uint32_t base = 0; base < n; base += LV_LP_CHUNK) {
+        const uint32_t cnt = min(LV_LP_CHUNK, n - base);
+        for (uint32_t j = lane; j < cnt; j += LV_WAVE) s[j] = make_float2(inc[size_t(b) + base + j], tang[size_t(b) + base + j].w);
+        __syncthreads();
+        if (lane == 0u) {
+            for (uint32_t j = 0; j < cnt; j++) {
+                const float2 v = s[j];
+                if (v.y == 0.0f) continue;
+                s[j].x = rotation;
+                rotation += v.x;
+            }
+        }
+        __syncthreads();
+        for (uint32_t j = lane; j < cnt; j += LV_WAVE) rotOut[size_t(b) + base + j] = s[j].x;
+        __syncthreads();
+    }
+}
+
 struct LvLineRef {       // per line, kept between tessellations
     uint32_t recOff;     // first record (= first entry of the mesh's line-point table)
     uint32_t segOff;     // first segment
@@ -131,9 +189,11 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lp_records(const float* __restrict
                                                          const uint32_t* __restrict__ off, const uint32_t* __restrict__ lineOf,
                                                          const uint32_t* __restrict__ rank, const uint32_t* __restrict__ lineValid,
                                                          const unsigned long long* __restrict__ packedOff, const float4* __restrict__ tang,
-                                                         const float4* __restrict__ normal, uint32_t numPoints,
+                                                         const float4* __restrict__ normal, const float* __restrict__ ribbon,
+                                                         const float* __restrict__ rot, uint32_t numPoints,
                                                          float4* __restrict__ recOut, uint32_t* __restrict__ segOut,
-                                                         uint32_t* __restrict__ recLine, LvLineRef* __restrict__ lineRef) {
+                                                         uint32_t* __restrict__ recLine, uint32_t* __restrict__ recPoint,
+                                                         LvLineRef* __restrict__ lineRef) {
     const uint32_t i = blockIdx.x * LV_BLOCK + threadIdx.x;
     if (i >= numPoints) return;
     const float4 t = tang[i];
@@ -148,12 +208,14 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lp_records(const float* __restrict
     const unsigned long long po = packedOff[li];
     const uint32_t recOff = uint32_t(po), segOff = uint32_t(po >> 32), r = recOff + o;
     if (o == 0u) { lineRef[li].recOff = recOff; lineRef[li].segOff = segOff; }
-    const float4 nn = normal[i];
+    // band data with elliptic tubes: cross(ribbon direction, tangent), not normalised (LineData.cpp:578-579); else the carried normal
+    const f3 nn = ribbon ? cross3(ld3(ribbon + 3 * size_t(i)), mk3(t.x, t.y, t.z)) : mk3(normal[i].x, normal[i].y, normal[i].z);
     const float a = attr ? attr[i] : 0.0f;
     recOut[3 * size_t(r)] = make_float4(pos[3 * size_t(i)], pos[3 * size_t(i) + 1], pos[3 * size_t(i) + 2], a);
-    recOut[3 * size_t(r) + 1] = make_float4(t.x, t.y, t.z, 0.0f);                       // lineRotation = 0
+    recOut[3 * size_t(r) + 1] = make_float4(t.x, t.y, t.z, rot ? rot[i] : 0.0f);        // lineRotation
     recOut[3 * size_t(r) + 2] = make_float4(nn.x, nn.y, nn.z, __uint_as_float(0u));     // lineStartIndex = 0 (LineDataFlow.cpp:2199-2207)
     recLine[r] = li;
+    recPoint[r] = i;
     if (o > 0u) {
         const size_t sgm = size_t(segOff) + o - 1u;
         segOut[2 * sgm] = r - 1u;
@@ -161,10 +223,48 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lp_records(const float* __restrict
     }
 }
 
+// ---- the mesh table's rotation (LineData.cpp:657-671): increments per table entry in parallel -- the step goes to the next ENTRY if it
+// belongs to the same trajectory (the next kept point), else 0 -- then one running sum across all lines
+__global__ __launch_bounds__(LV_BLOCK) void k_mesh_rot_inc(const float* __restrict__ pos, const float* __restrict__ helicity,
+                                                           const float* __restrict__ maxHelicity, const uint32_t* __restrict__ recLine,
+                                                           const uint32_t* __restrict__ recPoint, uint32_t numRecords,
+                                                           float* __restrict__ inc) {
+    const uint32_t r = blockIdx.x * LV_BLOCK + threadIdx.x;
+    if (r >= numRecords) return;
+    const uint32_t i = recPoint[r];
+    float step = 0.0f;
+    if (r + 1u < numRecords && recLine[r + 1u] == recLine[r]) step = len3(ld3(pos + 3 * size_t(recPoint[r + 1u])) - ld3(pos + 3 * size_t(i)));
+    inc[r] = helicity[i] / *maxHelicity * kPi * step / 0.005f;
+}
+
+// in place: inc[r] -> the sum of inc[0 .. r-1] in table order.  One block stages LV_ROT_CHUNK entries in LDS, thread 0 adds them in order
+#define LV_ROT_CHUNK 4096u
+__global__ __launch_bounds__(LV_BLOCK) void k_mesh_rot_scan(float* __restrict__ rot, uint32_t numRecords) {
+    __shared__ float s[LV_ROT_CHUNK];
+    float rotation = 0.0f;
+    for (uint32_t base = 0; base < numRecords; base += LV_ROT_CHUNK) {
+        const uint32_t cnt = min(LV_ROT_CHUNK, numRecords - base);
+        for (uint32_t j = threadIdx.x; j < cnt; j += LV_BLOCK) s[j] = rot[size_t(base) + j];
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            for (uint32_t j = 0; j < cnt; j++) {
+                const float v = s[j];
+                s[j] = rotation;
+                rotation += v;
+            }
+        }
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < cnt; j += LV_BLOCK) rot[size_t(base) + j] = s[j];
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------- a14: tessellation
 struct LvTessParams {
-    float circle[LV_PRISM_MAX_SUBDIV][3];   // initGlobalCircleVertexPositions (Tubes.cpp:34-51), radius included
-    float radius;
+    float circle[LV_PRISM_MAX_SUBDIV][3];   // initGlobalCircleVertexPositions (Tubes.cpp:34-51), radius included; band data: the ellipse
+    float ellNormal[LV_PRISM_MAX_SUBDIV][3];// band data: initGlobalEllipseVertexPositions' normals (Tubes.cpp:131-140)
+    float radiusT, radiusN, radiusB;        // the caps' frame scales (Tubes.cpp:237-238): all the tube radius, or min(nr, br), nr, br
+    uint32_t elliptic;                      // band data: ribbon normals, ellipse normals, caps through the NormalFrame inverse
     uint32_t n;                             // N = max(tube_num_subdivisions, 4)
     uint32_t nLat;                          // N / 2
     uint32_t capVerts, capIdx;              // per cap: nLon (nLat - 1) + 1 vertices, nLon (nLat - 1) 6 + nLon 3 indices
@@ -191,6 +291,36 @@ __global__ __launch_bounds__(LV_BLOCK) void k_tess_counts(const uint32_t* __rest
 __device__ __forceinline__ f3 lv_combine(f3 pt, f3 a, f3 b, f3 c) {
     return mk3((pt.x * a.x + pt.y * b.x) + pt.z * c.x, (pt.x * a.y + pt.y * b.y) + pt.z * c.y, (pt.x * a.z + pt.y * b.z) + pt.z * c.z);
 }
+// the normal matrix of an elliptic cap's frame (columns a, b, c): glm::inverse in cofactor form, transposed (host/Tubes.cpp NormalFrame)
+__device__ __forceinline__ f3 lv_normal_frame_mul(f3 a, f3 b, f3 c, f3 v) {
+    const float f[3][3] = {{a.x, a.y, a.z}, {b.x, b.y, b.z}, {c.x, c.y, c.z}};
+    const float oneOverDeterminant = 1.0f / (+ f[0][0] * (f[1][1] * f[2][2] - f[2][1] * f[1][2])
+                                              - f[1][0] * (f[0][1] * f[2][2] - f[2][1] * f[0][2])
+                                              + f[2][0] * (f[0][1] * f[1][2] - f[1][1] * f[0][2]));
+    float inv[3][3];
+    inv[0][0] = +(f[1][1] * f[2][2] - f[2][1] * f[1][2]) * oneOverDeterminant;
+    inv[1][0] = -(f[1][0] * f[2][2] - f[2][0] * f[1][2]) * oneOverDeterminant;
+    inv[2][0] = +(f[1][0] * f[2][1] - f[2][0] * f[1][1]) * oneOverDeterminant;
+    inv[0][1] = -(f[0][1] * f[2][2] - f[2][1] * f[0][2]) * oneOverDeterminant;
+    inv[1][1] = +(f[0][0] * f[2][2] - f[2][0] * f[0][2]) * oneOverDeterminant;
+    inv[2][1] = -(f[0][0] * f[2][1] - f[2][0] * f[0][1]) * oneOverDeterminant;
+    inv[0][2] = +(f[0][1] * f[1][2] - f[1][1] * f[0][2]) * oneOverDeterminant;
+    inv[1][2] = -(f[0][0] * f[1][2] - f[1][0] * f[0][2]) * oneOverDeterminant;
+    inv[2][2] = +(f[0][0] * f[1][1] - f[1][0] * f[0][1]) * oneOverDeterminant;
+    // m[col][row] = inv[row][col]; mul: (m[0][0] v.x + m[1][0] v.y) + m[2][0] v.z, ...
+    return mk3((inv[0][0] * v.x + inv[0][1] * v.y) + inv[0][2] * v.z, (inv[1][0] * v.x + inv[1][1] * v.y) + inv[1][2] * v.z,
+               (inv[2][0] * v.x + inv[2][1] * v.y) + inv[2][2] * v.z);
+}
+// the tessellation's line normal of record r: the record's (Gram-Schmidt) one, or for band data cross(ribbon direction, tangent)
+__device__ __forceinline__ f3 lv_tess_normal(const float4* __restrict__ rec, const float* __restrict__ ribbon,
+                                             const uint32_t* __restrict__ recPoint, uint32_t r) {
+    if (ribbon) {
+        const float4 t4 = rec[3 * size_t(r) + 1];
+        return cross3(ld3(ribbon + 3 * size_t(recPoint[r])), mk3(t4.x, t4.y, t4.z));
+    }
+    const float4 n4 = rec[3 * size_t(r) + 2];
+    return mk3(n4.x, n4.y, n4.z);
+}
 __device__ __forceinline__ void lv_store_vertex(lv_tube_vertex* V, size_t at, f3 p, uint32_t linePoint, f3 n, float phi) {
     float4* w = (float4*)(V + at);
     w[0] = make_float4(p.x, p.y, p.z, __uint_as_float(linePoint));
@@ -201,19 +331,22 @@ __device__ __forceinline__ void lv_store_vertex(lv_tube_vertex* V, size_t at, f3
 __global__ __launch_bounds__(LV_BLOCK) void k_tess_body(const float4* __restrict__ rec, const uint32_t* __restrict__ recLine,
                                                         const LvLineRef* __restrict__ lineRef, const uint32_t* __restrict__ lineValid,
                                                         const unsigned long long* __restrict__ vOff,
-                                                        const unsigned long long* __restrict__ iOff, uint32_t numRecords,
+                                                        const unsigned long long* __restrict__ iOff, const float* __restrict__ ribbon,
+                                                        const uint32_t* __restrict__ recPoint, uint32_t numRecords,
                                                         LvTessParams P, lv_tube_vertex* __restrict__ V, uint32_t* __restrict__ I) {
     const uint64_t g = uint64_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
     if (g >= uint64_t(numRecords) * P.n) return;
     const uint32_t r = uint32_t(g / P.n), j = uint32_t(g % P.n);
     const uint32_t li = recLine[r], k = r - lineRef[li].recOff, m = lineValid[li];
-    const float4 c4 = rec[3 * size_t(r)], t4 = rec[3 * size_t(r) + 1], n4 = rec[3 * size_t(r) + 2];
-    const f3 center = mk3(c4.x, c4.y, c4.z), tangent = mk3(t4.x, t4.y, t4.z), normal = mk3(n4.x, n4.y, n4.z);
+    const float4 c4 = rec[3 * size_t(r)], t4 = rec[3 * size_t(r) + 1];
+    const f3 center = mk3(c4.x, c4.y, c4.z), tangent = mk3(t4.x, t4.y, t4.z), normal = lv_tess_normal(rec, ribbon, recPoint, r);
     const f3 binormal = cross3(tangent, normal);
     const f3 off = lv_combine(mk3(P.circle[j][0], P.circle[j][1], P.circle[j][2]), normal, binormal, tangent);
     const f3 pos = mk3(off.x + center.x, off.y + center.y, off.z + center.z);
+    const f3 nrm = P.elliptic ? lv_combine(mk3(P.ellNormal[j][0], P.ellNormal[j][1], P.ellNormal[j][2]), normal, binormal, tangent)
+                              : norm3(pos - center);
     const uint32_t bodyV = uint32_t(vOff[li]) + P.capVerts;
-    lv_store_vertex(V, size_t(bodyV) + size_t(k) * P.n + j, pos, r, norm3(pos - center), float(j) / float(P.n) * kTwoPi);
+    lv_store_vertex(V, size_t(bodyV) + size_t(k) * P.n + j, pos, r, nrm, float(j) / float(P.n) * kTwoPi);
     if (k + 1u < m) {
         const uint32_t j1 = (j + 1u) % P.n;
         const uint32_t a = bodyV + k * P.n + j, b = bodyV + k * P.n + j1, c = bodyV + (k + 1u) * P.n + j1, d = bodyV + (k + 1u) * P.n + j;
@@ -230,7 +363,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_tess_caps(const float* __restrict_
                                                         const float4* __restrict__ rec, const LvLineRef* __restrict__ lineRef,
                                                         const uint32_t* __restrict__ lineValid, const unsigned long long* __restrict__ vOff,
                                                         const unsigned long long* __restrict__ iOff, uint32_t numLines, LvTessParams P,
-                                                        const float4* __restrict__ capTable, lv_tube_vertex* __restrict__ V,
+                                                        const float4* __restrict__ capTable, const float* __restrict__ ribbon,
+                                                        const uint32_t* __restrict__ recPoint, lv_tube_vertex* __restrict__ V,
                                                         uint32_t* __restrict__ I) {
     const uint32_t capTris = P.capIdx / 3u, slots = 2u * P.capVerts + 2u * capTris;
     const uint64_t g = uint64_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
@@ -262,18 +396,22 @@ __global__ __launch_bounds__(LV_BLOCK) void k_tess_caps(const float* __restrict_
             if (v == P.capVerts - 1u) { lat = nLat; lon = 0u; } else { lat = 1u + v / nLon; lon = v % nLon; }
         }
         const uint32_t r = start ? L.recOff : L.recOff + m - 1u;
-        const float4 n4 = rec[3 * size_t(r) + 2];
-        const f3 normal = mk3(n4.x, n4.y, n4.z);
+        const f3 normal = lv_tess_normal(rec, ribbon, recPoint, r);
         const float* c0 = pos + 3 * size_t(b + (start ? L.firstIdx : L.lastIdx));
         const float* c1 = pos + 3 * size_t(b + (start ? L.firstIdx + 1u : L.lastIdx - 1u));
         const f3 center = ld3(c0);
         const f3 tangent = norm3(center - ld3(c1));
         const f3 binormal = cross3(normal, tangent);
-        const f3 sT = P.radius * tangent, sN = P.radius * normal, sB = P.radius * binormal;
+        const f3 sT = P.radiusT * tangent, sN = P.radiusN * normal, sB = P.radiusB * binormal;
         const float4 e = capTable[2u * ((lat - 1u) * nLon + lon) + (start ? 0u : 1u)];
-        const f3 o = lv_combine(mk3(e.x, e.y, e.z), sN, sB, sT);
-        lv_store_vertex(V, size_t(start ? capStartV : capEndV) + v, mk3(o.x + center.x, o.y + center.y, o.z + center.z),
-                        r | 0x80000000u, norm3(o), e.w);
+        const f3 pt = mk3(e.x, e.y, e.z);
+        const f3 o = lv_combine(pt, sN, sB, sT);
+        const f3 p = mk3(o.x + center.x, o.y + center.y, o.z + center.z);
+        if (P.elliptic)   // normal through the inverse-transposed frame, the ZENITH angle in phi (host/Tubes.cpp:246-248)
+            lv_store_vertex(V, size_t(start ? capStartV : capEndV) + v, p, r | 0x80000000u, norm3(lv_normal_frame_mul(sN, sB, sT, pt)),
+                            kHalfPi * (1.0f - float(lat) / float(nLat)));
+        else
+            lv_store_vertex(V, size_t(start ? capStartV : capEndV) + v, p, r | 0x80000000u, norm3(o), e.w);
         return;
     }
     uint32_t q = slot - 2u * P.capVerts;
@@ -308,50 +446,35 @@ __global__ __launch_bounds__(LV_BLOCK) void k_tess_caps(const float* __restrict_
 }
 
 // the mesh's line-point table: the records with lineStartIndex = the line's first entry (LineDataFlow.cpp:1996-2020: it advances
-// when the trajectory index changes, i.e. it is the first record of the line)
+// when the trajectory index changes, i.e. it is the first record of the line), the tessellation's normal and the rotation of the
+// whole table (meshRot, computed once per data set; 0 without the rotating helicity bands)
 __global__ __launch_bounds__(LV_BLOCK) void k_tess_points(const float4* __restrict__ rec, const uint32_t* __restrict__ recLine,
-                                                          const LvLineRef* __restrict__ lineRef, uint32_t numRecords,
-                                                          float4* __restrict__ out) {
+                                                          const LvLineRef* __restrict__ lineRef, const float* __restrict__ ribbon,
+                                                          const uint32_t* __restrict__ recPoint, const float* __restrict__ meshRot,
+                                                          uint32_t numRecords, float4* __restrict__ out) {
     const uint32_t r = blockIdx.x * LV_BLOCK + threadIdx.x;
     if (r >= numRecords) return;
     out[3 * size_t(r)] = rec[3 * size_t(r)];
-    out[3 * size_t(r) + 1] = rec[3 * size_t(r) + 1];
-    float4 n = rec[3 * size_t(r) + 2];
-    n.w = __uint_as_float(lineRef[recLine[r]].recOff);
-    out[3 * size_t(r) + 2] = n;
+    float4 t = rec[3 * size_t(r) + 1];
+    t.w = meshRot ? meshRot[r] : 0.0f;
+    out[3 * size_t(r) + 1] = t;
+    const f3 n = lv_tess_normal(rec, ribbon, recPoint, r);
+    out[3 * size_t(r) + 2] = make_float4(n.x, n.y, n.z, __uint_as_float(lineRef[recLine[r]].recOff));
 }
 
 } // namespace
 
-// LineRenderer::setLineData(LineDataPtr&, bool) (LineRenderer.hpp:98) for plain flow lines, with LineDataFlow::setTrajectoryData's
-// arrays (LineDataFlow.cpp:468-578) instead of the host-built render data: see include/linevis_hip.h.
-int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attribute, const uint32_t* line_offsets, uint32_t num_lines) {
-    if (!ctx) return LV_E_INVALID;
-    if (!line_offsets) return lv_fail(ctx, LV_E_INVALID, "null line_offsets (num_lines + 1 entries, even for zero lines)");
-    if (line_offsets[0] != 0u) return lv_fail(ctx, LV_E_INVALID, "line_offsets[0] must be 0");
-    for (uint32_t l = 0; l < num_lines; l++)
-        if (line_offsets[l + 1] < line_offsets[l])
-            return lv_fail(ctx, LV_E_INVALID, "line_offsets must not decrease (line %u: %u -> %u)", l, line_offsets[l], line_offsets[l + 1]);
-    const uint32_t numPoints = line_offsets[num_lines];
-    if (numPoints && !positions) return lv_fail(ctx, LV_E_INVALID, "null positions");
-    if (numPoints > 0x03FFFFFFu) return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 points (leaf index field of the AO work queue)");
-    (void)hipSetDevice(ctx->device);
+// a2 from the trajectories in HBM at the current options: ribbon normals (use_ribbons + use_analytic_elliptic_tubes) or the carried
+// Gram-Schmidt normal, lineRotation with rotating_helicity_bands.  The set of kept points -- and so every offset -- does not depend on
+// the options: lv_ensure_line_points calls this again when they change and the mesh's tables stay valid.
+static int lv_write_line_points(lv_ctx* ctx) {
     lv_invalidate_bake(ctx);   // before any buffer is touched: a bake in flight on the second stream still reads the old ones
     hipStream_t st = ctx->stream;
-    int rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->trajPos, size_t(numPoints) * 12))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->trajAttr, size_t(numPoints) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->trajOff, size_t(num_lines + 1u) * 4))) return rc;
-    if (numPoints) LV_HIP(ctx, hipMemcpyAsync(ctx->trajPos.ptr, positions, size_t(numPoints) * 12, hipMemcpyHostToDevice, st));
-    if (numPoints && attribute) LV_HIP(ctx, hipMemcpyAsync(ctx->trajAttr.ptr, attribute, size_t(numPoints) * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->trajOff.ptr, line_offsets, size_t(num_lines + 1u) * 4, hipMemcpyHostToDevice, st));
-    ctx->trajNumLines = num_lines;
-    ctx->trajNumPoints = numPoints;
-    ctx->trajHasAttr = attribute != nullptr;
-    ctx->trajSet = false;
-
-    // ---- a2 on the device
+    const uint32_t num_lines = ctx->trajNumLines, numPoints = ctx->trajNumPoints;
+    const bool ribbonNormals = ctx->trajHasRibbons && ctx->opt.useRibbons && ctx->opt.ellipticTubes;
+    const bool rotation = ctx->trajHasHelicity && ctx->opt.helicityBands;
     const uint32_t* off = (const uint32_t*)ctx->trajOff.ptr;
+    int rc;
     size_t scanBytes = 0, scanBytes64 = 0;
     LV_HIP(ctx, rocprim::exclusive_scan(nullptr, scanBytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, size_t(numPoints) + 1,
                                         rocprim::plus<uint32_t>(), st));
@@ -360,10 +483,12 @@ int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attrib
     // scratch out of the build arena (dead once the records are written; the LBVH builds reuse it)
     struct Req { void** p; size_t bytes; };
     void *tang = nullptr, *normal = nullptr, *flags = nullptr, *rank = nullptr, *lineOf = nullptr, *packed = nullptr, *packedOff = nullptr,
-         *scanTmp = nullptr;
-    const Req reqs[] = {{&tang, size_t(numPoints) * 16}, {&normal, size_t(numPoints) * 16}, {&flags, (size_t(numPoints) + 1) * 4},
+         *scanTmp = nullptr, *inc = nullptr, *rot = nullptr;
+    const size_t rotBytes = rotation ? size_t(numPoints) * 4 : 0;
+    const Req reqs[] = {{&tang, size_t(numPoints) * 16}, {&normal, ribbonNormals ? 0 : size_t(numPoints) * 16}, {&flags, (size_t(numPoints) + 1) * 4},
                         {&rank, (size_t(numPoints) + 1) * 4}, {&lineOf, size_t(numPoints) * 4}, {&packed, (size_t(num_lines) + 1) * 8},
-                        {&packedOff, (size_t(num_lines) + 1) * 8}, {&scanTmp, std::max<size_t>(std::max(scanBytes, scanBytes64), 16)}};
+                        {&packedOff, (size_t(num_lines) + 1) * 8}, {&scanTmp, std::max<size_t>(std::max(scanBytes, scanBytes64), 16)},
+                        {&inc, rotBytes}, {&rot, rotBytes}};
     size_t total = 0;
     for (const Req& r : reqs) total += (r.bytes + 255) & ~size_t(255);
     if ((rc = lv_buf_reserve(ctx, ctx->buildArena, total))) return rc;
@@ -374,10 +499,12 @@ int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attrib
     if ((rc = lv_buf_reserve(ctx, ctx->trajLineValid, size_t(num_lines ? num_lines : 1u) * 4))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->trajLineRef, size_t(num_lines ? num_lines : 1u) * sizeof(LvLineRef)))) return rc;
     if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
+    const float* helicity = rotation ? (const float*)ctx->trajHelicity.ptr : nullptr;
+    const float* maxHelicity = (const float*)ctx->trajMaxHelicity.ptr;
     LV_HIP(ctx, hipEventRecord(ctx->ev[4], st));
     LV_HIP(ctx, hipMemsetAsync(ctx->trajLineRef.ptr, 0, size_t(num_lines ? num_lines : 1u) * sizeof(LvLineRef), st));
     k_lp_tangents<<<nblk(uint64_t(numPoints) + 1), LV_BLOCK, 0, st>>>((const float*)ctx->trajPos.ptr, off, num_lines, numPoints, (float4*)tang,
-                                                                      (uint32_t*)flags, (uint32_t*)lineOf);
+                                                                      (uint32_t*)flags, (uint32_t*)lineOf, helicity, maxHelicity, (float*)inc);
     {
         size_t tb = scanBytes;
         LV_HIP(ctx, rocprim::exclusive_scan(scanTmp, tb, (uint32_t*)flags, (uint32_t*)rank, 0u, size_t(numPoints) + 1,
@@ -391,19 +518,24 @@ int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attrib
                                             size_t(num_lines) + 1, rocprim::plus<unsigned long long>(), st));
     }
     LV_HIP(ctx, hipMemcpyAsync((void*)ctx->pinned, (const unsigned long long*)packedOff + num_lines, 8, hipMemcpyDeviceToHost, st));
-    if (num_lines)
+    if (num_lines && !ribbonNormals)   // ribbon normals are data parallel (k_lp_records)
         k_lp_normals<<<num_lines, LV_WAVE, 0, st>>>((const float4*)tang, off, (const uint32_t*)ctx->trajLineValid.ptr, (float4*)normal);
-    LV_HIP(ctx, hipStreamSynchronize(st));   // the totals size the outputs (host arrays were borrowed for the call only anyway)
+    if (num_lines && rotation)
+        k_lp_rotation<<<num_lines, LV_WAVE, 0, st>>>((const float4*)tang, (const float*)inc, off, (const uint32_t*)ctx->trajLineValid.ptr,
+                                                     (float*)rot);
+    LV_HIP(ctx, hipStreamSynchronize(st));   // the totals size the outputs
     const uint64_t totals = *(volatile unsigned long long*)ctx->pinned;
     const uint32_t numRecords = uint32_t(totals), numSegs = uint32_t(totals >> 32);
     if ((rc = lv_buf_reserve(ctx, ctx->points, size_t(numRecords) * sizeof(lv_line_point)))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->segIdx, size_t(numSegs) * 8))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->trajRecLine, size_t(numRecords ? numRecords : 1u) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->trajRecPoint, size_t(numRecords ? numRecords : 1u) * 4))) return rc;
     if (numPoints)
         k_lp_records<<<nblk(numPoints), LV_BLOCK, 0, st>>>(
-                (const float*)ctx->trajPos.ptr, attribute ? (const float*)ctx->trajAttr.ptr : nullptr, off, (const uint32_t*)lineOf,
+                (const float*)ctx->trajPos.ptr, ctx->trajHasAttr ? (const float*)ctx->trajAttr.ptr : nullptr, off, (const uint32_t*)lineOf,
                 (const uint32_t*)rank, (const uint32_t*)ctx->trajLineValid.ptr, (const unsigned long long*)packedOff, (const float4*)tang,
-                (const float4*)normal, numPoints, (float4*)ctx->points.ptr, (uint32_t*)ctx->segIdx.ptr, (uint32_t*)ctx->trajRecLine.ptr,
+                (const float4*)normal, ribbonNormals ? (const float*)ctx->trajRibbon.ptr : nullptr, rotation ? (const float*)rot : nullptr, numPoints,
+                (float4*)ctx->points.ptr, (uint32_t*)ctx->segIdx.ptr, (uint32_t*)ctx->trajRecLine.ptr, (uint32_t*)ctx->trajRecPoint.ptr,
                 (LvLineRef*)ctx->trajLineRef.ptr);
     LV_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     LV_HIP(ctx, hipGetLastError());
@@ -411,14 +543,96 @@ int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attrib
     ctx->evLinePointsValid = true;
     ctx->numPoints = numRecords;
     ctx->numSegs = numSegs;
-    ctx->accelValid = false;
+    ctx->accelValid = false;      // the segment LBVH's leaves carry the records' frames
+    ctx->trajPointsRibbon = ribbonNormals;
+    ctx->trajPointsHelicity = rotation;
+    return LV_OK;
+}
+
+int lv_ensure_line_points(lv_ctx* ctx) {
+    if (!ctx->trajSet) return LV_OK;                      // lines of lv_set_lines are the caller's
+    if (ctx->opt.useRibbons && !ctx->trajHasRibbons)
+        return lv_fail(ctx, LV_E_STATE, "use_ribbons: the trajectories were set without ribbon directions (lv_set_trajectories_with_bands)");
+    if (ctx->opt.helicityBands && !ctx->trajHasHelicity)
+        return lv_fail(ctx, LV_E_STATE, "rotating_helicity_bands: the trajectories were set without a helicity attribute "
+                                        "(lv_set_trajectories_with_bands)");
+    if (ctx->trajPointsRibbon == (ctx->opt.useRibbons && ctx->opt.ellipticTubes) && ctx->trajPointsHelicity == ctx->opt.helicityBands)
+        return LV_OK;
+    return lv_write_line_points(ctx);
+}
+
+// LineRenderer::setLineData(LineDataPtr&, bool) (LineRenderer.hpp:98) for flow lines, with LineDataFlow::setTrajectoryData's arrays
+// (LineDataFlow.cpp:468-578) instead of the host-built render data: see include/linevis_hip.h.
+int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const float* attribute, const uint32_t* line_offsets,
+                                   uint32_t num_lines, const lv_trajectory_bands* bands) {
+    if (!ctx) return LV_E_INVALID;
+    if (!line_offsets) return lv_fail(ctx, LV_E_INVALID, "null line_offsets (num_lines + 1 entries, even for zero lines)");
+    if (line_offsets[0] != 0u) return lv_fail(ctx, LV_E_INVALID, "line_offsets[0] must be 0");
+    for (uint32_t l = 0; l < num_lines; l++)
+        if (line_offsets[l + 1] < line_offsets[l])
+            return lv_fail(ctx, LV_E_INVALID, "line_offsets must not decrease (line %u: %u -> %u)", l, line_offsets[l], line_offsets[l + 1]);
+    const uint32_t numPoints = line_offsets[num_lines];
+    if (numPoints && !positions) return lv_fail(ctx, LV_E_INVALID, "null positions");
+    if (numPoints > 0x03FFFFFFu) return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 points (leaf index field of the AO work queue)");
+    const float* ribbon = bands ? bands->ribbon_directions : nullptr;
+    const float* helicity = bands ? bands->helicity : nullptr;
+    const float givenMaxHelicity = bands ? bands->max_helicity : 0.0f;
+    if (helicity && !(givenMaxHelicity <= FLT_MAX))
+        return lv_fail(ctx, LV_E_INVALID, "max_helicity must be finite (<= 0: reduced on the device)");
+    (void)hipSetDevice(ctx->device);
+    lv_invalidate_bake(ctx);
+    hipStream_t st = ctx->stream;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->trajPos, size_t(numPoints) * 12))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->trajAttr, size_t(numPoints) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->trajOff, size_t(num_lines + 1u) * 4))) return rc;
+    if (ribbon && (rc = lv_buf_reserve(ctx, ctx->trajRibbon, size_t(numPoints) * 12))) return rc;
+    if (helicity && (rc = lv_buf_reserve(ctx, ctx->trajHelicity, size_t(numPoints) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->trajMaxHelicity, 4))) return rc;
+    if (numPoints) LV_HIP(ctx, hipMemcpyAsync(ctx->trajPos.ptr, positions, size_t(numPoints) * 12, hipMemcpyHostToDevice, st));
+    if (numPoints && attribute) LV_HIP(ctx, hipMemcpyAsync(ctx->trajAttr.ptr, attribute, size_t(numPoints) * 4, hipMemcpyHostToDevice, st));
+    if (numPoints && ribbon) LV_HIP(ctx, hipMemcpyAsync(ctx->trajRibbon.ptr, ribbon, size_t(numPoints) * 12, hipMemcpyHostToDevice, st));
+    if (numPoints && helicity) LV_HIP(ctx, hipMemcpyAsync(ctx->trajHelicity.ptr, helicity, size_t(numPoints) * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->trajOff.ptr, line_offsets, size_t(num_lines + 1u) * 4, hipMemcpyHostToDevice, st));
+    if (givenMaxHelicity > 0.0f) {   // LineDataFlow::maxHelicity as given
+        LV_HIP(ctx, hipMemcpyAsync(ctx->trajMaxHelicity.ptr, &givenMaxHelicity, 4, hipMemcpyHostToDevice, st));
+    } else {                         // max |helicity| over all points (0 bits = 0.0f for an empty set or without helicity)
+        LV_HIP(ctx, hipMemsetAsync(ctx->trajMaxHelicity.ptr, 0, 4, st));
+        if (numPoints && helicity)
+            k_abs_max<<<nblk(numPoints), LV_BLOCK, 0, st>>>((const float*)ctx->trajHelicity.ptr, numPoints, (uint32_t*)ctx->trajMaxHelicity.ptr);
+    }
+    ctx->trajNumLines = num_lines;
+    ctx->trajNumPoints = numPoints;
+    ctx->trajHasAttr = attribute != nullptr;
+    ctx->trajHasRibbons = ribbon != nullptr;
+    ctx->trajHasHelicity = helicity != nullptr;
+    ctx->trajSet = false;
+    if ((rc = lv_write_line_points(ctx))) return rc;   // (synchronises: the host arrays were borrowed for the call only)
+    if (helicity && ctx->numPoints) {
+        // the mesh table's rotation runs on across all lines and depends on nothing a tessellation changes: once per data set
+        const uint32_t numRecords = ctx->numPoints;
+        if ((rc = lv_buf_reserve(ctx, ctx->trajMeshRot, size_t(numRecords) * 4))) return rc;
+        k_mesh_rot_inc<<<nblk(numRecords), LV_BLOCK, 0, st>>>((const float*)ctx->trajPos.ptr, (const float*)ctx->trajHelicity.ptr,
+                                                               (const float*)ctx->trajMaxHelicity.ptr, (const uint32_t*)ctx->trajRecLine.ptr,
+                                                               (const uint32_t*)ctx->trajRecPoint.ptr, numRecords, (float*)ctx->trajMeshRot.ptr);
+        k_mesh_rot_scan<<<1, LV_BLOCK, 0, st>>>((float*)ctx->trajMeshRot.ptr, numRecords);
+        LV_HIP(ctx, hipEventRecord(ctx->ev[6], st));   // ms_line_points: a2 + this chain
+        LV_HIP(ctx, hipGetLastError());
+        LV_HIP(ctx, hipStreamSynchronize(st));
+    }
     ctx->trajSet = true;
     ctx->triMeshSet = false;     // tessellated on demand (lv_ensure_tube_mesh)
     ctx->triMeshFromTraj = false;
     ctx->triAccelValid = false;
     ctx->aoGlobalFrameNumber = 0;   // VulkanRayTracedAmbientOcclusionPass::setLineData (.cpp:437-460), as lv_set_lines
     ctx->lastFrameViewProjValid = false;
-    return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_set_trajectories(p, positions, attribute, line_offsets, num_lines); });
+    return lv_forward_to_ranks(ctx, [&](lv_ctx* p) {
+        return lv_set_trajectories_with_bands(p, positions, attribute, line_offsets, num_lines, bands);
+    });
+}
+
+int lv_set_trajectories(lv_ctx* ctx, const float* positions, const float* attribute, const uint32_t* line_offsets, uint32_t num_lines) {
+    return lv_set_trajectories_with_bands(ctx, positions, attribute, line_offsets, num_lines, nullptr);
 }
 
 // the triangle tubes of lv_set_trajectories' lines at the current line width / tube_num_subdivisions
@@ -430,8 +644,15 @@ static int lv_tessellate_tubes(lv_ctx* ctx) {
     memset(&P, 0, sizeof(P));
     const int N = std::max(int(ctx->opt.tubeNumSubdivisions), 4);
     if (N > LV_PRISM_MAX_SUBDIV) return lv_fail(ctx, LV_E_INVALID, "tube_num_subdivisions = %d: at most %d on the device tessellator", N, LV_PRISM_MAX_SUBDIV);
-    const float tubeRadius = ctx->opt.lineWidth * 0.5f;
-    P.radius = tubeRadius;
+    // band data (use_ribbons): the elliptic tubes of getLinePassTubeTriangleMeshRenderData with semi-axes band_width / 2 *
+    // min_band_thickness along cross(ribbon, tangent) and band_width / 2 across (host/LineData.cpp:644-649)
+    const bool elliptic = ctx->opt.useRibbons;
+    const float binormalRadius = ctx->opt.bandWidth * 0.5f, normalRadius = binormalRadius * ctx->opt.minBandThickness;
+    const float tubeRadius = elliptic ? normalRadius : ctx->opt.lineWidth * 0.5f;
+    P.elliptic = elliptic ? 1u : 0u;
+    P.radiusT = elliptic ? std::min(normalRadius, binormalRadius) : tubeRadius;
+    P.radiusN = tubeRadius;
+    P.radiusB = elliptic ? binormalRadius : tubeRadius;
     P.n = uint32_t(N);
     P.nLat = uint32_t(N / 2);
     P.capVerts = P.n * (P.nLat - 1u) + 1u;
@@ -445,6 +666,16 @@ static int lv_tessellate_tubes(lv_ctx* ctx) {
             const float tx = -py, ty = px;
             px = px + tangentialFactor * tx; py = py + tangentialFactor * ty;
             px = px * radialFactor; py = py * radialFactor;
+        }
+    }
+    if (elliptic) {   // initGlobalEllipseVertexPositions (host/Tubes.cpp:131-140)
+        for (int i = 0; i < N; i++) {
+            const float t = float(i) / float(N) * kTwoPi;
+            const float cosAngle = std::cos(t), sinAngle = std::sin(t);
+            P.circle[i][0] = normalRadius * cosAngle; P.circle[i][1] = binormalRadius * sinAngle; P.circle[i][2] = 0.0f;
+            const float ex = binormalRadius * cosAngle, ey = normalRadius * sinAngle, ez = 0.0f;
+            const float l = std::sqrt((ex * ex + ey * ey) + ez * ez);
+            P.ellNormal[i][0] = ex / l; P.ellNormal[i][1] = ey / l; P.ellNormal[i][2] = ez / l;
         }
     }
     // unit-sphere points of the cap rings, shared by all caps (CappedTriangleTubesCPU.cpp:57-75,146-164)
@@ -495,15 +726,20 @@ static int lv_tessellate_tubes(lv_ctx* ctx) {
     const float4* rec = (const float4*)ctx->points.ptr;
     const uint32_t* recLine = (const uint32_t*)ctx->trajRecLine.ptr;
     const LvLineRef* lineRef = (const LvLineRef*)ctx->trajLineRef.ptr;
+    const float* ribbon = elliptic ? (const float*)ctx->trajRibbon.ptr : nullptr;
+    const uint32_t* recPoint = (const uint32_t*)ctx->trajRecPoint.ptr;
+    const float* meshRot = ctx->opt.helicityBands ? (const float*)ctx->trajMeshRot.ptr : nullptr;
     if (numRecords) {
-        k_tess_body<<<nblk(uint64_t(numRecords) * P.n), LV_BLOCK, 0, st>>>(rec, recLine, lineRef, lineValid, vOff, iOff, numRecords, P,
-                                                                          (lv_tube_vertex*)ctx->triVerts.ptr, (uint32_t*)ctx->triIdx.ptr);
-        k_tess_points<<<nblk(numRecords), LV_BLOCK, 0, st>>>(rec, recLine, lineRef, numRecords, (float4*)ctx->triPoints.ptr);
+        k_tess_body<<<nblk(uint64_t(numRecords) * P.n), LV_BLOCK, 0, st>>>(rec, recLine, lineRef, lineValid, vOff, iOff, ribbon, recPoint,
+                                                                          numRecords, P, (lv_tube_vertex*)ctx->triVerts.ptr,
+                                                                          (uint32_t*)ctx->triIdx.ptr);
+        k_tess_points<<<nblk(numRecords), LV_BLOCK, 0, st>>>(rec, recLine, lineRef, ribbon, recPoint, meshRot, numRecords,
+                                                             (float4*)ctx->triPoints.ptr);
     }
     if (numLines) {
         const uint64_t slots = 2ull * P.capVerts + 2ull * (P.capIdx / 3u);
         k_tess_caps<<<nblk(uint64_t(numLines) * slots), LV_BLOCK, 0, st>>>((const float*)ctx->trajPos.ptr, off, rec, lineRef, lineValid, vOff, iOff,
-                                                                           numLines, P, capTable, (lv_tube_vertex*)ctx->triVerts.ptr,
+                                                                           numLines, P, capTable, ribbon, recPoint, (lv_tube_vertex*)ctx->triVerts.ptr,
                                                                            (uint32_t*)ctx->triIdx.ptr);
     }
     LV_HIP(ctx, hipEventRecord(ctx->ev[9], st));
@@ -516,6 +752,10 @@ static int lv_tessellate_tubes(lv_ctx* ctx) {
     ctx->triMeshFromTraj = true;
     ctx->triMeshLineWidth = ctx->opt.lineWidth;
     ctx->triMeshSubdivisions = ctx->opt.tubeNumSubdivisions;
+    ctx->triMeshRibbons = ctx->opt.useRibbons;
+    ctx->triMeshHelicity = ctx->opt.helicityBands;
+    ctx->triMeshBandWidth = ctx->opt.bandWidth;
+    ctx->triMeshMinBandThickness = ctx->opt.minBandThickness;
     ctx->triAccelValid = false;
     return LV_OK;
 }
@@ -523,11 +763,15 @@ static int lv_tessellate_tubes(lv_ctx* ctx) {
 int lv_ensure_tube_mesh(lv_ctx* ctx) {
     if (!ctx->trajSet) return LV_OK;                      // meshes of lv_set_tube_triangle_mesh are the caller's
     if (ctx->triMeshSet && !ctx->triMeshFromTraj) return LV_OK;   // the caller replaced the mesh after lv_set_trajectories
-    if (ctx->triMeshSet && ctx->triMeshLineWidth == ctx->opt.lineWidth && ctx->triMeshSubdivisions == ctx->opt.tubeNumSubdivisions)
+    int rc;
+    if ((rc = lv_ensure_line_points(ctx))) return rc;     // also: use_ribbons / rotating_helicity_bands need their arrays
+    const LvOptions& o = ctx->opt;
+    // the cache key of getLinePassTubeTriangleMeshRenderData (host/LineData.cpp:633-636)
+    if (ctx->triMeshSet && ctx->triMeshSubdivisions == o.tubeNumSubdivisions && ctx->triMeshRibbons == o.useRibbons &&
+        ctx->triMeshHelicity == o.helicityBands &&
+        (o.useRibbons ? ctx->triMeshBandWidth == o.bandWidth && ctx->triMeshMinBandThickness == o.minBandThickness
+                      : ctx->triMeshLineWidth == o.lineWidth))
         return LV_OK;
-    if (ctx->opt.useRibbons || ctx->opt.helicityBands)
-        return lv_fail(ctx, LV_E_STATE, "lv_set_trajectories tessellates plain flow lines; band data / rotating helicity bands need "
-                                        "lv_set_lines + lv_set_tube_triangle_mesh (host/LineData.cpp)");
     return lv_tessellate_tubes(ctx);
 }
 
@@ -535,6 +779,8 @@ int lv_get_lines(lv_ctx* ctx, lv_line_point* out_points, uint32_t max_points, ui
                  uint32_t* out_num_points, uint32_t* out_num_segments) {
     if (!ctx) return LV_E_INVALID;
     (void)hipSetDevice(ctx->device);
+    int rc;
+    if ((rc = lv_ensure_line_points(ctx))) return rc;
     if (out_num_points) *out_num_points = ctx->numPoints;
     if (out_num_segments) *out_num_segments = ctx->numSegs;
     if (out_points) {

@@ -2725,6 +2725,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         return lv_fail(ctx, LV_E_INVALID, "rotating_helicity_bands and use_ribbons exclude each other (LineDataFlow.cpp:470,601-604)");
     if (ctx->opt.rtLss && ctx->opt.useRibbons && ctx->opt.ellipticTubes)
         return lv_fail(ctx, LV_E_INVALID, "Elliptic Tubes belong to the AABB geometry mode (VulkanRayTracer.cpp:198), not to Linear Swept Spheres");
+    if ((rc = lv_ensure_line_points(ctx))) return rc;   // lv_set_trajectories' records follow the band / helicity switches
     if (!ctx->accelValid || ctx->accelLineWidth != lv_accel_width(ctx))
         if ((rc = lv_bvh_build(ctx))) return rc;
     const bool needTriangles = (ctx->opt.useAmbientOcclusion && ctx->opt.aoPrebaked) ||
@@ -3130,6 +3131,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
 int lv_frame_trace_rays(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n, float* outT,
                         uint32_t* outSeg, uint32_t* outKind) {
     int rc;
+    if ((rc = lv_ensure_line_points(ctx))) return rc;
     if (!ctx->accelValid || ctx->accelLineWidth != lv_accel_width(ctx))
         if ((rc = lv_bvh_build(ctx))) return rc;
     if (n == 0) return LV_OK;

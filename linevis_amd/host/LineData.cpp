@@ -460,11 +460,41 @@ void LineDataFlow::setTrajectoryData(const Trajectories& newTrajectories, const 
     dirty = true;
 }
 
-// the arrays lv_set_trajectories takes; band data and the rotating helicity bands (ribbon normals / a rotation that runs on across all
-// lines) keep the host-built render data
+// the arrays lv_set_trajectories takes (plain flow lines only: band data and the rotating helicity bands go through the overload below)
 bool LineDataFlow::getTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets) {
     if ((useRibbons && hasBandsData) || getUseRotatingHelicityBands()) return false;
     if (numTotalTrajectoryPoints > 0x03FFFFFFu) return false;
+    copyTrajectoryArrays(positions, attribute, lineOffsets);
+    return true;
+}
+
+// the arrays of lv_set_trajectories_with_bands: + ribbon directions, the helicity attribute and maxHelicity whenever the data has them
+bool LineDataFlow::getTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets,
+                                       std::vector<float>& ribbonDirections, std::vector<float>& helicity, float& maxHelicityOut) {
+    ribbonDirections.clear();
+    helicity.clear();
+    maxHelicityOut = 0.0f;
+    if (numTotalTrajectoryPoints > 0x03FFFFFFu) return false;
+    copyTrajectoryArrays(positions, attribute, lineOffsets);
+    if (hasBandsData) {
+        ribbonDirections.resize(3 * numTotalTrajectoryPoints);
+        for (size_t li = 0; li < trajectories.size() && li < ribbonsDirections.size(); li++) {
+            const size_t n = std::min(trajectories[li].positions.size(), ribbonsDirections[li].size());
+            if (n) memcpy(ribbonDirections.data() + 3 * size_t(lineOffsets[li]), ribbonsDirections[li].data(), n * sizeof(vec3));
+        }
+    }
+    if (hasHelicity) {
+        helicity.resize(numTotalTrajectoryPoints);
+        for (size_t li = 0; li < trajectories.size(); li++) {
+            const size_t n = trajectories[li].positions.size();
+            if (n) memcpy(helicity.data() + lineOffsets[li], trajectories[li].attributes[size_t(helicityAttributeIndex)].data(), n * sizeof(float));
+        }
+        maxHelicityOut = maxHelicity;
+    }
+    return true;
+}
+
+void LineDataFlow::copyTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets) const {
     positions.resize(3 * numTotalTrajectoryPoints);
     attribute.assign(numTotalTrajectoryPoints, 0.0f);
     lineOffsets.assign(trajectories.size() + 1, 0u);
@@ -478,7 +508,6 @@ bool LineDataFlow::getTrajectoryArrays(std::vector<float>& positions, std::vecto
         at += n;
         lineOffsets[li + 1] = uint32_t(at);
     }
-    return true;
 }
 
 size_t LineDataFlow::getNumLineSegments() {

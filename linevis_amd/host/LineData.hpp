@@ -146,6 +146,16 @@ public:
         (void)positions; (void)attribute; (void)lineOffsets;
         return false;
     }
+    /// The same arrays for lv_set_trajectories_with_bands, also for band data and the rotating helicity bands: the ribbon directions
+    /// (3 floats per point; empty without band data), the helicity attribute (1 float per point; empty without one) and maxHelicity --
+    /// filled whenever the data has them, whatever use_ribbons / rotating_helicity_bands say, so that toggling those needs no upload.
+    virtual bool getTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets,
+                                     std::vector<float>& ribbonDirections, std::vector<float>& helicity, float& maxHelicityOut) {
+        ribbonDirections.clear();
+        helicity.clear();
+        maxHelicityOut = 0.0f;
+        return getTrajectoryArrays(positions, attribute, lineOffsets);
+    }
     uint64_t getDataGeneration() const { return dataGeneration; }
 
     /// dataset-side settings keys: attribute, tube_num_subdivisions, use_capped_tubes, use_halos
@@ -214,8 +224,11 @@ public:
     TubeTriangleRenderData getLinePassTubeTriangleMeshRenderData(bool isRasterizer, bool vulkanRayTracing) override;
     std::vector<std::vector<vec3>> getFilteredLines(LineRenderer* lineRenderer) override;
     bool getTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets) override;
+    bool getTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets,
+                             std::vector<float>& ribbonDirections, std::vector<float>& helicity, float& maxHelicityOut) override;
 
 private:
+    void copyTrajectoryArrays(std::vector<float>& positions, std::vector<float>& attribute, std::vector<uint32_t>& lineOffsets) const;
     Trajectories trajectories;
     std::vector<std::vector<vec3>> ribbonsDirections; // LineDataFlow.hpp:160
     bool verticesNormalized = false;

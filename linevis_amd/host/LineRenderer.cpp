@@ -403,32 +403,6 @@ bool LineRenderer::uploadFrameState() {
         // elliptic tubes with USE_BANDS; the ray-entry PPLL of this build gathers the entry hits of the analytic elliptic tubelets)
         const bool bands = lineData->getUseBands();
         const bool elliptic = bands && getUseAnalyticEllipticTubes();
-        // plain flow lines: the trajectories themselves go to HBM (once per data set) and the device writes the line points, the index
-        // pairs and -- whenever a frame needs them at another line width -- the triangle tubes; everything else: host-built render data
-        deviceGeometry = false;
-        if (useDeviceGeometry && !bands && !lineData->getUseRotatingHelicityBands()) {
-            if (uploadedTrajectoryData == lineData.get() && uploadedTrajectoryGeneration == lineData->getDataGeneration()) {
-                deviceGeometry = true;     // only the line width / the tessellation settings changed: nothing to upload
-            } else {
-                std::vector<float> positions, attribute;
-                std::vector<uint32_t> lineOffsets;
-                if (lineData->getTrajectoryArrays(positions, attribute, lineOffsets)) {
-                    if (!check(lv_set_trajectories(ctx, positions.data(), attribute.data(), lineOffsets.data(), uint32_t(lineOffsets.size() - 1)),
-                               "lv_set_trajectories"))
-                        return false;
-                    uploadedTrajectoryData = lineData.get();
-                    uploadedTrajectoryGeneration = lineData->getDataGeneration();
-                    deviceGeometry = true;
-                }
-            }
-        }
-        if (!deviceGeometry) {
-            uploadedTrajectoryData = nullptr;
-            TubeAabbRenderData d = lineData->getLinePassTubeAabbRenderData(false, elliptic);
-            if (!check(lv_set_lines(ctx, d.linePointDataBuffer.data(), uint32_t(d.linePointDataBuffer.size()),
-                                    d.indexBuffer.data(), uint32_t(d.indexBuffer.size() / 2)), "lv_set_lines"))
-                return false;
-        }
         setOption("use_ribbons", bands ? "true" : "false");
         setOption("use_analytic_elliptic_tubes", elliptic ? "true" : "false");
         setOption("thick_bands", LineData::getRenderThickBands() ? "true" : "false");
@@ -460,6 +434,39 @@ bool LineRenderer::uploadFrameState() {
         setOption("use_capped_tubes", lineData->getUseCappedTubesDefine(isRasterizer) ? "true" : "false");
         setOption("use_halos", lineData->getUseHalos() ? "true" : "false");
         setOption("tube_num_subdivisions", std::to_string(lineData->getTubeNumSubdivisions()));
+        // the trajectories themselves go to HBM (once per data set, with the ribbon directions and the helicity attribute when the data has
+        // them) and the device writes the line points, the index pairs and -- whenever a frame needs them at another line width / band
+        // setting -- the triangle tubes; use_device_geometry = false or more than 2^26-1 points: host-built render data.  After the
+        // switches above, so that the records are written once for them.
+        deviceGeometry = false;
+        if (useDeviceGeometry) {
+            if (uploadedTrajectoryData == lineData.get() && uploadedTrajectoryGeneration == lineData->getDataGeneration()) {
+                deviceGeometry = true;     // only the line width / the band / tessellation settings changed: nothing to upload
+            } else {
+                std::vector<float> positions, attribute, ribbons, helicity;
+                std::vector<uint32_t> lineOffsets;
+                float maxHelicity = 0.0f;
+                if (lineData->getTrajectoryArrays(positions, attribute, lineOffsets, ribbons, helicity, maxHelicity)) {
+                    const lv_trajectory_bands b = {ribbons.empty() ? nullptr : ribbons.data(), helicity.empty() ? nullptr : helicity.data(),
+                                                   maxHelicity};
+                    if (!check(lv_set_trajectories_with_bands(ctx, positions.data(), attribute.data(), lineOffsets.data(),
+                                                              uint32_t(lineOffsets.size() - 1),
+                                                              (b.ribbon_directions || b.helicity) ? &b : nullptr),
+                               "lv_set_trajectories_with_bands"))
+                        return false;
+                    uploadedTrajectoryData = lineData.get();
+                    uploadedTrajectoryGeneration = lineData->getDataGeneration();
+                    deviceGeometry = true;
+                }
+            }
+        }
+        if (!deviceGeometry) {
+            uploadedTrajectoryData = nullptr;
+            TubeAabbRenderData d = lineData->getLinePassTubeAabbRenderData(false, elliptic);
+            if (!check(lv_set_lines(ctx, d.linePointDataBuffer.data(), uint32_t(d.linePointDataBuffer.size()),
+                                    d.indexBuffer.data(), uint32_t(d.indexBuffer.size() / 2)), "lv_set_lines"))
+                return false;
+        }
         lineData->setDirty(false);
         linesDirty = false;
         tfDirty = true; // attribute range may have changed with the data

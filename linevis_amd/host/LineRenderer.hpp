@@ -248,7 +248,7 @@ protected:
     bool isRasterizer = false;
     bool dirty = true, reRender = true, internalReRender = false;
     bool tfDirty = true, linesDirty = true, triangleMeshDirty = true;
-    // device geometry (lv_set_trajectories): on by default for plain flow lines; use_device_geometry = false keeps the host-built
+    // device geometry (lv_set_trajectories_with_bands): on by default for flow lines; use_device_geometry = false keeps the host-built
     // render data (build-owned key).  uploadedTrajectory*: which data set's arrays sit in HBM
     bool useDeviceGeometry = true, deviceGeometry = false;
     const LineData* uploadedTrajectoryData = nullptr;

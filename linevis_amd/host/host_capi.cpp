@@ -147,6 +147,24 @@ void lvh_flow_get_trajectories(void* hp, float* positions, float* attributes, ui
     }
     if (lineOffsets) lineOffsets[tr.size()] = off;
 }
+/// LineData::getTrajectoryArrays with the band arrays (what LineRenderer hands to lv_set_trajectories_with_bands): positions n*3, the
+/// selected attribute n, offsets nLines+1, ribbon directions n*3 and helicity n (each written only if the data has it; NULL: skipped);
+/// outFlags: bit 0 = ribbon directions, bit 1 = helicity.  Returns 0 if the data has no device form (more than 2^26-1 points).
+int lvh_flow_get_trajectory_arrays_bands(void* hp, float* positions, float* attribute, uint32_t* lineOffsets, float* ribbons,
+                                         float* helicity, float* outMaxHelicity, uint32_t* outFlags) {
+    std::vector<float> p, a, r, h;
+    std::vector<uint32_t> o;
+    float maxHelicity = 0.0f;
+    if (!static_cast<FlowHandle*>(hp)->data->getTrajectoryArrays(p, a, o, r, h, maxHelicity)) return 0;
+    if (positions && !p.empty()) memcpy(positions, p.data(), p.size() * 4);
+    if (attribute && !a.empty()) memcpy(attribute, a.data(), a.size() * 4);
+    if (lineOffsets) memcpy(lineOffsets, o.data(), o.size() * 4);
+    if (ribbons && !r.empty()) memcpy(ribbons, r.data(), r.size() * 4);
+    if (helicity && !h.empty()) memcpy(helicity, h.data(), h.size() * 4);
+    if (outMaxHelicity) *outMaxHelicity = maxHelicity;
+    if (outFlags) *outFlags = (r.empty() ? 0u : 1u) | (h.empty() ? 0u : 2u);
+    return 1;
+}
 
 /// getLinePassTubeAabbRenderData at the given line width; returns the counts, data fetched with lvh_flow_copy_render_data.
 void lvh_flow_build_render_data(void* hp, float lineWidth, uint32_t* outNumPoints, uint32_t* outNumSegments) {

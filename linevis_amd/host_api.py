@@ -48,6 +48,7 @@ def load():
         "lvh_flow_attribute_range": (None, [vp, vp]),
         "lvh_flow_bounding_box": (None, [vp, vp]),
         "lvh_flow_get_trajectories": (None, [vp, vp, vp, vp]),
+        "lvh_flow_get_trajectory_arrays_bands": (i32, [vp, vp, vp, vp, vp, vp, C.POINTER(f32), C.POINTER(u32)]),
         "lvh_flow_build_render_data": (None, [vp, f32, C.POINTER(u32), C.POINTER(u32)]),
         "lvh_flow_copy_render_data": (None, [vp, vp, vp, vp]),
         "lvh_flow_build_triangle_data": (None, [vp, f32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -251,6 +252,21 @@ class LineDataFlow:
         off = np.empty(l + 1, dtype=np.uint32)
         self.L.lvh_flow_get_trajectories(self.h, _p(pos), _p(att), _p(off))
         return pos, att, off
+
+    def trajectory_arrays_bands(self):
+        """LineData::getTrajectoryArrays with the band arrays (lv_set_trajectories_with_bands' input): dict of positions [P,3], attribute
+        [P], line_offsets [L+1], ribbon_directions [P,3] or None, helicity [P] or None, max_helicity; None if there is no device form."""
+        n, l = self.num_points, self.num_lines
+        pos = np.zeros((n, 3), dtype=np.float32)
+        att = np.zeros(n, dtype=np.float32)
+        off = np.zeros(l + 1, dtype=np.uint32)
+        rib = np.zeros((n, 3), dtype=np.float32)
+        hel = np.zeros(n, dtype=np.float32)
+        mh, flags = C.c_float(), C.c_uint32()
+        if not self.L.lvh_flow_get_trajectory_arrays_bands(self.h, _p(pos), _p(att), _p(off), _p(rib), _p(hel), C.byref(mh), C.byref(flags)):
+            return None
+        return dict(positions=pos, attribute=att, line_offsets=off, ribbon_directions=rib if flags.value & 1 else None,
+                    helicity=hel if flags.value & 2 else None, max_helicity=mh.value)
 
     def tube_aabb_render_data(self, line_width):
         """getLinePassTubeAabbRenderData: (points[48 B records], seg_indices[S,2], aabbs[S,6])."""
