@@ -36,6 +36,9 @@ extern "C" {
 
 /* RenderingMode ids, src/Renderers/RenderingModes.hpp:32-53 */
 #define LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST 2
+/* Multi-Layer Alpha Blending (src/Renderers/OIT/MLABRenderer.cpp) over the fragments of mode 2's rasterised prism; see
+ * mlab_num_layers and lv_mlab_resolve_buffers below */
+#define LV_RENDERING_MODE_MLAB 3
 #define LV_RENDERING_MODE_VULKAN_RAY_TRACER 11
 
 /* struct LinePointDataUnified, src/LineData/LineRenderData.hpp:99-106 -- byte-identical (48 B). */
@@ -241,6 +244,17 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *                                                                       (VulkanRayTracer.cpp:226-278)
  *   use_mlat (multi-layer alpha tracing instead of the transparency loop; either geometry mode), mlat_num_nodes
  *   (power of two in [1, 32], default 8)                                (VulkanRayTracer.cpp:266-275, .hpp:133-134)
+ *   mlab_num_layers: numLayers K of rendering mode 3, 1 ... 64 (default 8)  (MLABRenderer.cpp:133-135,330).  Mode 3 folds,
+ *   per pixel, the fragments mode 2 keeps (alpha >= 0.001; RTAO, depth cues, band data and rotating helicity bands as in mode 2)
+ *   in primitive order -- index-buffer order: segment by segment, triangles 2k, 2k + 1 of a segment -- which is the order of the
+ *   reference's default ordered fragment shader interlock; sync modes 0/1/2 of the reference all give this result (primitive
+ *   order is one of the orders their races can produce; NO_SYNC's lost updates are not reproduced).  Rules this build owns:
+ *   the window depth gl_FragCoord.z is clip.z / clip.w of the fragment's interpolated world position (rows of proj * view in
+ *   one fixed float32 order); a pixel whose alphaOut = 1 - transmittance is 0 shows the background (the reference divides 0 / 0).
+ *   No fragment is dropped: the fragment pool grows (one host synchronisation per mode-3 frame reads what the rasteriser
+ *   needed) and a frame whose pool cannot be allocated, or with a pixel covered by more than 65534 fragments, returns
+ *   LV_E_CAPACITY.  ppll_fragment_source = capsule_entry is LV_E_INVALID in mode 3; ppll_max_num_frags and sorting_mode are
+ *   ignored; the fold is timed as LV_KERNEL_PPLL_RESOLVE / ms_ppll_resolve.
  *   use_capped_tubes, use_halos, tube_num_subdivisions                  (LineData.cpp:87-181)
  *   max_depth_complexity                                                (VulkanRayTracer.hpp:139)
  *   ppll_max_num_frags, ppll_expected_avg_depth_complexity, ppll_tile_width, ppll_tile_height
@@ -346,7 +360,8 @@ int lv_build_accel(lv_ctx* ctx);
 
 /* LineRenderer::render() (LineRenderer.hpp:112) for mode 11 (VulkanRayTracer::render, VulkanRayTracer.cpp:131-154:
  * depth range -> RTAO iterations -> colour pass) or mode 2 (PerPixelLinkedListLineRenderer::render,
- * PerPixelLinkedListLineRenderer.cpp:399-427: clear -> gather -> resolve) restricted to the pixel rectangle
+ * PerPixelLinkedListLineRenderer.cpp:399-427: clear -> gather -> resolve) or mode 3 (MLABRenderer::render: the same
+ * gather, then the fold and resolve of MLAB) restricted to the pixel rectangle
  * [x0, x0+w) x [y0, y0+h) of the viewport.  out: w*h*4 bytes. */
 int lv_render(lv_ctx* ctx, int rendering_mode, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint8_t* out_rgba8);
 int lv_render_device(lv_ctx* ctx, int rendering_mode, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -502,6 +517,13 @@ int lv_ppll_get_buffers(lv_ctx* ctx, uint32_t* out_nodes, uint64_t max_nodes, ui
 int lv_ppll_resolve_buffers(lv_ctx* ctx, const uint32_t* nodes, uint64_t num_nodes, const uint32_t* start_offset,
                             uint64_t num_pixels, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                             uint8_t* out_rgba8);
+/* Test entry point of mode 3's fold (MLABGather.glsl:38-60 in primitive order + MLABResolve.glsl:51-77 + the blend over the
+ * background), the counterpart of lv_ppll_resolve_buffers.  entries = 3 uint32 per fragment {packUnorm4x8(rgb * a, 1 - a), window
+ * depth (float bits), primitive key}; pixel p = y * w + x of the w x h rectangle owns entries [offsets[p], offsets[p + 1])
+ * (offsets: w * h + 1 values from 0 to num_entries) in any order -- they are folded in ascending key order.  Keys are unique within
+ * a pixel and not 0xFFFFFFFF; at most 65535 entries per pixel.  K = mlab_num_layers. */
+int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                            uint32_t h, uint8_t* out_rgba8);
 /* LBVH export for structural tests: compressed 4-wide nodes of 16 uint32/float words (64 B) each -- words 0-2 grid
  * origin xyz, words 3-5 grid scale xyz (floats), words 6-8 qmin x/y/z and words 9-11 qmax x/y/z (byte k = child slot
  * k; decoded plane = origin + q * scale), words 12-15 child references (bit 31 = leaf, 0xFFFFFFFF = empty slot);

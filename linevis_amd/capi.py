@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "linevis_hip.h")
 
 LV_OK = 0
 MODE_PPLL = 2          # RENDERING_MODE_PER_PIXEL_LINKED_LIST, src/Renderers/RenderingModes.hpp:32-53
+MODE_MLAB = 3          # RENDERING_MODE_MLAB (Multi-Layer Alpha Blending over mode 2's fragments)
 MODE_RAY_TRACER = 11   # RENDERING_MODE_VULKAN_RAY_TRACER
 
 LINE_POINT_DTYPE = np.dtype([("linePosition", "<f4", 3), ("lineAttribute", "<f4"),
@@ -102,7 +103,7 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -172,6 +173,7 @@ def load():
         ("lv_get_ao", [vp, vp]),
         ("lv_ppll_get_buffers", [vp, vp, u64, vp, u64, C.POINTER(u32)]),
         ("lv_ppll_resolve_buffers", [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp]),
+        ("lv_mlab_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
         ("lv_set_trajectories", [vp, vp, vp, vp, u32]),
@@ -543,6 +545,17 @@ class Context:
         s = np.ascontiguousarray(start_offset, dtype=np.uint32)
         out = np.empty((h, w, 4), dtype=np.uint8)
         self._ck(self.L.lv_ppll_resolve_buffers(self.h, _p(n), n.shape[0], _p(s), s.shape[0], x0, y0, w, h, _p(out)))
+        return out
+
+    def mlab_resolve(self, entries, offsets, w, h):
+        """Mode 3's fold of caller-supplied runs (lv_mlab_resolve_buffers): entries = (n, 3) uint32 {colour, depth bits, key},
+        pixel p = y * w + x owns entries[offsets[p]:offsets[p + 1]] in any order.  Returns (h, w, 4) uint8."""
+        e = np.ascontiguousarray(entries, dtype=np.uint32).reshape(-1, 3)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if o.shape[0] != w * h + 1:
+            raise ValueError("offsets must hold w * h + 1 values")
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        self._ck(self.L.lv_mlab_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out)))
         return out
 
     def get_accel(self, num_nodes, num_leaves):

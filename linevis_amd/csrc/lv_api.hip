@@ -100,7 +100,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
-            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
+            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
@@ -626,6 +626,10 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // addSliderIntPowerOfTwo("#MLAT Nodes", 1, 32), VulkanRayTracer.cpp:218
         if (!parseUint(value, u) || u == 0 || u > 32 || (u & (u - 1)) != 0) return bad();
         o.mlatNumNodes = u;
+    } else if (k == "mlab_num_layers") {
+        // numLayers of the MLAB renderer (rendering mode 3): ImGui::SliderInt("Num Layers", 1, 64), MLABRenderer.cpp:330
+        if (!parseUint(value, u) || u == 0 || u > 64) return bad();
+        o.mlabNumLayers = u;
     } else if (k == "mlat_record_trace") {
         o.mlatRecordTrace = parseBool(value);
     } else if (k == "mlat_trace_capacity") {
@@ -1281,6 +1285,14 @@ int lv_ppll_resolve_buffers(lv_ctx* ctx, const uint32_t* nodes, uint64_t num_nod
     if ((num_nodes && !nodes) || !start_offset || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
     (void)hipSetDevice(ctx->device);
     return lv_frame_ppll_resolve_only(ctx, nodes, num_nodes, start_offset, num_pixels, x0, y0, w, h, out);
+}
+
+int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                            uint32_t h, uint8_t* out) {
+    if (!ctx) return LV_E_INVALID;
+    if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_mlab_resolve_only(ctx, entries, num_entries, offsets, w, h, out);
 }
 
 int lv_get_accel(lv_ctx* ctx, void* out_nodes, uint64_t max_nodes, uint32_t* out_leaf_segment, uint64_t max_leaves) {

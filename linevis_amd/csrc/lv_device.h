@@ -125,6 +125,8 @@ struct LvDevCounters {
     // k_ao_rays leaf-test diagnostics (collect_stats): tests that found a hit inside the interval, tests the conservative
     // axis-distance pre-test lets through, tests axis + bounding-sphere pre-tests let through
     unsigned long long aoPrimHits, aoPrimMayAxis, aoPrimMayBoth;
+    uint32_t mlabLongPixels;     // MLAB: pixels whose run k_mlab_resolve handed to k_mlab_resolve_long
+    uint32_t mlabSaturated;      // MLAB: 1 when a pixel's 16-bit fragment count saturated (the rasteriser dropped fragments)
 };
 
 struct f3 { float x, y, z; };

@@ -77,6 +77,7 @@ struct LvOptions {
     int rtaoGeometry = 0;                     // rtao_geometry: 0 = auto (the reference's triangle tubes once lv_set_tube_triangle_mesh was called), 1 = capsules, 2 = triangle_tubes
     bool useMlat = false;                     // VulkanRayTracer.hpp:133
     uint32_t mlatNumNodes = 8;                // :134
+    uint32_t mlabNumLayers = 8;               // mlab_num_layers: numLayers of rendering mode 3, 1 ... 64 (MLABRenderer.cpp:133-135,330)
     // EAW denoiser of the RTAO pass (ambient_occlusion_denoiser; AO defaults of createDenoiserObject, Denoiser.cpp:54-62)
     bool eawEnabled = false;
     uint32_t eawIterations = 3;               // eaw_denoiser_iterations (GUI range 0..5, EAWDenoiser.cpp:437)
@@ -229,6 +230,9 @@ struct lv_ctx {
     LvDeviceBuffer prismLeafList;             // raster_prism, sharded frames: segments that can touch the frame's tile list (k_ppll_cull_segments)
     LvDeviceBuffer ppllCoarse;                // raster_prism, sharded frames: 32 x 32-pixel cells that hold requested pixels (k_ppll_mark_tiles)
     LvDeviceBuffer ppllOverflow;              // raster_prism: pixel addresses with more kept fragments than ppllMaxNumFrags (k_ppll_pixel_pass)
+    LvDeviceBuffer mlabLong;                  // mode 3: {pixel address, output index} of the pixels k_mlab_resolve_long folds
+    LvDeviceBuffer mlabStatsSnap;             // mode 3 with collect_stats: the statistics counters before the front end (pool regrowth)
+    uint64_t mlabPoolSlots = 0;               // mode 3: fragment slots the largest frame so far needed (the pool never drops one)
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
     LvDeviceBuffer accum;                     // rgba8 of the previous accumulated frame (full viewport)
@@ -364,6 +368,8 @@ inline void lv_invalidate_bake(lv_ctx* ctx) {
     ctx->bakeGeneration++;
 }
 int lv_frame_depth_range(lv_ctx* ctx);
+int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
+                               uint32_t h, uint8_t* out);
 int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numNodes, const uint32_t* start,
                                uint64_t numPixels, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint8_t* out);
 void lv_fill_uniforms(const lv_ctx* ctx, LvUniforms& U);

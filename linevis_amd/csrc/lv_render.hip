@@ -1121,7 +1121,44 @@ __device__ __forceinline__ uint32_t lv_run_start(const uint32_t* __restrict__ st
 // array, so that every pixel's fragments form one contiguous run in the order the coverage kernel met them.  A fragment the shader
 // discards (alpha < 0.001, :34) or the `kept` rules reject leaves a DEAD entry {0, LV_PPLL_DEAD} that the resolve pass steps over,
 // and is counted in the upper 16 bits of the pixel's count word.  No atomics on the pool, none per kept fragment.
-template <bool STATS, int SHADE = LV_SHADE_PLAIN, int FAST = 0>
+// MLAB (rendering mode 3, MLABGather.glsl:63-91): the entry is 12 B {packUnorm4x8(rgb * a, 1 - a), window depth, primitive key}
+// instead, the key = leafSeg[leaf] << 6 | triangle orders the pixel's fragments as the reference's ordered interlock folds them
+// (index-buffer order: segment by segment, triangles 2k, 2k + 1 of a segment); a discarded fragment is {0, LV_PPLL_DEAD, LV_MLAB_NO_KEY}.
+#define LV_MLAB_NO_KEY 0xFFFFFFFFu
+// window depth gl_FragCoord.z = clip.z / clip.w of a world position: rows z and w of proj * view in lv_clip_rows' order
+__device__ __forceinline__ float lv_window_depth(const LvUniforms& U, f3 p) {
+    float mz[4], mw[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        mz[c] = 0.0f; mw[c] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {   // column-major 4 x 4
+            mz[c] += U.proj[4 * k + 2] * U.view[4 * c + k];
+            mw[c] += U.proj[4 * k + 3] * U.view[4 * c + k];
+        }
+    }
+    const float cz = ((mz[0] * p.x + mz[1] * p.y) + mz[2] * p.z) + mz[3];
+    const float cw = ((mw[0] * p.x + mw[1] * p.y) + mw[2] * p.z) + mw[3];
+    return cz / cw;
+}
+// the interpolated world position of the fragment (leaf, triangle tt) on the viewing ray d: the steps of lv_shade_prism up to I.pos, on
+// the same operands (the normals do not enter the position).  The MLAB instances recompute them (about 0.04 ms of config 4's fragment
+// stage) rather than pass I.pos out of lv_shade_prism: an output argument there changed the code of the mode-2 instances
+// (scheduling of the helicity variants), which must stay as they are.
+__device__ __forceinline__ f3 lv_prism_frag_pos(const LvSceneDev& S, const LvUniforms& U, const float* ringTab, f3 d, uint32_t leaf, uint32_t tt) {
+    const LvPrismDev& R = S.prism;
+    uint32_t pi[2];
+    LvPrismPoint pt[2];
+    lv_prism_frames(S, leaf, S.segs[2 * size_t(leaf)], S.segs[2 * size_t(leaf) + 1], pt, pi);
+    const LvPrismTri T = lv_prism_tri_setup(ringTab, R.n, pt, pi, R.radius, tt);
+    f3 nrm[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) nrm[i] = norm3q<false>(T.dir[i]);
+    const f3 cam = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
+    const LvPrismPlanes pl = lv_prism_planes(R, T, cam, d);
+    return lv_prism_interpolate(T, nrm, pl, d).pos;
+}
+template <bool STATS, int SHADE = LV_SHADE_PLAIN, int FAST = 0, bool MLAB = false>
 __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_SHADE_MIN_WAVES) void k_ppll_shade_prism(const LvUniforms U, const LvSceneDev S,
                                                                    const uint32_t* __restrict__ records, uint2* __restrict__ frags,
                                                                    const uint32_t* __restrict__ pixelOffset,
@@ -1161,11 +1198,25 @@ __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_SHADE_MIN_WAVES) void k_ppll_sha
         if (STATS && kept) hits++;
         const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
         const size_t dst = size_t(lv_run_start(pixelOffset, blockBase, addr)) + rank;
-        if (kept && color.w >= 0.001f) {   // gatherFragment: discard below, LinkedListGather.glsl:34
-            frags[dst] = make_uint2(lv_pack_unorm4x8(color), __float_as_uint(depth));
+        if (kept && color.w >= 0.001f) {   // gatherFragment: discard below, LinkedListGather.glsl:34 (MLABGather.glsl:64)
+            if constexpr (MLAB) {
+                f4 m;   // packUnorm4x8(vec4(color.rgb * color.a, 1.0 - color.a)), MLABGather.glsl:76
+                m.x = color.x * color.w; m.y = color.y * color.w; m.z = color.z * color.w; m.w = 1.0f - color.w;
+                uint32_t* e = reinterpret_cast<uint32_t*>(frags) + 3 * dst;
+                e[0] = lv_pack_unorm4x8(m);
+                e[1] = __float_as_uint(lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt)));
+                e[2] = (S.leafSeg[leaf] << 6) | tt;
+            } else {
+                frags[dst] = make_uint2(lv_pack_unorm4x8(color), __float_as_uint(depth));
+            }
             localSum++;
         } else {
-            frags[dst] = make_uint2(0u, LV_PPLL_DEAD);
+            if constexpr (MLAB) {
+                uint32_t* e = reinterpret_cast<uint32_t*>(frags) + 3 * dst;
+                e[0] = 0u; e[1] = LV_PPLL_DEAD; e[2] = LV_MLAB_NO_KEY;
+            } else {
+                frags[dst] = make_uint2(0u, LV_PPLL_DEAD);
+            }
             atomicAdd(&fragCount[addr], 0x10000u);
             localDead++;
         }
@@ -2039,6 +2090,253 @@ __global__ __launch_bounds__(LV_WAVE) void k_ppll_resolve(const LvUniforms U, co
     }
 }
 
+// ================================================================ MLAB (rendering mode 3)
+// Multi-Layer Alpha Blending [Salvi and Vaidyanathan 2014] as MLABRenderer runs it with its default ordered fragment shader interlock
+// (MLABRenderer.hpp:133-135): every pixel folds its fragments in primitive order into K = numLayers nodes.  Gather, then fold: the
+// fragment stage (k_ppll_shade_prism<..., MLAB = true>) leaves each pixel's fragments as one contiguous run of 12-B entries {colour,
+// window depth, primitive key}; k_mlab_resolve orders a run by key and folds it into K + 1 nodes held in registers -- no K x W x H
+// node buffer and no per-pixel lock.  Runs longer than a lane's LDS share go to k_mlab_resolve_long (one workgroup per pixel).
+#define LV_MLAB_INFINITE 1e30f      // DISTANCE_INFINITE (MLABHeader.glsl)
+#define LV_MLAB_CLEAR 0xFF000000u   // clearPixel's premulColor: rgb 0, transmittance 1 (MLABHeader.glsl:186)
+#ifndef LV_MLAB_LDS
+#define LV_MLAB_LDS 32u             // run entries one lane of k_mlab_resolve orders in LDS (12 B each: 24 KB per wave)
+#endif
+#define LV_MLAB_LONG_BLOCK 256u     // threads of k_mlab_resolve_long
+#define LV_MLAB_LONG_TILE 1024u     // keys per LDS tile of its ranking pass
+
+// K + 1 nodes {depth, premulColor} for K <= C: every loop over the nodes is unrolled with a runtime guard (a runtime index would put
+// the arrays in scratch memory)
+template <int C>
+struct LvMlabNodes {
+    float d[C + 1];
+    uint32_t c[C + 1];
+    __device__ __forceinline__ void clear() {   // clearPixel
+#pragma unroll
+        for (int i = 0; i <= C; i++) { d[i] = LV_MLAB_INFINITE; c[i] = LV_MLAB_CLEAR; }
+    }
+    // loadFragmentNodes (node K = DISTANCE_INFINITE, MLABHeader.glsl:161) + multiLayerAlphaBlending (MLABGather.glsl:38-60)
+    __device__ __forceinline__ void insert(float fd, uint32_t fc, uint32_t K) {
+#pragma unroll
+        for (int i = 0; i <= C; i++) {
+            if (uint32_t(i) == K) d[i] = LV_MLAB_INFINITE;   // (the passes before i = K touched nodes < K only)
+            if (uint32_t(i) <= K && fd <= d[i]) {             // one bubble pass over K + 1 entries
+                const float td = d[i];
+                const uint32_t tc = c[i];
+                d[i] = fd; c[i] = fc;
+                fd = td; fc = tc;
+            }
+        }
+        float dK = LV_MLAB_INFINITE;
+        uint32_t cK = 0u, cP = 0u;
+#pragma unroll
+        for (int i = 0; i <= C; i++) {
+            if (uint32_t(i) == K) { dK = d[i]; cK = c[i]; }
+            if (uint32_t(i) + 1u == K) cP = c[i];
+        }
+        if (dK != LV_MLAB_INFINITE) {   // merge nodes K - 1 and K; the merged node keeps the depth of node K - 1
+            const f4 src = lv_unpack_unorm4x8(cP), dst = lv_unpack_unorm4x8(cK);
+            f4 m;
+            m.x = src.x + dst.x * src.w;
+            m.y = src.y + dst.y * src.w;
+            m.z = src.z + dst.z * src.w;
+            m.w = src.w * dst.w;   // transmittance
+            const uint32_t merged = lv_pack_unorm4x8(m);
+#pragma unroll
+            for (int i = 0; i < C; i++)
+                if (uint32_t(i) + 1u == K) c[i] = merged;
+        }
+    }
+    // MLABResolve.glsl:51-77, then BACK_TO_FRONT_STRAIGHT_ALPHA over the clear colour (MLABRenderer.cpp:78) as mode 2's resolve
+    // writes it; alphaOut = 0 (no fragment, or only fragments whose 1 - a packs to 255) gives the background
+    __device__ __forceinline__ uint32_t resolve(const LvUniforms& U, uint32_t K) const {
+        float col[3] = {0.0f, 0.0f, 0.0f}, tr = 1.0f;
+#pragma unroll
+        for (int i = 0; i < C; i++) {
+            if (uint32_t(i) < K) {
+                const f4 src = lv_unpack_unorm4x8(c[i]);
+                col[0] = col[0] + tr * src.x;
+                col[1] = col[1] + tr * src.y;
+                col[2] = col[2] + tr * src.z;
+                tr *= src.w;
+            }
+        }
+        const float a = 1.0f - tr;
+        f4 r;
+        r.x = U.background[0]; r.y = U.background[1]; r.z = U.background[2]; r.w = U.background[3];
+        if (a > 0.0f) {
+            r.x = (col[0] / a) * a + U.background[0] * (1.0f - a);
+            r.y = (col[1] / a) * a + U.background[1] * (1.0f - a);
+            r.z = (col[2] / a) * a + U.background[2] * (1.0f - a);
+            r.w = a + U.background[3] * (1.0f - a);
+        }
+        return lv_pack_unorm4x8(r);
+    }
+};
+
+// start of a pixel's run: frames address the runs through k_ppll_scan's block bases, lv_mlab_resolve_buffers with absolute offsets
+__device__ __forceinline__ uint32_t lv_mlab_run_start(const uint32_t* __restrict__ startOffset, const uint32_t* __restrict__ blockBase,
+                                                      uint32_t addr) {
+    return blockBase ? lv_run_start(startOffset, blockBase, addr) : startOffset[addr];
+}
+
+// One lane per pixel, one wave per workgroup, the cells and groups of k_ppll_resolve.  The lane copies the live entries of its run
+// into LDS, builds a 4-ary min-heap on the key and folds the entries as it pops them (no early stop).  A run of more than LV_MLAB_LDS
+// entries is appended to longList {pixel address, output index}; k_mlab_resolve_long writes that pixel.  An entry per (tile, pixel)
+// pair -- a tile list may repeat or overlap pixels --: longCap = tiles x tile pixels entries (the append is clamped to it as well).
+template <int C>
+__global__ __launch_bounds__(LV_WAVE) void k_mlab_resolve(const LvUniforms U, const LvTiles T, const uint32_t* __restrict__ frags,
+                                                          const uint32_t* __restrict__ startOffset,
+                                                          const uint32_t* __restrict__ blockBase,
+                                                          const uint32_t* __restrict__ fragCount, uint32_t* __restrict__ out,
+                                                          uint32_t numGroups, uint32_t K, uint2* __restrict__ longList,
+                                                          uint32_t longCap, LvDevCounters* dc) {
+    __shared__ uint32_t s_key[LV_MLAB_LDS][LV_WAVE], s_col[LV_MLAB_LDS][LV_WAVE];
+    __shared__ float s_dep[LV_MLAB_LDS][LV_WAVE];
+    const uint32_t lane = threadIdx.x;
+    uint32_t maxCount = 0u;
+    // hole-based sink of a 4-ary min-heap on the key (keys are unique within a pixel)
+    auto sink = [&](uint32_t x, uint32_t cnt) {
+        const uint32_t k = s_key[x][lane], c = s_col[x][lane];
+        const float dd = s_dep[x][lane];
+        for (;;) {
+            const uint32_t t = 4u * x + 1u;
+            if (t >= cnt) break;
+            uint32_t best = t, bk = s_key[t][lane];
+            for (uint32_t u = 1u; u < 4u; u++)
+                if (t + u < cnt && s_key[t + u][lane] < bk) { best = t + u; bk = s_key[t + u][lane]; }
+            if (k < bk) break;
+            s_key[x][lane] = bk; s_col[x][lane] = s_col[best][lane]; s_dep[x][lane] = s_dep[best][lane];
+            x = best;
+        }
+        s_key[x][lane] = k; s_col[x][lane] = c; s_dep[x][lane] = dd;
+    };
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        const bool inTile = lx < T.tileW && ly < T.tileH;
+        if (!__any(inTile)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        const uint32_t outIndex = (tile * T.tileH + ly) * T.tileW + lx;
+        const bool inView = inTile && x < U.width && y < U.height;
+        bool write = inTile;
+        LvMlabNodes<C> L;
+        L.clear();
+        if (inView) {
+            const uint32_t addr = lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+            const uint32_t v = fragCount[addr];
+            const uint32_t n = v & 0xFFFFu;   // entries of the run; v >> 16 of them are dead
+            maxCount = max(maxCount, n - (v >> 16));
+            if (n > LV_MLAB_LDS) {
+                const uint32_t item = atomicAdd(&dc->mlabLongPixels, 1u);
+                if (item < longCap) longList[item] = make_uint2(addr, outIndex);
+                write = false;
+            } else {
+                const uint32_t* __restrict__ run = frags + 3 * size_t(lv_mlab_run_start(startOffset, blockBase, addr));
+                uint32_t m = 0u;
+                for (uint32_t j = 0u; j < n; j++) {
+                    const uint32_t key = run[3 * j + 2];
+                    if (key == LV_MLAB_NO_KEY) continue;
+                    s_key[m][lane] = key;
+                    s_col[m][lane] = run[3 * j + 0];
+                    s_dep[m][lane] = __uint_as_float(run[3 * j + 1]);
+                    m++;
+                }
+                for (uint32_t i = m > 1u ? (m - 2u) / 4u + 1u : 0u; i > 0u; --i) sink(i - 1u, m);
+                for (uint32_t left = m; left > 0u; --left) {
+                    L.insert(s_dep[0][lane], s_col[0][lane], K);
+                    if (left > 1u) {
+                        s_key[0][lane] = s_key[left - 1u][lane];
+                        s_col[0][lane] = s_col[left - 1u][lane];
+                        s_dep[0][lane] = s_dep[left - 1u][lane];
+                        sink(0u, left - 1u);
+                    }
+                }
+            }
+        }
+        const uint32_t packed = L.resolve(U, K);
+        if (write) out[outIndex] = packed;
+    }
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) maxCount = max(maxCount, (uint32_t)__shfl_xor(maxCount, ofs, 64));
+    if (lane == 0 && maxCount > 0u) atomicMax(&dc->maxDepthComplexity, maxCount);
+}
+
+// The pixels k_mlab_resolve listed, one workgroup each (persistent grid).  Ranking: the rank of a live entry is the number of live
+// keys below its key (dead entries carry LV_MLAB_NO_KEY, above every key), counted against LDS tiles of the run's keys; entry j
+// goes to scratch[run start + rank] -- every entry of the run is read, none is skipped, whatever the run's length.  Then the
+// workgroup stages the ordered run through LDS and one lane folds it.
+template <int C>
+__global__ __launch_bounds__(LV_MLAB_LONG_BLOCK) void k_mlab_resolve_long(const LvUniforms U, const uint32_t* __restrict__ frags,
+                                                                         const uint32_t* __restrict__ startOffset,
+                                                                         const uint32_t* __restrict__ blockBase,
+                                                                         const uint32_t* __restrict__ fragCount,
+                                                                         uint32_t* __restrict__ out, uint32_t K,
+                                                                         const uint2* __restrict__ longList, uint32_t longCap,
+                                                                         uint2* __restrict__ scratch, const LvDevCounters* dc) {
+    __shared__ uint32_t s_tile[LV_MLAB_LONG_TILE];
+    __shared__ uint2 s_ordered[LV_MLAB_LONG_BLOCK];
+    const uint32_t tid = threadIdx.x, count = min(dc->mlabLongPixels, longCap);
+    for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
+        const uint2 li = longList[item];
+        const uint32_t addr = li.x, outIndex = li.y;
+        const uint32_t start = lv_mlab_run_start(startOffset, blockBase, addr);
+        const uint32_t v = fragCount[addr], n = v & 0xFFFFu, live = n - (v >> 16);
+        const uint32_t* __restrict__ run = frags + 3 * size_t(start);
+        for (uint32_t b = 0u; b < n; b += 4u * LV_MLAB_LONG_BLOCK) {
+            uint32_t key[4], rank[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const uint32_t j = b + uint32_t(e) * LV_MLAB_LONG_BLOCK + tid;
+                key[e] = j < n ? run[3 * size_t(j) + 2] : LV_MLAB_NO_KEY;
+            }
+            for (uint32_t t0 = 0u; t0 < n; t0 += LV_MLAB_LONG_TILE) {
+                __syncthreads();
+                for (uint32_t i = tid; i < LV_MLAB_LONG_TILE; i += LV_MLAB_LONG_BLOCK)
+                    s_tile[i] = t0 + i < n ? run[3 * size_t(t0 + i) + 2] : LV_MLAB_NO_KEY;
+                __syncthreads();
+                const uint32_t m = min(LV_MLAB_LONG_TILE, n - t0);
+                for (uint32_t i = 0u; i < m; i++) {
+                    const uint32_t k = s_tile[i];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) rank[e] += k < key[e] ? 1u : 0u;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const uint32_t j = b + uint32_t(e) * LV_MLAB_LONG_BLOCK + tid;
+                if (key[e] != LV_MLAB_NO_KEY && rank[e] < live)
+                    scratch[size_t(start) + rank[e]] = make_uint2(run[3 * size_t(j) + 0], run[3 * size_t(j) + 1]);
+            }
+        }
+        __syncthreads();
+        LvMlabNodes<C> L;
+        L.clear();
+        for (uint32_t b = 0u; b < live; b += LV_MLAB_LONG_BLOCK) {
+            if (b + tid < live) s_ordered[tid] = scratch[size_t(start) + b + tid];
+            __syncthreads();
+            if (tid == 0u) {
+                const uint32_t m = min(LV_MLAB_LONG_BLOCK, live - b);
+                for (uint32_t i = 0u; i < m; i++) L.insert(__uint_as_float(s_ordered[i].y), s_ordered[i].x, K);
+            }
+            __syncthreads();
+        }
+        if (tid == 0u) out[outIndex] = L.resolve(U, K);
+    }
+}
+
+// Frames of mode 3: 1 in dc->mlabSaturated when a pixel's 16-bit record count saturated (the rasteriser then drops its fragments)
+__global__ __launch_bounds__(LV_BLOCK) void k_mlab_check_counts(const uint4* __restrict__ fragCount, size_t n4, LvDevCounters* dc) {
+    const size_t i = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (i >= n4) return;
+    const uint4 v = fragCount[i];
+    const bool full = (v.x & 0xFFFFu) == 0xFFFFu || (v.y & 0xFFFFu) == 0xFFFFu || (v.z & 0xFFFFu) == 0xFFFFu || (v.w & 0xFFFFu) == 0xFFFFu;
+    if (full) atomicOr(&dc->mlabSaturated, 1u);
+}
+
 // ================================================================ depth range
 __global__ __launch_bounds__(LV_BLOCK) void k_depth_minmax(const LvUniforms U, const lv_line_point* __restrict__ points,
                                                            uint32_t numPoints, LvDevCounters* dc) {
@@ -2698,10 +2996,45 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
     return LV_OK;
 }
 
+// The fold of mode 3 over the runs in ctx->ppllNodes / ppllStart (+ blockBase) / ppllCount: K = mlab_num_layers picks the node
+// capacity C in {8, 16, 32, 64}; scratch holds the ordered long runs (>= the fragment array's entries x 8 B)
+static int lv_mlab_fold(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, uint32_t numGroups, const uint32_t* blockBase, uint32_t* out,
+                        uint2* scratch, LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    // the long list holds one entry per (tile, pixel) pair of the tile list: repeated or overlapping tiles list a pixel more than once
+    const uint64_t longCap64 = uint64_t(T.numTiles) * T.tileW * T.tileH;
+    if (longCap64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t longCap = uint32_t(longCap64);
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->mlabLong, size_t(longCap) * 8))) return rc;
+    const uint32_t K = ctx->opt.mlabNumLayers;
+    const uint32_t* frags = (const uint32_t*)ctx->ppllNodes.ptr;
+    const uint32_t* so = (const uint32_t*)ctx->ppllStart.ptr;
+    const uint32_t* cnt = (const uint32_t*)ctx->ppllCount.ptr;
+    uint2* const longList = (uint2*)ctx->mlabLong.ptr;
+    const uint32_t longGrid = uint32_t(ctx->numCUs) * 2u;
+#define LV_LAUNCH_MLAB(C)                                                                                                     \
+    do {                                                                                                                       \
+        k_mlab_resolve<C><<<numGroups, LV_WAVE, 0, st>>>(U, T, frags, so, blockBase, cnt, out, numGroups, K, longList, longCap, dc); \
+        k_mlab_resolve_long<C><<<longGrid, LV_MLAB_LONG_BLOCK, 0, st>>>(U, frags, so, blockBase, cnt, out, K, longList, longCap,   \
+                                                                        scratch, dc);                                           \
+    } while (0)
+    if (K <= 8u) LV_LAUNCH_MLAB(8);
+    else if (K <= 16u) LV_LAUNCH_MLAB(16);
+    else if (K <= 32u) LV_LAUNCH_MLAB(32);
+    else LV_LAUNCH_MLAB(64);
+#undef LV_LAUNCH_MLAB
+    return LV_OK;
+}
+
 int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
                     uint32_t tileH, void* outDevice) {
-    if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST)
-        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL)", mode);
+    if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB)
+        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB)", mode);
+    const bool mlab = mode == LV_RENDERING_MODE_MLAB;
+    if (mlab && ctx->opt.ppllFragmentSource == 1)
+        return lv_fail(ctx, LV_E_INVALID, "mode 3 (MLAB) folds the fragments of the rasterised prism: ppll_fragment_source = "
+                                          "capsule_entry is not supported");
     if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_set_camera has not been called");
     if (!ctx->tf.ptr || ctx->tfN == 0) return lv_fail(ctx, LV_E_STATE, "lv_set_transfer_function has not been called");
     if (!ctx->points.ptr && ctx->numSegs) return lv_fail(ctx, LV_E_STATE, "lv_set_lines has not been called");
@@ -2713,7 +3046,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         // tubes (rtao_geometry = triangle_tubes); MLAT over the same geometries; the PPLL gather over the analytic tubelets /
         // capsules.  The static prebaker bakes band data on the elliptic cross-section against the elliptic triangle tubes the caller
         // passed (VulkanAmbientOcclusionBaker.glsl:200-257) and is looked up with the band's own angle (phiLine of the tubelets).
-        if (mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && (ctx->opt.rtTriangleMesh || ctx->opt.rtLss))
+        if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab) && (ctx->opt.rtTriangleMesh || ctx->opt.rtLss))
             return lv_fail(ctx, LV_E_INVALID, "use_ribbons: the PPLL gather of band data runs over the analytic tubelets / capsules "
                                               "(geometry_mode \"AABBs\")");
         if (ctx->opt.rtTriangleMesh && ctx->opt.ellipticTubes)
@@ -2890,7 +3223,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[7], st));
     // The colour pass of a raster_prism frame with the segment rasteriser has no tile kernel: only its resolve pass could use the
     // dispatch order, and measured it does not (config 4: 0.134 ms as numbered, 0.145 ms heaviest first + 11 us for k_group_order)
-    if (mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && lv_ppll_prism_source(ctx) && !ctx->opt.ppllPrismLbvhWalk &&
+    if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab) && lv_ppll_prism_source(ctx) && !ctx->opt.ppllPrismLbvhWalk &&
         !ctx->groupOrderSorted) {
         T.groupOrder = nullptr;
         T.groupCost = nullptr;
@@ -2974,15 +3307,30 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         if (uint64_t(gridTiles) * numSlices > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
         // physical pool = the reference's linkedListSize + the tail every wave of the gather may leave unused in its last
         // chunk of node slots (k_ppll_gather / k_ppll_raster_prism), so that the effective capacity is never below the reference's
-        uint64_t poolSlots64 = uint64_t(U.ppllLinkedListSize) +
-                               (segmentRaster ? uint64_t(rasterGrid) * (LV_BLOCK / LV_WAVE) * LV_PRISM_RASTER_CHUNK
-                                              : uint64_t(gridTiles) * numSlices * (LV_BLOCK / LV_WAVE) * LV_PPLL_CHUNK);
+        const uint64_t chunkSlack = segmentRaster ? uint64_t(rasterGrid) * (LV_BLOCK / LV_WAVE) * LV_PRISM_RASTER_CHUNK
+                                                  : uint64_t(gridTiles) * numSlices * (LV_BLOCK / LV_WAVE) * LV_PPLL_CHUNK;
+        uint64_t poolSlots64 = uint64_t(U.ppllLinkedListSize) + chunkSlack;
+        // MLAB drops no fragment (the reference's MLAB has no pool): it starts from the linkedListSize of the options (no chunk slack:
+        // a frame that needs more slots grows the pool below) or from what the largest mode-3 frame so far needed
+        if (mlab) poolSlots64 = std::max<uint64_t>(U.ppllLinkedListSize, ctx->mlabPoolSlots);
         if (poolSlots64 > 0xFFFFFFF0ull) poolSlots64 = 0xFFFFFFF0ull; // node indices are 32 bit
-        const uint32_t poolSlots = uint32_t(poolSlots64);
-        if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(poolSlots) * 12))) return rc;
+        uint32_t poolSlots = uint32_t(poolSlots64);
+        bool mlabGrown = false;
+        // a regrown mode-3 frame runs its front end twice: the statistics it adds (rays, nodes, prims, hits; k_ppll_clear resets the
+        // fragment counters) are restored from this copy before the second run.  (The per-kernel timers keep both runs' launches.)
+        const bool mlabStatsSnap = mlab && stats;
+        if (mlabStatsSnap) {
+            if ((rc = lv_buf_reserve(ctx, ctx->mlabStatsSnap, 4 * sizeof(unsigned long long)))) return rc;
+            LV_HIP(ctx, hipMemcpyAsync(ctx->mlabStatsSnap.ptr, &dc->rays, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+        }
+    mlab_regrow:   // (mode 3: the rasteriser needed more record slots than the pool held -- grown, and the front end runs again)
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(poolSlots) * 12)))
+            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "MLAB: cannot allocate a fragment pool of %u entries", poolSlots) : rc;
         // raster_prism: the coverage kernel writes 12-B records {pixel, leaf | triangle, rank} into a pool of their own; ppllNodes then
-        // holds the fragment array (8-B {colour, depth} entries, one contiguous run per pixel), ppllStart the runs' offsets
-        if (prismSource && (rc = lv_buf_reserve(ctx, ctx->prismRecords, size_t(poolSlots) * 12))) return rc;
+        // holds the fragment array (8-B {colour, depth} entries, one contiguous run per pixel -- 12-B {colour, window depth, key} in
+        // mode 3), ppllStart the runs' offsets
+        if (prismSource && (rc = lv_buf_reserve(ctx, ctx->prismRecords, size_t(poolSlots) * 12)))
+            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "MLAB: cannot allocate a record pool of %u entries", poolSlots) : rc;
         ctx->ppllArrays = prismSource;
         uint32_t* gatherPool = prismSource ? (uint32_t*)ctx->prismRecords.ptr : (uint32_t*)ctx->ppllNodes.ptr;
         const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
@@ -3051,6 +3399,32 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         }
 #undef LV_LAUNCH_GATHER2
 #undef LV_LAUNCH_GATHER
+        if (mlab) {
+            // mode 3 drops no fragment and never returns a silently wrong frame: read back what the rasteriser reserved and whether a
+            // pixel's 16-bit record count saturated -- one host synchronisation per mode-3 frame -- and grow the pool and run the
+            // front end again when it held too few slots
+            k_mlab_check_counts<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>((const uint4*)ctx->ppllCount.ptr, padded4, dc);
+            if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
+            volatile uint32_t* pin = ctx->pinned + 14;   // (words 14, 15 of the pinned block)
+            LV_HIP(ctx, hipMemcpyAsync((void*)pin, &dc->fragAlloc, 4, hipMemcpyDeviceToHost, st));
+            LV_HIP(ctx, hipMemcpyAsync((void*)(pin + 1), &dc->mlabSaturated, 4, hipMemcpyDeviceToHost, st));
+            LV_HIP(ctx, hipStreamSynchronize(st));
+            const uint32_t need = pin[0], saturated = pin[1];
+            if (saturated)
+                return lv_fail(ctx, LV_E_CAPACITY, "MLAB: a pixel is covered by more than 65534 fragments (16-bit per-pixel count)");
+            if (need > poolSlots) {
+                const uint64_t grown = uint64_t(need) + chunkSlack;
+                if (mlabGrown || grown > 0xFFFFFFF0ull)
+                    return lv_fail(ctx, LV_E_CAPACITY, "MLAB: the frame needs %llu fragment slots (pool: %u)",
+                                   (unsigned long long)grown, poolSlots);
+                poolSlots = uint32_t(grown);
+                ctx->mlabPoolSlots = poolSlots;
+                mlabGrown = true;
+                if (mlabStatsSnap)
+                    LV_HIP(ctx, hipMemcpyAsync(&dc->rays, ctx->mlabStatsSnap.ptr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+                goto mlab_regrow;
+            }
+        }
         uint32_t* blockBase = nullptr;
         if (prismSource) {
             // per-pixel counts -> offsets of the pixels' runs + the list of the pixels with more records than the sort arrays hold
@@ -3060,34 +3434,44 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             if ((rc = lv_buf_reserve(ctx, ctx->scanTemp, (2 * size_t(scanBlocks) + 1) * 4))) return rc;
             uint32_t* blockTotals = (uint32_t*)ctx->scanTemp.ptr;
             blockBase = blockTotals + scanBlocks;
+            // (mode 3 keeps every fragment: no pixel goes on the list)
             k_ppll_scan<<<scanBlocks, LV_BLOCK, 0, st>>>((const uint32_t*)ctx->ppllCount.ptr, (uint32_t*)ctx->ppllStart.ptr, numAddr,
-                                                        blockTotals, U.ppllMaxNumFrags, (uint32_t*)ctx->ppllOverflow.ptr, dc);
+                                                        blockTotals, mlab ? 0xFFFFFFFFu : U.ppllMaxNumFrags,
+                                                        (uint32_t*)ctx->ppllOverflow.ptr, dc);
             k_ppll_scan_bases<<<1, LV_BLOCK, 0, st>>>(blockTotals, blockBase, scanBlocks);
             ctx->ppllScanBlocks = scanBlocks;
             const uint32_t shadeGrid = uint32_t(ctx->numCUs) * LV_PRISM_SHADE_BLOCKS_PER_CU;
-#define LV_LAUNCH_SHADE(ST)                                                                                                     \
+#define LV_LAUNCH_SHADE(ST, ML)                                                                                                 \
     if (S.prism.bands)                                                                                                          \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_BANDS><<<shadeGrid, LV_BLOCK, 0, st>>>(         \
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_BANDS, 0, ML><<<shadeGrid, LV_BLOCK, 0, st>>>(  \
             U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
             blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)));                                                         \
     else if (U.useHelicityBands)                                                                                                \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_HELICITY><<<shadeGrid, LV_BLOCK, 0, st>>>(      \
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_HELICITY, 0, ML><<<shadeGrid, LV_BLOCK, 0, st>>>( \
             U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
             blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)));                                                         \
     else                                                                                                                        \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST><<<shadeGrid, LV_BLOCK, 0, st>>>(                         \
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_PLAIN, 0, ML><<<shadeGrid, LV_BLOCK, 0, st>>>(  \
+            U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
+            blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)))
+#define LV_LAUNCH_SHADE_FAST(ML)                                                                                                \
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<false, LV_SHADE_PLAIN, 2, ML><<<shadeGrid, LV_BLOCK, 0, st>>>( \
             U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
             blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)))
             // shading_numerics = fast: the plain-tube fragment stage with the raster colour (the only variant whose alpha cannot follow
             // the halo coordinate); every other variant keeps the exact arithmetic
-            if (ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour)
-                LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<false, LV_SHADE_PLAIN, 2><<<shadeGrid, LV_BLOCK, 0, st>>>(
-                        U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,
-                        blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)));
-            else if (stats) LV_LAUNCH_SHADE(true); else LV_LAUNCH_SHADE(false);
+            const bool fastShade = ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
+            if (mlab) {
+                if (fastShade) LV_LAUNCH_SHADE_FAST(true);
+                else if (stats) LV_LAUNCH_SHADE(true, true); else LV_LAUNCH_SHADE(false, true);
+            } else {
+                if (fastShade) LV_LAUNCH_SHADE_FAST(false);
+                else if (stats) LV_LAUNCH_SHADE(true, false); else LV_LAUNCH_SHADE(false, false);
+            }
+#undef LV_LAUNCH_SHADE_FAST
 #undef LV_LAUNCH_SHADE
             // the listed pixels: their nearest ppllMaxNumFrags fragments to the front of the run
-            k_ppll_select_nearest<<<uint32_t(ctx->numCUs) * 16u, LV_WAVE, 0, st>>>(
+            if (!mlab) k_ppll_select_nearest<<<uint32_t(ctx->numCUs) * 16u, LV_WAVE, 0, st>>>(
                     U, (uint2*)ctx->ppllNodes.ptr, (uint2*)ctx->prismRecords.ptr, (const uint32_t*)ctx->ppllStart.ptr, blockBase,
                     (const uint32_t*)ctx->ppllCount.ptr, (const uint32_t*)ctx->ppllOverflow.ptr, dc);
         }
@@ -3097,6 +3481,16 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         const uint64_t groups64 = uint64_t(numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;   // 8 x 8 cells of the 64 x 64 groups
         if (groups64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
         const uint32_t numGroups = uint32_t(groups64);
+        if (mlab) {
+            // the fold: k_mlab_resolve, then the pixels with long runs (k_mlab_resolve_long); both in the LV_KERNEL_PPLL_RESOLVE slot
+            const bool timed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RESOLVE) & 1u) != 0u;
+            if (timed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 0), st));
+            if ((rc = lv_mlab_fold(ctx, U, T, numGroups, blockBase, out, (uint2*)ctx->prismRecords.ptr, dc))) return rc;
+            if (timed) {
+                LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 1), st));
+                ctx->kernelLaunches[LV_KERNEL_PPLL_RESOLVE]++;
+            }
+        } else {
         const size_t ldsBytes = size_t(U.ppllMaxNumFrags) * LV_WAVE * 8;
 #define LV_LAUNCH_RESOLVE(LDS, PQ, GRID, BYTES, SCRATCH)                                                                        \
     do {                                                                                                                       \
@@ -3119,6 +3513,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             else LV_LAUNCH_RESOLVE(false, false, grid, 0, (uint32_t*)ctx->ppllScratch.ptr);
         }
 #undef LV_LAUNCH_RESOLVE
+        }
     }
     LV_HIP(ctx, hipGetLastError());
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[3], st));
@@ -3205,6 +3600,66 @@ int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numN
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(w) * h * 4, hipMemcpyDeviceToHost, st));
     LV_HIP(ctx, hipStreamSynchronize(st));
+    return LV_OK;
+}
+
+// lv_mlab_resolve_buffers: the caller's runs (pixel p of the w x h rectangle owns entries [offsets[p], offsets[p + 1])) through the
+// fold of mode 3 -- k_mlab_resolve with row-major addressing (one 1 x 1-pixel tiling, absolute run starts) and k_mlab_resolve_long
+int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
+                               uint32_t h, uint8_t* out) {
+    const uint64_t numPixels = uint64_t(w) * h;
+    if (numEntries >= 0xFFFFFFF0ull || numPixels > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
+    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
+    std::vector<uint32_t> start(numPixels), count(numPixels);
+    for (uint64_t p = 0; p < numPixels; p++) {
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > 0xFFFFu)
+            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most 65535 entries per pixel", (unsigned long long)p);
+        start[p] = uint32_t(offsets[p]);
+        count[p] = uint32_t(offsets[p + 1] - offsets[p]);
+    }
+    for (uint64_t i = 0; i < numEntries; i++)
+        if (entries[3 * i + 2] == LV_MLAB_NO_KEY) return lv_fail(ctx, LV_E_INVALID, "entry %llu: key 0xFFFFFFFF is reserved", (unsigned long long)i);
+    {   // keys unique within a pixel: the ordering ranks by key (a repeated key would leave a rank unwritten)
+        std::vector<uint32_t> keys;
+        for (uint64_t p = 0; p < numPixels; p++) {
+            keys.clear();
+            for (uint64_t i = offsets[p]; i < offsets[p + 1]; i++) keys.push_back(entries[3 * i + 2]);
+            std::sort(keys.begin(), keys.end());
+            if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
+                return lv_fail(ctx, LV_E_INVALID, "pixel %llu: keys must be unique within a pixel", (unsigned long long)p);
+        }
+    }
+    LvUniforms U;
+    lv_fill_uniforms(ctx, U);
+    U.width = w; U.height = h;
+    U.ppllTileW = 1u; U.ppllTileH = 1u; U.ppllPaddedW = w; U.ppllPaddedH = h;   // address = y * w + x
+    hipStream_t st = ctx->stream;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(numEntries ? numEntries : 1) * 12))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, size_t(numEntries ? numEntries : 1) * 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, size_t(numPixels) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
+    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 12, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    const uint32_t txy[2] = {0u, 0u};
+    ctx->tilesUploaded = false; // tilesDev is overwritten below
+    LV_HIP(ctx, hipMemcpyAsync(ctx->tilesDev.ptr, txy, 8, hipMemcpyHostToDevice, st));
+    LvTiles T{};
+    T.tilesXY = (const uint32_t*)ctx->tilesDev.ptr;
+    T.numTiles = 1; T.tileW = w; T.tileH = h;
+    T.blocksX = ((w + 63u) / 64u) * 4u; T.blocksY = ((h + 63u) / 64u) * 4u;
+    const uint32_t numGroups = (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;
+    if ((rc = lv_mlab_fold(ctx, U, T, numGroups, nullptr, (uint32_t*)ctx->outDev.ptr, (uint2*)ctx->ppllScratch.ptr,
+                           (LvDevCounters*)ctx->counters.ptr)))
+        return rc;
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(numPixels) * 4, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));   // (also: start / count are host vectors of this call)
     return LV_OK;
 }
 

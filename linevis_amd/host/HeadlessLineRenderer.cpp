@@ -29,6 +29,8 @@ void HeadlessLineRenderer::createRenderer(RenderingMode mode) {
     lineRenderer.reset(); // one context at a time: the old plugin releases its device memory first
     if (mode == RENDERING_MODE_PER_PIXEL_LINKED_LIST)
         lineRenderer.reset(new HipPerPixelLinkedListLineRenderer(&sceneData, transferFunctionWindow));
+    else if (mode == RENDERING_MODE_MLAB)
+        lineRenderer.reset(new HipMLABRenderer(&sceneData, transferFunctionWindow));
     else
         lineRenderer.reset(new HipRayTracer(&sceneData, transferFunctionWindow));
     lineRenderer->initialize();

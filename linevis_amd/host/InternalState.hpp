@@ -57,6 +57,24 @@ inline void getTestModesVulkanRayTracing(std::vector<InternalState>& states, Int
     states.push_back(state);
 }
 
+/// getTestModesMlab, src/Utils/InternalState.cpp:60-87: the four synchronisation states of the MLAB renderer (rendering mode 3).
+/// syncMode: 0 = NO_SYNC, 1 = SYNC_FRAGMENT_SHADER_INTERLOCK, 2 = SYNC_SPINLOCK (SyncMode.hpp:38-40).  Not part of getTestModes().
+inline void getTestModesMlab(std::vector<InternalState>& states, InternalState state) {
+    state.renderingMode = 3;
+    state.name = "MLAB (No Sync)";
+    state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"syncMode", "0"}});
+    states.push_back(state);
+    state.name = "MLAB (Spinlock)";
+    state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"syncMode", "2"}});
+    states.push_back(state);
+    state.name = "MLAB (Unordered Interlock)";
+    state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"syncMode", "1"}, {"useOrderedFragmentShaderInterlock", "false"}});
+    states.push_back(state);
+    state.name = "MLAB (Ordered Interlock)";
+    state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"syncMode", "1"}, {"useOrderedFragmentShaderInterlock", "true"}});
+    states.push_back(state);
+}
+
 /// The hot-path subset of getTestModes() (InternalState.cpp:641-644 -> getTestModesOIT, :149-214): 1920 x 1080, PPLL + the ray tracer
 /// states, every state twice for the error measure.
 inline std::vector<InternalState> getTestModes(bool runStatesTwoTimesForErrorMeasure = true) {

@@ -678,6 +678,42 @@ bool HipPerPixelLinkedListLineRenderer::setNewSettings(const SettingsMap& settin
     return r;
 }
 
+HipMLABRenderer::HipMLABRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Multi-Layer Alpha Blending Renderer", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipMLABRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipMLABRenderer::setNewState(const InternalState& newState) {
+    currentStateName = newState.name;
+    newState.rendererSettings.getValueOpt("numLayers", numLayers);
+    newState.rendererSettings.getValueOpt("useOrderedFragmentShaderInterlock", useOrderedFragmentShaderInterlock);
+    newState.rendererSettings.getValueOpt("syncMode", syncMode);
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipMLABRenderer::render() {
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    setOption("mlab_num_layers", std::to_string(numLayers));
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_MLAB); // clear -> gather -> fold and resolve
+}
+
+bool HipMLABRenderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    settings.getValueOpt("numLayers", numLayers);
+    for (const char* key : {"ppll_expected_avg_depth_complexity", "ppll_tile_width", "ppll_tile_height", "ppll_fragment_source",
+                            "ppll_fragment_colour", "ppll_prism_rasteriser"}) {
+        std::string s;
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
 void HipPerPixelLinkedListLineRenderer::computeStatistics(uint64_t& totalNumFragments, uint32_t& maxComplexity) {
     lv_stats s = getStatistics();
     totalNumFragments = s.fragments;

@@ -25,6 +25,7 @@ namespace lv {
 enum RenderingMode : int32_t {
     RENDERING_MODE_NONE = -1,
     RENDERING_MODE_PER_PIXEL_LINKED_LIST = 2,
+    RENDERING_MODE_MLAB = 3,
     RENDERING_MODE_VULKAN_RAY_TRACER = 11,
 };
 
@@ -321,6 +322,31 @@ public:
 
 private:
     std::string currentStateName;
+};
+
+/// "Multi-Layer Alpha Blending" plugin (src/Renderers/OIT/MLABRenderer.hpp) re-hosted on HIP: the fragments of the PPLL plugin's
+/// rasterised prism folded per pixel in primitive order into numLayers nodes (rendering mode 3).
+class HipMLABRenderer : public LineRenderer {
+public:
+    HipMLABRenderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_MLAB; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    /// MLABRenderer::setNewState (MLABRenderer.cpp:133-159): numLayers, syncMode, useOrderedFragmentShaderInterlock.  Every sync
+    /// mode folds in primitive order here (the order of the ordered interlock, one of the orders the others can produce).
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    bool setNewSettings(const SettingsMap& settings) override;
+    bool getUseAnalyticEllipticTubes() const override { return true; }
+    int getNumLayers() const { return numLayers; }
+    int getSyncMode() const { return syncMode; }
+    bool getUseOrderedFragmentShaderInterlock() const { return useOrderedFragmentShaderInterlock; }
+
+private:
+    std::string currentStateName;
+    int numLayers = 8;                              // MLABRenderer.hpp:133
+    int syncMode = 1;                               // SYNC_FRAGMENT_SHADER_INTERLOCK (SyncMode.hpp:38-40), .hpp:134
+    bool useOrderedFragmentShaderInterlock = true;  // .hpp:135
 };
 
 } // namespace lv

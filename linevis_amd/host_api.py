@@ -80,6 +80,9 @@ def load():
         "lvh_renderer_set_state": (None, [vp, cp, i32, C.POINTER(cp), C.POINTER(cp), u32, C.POINTER(cp), C.POINTER(cp), u32, i32, i32, i32, i32]),
         "lvh_test_modes_count": (u32, [i32]),
         "lvh_test_mode": (u32, [i32, u32, vp, u32]),
+        "lvh_test_modes_mlab_count": (u32, []),
+        "lvh_test_mode_mlab": (u32, [u32, vp, u32]),
+        "lvh_renderer_mlab_state": (i32, [vp, vp]),
         "lvh_renderer_destroy": (None, [vp]),
         "lvh_renderer_set_resolution": (None, [vp, u32, u32]),
         "lvh_renderer_set_line_data": (None, [vp, vp, i32]),
@@ -476,8 +479,27 @@ def get_test_modes(twice=True):
     return out
 
 
+def _parse_test_mode(text):
+    lines = text.split("\n")
+    settings = dict(l.split("=", 1) for l in lines[4:] if "=" in l)
+    return (lines[0], int(lines[1]), (int(lines[2]), int(lines[3])), settings)
+
+
+def get_test_modes_mlab():
+    """The four states of the MLAB renderer (lv::getTestModesMlab = InternalState.cpp:60-87), same tuple form as get_test_modes;
+    not part of get_test_modes."""
+    L = load()
+    out = []
+    for i in range(L.lvh_test_modes_mlab_count()):
+        n = L.lvh_test_mode_mlab(i, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        L.lvh_test_mode_mlab(i, buf, n + 1)
+        out.append(_parse_test_mode(buf.value.decode()))
+    return out
+
+
 class HeadlessLineRenderer:
-    """lv::HeadlessLineRenderer: fixed-camera harness around one renderer plugin (mode 11 or 2)."""
+    """lv::HeadlessLineRenderer: fixed-camera harness around one renderer plugin (mode 11, 2 or 3)."""
 
     def __init__(self, mode=capi.MODE_RAY_TRACER, device=0, devices=None, transport="rccl"):
         """devices = [d0, d1, ...]: the plugin drives one context per device (SceneData::deviceOrdinals -> lv_create_multi)."""
@@ -568,6 +590,13 @@ class HeadlessLineRenderer:
     @property
     def rendering_mode(self):
         return int(self.L.lvh_renderer_rendering_mode(self.h))
+
+    def mlab_state(self):
+        """{numLayers, syncMode, useOrderedFragmentShaderInterlock} of the mode-3 plugin (None for the other plugins)."""
+        v = np.zeros(3, dtype=np.int32)
+        if self.L.lvh_renderer_mlab_state(self.h, _p(v)) != 0:
+            return None
+        return {"numLayers": int(v[0]), "syncMode": int(v[1]), "useOrderedFragmentShaderInterlock": bool(v[2])}
 
     def needs_re_render(self):
         return bool(self.L.lvh_renderer_needs_re_render(self.h))
