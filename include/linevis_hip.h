@@ -220,7 +220,25 @@ int lv_set_transfer_function(lv_ctx* ctx, const float* rgba, uint32_t n, float a
 int lv_set_twist_line_texture(lv_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height);
 
 /* SceneData camera + viewport (src/Renderers/SceneData.hpp:49-85) and LineRenderer::onResolutionChanged
- * (LineRenderer.hpp:127); inverses are taken inside as LineData::updateVulkanUniformBuffers does (LineData.cpp:1290-1291). */
+ * (LineRenderer.hpp:127); inverses are taken inside as LineData::updateVulkanUniformBuffers does (LineData.cpp:1290-1291).
+ * Matrices are float32, column-major (flat index = column * 4 + row).
+ *
+ * What the kernels' camera arithmetic covers, and the tests exercise (tests/cameras.py):
+ *   view  rigid (rotation + translation, any roll, any target, the eye anywhere -- also inside the data set), looking down -z_view;
+ *         last row 0 0 0 1.  An affine view that is not rigid is accepted, but distances (depth cues, near / far, AO radius) are then
+ *         no longer world distances.
+ *   proj  perspective with clip.w = -z_view (last row 0 0 -1 0), depth in 0..1; proj[5] < 0 puts image row 0 at the top (the
+ *         convention the frames are compared in).  proj[0] and proj[5] are free: any field of view, and non-square pixels (an aspect
+ *         other than width / height).  Lens shift (proj[8], proj[9] != 0: off-centre frusta of tiled and stereo embedders) is covered,
+ *         the conservative screen bounds of the sharded PPLL take it into account.  The other entries of rows 0 and 1 are assumed
+ *         zero by those bounds.
+ *   near_dist / far_dist   the planes proj was built from: fragments of modes 2 / 3 are kept iff near_dist <= -z_view <= far_dist and
+ *         the depth range of the depth cues is clamped to them.  far_dist / near_dist up to 1e7 is covered.
+ *   fov_y  the vertical field of view proj was built from (halo / outline widths in pixels).
+ * LV_E_INVALID, with the previous camera and viewport left in force, for: a non-finite entry or scalar; a view or projection whose
+ * determinant is zero, non-finite or below 1e-5 of the product of its column norms (numerically singular); a view whose last row is not
+ * 0 0 0 1; a projection whose last row is not 0 0 -1 0 (an orthographic one in particular: rays start at the camera position);
+ * near_dist <= 0; far_dist <= near_dist; fov_y outside (0, pi).  A multi-device handle answers for all its ranks. */
 int lv_set_camera(lv_ctx* ctx, const float view[16], const float proj[16], float fov_y, float near_dist,
                   float far_dist, uint32_t viewport_width, uint32_t viewport_height);
 

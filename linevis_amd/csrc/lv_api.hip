@@ -48,7 +48,7 @@ void lv_mat4_mul(const float* A, const float* B, float* out) {
     memcpy(out, r, sizeof r);
 }
 
-void lv_mat4_inverse(const float* m, float* inv) {
+float lv_mat4_inverse(const float* m, float* inv) {
     float c00 = m[10] * m[15] - m[14] * m[11];
     float c02 = m[6] * m[15] - m[14] * m[7];
     float c03 = m[6] * m[11] - m[10] * m[7];
@@ -91,6 +91,18 @@ void lv_mat4_inverse(const float* m, float* inv) {
     inv[4] = i10 * r;  inv[5] = i11 * r;  inv[6] = i12 * r;  inv[7] = i13 * r;
     inv[8] = i20 * r;  inv[9] = i21 * r;  inv[10] = i22 * r; inv[11] = i23 * r;
     inv[12] = i30 * r; inv[13] = i31 * r; inv[14] = i32 * r; inv[15] = i33 * r;
+    return det;
+}
+
+// lv_set_camera's admission test of one matrix: finite entries, and a determinant that is not lost in the rounding of its own
+// cofactor expansion -- |det| against Hadamard's bound (the product of the column norms), which makes the test independent of the
+// scale of the columns (near / far = 0.001 / 10000 gives a ratio of 0.7, a rigid view matrix 1)
+static bool lv_mat4_invertible(const float* m, const float* inv, float det) {
+    float hadamard = 1.0f;
+    for (int c = 0; c < 4; c++) hadamard *= sqrtf(((m[4 * c] * m[4 * c] + m[4 * c + 1] * m[4 * c + 1]) + m[4 * c + 2] * m[4 * c + 2]) + m[4 * c + 3] * m[4 * c + 3]);
+    for (int i = 0; i < 16; i++)
+        if (!std::isfinite(m[i]) || !std::isfinite(inv[i])) return false;
+    return std::isfinite(det) && std::isfinite(hadamard) && fabsf(det) > 1e-5f * hadamard;
 }
 
 // every device buffer a context owns: freed by lv_destroy, summed by lv_get_stats (device_bytes)
@@ -432,10 +444,23 @@ int lv_set_camera(lv_ctx* ctx, const float view[16], const float proj[16], float
     if (!view || !proj || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "invalid camera / viewport");
     // (pixel coordinates travel as 16-bit pairs through the wave-local queues and the PPLL fragment records)
     if (w > 0xFFFFu || h > 0xFFFFu) return lv_fail(ctx, LV_E_CAPACITY, "viewport %u x %u: at most 65535 pixels per side", w, h);
+    // what the kernels' camera arithmetic covers (include/linevis_hip.h); a rejected call leaves the previous camera in force
+    if (!(std::isfinite(fov_y) && fov_y > 0.0f && fov_y < 3.14159265f)) return lv_fail(ctx, LV_E_INVALID, "fov_y must lie in (0, pi)");
+    if (!(std::isfinite(near_dist) && std::isfinite(far_dist) && near_dist > 0.0f && far_dist > near_dist))
+        return lv_fail(ctx, LV_E_INVALID, "clip distances must satisfy 0 < near_dist < far_dist < infinity");
+    float invView[16], invProj[16];
+    const float detView = lv_mat4_inverse(view, invView), detProj = lv_mat4_inverse(proj, invProj);
+    if (!lv_mat4_invertible(view, invView, detView)) return lv_fail(ctx, LV_E_INVALID, "view matrix is not finite or singular");
+    if (!lv_mat4_invertible(proj, invProj, detProj)) return lv_fail(ctx, LV_E_INVALID, "projection matrix is not finite or singular");
+    if (view[3] != 0.0f || view[7] != 0.0f || view[11] != 0.0f || view[15] != 1.0f)
+        return lv_fail(ctx, LV_E_INVALID, "view matrix is not affine (last row must be 0 0 0 1)");
+    // rays start at the camera position and clip.w is taken for the view-space distance: a perspective projection with w = -z_view
+    if (proj[3] != 0.0f || proj[7] != 0.0f || proj[11] != -1.0f || proj[15] != 0.0f)
+        return lv_fail(ctx, LV_E_INVALID, "projection is not a perspective projection with clip.w = -z_view (last row must be 0 0 -1 0)");
     memcpy(ctx->view, view, 64);
     memcpy(ctx->proj, proj, 64);
-    lv_mat4_inverse(ctx->view, ctx->invView);
-    lv_mat4_inverse(ctx->proj, ctx->invProj);
+    memcpy(ctx->invView, invView, 64);
+    memcpy(ctx->invProj, invProj, 64);
     ctx->fovY = fov_y;
     ctx->nearDist = near_dist;
     ctx->farDist = far_dist;

@@ -383,5 +383,5 @@ int lv_flow_set_grid(lv_ctx* ctx, const float* vectorField, uint32_t xs, uint32_
 int lv_flow_trace(lv_ctx* ctx, const float* seeds, uint32_t numSeeds, const lv_streamline_settings* settings);
 int lv_flow_trace_max_helicity_first(lv_ctx* ctx, const float* helicityField, const lv_streamline_settings* settings,
                                      const lv_helicity_seeding_settings* seeding);
-void lv_mat4_inverse(const float* m, float* inv);
+float lv_mat4_inverse(const float* m, float* inv);   // returns the determinant
 void lv_mat4_mul(const float* A, const float* B, float* out);

@@ -1541,8 +1541,9 @@ __global__ __launch_bounds__(LV_BLOCK) void k_ppll_cull_segments(const LvUniform
                 const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
                 const float sx = (ccx / cw + 1.0f) * halfW, sy = (ccy / cw + 1.0f) * halfH;
                 // |d screen| <= f r / (w - r) (1 + |x / w|) for a point within r of the centre: tangent of the off-axis angle from the
-                // centre's own clip coordinates, 25 % and 2 pixels on top
-                const float tanOff = fabsf(ccx / cw) / fabsf(U.proj[0]) + fabsf(ccy / cw) / fabsf(U.proj[5]);
+                // centre's own clip coordinates, 25 % and 2 pixels on top.  With a lens shift (proj[8], proj[9] != 0: clip.x = proj[0] x
+                // + proj[8] z) the view-space tangent is (ndc + shift) / proj[0]; bounded by the sum of the magnitudes (adds 0 without)
+                const float tanOff = (fabsf(ccx / cw) + fabsf(U.proj[8])) / fabsf(U.proj[0]) + (fabsf(ccy / cw) + fabsf(U.proj[9])) / fabsf(U.proj[5]);
                 const float rp = 1.25f * (1.0f + tanOff) * R.radius * fmaxf(fabsf(U.proj[0]) * halfW, fabsf(U.proj[5]) * halfH) / (cw - R.radius) + 2.0f;
                 lo[0] = fminf(lo[0], sx - rp); hi[0] = fmaxf(hi[0], sx + rp); lo[1] = fminf(lo[1], sy - rp); hi[1] = fmaxf(hi[1], sy + rp);
             }

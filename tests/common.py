@@ -10,6 +10,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from linevis_amd import camera, scenes, transfer_function as tfm  # noqa: E402
+from linevis_amd.camera import default_camera  # noqa: E402
 from oracle import lvo  # noqa: E402
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
@@ -23,13 +24,16 @@ class Case:
     """A scene + camera + settings, convertible to oracle params and to lv_set_option calls."""
 
     def __init__(self, points, seg, tf, width, height, line_width, camera_pos=camera.DEFAULT_POSITION,
-                 background=(1.0, 1.0, 1.0, 1.0), **settings):
+                 background=(1.0, 1.0, 1.0, 1.0), camera=None, **settings):
         self.points = np.ascontiguousarray(points, dtype=lvo.LINE_POINT_DTYPE)
         self.seg = np.ascontiguousarray(seg, dtype=np.uint32).reshape(-1, 2)
         self.tf = np.ascontiguousarray(tf, dtype=np.float32).reshape(-1, 4)
         self.width, self.height = int(width), int(height)
         self.line_width = float(np.float32(line_width))
-        self.view, self.proj, self.fovy, self.near, self.far = camera.default_camera(width, height, camera_pos)
+        self.view, self.proj, self.fovy, self.near, self.far = default_camera(width, height, camera_pos)
+        if camera is not None:       # a camera description of tests/cameras.py (or its name) instead of the default camera
+            import cameras
+            cameras.apply_camera(self, camera)
         self.background = tuple(float(x) for x in background)
         # reference SettingsMap keys (LineRenderer.cpp:433-498, VulkanRayTracer.cpp:226-278, ...)
         self.settings = dict(settings)

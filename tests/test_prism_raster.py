@@ -68,9 +68,12 @@ def triangles64(c, n_sub):
     return seg, out
 
 
-def screen_space_rasteriser(c, P, n_sub, tile=None):
+def screen_space_rasteriser(c, P, n_sub, tile=None, near_far=None, behind_camera=False):
     """Independent float64 rasteriser; returns dict pixel -> list of fragments (seg, tri, weights(3), margin) where margin = the
-    smallest normalised screen-space barycentric (how far inside the triangle the pixel centre lies)."""
+    smallest normalised screen-space barycentric (how far inside the triangle the pixel centre lies).
+    near_far = (near, far): the fragment stage's acceptance near <= -z_view <= far of the interpolated position (float64); a fragment
+    within 1e-5 (relative) of a plane is returned with margin 0 (either answer).  behind_camera: triangles with a vertex on or behind
+    the camera plane (clip.w <= 0) have no screen-space triangle; they are rasterised in homogeneous coordinates instead of skipped."""
     W, H = c.width, c.height
     view = np.asarray(c.view, np.float64).reshape(4, 4).T
     proj = np.asarray(c.proj, np.float64).reshape(4, 4).T
@@ -89,11 +92,38 @@ def screen_space_rasteriser(c, P, n_sub, tile=None):
             V = np.array([pos[p, k] for p, k in zip(pi, ki)])
             S = np.array([win[p, k] for p, k in zip(pi, ki)])
             wc = np.array([clip[p, k, 3] for p, k in zip(pi, ki)])
-            if np.any(wc <= 0):
-                continue                                   # (no test scene reaches behind the camera)
+            if np.any(wc <= 0) and not behind_camera:
+                continue                                   # (the default camera's test scenes do not reach behind the camera)
             # front side = where the outward geometric normal points (both triangles of the pattern wind the same way)
             g = np.cross(V[1] - V[0], V[2] - V[0])
             if np.dot(g, cam - V[0]) <= 0:
+                continue
+            zv = V @ view[2, :3] + view[2, 3]              # view-space z of the vertices (near / far acceptance)
+
+            def accept(wts):
+                """margin factor of the near / far acceptance: None = outside, 0.0 = within 1e-5 of a plane, 1.0 = inside"""
+                if near_far is None:
+                    return 1.0
+                d = -float(wts @ zv)
+                if any(abs(d - pl) <= 1e-5 * pl for pl in near_far):
+                    return 0.0
+                return 1.0 if near_far[0] <= d <= near_far[1] else None
+            if np.any(wc <= 0):
+                # homogeneous rasterisation: lambda = M^-1 (px, py, 1) with the columns (x_win * w, y_win * w, w) of the vertices are
+                # the clip-space barycentrics of the point of the triangle's plane seen through the pixel, scaled to clip.w = 1;
+                # it lies inside the triangle (and in front of the camera) iff all three are >= 0
+                ci = np.array([clip[p, k] for p, k in zip(pi, ki)])
+                M = np.stack([(ci[:, 0] + ci[:, 3]) * 0.5 * W, (ci[:, 1] + ci[:, 3]) * 0.5 * H, ci[:, 3]])
+                if abs(np.linalg.det(M)) < 1e-300:
+                    continue
+                Mi = np.linalg.inv(M)
+                ys, xs = np.mgrid[y0:y0 + h, x0:x0 + w]
+                lam = np.stack([xs.ravel() + 0.5, ys.ravel() + 0.5, np.ones(xs.size)], 1) @ Mi.T
+                for j in np.nonzero((lam >= 0).all(axis=1))[0]:
+                    wts = lam[j] / lam[j].sum()
+                    f = accept(wts)
+                    if f is not None:
+                        frags.setdefault((int(xs.ravel()[j]), int(ys.ravel()[j])), []).append((s, tt, wts, float(wts.min()) * f))
                 continue
             lo = np.floor(S.min(0) - 0.5).astype(int)
             hi = np.ceil(S.max(0) - 0.5).astype(int)
@@ -107,7 +137,9 @@ def screen_space_rasteriser(c, P, n_sub, tile=None):
                     if a.min() < 0:
                         continue
                     pw = a / wc
-                    frags.setdefault((px, py), []).append((s, tt, pw / pw.sum(), float(a.min())))
+                    f = accept(pw / pw.sum())
+                    if f is not None:
+                        frags.setdefault((px, py), []).append((s, tt, pw / pw.sum(), float(a.min()) * f))
     return frags, pos, nrm, cam
 
 
