@@ -39,6 +39,9 @@ extern "C" {
 /* Multi-Layer Alpha Blending (src/Renderers/OIT/MLABRenderer.cpp) over the fragments of mode 2's rasterised prism; see
  * mlab_num_layers and lv_mlab_resolve_buffers below */
 #define LV_RENDERING_MODE_MLAB 3
+/* Moment-based order-independent transparency (src/Renderers/OIT/MBOITRenderer.cpp) with power moments stored as float32, over the
+ * fragments of mode 2's rasterised prism; see mboit_num_moments and lv_mboit_resolve_buffers below */
+#define LV_RENDERING_MODE_MBOIT 6
 #define LV_RENDERING_MODE_VULKAN_RAY_TRACER 11
 
 /* struct LinePointDataUnified, src/LineData/LineRenderData.hpp:99-106 -- byte-identical (48 B). */
@@ -111,6 +114,9 @@ typedef struct lv_stats {
     uint32_t num_tri_nodes;        /* 64-byte nodes of the triangle LBVH */
     uint32_t tri_leaf_bytes;       /* leaf data per leaf of the triangle LBVH as built: 64 = a pair record (triangle_leaf_records =
                                     * pairs), else 48 x triangle_leaf_size; 0 before the build */
+    uint32_t mboit_degenerate_pixels; /* mode 6, collect_stats: pixels with b_0 over the threshold that show the background because
+                                       * every fragment's transmittance reconstructed to 0 or NaN (a_sum == 0); one count per
+                                       * (tile, pixel) pair of the tile list */
 } lv_stats;
 
 #define LV_KERNEL_AO_PRIMARY 0
@@ -273,6 +279,21 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   needed) and a frame whose pool cannot be allocated, or with a pixel covered by more than 65534 fragments, returns
  *   LV_E_CAPACITY.  ppll_fragment_source = capsule_entry is LV_E_INVALID in mode 3; ppll_max_num_frags and sorting_mode are
  *   ignored; the fold is timed as LV_KERNEL_PPLL_RESOLVE / ms_ppll_resolve.
+ *   mboit_num_moments: 4 | 6 | 8 power moments of rendering mode 6 (default 4)   (MBOITRenderer.cpp:41-45).  Mode 6 sweeps, per
+ *   pixel, ALL fragments the fragment stage of mode 2 produces (the alpha < 0.001 discard of modes 2 and 3 is not MBOIT's; its own
+ *   rules are transmittance > 0.9999999 per fragment in the moment pass and b_0 < 0.00100050033 per pixel) twice: power moments of
+ *   the absorbance over the log-warped view depth, then per fragment the reconstructed transmittance and the colour sums, then the
+ *   blend over the background.  Rules this build owns: the view depth is row z of the view matrix applied to the
+ *   fragment's interpolated world position in one fixed float32 order; the log depth range is computed from the eight corners of
+ *   the line points' box with the build's log; per-pixel sums are sums of 64-bit fixed-point terms rint(term * 2^36) (|term|
+ *   saturates at 1024), so the frame does not depend on the order of the fragments; log / exp / atan2 / sin / cos are the build's
+ *   fixed float32 definitions and fma() is fused; a pixel whose colour weight sum is 0 although b_0 is over the threshold (the
+ *   reconstruction degenerated: typically a single fragment with the default bias) shows the background and is counted in
+ *   lv_stats.mboit_degenerate_pixels.  Pool, LV_E_CAPACITY, capsule_entry and the timer slot as mlab_num_layers above.
+ *   mboit_overestimation: overestimationBeta in [0, 1] (default 0.1)    (MBOITRenderer.cpp:45,609)
+ *   mboit_moment_bias: "auto" (default; 5e-7 / 5e-6 / 5e-5 for 4 / 6 / 8 moments, MBOITRenderer.cpp:136-145) or a float in (0, 0.1]
+ *   mboit_use_power_moments ("true" only), mboit_pixel_format ("Float" only): trigonometric moments and the 16-bit quantised
+ *   storage are not built; "false" / "UNORM" return LV_E_INVALID
  *   use_capped_tubes, use_halos, tube_num_subdivisions                  (LineData.cpp:87-181)
  *   max_depth_complexity                                                (VulkanRayTracer.hpp:139)
  *   ppll_max_num_frags, ppll_expected_avg_depth_complexity, ppll_tile_width, ppll_tile_height
@@ -379,7 +400,8 @@ int lv_build_accel(lv_ctx* ctx);
 /* LineRenderer::render() (LineRenderer.hpp:112) for mode 11 (VulkanRayTracer::render, VulkanRayTracer.cpp:131-154:
  * depth range -> RTAO iterations -> colour pass) or mode 2 (PerPixelLinkedListLineRenderer::render,
  * PerPixelLinkedListLineRenderer.cpp:399-427: clear -> gather -> resolve) or mode 3 (MLABRenderer::render: the same
- * gather, then the fold and resolve of MLAB) restricted to the pixel rectangle
+ * gather, then the fold and resolve of MLAB) or mode 6 (MBOITRenderer::render, MBOITRenderer.cpp:472-482: depth range -> the
+ * same gather -> moments, reconstruction and blend) restricted to the pixel rectangle
  * [x0, x0+w) x [y0, y0+h) of the viewport.  out: w*h*4 bytes. */
 int lv_render(lv_ctx* ctx, int rendering_mode, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint8_t* out_rgba8);
 int lv_render_device(lv_ctx* ctx, int rendering_mode, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -542,6 +564,13 @@ int lv_ppll_resolve_buffers(lv_ctx* ctx, const uint32_t* nodes, uint64_t num_nod
  * a pixel and not 0xFFFFFFFF; at most 65535 entries per pixel.  K = mlab_num_layers. */
 int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                             uint32_t h, uint8_t* out_rgba8);
+/* Test entry point of mode 6's two sweeps (MBOITPass1.glsl + MomentOIT.glsl generateMoments, MBOITPass2.glsl + resolveMoments,
+ * MBOITBlend.glsl and the blend over the background).  entries = 5 uint32 per fragment: the float bits of {r, g, b, a, view depth}
+ * (depth bits 0xFFFFFFFF are reserved); pixel p = y * w + x owns entries [offsets[p], offsets[p + 1]) in any order, at most 65534
+ * per pixel.  N = mboit_num_moments; overestimation and bias from the options.  out_moments (may be NULL): w * h * (1 + N)
+ * floats, b_0 then the normalised b_1 ... b_N of each pixel, zeros where b_0 is under the threshold. */
+int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                             uint32_t h, float log_depth_min, float log_depth_max, float* out_moments, uint8_t* out_rgba8);
 /* LBVH export for structural tests: compressed 4-wide nodes of 16 uint32/float words (64 B) each -- words 0-2 grid
  * origin xyz, words 3-5 grid scale xyz (floats), words 6-8 qmin x/y/z and words 9-11 qmax x/y/z (byte k = child slot
  * k; decoded plane = origin + q * scale), words 12-15 child references (bit 31 = leaf, 0xFFFFFFFF = empty slot);

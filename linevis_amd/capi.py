@@ -16,6 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "linevis_hip.h")
 LV_OK = 0
 MODE_PPLL = 2          # RENDERING_MODE_PER_PIXEL_LINKED_LIST, src/Renderers/RenderingModes.hpp:32-53
 MODE_MLAB = 3          # RENDERING_MODE_MLAB (Multi-Layer Alpha Blending over mode 2's fragments)
+MODE_MBOIT = 6         # RENDERING_MODE_MBOIT (moment-based OIT, power moments as float32, over mode 2's fragments)
 MODE_RAY_TRACER = 11   # RENDERING_MODE_VULKAN_RAY_TRACER
 
 LINE_POINT_DTYPE = np.dtype([("linePosition", "<f4", 3), ("lineAttribute", "<f4"),
@@ -43,7 +44,7 @@ class Stats(C.Structure):
                 ("ppll_pool_nodes", C.c_uint64), ("ao_prim_hits", C.c_uint64), ("ao_prim_may_axis", C.c_uint64),
                 ("ao_prim_may_both", C.c_uint64),
                 ("ms_tri_accel_build", C.c_float), ("ms_tessellate", C.c_float), ("ms_line_points", C.c_float),
-                ("num_tri_nodes", C.c_uint32), ("tri_leaf_bytes", C.c_uint32)]
+                ("num_tri_nodes", C.c_uint32), ("tri_leaf_bytes", C.c_uint32), ("mboit_degenerate_pixels", C.c_uint32)]
 
     def as_dict(self):
         d = {}
@@ -103,7 +104,7 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -174,6 +175,7 @@ def load():
         ("lv_ppll_get_buffers", [vp, vp, u64, vp, u64, C.POINTER(u32)]),
         ("lv_ppll_resolve_buffers", [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp]),
         ("lv_mlab_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp]),
+        ("lv_mboit_resolve_buffers", [vp, vp, u64, vp, u32, u32, C.c_float, C.c_float, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
         ("lv_set_trajectories", [vp, vp, vp, vp, u32]),
@@ -557,6 +559,21 @@ class Context:
         out = np.empty((h, w, 4), dtype=np.uint8)
         self._ck(self.L.lv_mlab_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out)))
         return out
+
+    def mboit_resolve(self, entries, offsets, w, h, log_depth_min, log_depth_max, num_moments=4):
+        """Mode 6's two sweeps over caller-supplied runs (lv_mboit_resolve_buffers) with mboit_num_moments = num_moments: entries =
+        (n, 5) float32 {r, g, b, a, view depth}, pixel p = y * w + x owns entries[offsets[p]:offsets[p + 1]] in any order.
+        Returns ((h, w, 4) uint8, (h, w, 1 + num_moments) float32: b_0 and the normalised moments)."""
+        self.set_option("mboit_num_moments", int(num_moments))
+        e = np.ascontiguousarray(entries, dtype=np.float32).reshape(-1, 5)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if o.shape[0] != w * h + 1:
+            raise ValueError("offsets must hold w * h + 1 values")
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        mom = np.zeros((h, w, 1 + int(num_moments)), dtype=np.float32)
+        self._ck(self.L.lv_mboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, float(log_depth_min), float(log_depth_max),
+                                                 _p(mom), _p(out)))
+        return out, mom
 
     def get_accel(self, num_nodes, num_leaves):
         nodes = np.zeros((max(num_nodes, 1), 16), dtype=np.uint32)

@@ -655,6 +655,26 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // numLayers of the MLAB renderer (rendering mode 3): ImGui::SliderInt("Num Layers", 1, 64), MLABRenderer.cpp:330
         if (!parseUint(value, u) || u == 0 || u > 64) return bad();
         o.mlabNumLayers = u;
+    } else if (k == "mboit_num_moments") {
+        // numMoments of the MBOIT renderer (rendering mode 6): the combo box offers 4, 6 and 8 (MBOITRenderer.cpp:41,560-566)
+        if (!parseUint(value, u) || (u != 4 && u != 6 && u != 8)) return bad();
+        o.mboitNumMoments = u;
+    } else if (k == "mboit_overestimation") {
+        // overestimationBeta: ImGui::SliderFloat("Overestimation", 0.0f, 1.0f), MBOITRenderer.cpp:609
+        if (!parseFloat(value, f) || !(f >= 0.0f && f <= 1.0f)) return bad();
+        o.mboitOverestimation = f;
+    } else if (k == "mboit_moment_bias") {
+        if (strcmp(value, "auto") == 0) o.mboitMomentBias = 0.0f;
+        else {
+            if (!parseFloat(value, f) || !(f > 0.0f && f <= 0.1f)) return bad();
+            o.mboitMomentBias = f;
+        }
+    } else if (k == "mboit_use_power_moments") {
+        if (strcmp(value, "true") != 0 && strcmp(value, "1") != 0)
+            return lv_fail(ctx, LV_E_INVALID, "mboit_use_power_moments = '%s': trigonometric moments are not built (power moments only)", value);
+    } else if (k == "mboit_pixel_format") {
+        if (strcmp(value, "Float") != 0)
+            return lv_fail(ctx, LV_E_INVALID, "mboit_pixel_format = '%s': the 16-bit quantised (UNORM) moment storage is not built (Float only)", value);
     } else if (k == "mlat_record_trace") {
         o.mlatRecordTrace = parseBool(value);
     } else if (k == "mlat_trace_capacity") {
@@ -941,6 +961,7 @@ static int lv_get_stats_impl(lv_ctx* ctx, lv_stats* out, bool aggregate) {
         s.ao_prim_hits = hc.aoPrimHits;
         s.ao_prim_may_axis = hc.aoPrimMayAxis;
         s.ao_prim_may_both = hc.aoPrimMayBoth;
+        s.mboit_degenerate_pixels = hc.mboitDegenerate;
         for (int k = 0; k < 3; k++) { s.ao_phase_iterations[k] = hc.aoPhaseIters[k]; s.ao_phase_lanes[k] = hc.aoPhaseLanes[k]; }
     }
     for (int k = 0; k < 8; k++) { s.ms_kernel_avg[k] = 0.0f; s.kernel_launches[k] = 0; }
@@ -970,6 +991,7 @@ static int lv_get_stats_impl(lv_ctx* ctx, lv_stats* out, bool aggregate) {
         out->ao_rays_traced += ps.ao_rays_traced; out->ao_nodes_visited += ps.ao_nodes_visited; out->ao_prims_tested += ps.ao_prims_tested;
         out->ao_prim_hits += ps.ao_prim_hits; out->ao_prim_may_axis += ps.ao_prim_may_axis; out->ao_prim_may_both += ps.ao_prim_may_both;
         out->max_depth_complexity = ps.max_depth_complexity > out->max_depth_complexity ? ps.max_depth_complexity : out->max_depth_complexity;
+        out->mboit_degenerate_pixels += ps.mboit_degenerate_pixels;
         out->device_bytes += ps.device_bytes;
     }
     (void)hipSetDevice(ctx->device);
@@ -1318,6 +1340,14 @@ int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_e
     if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
     (void)hipSetDevice(ctx->device);
     return lv_frame_mlab_resolve_only(ctx, entries, num_entries, offsets, w, h, out);
+}
+
+int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                             uint32_t h, float log_depth_min, float log_depth_max, float* out_moments, uint8_t* out) {
+    if (!ctx) return LV_E_INVALID;
+    if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_mboit_resolve_only(ctx, entries, num_entries, offsets, w, h, log_depth_min, log_depth_max, out_moments, out);
 }
 
 int lv_get_accel(lv_ctx* ctx, void* out_nodes, uint64_t max_nodes, uint32_t* out_leaf_segment, uint64_t max_leaves) {

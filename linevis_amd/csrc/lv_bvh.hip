@@ -1391,6 +1391,7 @@ int lv_bvh_build(lv_ctx* ctx) {
     const uint32_t n = ctx->numSegs;
     hipStream_t st = ctx->stream;
     ctx->accelValid = false;
+    ctx->mboitBoxValid = false;   // (every change of the line points comes through here before the next frame)
     ctx->bvhDepth = 0;
     ctx->numNodes = 0;
     if (n == 0) {

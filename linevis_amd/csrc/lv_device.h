@@ -125,8 +125,10 @@ struct LvDevCounters {
     // k_ao_rays leaf-test diagnostics (collect_stats): tests that found a hit inside the interval, tests the conservative
     // axis-distance pre-test lets through, tests axis + bounding-sphere pre-tests let through
     unsigned long long aoPrimHits, aoPrimMayAxis, aoPrimMayBoth;
-    uint32_t mlabLongPixels;     // MLAB: pixels whose run k_mlab_resolve handed to k_mlab_resolve_long
-    uint32_t mlabSaturated;      // MLAB: 1 when a pixel's 16-bit fragment count saturated (the rasteriser dropped fragments)
+    uint32_t mlabLongPixels;     // MLAB: pixels whose run k_mlab_resolve handed to k_mlab_resolve_long (MBOIT: k_mboit_resolve / _long)
+    uint32_t mlabSaturated;      // MLAB, MBOIT: 1 when a pixel's 16-bit fragment count saturated (the rasteriser dropped fragments)
+    uint32_t mboitDegenerate;    // MBOIT (collect_stats): pixels with b_0 over the threshold that end as background (a_sum == 0)
+    uint32_t mboitBoxOrd[6];     // MBOIT: lv_f2ord of max(-x), max(-y), max(-z), max(x), max(y), max(z) over the line points
 };
 
 struct f3 { float x, y, z; };

@@ -78,6 +78,9 @@ struct LvOptions {
     bool useMlat = false;                     // VulkanRayTracer.hpp:133
     uint32_t mlatNumNodes = 8;                // :134
     uint32_t mlabNumLayers = 8;               // mlab_num_layers: numLayers of rendering mode 3, 1 ... 64 (MLABRenderer.cpp:133-135,330)
+    uint32_t mboitNumMoments = 4;             // mboit_num_moments: 4 | 6 | 8 power moments of rendering mode 6 (MBOITRenderer.cpp:41-45)
+    float mboitOverestimation = 0.1f;         // mboit_overestimation: overestimationBeta in [0, 1] (MBOITRenderer.cpp:45,609)
+    float mboitMomentBias = 0.0f;             // mboit_moment_bias: 0 = auto (5e-7 / 5e-6 / 5e-5 for 4 / 6 / 8, MBOITRenderer.cpp:136-145), else (0, 0.1]
     // EAW denoiser of the RTAO pass (ambient_occlusion_denoiser; AO defaults of createDenoiserObject, Denoiser.cpp:54-62)
     bool eawEnabled = false;
     uint32_t eawIterations = 3;               // eaw_denoiser_iterations (GUI range 0..5, EAWDenoiser.cpp:437)
@@ -232,7 +235,9 @@ struct lv_ctx {
     LvDeviceBuffer ppllOverflow;              // raster_prism: pixel addresses with more kept fragments than ppllMaxNumFrags (k_ppll_pixel_pass)
     LvDeviceBuffer mlabLong;                  // mode 3: {pixel address, output index} of the pixels k_mlab_resolve_long folds
     LvDeviceBuffer mlabStatsSnap;             // mode 3 with collect_stats: the statistics counters before the front end (pool regrowth)
-    uint64_t mlabPoolSlots = 0;               // mode 3: fragment slots the largest frame so far needed (the pool never drops one)
+    uint64_t mlabPoolSlots = 0;               // modes 3 and 6: fragment slots the largest frame so far needed (the pool never drops one)
+    uint32_t mboitBoxOrd[6] = {0, 0, 0, 0, 0, 0};   // mode 6: k_mboit_points_box's result for the current line points (lv_bvh_build resets)
+    bool mboitBoxValid = false;
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
     LvDeviceBuffer accum;                     // rgba8 of the previous accumulated frame (full viewport)
@@ -370,6 +375,8 @@ inline void lv_invalidate_bake(lv_ctx* ctx) {
 int lv_frame_depth_range(lv_ctx* ctx);
 int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
                                uint32_t h, uint8_t* out);
+int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
+                                uint32_t h, float logDepthMin, float logDepthMax, float* outMoments, uint8_t* out);
 int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numNodes, const uint32_t* start,
                                uint64_t numPixels, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint8_t* out);
 void lv_fill_uniforms(const lv_ctx* ctx, LvUniforms& U);

@@ -22,6 +22,7 @@
 #include "lv_internal.h"
 #include "lv_trace.h"
 #include "lv_tile.h"
+#include "lv_mboit.h"
 
 namespace {
 
@@ -1158,7 +1159,18 @@ __device__ __forceinline__ f3 lv_prism_frag_pos(const LvSceneDev& S, const LvUni
     const LvPrismPlanes pl = lv_prism_planes(R, T, cam, d);
     return lv_prism_interpolate(T, nrm, pl, d).pos;
 }
-template <bool STATS, int SHADE = LV_SHADE_PLAIN, int FAST = 0, bool MLAB = false>
+// MBOIT (rendering mode 6, MBOITPass1.glsl:44-52 / MBOITPass2.glsl:21-37): the entry is the straight float32 colour gatherFragment
+// receives (16 B, entry dst of the colour array) and the view depth -screenSpacePosition.z (4 B, entry dst of the depth array that
+// starts poolSlots colour entries in); only the `kept` rules discard (the alpha < 0.001 discard lives in the gather shaders of modes
+// 2 and 3, not in MBOIT's); a discarded fragment's depth word is LV_PPLL_DEAD.
+#define LV_ENTRY_PPLL 0
+#define LV_ENTRY_MLAB 1
+#define LV_ENTRY_MBOIT 2
+// view depth of a world position: row z of the view matrix in one fixed float32 order, negated
+__device__ __forceinline__ float lv_view_depth(const LvUniforms& U, f3 p) {
+    return -(((U.view[2] * p.x + U.view[6] * p.y) + U.view[10] * p.z) + U.view[14]);
+}
+template <bool STATS, int SHADE = LV_SHADE_PLAIN, int FAST = 0, int ENTRY = LV_ENTRY_PPLL>
 __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_SHADE_MIN_WAVES) void k_ppll_shade_prism(const LvUniforms U, const LvSceneDev S,
                                                                    const uint32_t* __restrict__ records, uint2* __restrict__ frags,
                                                                    const uint32_t* __restrict__ pixelOffset,
@@ -1198,8 +1210,13 @@ __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_SHADE_MIN_WAVES) void k_ppll_sha
         if (STATS && kept) hits++;
         const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
         const size_t dst = size_t(lv_run_start(pixelOffset, blockBase, addr)) + rank;
-        if (kept && color.w >= 0.001f) {   // gatherFragment: discard below, LinkedListGather.glsl:34 (MLABGather.glsl:64)
-            if constexpr (MLAB) {
+        if (kept && (ENTRY == LV_ENTRY_MBOIT || color.w >= 0.001f)) {   // gatherFragment: discard below, LinkedListGather.glsl:34 (MLABGather.glsl:64)
+            if constexpr (ENTRY == LV_ENTRY_MBOIT) {
+                reinterpret_cast<uint4*>(frags)[dst] = make_uint4(__float_as_uint(color.x), __float_as_uint(color.y),
+                                                                  __float_as_uint(color.z), __float_as_uint(color.w));
+                (reinterpret_cast<uint32_t*>(frags) + 4 * size_t(poolSlots))[dst] =
+                        __float_as_uint(lv_view_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt)));
+            } else if constexpr (ENTRY == LV_ENTRY_MLAB) {
                 f4 m;   // packUnorm4x8(vec4(color.rgb * color.a, 1.0 - color.a)), MLABGather.glsl:76
                 m.x = color.x * color.w; m.y = color.y * color.w; m.z = color.z * color.w; m.w = 1.0f - color.w;
                 uint32_t* e = reinterpret_cast<uint32_t*>(frags) + 3 * dst;
@@ -1211,7 +1228,9 @@ __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_SHADE_MIN_WAVES) void k_ppll_sha
             }
             localSum++;
         } else {
-            if constexpr (MLAB) {
+            if constexpr (ENTRY == LV_ENTRY_MBOIT) {
+                (reinterpret_cast<uint32_t*>(frags) + 4 * size_t(poolSlots))[dst] = LV_PPLL_DEAD;
+            } else if constexpr (ENTRY == LV_ENTRY_MLAB) {
                 uint32_t* e = reinterpret_cast<uint32_t*>(frags) + 3 * dst;
                 e[0] = 0u; e[1] = LV_PPLL_DEAD; e[2] = LV_MLAB_NO_KEY;
             } else {
@@ -2338,6 +2357,156 @@ __global__ __launch_bounds__(LV_BLOCK) void k_mlab_check_counts(const uint4* __r
     if (full) atomicOr(&dc->mlabSaturated, 1u);
 }
 
+// ================================================================ MBOIT (rendering mode 6)
+// Moment-based order-independent transparency [Muenstermann et al. 2018] as MBOITRenderer runs it with power moments stored as
+// float32 (4 / 6 / 8 of them): the fragment stage (k_ppll_shade_prism<..., LV_ENTRY_MBOIT>) leaves each pixel's fragments as one
+// contiguous run -- straight float32 colour in a 16-B array, view depth in a 4-B array behind it --, and one kernel sweeps a run
+// twice: moments (generateMoments), then per fragment the reconstructed transmittance and the weighted colour sums
+// (resolveMoments + MBOITPass2), then the blend (MBOITBlend).  A pixel's moments live in registers between the sweeps: no moment
+// image, no atomics on memory, no ordering.  Every sum is a sum of 64-bit fixed-point terms (lv_mboit.h), so the frame does not
+// depend on the order the rasteriser left the fragments in.  Short runs: one lane per pixel (k_mboit_resolve); runs of more than
+// LV_MBOIT_LONG entries: one wave per pixel, the lanes striding over the run and the integer sums reduced over the wave
+// (k_mboit_resolve_long), listed as k_mlab_resolve lists its long pixels.
+#ifndef LV_MBOIT_LONG
+#define LV_MBOIT_LONG 32u   // config 4, resolve of N = 4: 0.327 / 0.172 / 0.181 / 0.270 ms at 16 / 32 / 48 / 128
+#endif
+
+// a run of n entries, this lane taking first, first + step, ...; WAVE: the 64 lanes share the run (sums reduced over the wave, every
+// lane returns the pixel).  mom (nullable): b_0 and the normalised moments of the pixel, zeros under the threshold.
+template <int N, bool WAVE>
+__device__ __forceinline__ uint32_t lv_mboit_run(const LvUniforms& U, const LvMboitParams& M, const uint4* __restrict__ rgba,
+                                                 const uint32_t* __restrict__ zbits, uint32_t n, uint32_t first, uint32_t step,
+                                                 float* __restrict__ mom, uint32_t& degenerate) {
+    long long s[1 + N];
+#pragma unroll
+    for (int k = 0; k <= N; k++) s[k] = 0;
+    for (uint32_t j = first; j < n; j += step) {
+        const uint32_t zb = zbits[j];
+        if (zb == LV_PPLL_DEAD) continue;
+        lv_mboit_moments<N>(__uint_as_float(rgba[j].w), __uint_as_float(zb), M, s);
+    }
+    if (WAVE) {
+#pragma unroll
+        for (int k = 0; k <= N; k++) s[k] = (long long)lv_wave_sum_u64((unsigned long long)s[k]);
+    }
+    float b_0, nb[N];
+    LvMboitPixel<N> X;
+    const bool covered = lv_mboit_pixel<N>(s, M, b_0, nb, X);
+    if (mom && first == 0u) {
+        mom[0] = covered ? b_0 : 0.0f;
+#pragma unroll
+        for (int k = 0; k < N; k++) mom[1 + k] = covered ? nb[k] : 0.0f;
+    }
+    long long c[4] = {0, 0, 0, 0};
+    if (covered) {
+        for (uint32_t j = first; j < n; j += step) {
+            const uint32_t zb = zbits[j];
+            if (zb == LV_PPLL_DEAD) continue;
+            const uint4 q = rgba[j];
+            f4 col;
+            col.x = __uint_as_float(q.x); col.y = __uint_as_float(q.y); col.z = __uint_as_float(q.z); col.w = __uint_as_float(q.w);
+            lv_mboit_colour<N>(col, __uint_as_float(zb), b_0, X, M, c);
+        }
+        if (WAVE) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) c[k] = (long long)lv_wave_sum_u64((unsigned long long)c[k]);
+        }
+        if (c[3] == 0 && first == 0u) degenerate++;
+    }
+    return lv_mboit_blend(U, covered, b_0, c);
+}
+
+// One lane per pixel, one wave per workgroup, the cells and groups of k_ppll_resolve / k_mlab_resolve.  rgba / zbits: the colour and
+// the view-depth array, indexed alike.  Long runs go to longList {pixel address, output index}: one entry per (tile, pixel) pair,
+// longCap = tiles x tile pixels.  moments (nullable): (1 + N) floats per output index.
+template <int N>
+__global__ __launch_bounds__(LV_WAVE) void k_mboit_resolve(const LvUniforms U, const LvTiles T, const LvMboitParams M,
+                                                           const uint4* __restrict__ rgba, const uint32_t* __restrict__ zbits,
+                                                           const uint32_t* __restrict__ startOffset,
+                                                           const uint32_t* __restrict__ blockBase,
+                                                           const uint32_t* __restrict__ fragCount, uint32_t* __restrict__ out,
+                                                           uint32_t numGroups, uint2* __restrict__ longList, uint32_t longCap,
+                                                           float* __restrict__ moments, LvDevCounters* dc) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t maxCount = 0u, degenerate = 0u;
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        const bool inTile = lx < T.tileW && ly < T.tileH;
+        if (!__any(inTile)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        const uint32_t outIndex = (tile * T.tileH + ly) * T.tileW + lx;
+        const bool inView = inTile && x < U.width && y < U.height;
+        bool write = inTile;
+        uint32_t n = 0u, start = 0u;
+        if (inView) {
+            const uint32_t addr = lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+            const uint32_t v = fragCount[addr];
+            n = v & 0xFFFFu;   // entries of the run; v >> 16 of them are dead
+            maxCount = max(maxCount, n - (v >> 16));
+            if (n > LV_MBOIT_LONG) {
+                const uint32_t item = atomicAdd(&dc->mlabLongPixels, 1u);
+                if (item < longCap) longList[item] = make_uint2(addr, outIndex);
+                write = false;
+                n = 0u;
+            } else if (n) {
+                start = lv_mlab_run_start(startOffset, blockBase, addr);
+            }
+        }
+        float* mom = (moments && write) ? moments + size_t(outIndex) * (1 + N) : nullptr;
+        const uint32_t packed = lv_mboit_run<N, false>(U, M, rgba + start, zbits + start, n, 0u, 1u, mom, degenerate);
+        if (write) out[outIndex] = packed;
+    }
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) {
+        maxCount = max(maxCount, (uint32_t)__shfl_xor(maxCount, ofs, 64));
+        degenerate += (uint32_t)__shfl_xor(degenerate, ofs, 64);
+    }
+    if (lane == 0 && maxCount > 0u) atomicMax(&dc->maxDepthComplexity, maxCount);
+    if (M.stats && lane == 0 && degenerate > 0u) atomicAdd(&dc->mboitDegenerate, degenerate);
+}
+
+// The pixels k_mboit_resolve listed, one wave each (persistent grid)
+template <int N>
+__global__ __launch_bounds__(LV_WAVE) void k_mboit_resolve_long(const LvUniforms U, const LvMboitParams M, const uint4* __restrict__ rgba,
+                                                                const uint32_t* __restrict__ zbits,
+                                                                const uint32_t* __restrict__ startOffset,
+                                                                const uint32_t* __restrict__ blockBase,
+                                                                const uint32_t* __restrict__ fragCount, uint32_t* __restrict__ out,
+                                                                const uint2* __restrict__ longList, uint32_t longCap,
+                                                                float* __restrict__ moments, LvDevCounters* dc) {
+    const uint32_t lane = threadIdx.x, count = min(dc->mlabLongPixels, longCap);
+    uint32_t degenerate = 0u;
+    for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
+        const uint2 li = longList[item];
+        const uint32_t start = lv_mlab_run_start(startOffset, blockBase, li.x);
+        const uint32_t n = fragCount[li.x] & 0xFFFFu;
+        float* mom = moments ? moments + size_t(li.y) * (1 + N) : nullptr;
+        const uint32_t packed = lv_mboit_run<N, true>(U, M, rgba + start, zbits + start, n, lane, LV_WAVE, mom, degenerate);
+        if (lane == 0u) out[li.y] = packed;
+    }
+    if (M.stats && lane == 0u && degenerate > 0u) atomicAdd(&dc->mboitDegenerate, degenerate);
+}
+
+// the box of the line points for computeDepthRange (MBOITRenderer.cpp:485): six ordered maxima (the minima as maxima of -x)
+__global__ __launch_bounds__(LV_BLOCK) void k_mboit_points_box(const lv_line_point* __restrict__ points, uint32_t numPoints, LvDevCounters* dc) {
+    float v[6] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    for (uint32_t i = blockIdx.x * LV_BLOCK + threadIdx.x; i < numPoints; i += gridDim.x * LV_BLOCK) {
+        const float* p = points[i].linePosition;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { v[k] = fmaxf(v[k], -p[k]); v[3 + k] = fmaxf(v[3 + k], p[k]); }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        v[k] = lv_wave_max(v[k]);
+        if (lv_lane() == 0) atomicMax(&dc->mboitBoxOrd[k], lv_f2ord(v[k]));
+    }
+}
+
 // ================================================================ depth range
 __global__ __launch_bounds__(LV_BLOCK) void k_depth_minmax(const LvUniforms U, const lv_line_point* __restrict__ points,
                                                            uint32_t numPoints, LvDevCounters* dc) {
@@ -3028,14 +3197,102 @@ static int lv_mlab_fold(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, uint
     return LV_OK;
 }
 
+// log(x) of mode 6's depth range on the host: lv_log_det of the device (lv_log2_det x ln 2), so that the range is the same float32
+// bits wherever the library runs (the reference calls std::log)
+static float lv_log_det_host(float x) {
+    uint32_t bits;
+    memcpy(&bits, &x, 4);
+    int e = int((bits >> 23) & 0xFFu) - 127;
+    const uint32_t mb = (bits & 0x007FFFFFu) | 0x3F800000u;
+    float m;
+    memcpy(&m, &mb, 4);
+    if (m > 1.41421356f) { m = m * 0.5f; e = e + 1; }
+    const float f = m - 1.0f;
+    const float s = f / (2.0f + f);
+    const float z = s * s;
+    const float P = 0.333333333f + z * (0.2f + z * (0.142857143f + z * 0.111111111f));
+    const float ln = 2.0f * s + (2.0f * s) * (z * P);
+    return (float(e) + ln * 1.44269504f) * 0.693147181f;
+}
+
+// MBOITRenderer::computeDepthRange (MBOITRenderer.cpp:484-503) + the moment uniforms: boxOrd = k_mboit_points_box's six values.
+// The eight corners of the points' box through row z of the view matrix (lv_view_depth's order), -max z - 0.1 / -min z + 0.1,
+// clamped to near / far in the reference's four steps.
+static LvMboitParams lv_mboit_params(const lv_ctx* ctx, const LvUniforms& U, const uint32_t* boxOrd, bool stats) {
+    auto ord2f = [](uint32_t u) {
+        const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+        float f;
+        memcpy(&f, &b, 4);
+        return f;
+    };
+    float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};
+    if (ctx->numPoints)
+        for (int k = 0; k < 3; k++) { lo[k] = -ord2f(boxOrd[k]); hi[k] = ord2f(boxOrd[3 + k]); }
+    float zMin = 0.0f, zMax = 0.0f;
+    for (int k = 0; k < 8; k++) {
+        const float x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
+        const float vz = ((U.view[2] * x + U.view[6] * y) + U.view[10] * z) + U.view[14];
+        zMin = k ? std::min(zMin, vz) : vz;
+        zMax = k ? std::max(zMax, vz) : vz;
+    }
+    float minViewZ = -zMax - 0.1f, maxViewZ = -zMin + 0.1f;
+    minViewZ = std::max(minViewZ, U.nearDist);
+    maxViewZ = std::min(maxViewZ, U.farDist);
+    minViewZ = std::min(minViewZ, U.farDist);
+    maxViewZ = std::max(maxViewZ, U.nearDist);
+    LvMboitParams M;
+    M.logDepthMin = lv_log_det_host(minViewZ);
+    M.logDepthMax = lv_log_det_host(maxViewZ);
+    M.overestimation = ctx->opt.mboitOverestimation;
+    // moment_bias of MBOITRenderer.cpp:136-145 unless mboit_moment_bias overrides it
+    const uint32_t N = ctx->opt.mboitNumMoments;
+    M.momentBias = ctx->opt.mboitMomentBias > 0.0f ? ctx->opt.mboitMomentBias : (N == 4u ? 5e-7f : N == 6u ? 5e-6f : 5e-5f);
+    M.stats = stats ? 1u : 0u;
+    return M;
+}
+
+// The two sweeps of mode 6 over the runs in ctx->ppllNodes (colours, then the view depths depthBase entries in) / ppllStart
+// (+ blockBase) / ppllCount: k_mboit_resolve, then the listed long runs
+static int lv_mboit_resolve(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, const LvMboitParams& M, uint32_t numGroups,
+                            uint32_t depthBase, const uint32_t* blockBase, uint32_t* out, float* moments, LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    const uint64_t longCap64 = uint64_t(T.numTiles) * T.tileW * T.tileH;   // one entry per (tile, pixel) pair, as lv_mlab_fold
+    if (longCap64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t longCap = uint32_t(longCap64);
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->mlabLong, size_t(longCap) * 8))) return rc;
+    const uint4* rgba = (const uint4*)ctx->ppllNodes.ptr;
+    const uint32_t* zbits = (const uint32_t*)ctx->ppllNodes.ptr + 4 * size_t(depthBase);
+    const uint32_t* so = (const uint32_t*)ctx->ppllStart.ptr;
+    const uint32_t* cnt = (const uint32_t*)ctx->ppllCount.ptr;
+    uint2* const longList = (uint2*)ctx->mlabLong.ptr;
+    const uint32_t longGrid = uint32_t(ctx->numCUs) * 16u;
+#define LV_LAUNCH_MBOIT(N)                                                                                                      \
+    do {                                                                                                                        \
+        k_mboit_resolve<N><<<numGroups, LV_WAVE, 0, st>>>(U, T, M, rgba, zbits, so, blockBase, cnt, out, numGroups, longList,    \
+                                                          longCap, moments, dc);                                                \
+        k_mboit_resolve_long<N><<<longGrid, LV_WAVE, 0, st>>>(U, M, rgba, zbits, so, blockBase, cnt, out, longList, longCap,     \
+                                                              moments, dc);                                                     \
+    } while (0)
+    if (ctx->opt.mboitNumMoments == 4u) LV_LAUNCH_MBOIT(4);
+    else if (ctx->opt.mboitNumMoments == 6u) LV_LAUNCH_MBOIT(6);
+    else LV_LAUNCH_MBOIT(8);
+#undef LV_LAUNCH_MBOIT
+    return LV_OK;
+}
+
 int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
                     uint32_t tileH, void* outDevice) {
-    if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB)
-        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB)", mode);
-    const bool mlab = mode == LV_RENDERING_MODE_MLAB;
+    if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
+        mode != LV_RENDERING_MODE_MBOIT)
+        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 6 = MBOIT)", mode);
+    // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
+    const bool mboit = mode == LV_RENDERING_MODE_MBOIT;
+    const bool mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
+    const char* const poolName = mboit ? "MBOIT" : "MLAB";
     if (mlab && ctx->opt.ppllFragmentSource == 1)
-        return lv_fail(ctx, LV_E_INVALID, "mode 3 (MLAB) folds the fragments of the rasterised prism: ppll_fragment_source = "
-                                          "capsule_entry is not supported");
+        return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
+                                          "capsule_entry is not supported", mode, poolName);
     if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_set_camera has not been called");
     if (!ctx->tf.ptr || ctx->tfN == 0) return lv_fail(ctx, LV_E_STATE, "lv_set_transfer_function has not been called");
     if (!ctx->points.ptr && ctx->numSegs) return lv_fail(ctx, LV_E_STATE, "lv_set_lines has not been called");
@@ -3325,13 +3582,14 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             LV_HIP(ctx, hipMemcpyAsync(ctx->mlabStatsSnap.ptr, &dc->rays, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
         }
     mlab_regrow:   // (mode 3: the rasteriser needed more record slots than the pool held -- grown, and the front end runs again)
-        if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(poolSlots) * 12)))
-            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "MLAB: cannot allocate a fragment pool of %u entries", poolSlots) : rc;
+        // (mode 6: 16-B colours + 4-B view depths per entry)
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(poolSlots) * (mboit ? 20 : 12))))
+            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "%s: cannot allocate a fragment pool of %u entries", poolName, poolSlots) : rc;
         // raster_prism: the coverage kernel writes 12-B records {pixel, leaf | triangle, rank} into a pool of their own; ppllNodes then
         // holds the fragment array (8-B {colour, depth} entries, one contiguous run per pixel -- 12-B {colour, window depth, key} in
         // mode 3), ppllStart the runs' offsets
         if (prismSource && (rc = lv_buf_reserve(ctx, ctx->prismRecords, size_t(poolSlots) * 12)))
-            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "MLAB: cannot allocate a record pool of %u entries", poolSlots) : rc;
+            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "%s: cannot allocate a record pool of %u entries", poolName, poolSlots) : rc;
         ctx->ppllArrays = prismSource;
         uint32_t* gatherPool = prismSource ? (uint32_t*)ctx->prismRecords.ptr : (uint32_t*)ctx->ppllNodes.ptr;
         const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
@@ -3409,14 +3667,26 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             volatile uint32_t* pin = ctx->pinned + 14;   // (words 14, 15 of the pinned block)
             LV_HIP(ctx, hipMemcpyAsync((void*)pin, &dc->fragAlloc, 4, hipMemcpyDeviceToHost, st));
             LV_HIP(ctx, hipMemcpyAsync((void*)(pin + 1), &dc->mlabSaturated, 4, hipMemcpyDeviceToHost, st));
+            const bool readBox = mboit && !ctx->mboitBoxValid;
+            if (readBox) {
+                // mode 6, first frame on these line points: their box for the log depth range, read back with the same
+                // synchronisation (words 2 ... 7 of the pinned block)
+                if (ctx->numPoints)
+                    k_mboit_points_box<<<std::min(nblocks(ctx->numPoints), 256u), LV_BLOCK, 0, st>>>(S.points, ctx->numPoints, dc);
+                LV_HIP(ctx, hipMemcpyAsync((void*)(ctx->pinned + 2), dc->mboitBoxOrd, 24, hipMemcpyDeviceToHost, st));
+            }
             LV_HIP(ctx, hipStreamSynchronize(st));
+            if (readBox) {
+                for (int k = 0; k < 6; k++) ctx->mboitBoxOrd[k] = ctx->pinned[2 + k];
+                ctx->mboitBoxValid = true;
+            }
             const uint32_t need = pin[0], saturated = pin[1];
             if (saturated)
-                return lv_fail(ctx, LV_E_CAPACITY, "MLAB: a pixel is covered by more than 65534 fragments (16-bit per-pixel count)");
+                return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than 65534 fragments (16-bit per-pixel count)", poolName);
             if (need > poolSlots) {
                 const uint64_t grown = uint64_t(need) + chunkSlack;
                 if (mlabGrown || grown > 0xFFFFFFF0ull)
-                    return lv_fail(ctx, LV_E_CAPACITY, "MLAB: the frame needs %llu fragment slots (pool: %u)",
+                    return lv_fail(ctx, LV_E_CAPACITY, "%s: the frame needs %llu fragment slots (pool: %u)", poolName,
                                    (unsigned long long)grown, poolSlots);
                 poolSlots = uint32_t(grown);
                 ctx->mlabPoolSlots = poolSlots;
@@ -3462,12 +3732,15 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             // shading_numerics = fast: the plain-tube fragment stage with the raster colour (the only variant whose alpha cannot follow
             // the halo coordinate); every other variant keeps the exact arithmetic
             const bool fastShade = ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
-            if (mlab) {
-                if (fastShade) LV_LAUNCH_SHADE_FAST(true);
-                else if (stats) LV_LAUNCH_SHADE(true, true); else LV_LAUNCH_SHADE(false, true);
+            if (mboit) {
+                if (fastShade) LV_LAUNCH_SHADE_FAST(LV_ENTRY_MBOIT);
+                else if (stats) LV_LAUNCH_SHADE(true, LV_ENTRY_MBOIT); else LV_LAUNCH_SHADE(false, LV_ENTRY_MBOIT);
+            } else if (mlab) {
+                if (fastShade) LV_LAUNCH_SHADE_FAST(LV_ENTRY_MLAB);
+                else if (stats) LV_LAUNCH_SHADE(true, LV_ENTRY_MLAB); else LV_LAUNCH_SHADE(false, LV_ENTRY_MLAB);
             } else {
-                if (fastShade) LV_LAUNCH_SHADE_FAST(false);
-                else if (stats) LV_LAUNCH_SHADE(true, false); else LV_LAUNCH_SHADE(false, false);
+                if (fastShade) LV_LAUNCH_SHADE_FAST(LV_ENTRY_PPLL);
+                else if (stats) LV_LAUNCH_SHADE(true, LV_ENTRY_PPLL); else LV_LAUNCH_SHADE(false, LV_ENTRY_PPLL);
             }
 #undef LV_LAUNCH_SHADE_FAST
 #undef LV_LAUNCH_SHADE
@@ -3486,7 +3759,10 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             // the fold: k_mlab_resolve, then the pixels with long runs (k_mlab_resolve_long); both in the LV_KERNEL_PPLL_RESOLVE slot
             const bool timed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RESOLVE) & 1u) != 0u;
             if (timed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 0), st));
-            if ((rc = lv_mlab_fold(ctx, U, T, numGroups, blockBase, out, (uint2*)ctx->prismRecords.ptr, dc))) return rc;
+            if (mboit) {
+                const LvMboitParams M = lv_mboit_params(ctx, U, ctx->mboitBoxOrd, stats);
+                if ((rc = lv_mboit_resolve(ctx, U, T, M, numGroups, poolSlots, blockBase, out, nullptr, dc))) return rc;
+            } else if ((rc = lv_mlab_fold(ctx, U, T, numGroups, blockBase, out, (uint2*)ctx->prismRecords.ptr, dc))) return rc;
             if (timed) {
                 LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 1), st));
                 ctx->kernelLaunches[LV_KERNEL_PPLL_RESOLVE]++;
@@ -3661,6 +3937,68 @@ int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(numPixels) * 4, hipMemcpyDeviceToHost, st));
     LV_HIP(ctx, hipStreamSynchronize(st));   // (also: start / count are host vectors of this call)
+    return LV_OK;
+}
+
+// lv_mboit_resolve_buffers: the caller's runs through the two sweeps of mode 6 (row-major addressing, absolute run starts, as
+// lv_frame_mlab_resolve_only); entries = 5 words {r, g, b, a, view depth}, split into the colour and the depth array on upload
+int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
+                                uint32_t h, float logDepthMin, float logDepthMax, float* outMoments, uint8_t* out) {
+    const uint64_t numPixels = uint64_t(w) * h;
+    const uint32_t N = ctx->opt.mboitNumMoments;
+    if (numEntries >= 0xFFFFFFF0ull / 5 || numPixels > 0x7FFFFFF0ull / (1 + N)) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
+    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
+    std::vector<uint32_t> start(numPixels), count(numPixels);
+    for (uint64_t p = 0; p < numPixels; p++) {
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > 0xFFFEu)
+            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most 65534 entries per pixel", (unsigned long long)p);
+        start[p] = uint32_t(offsets[p]);
+        count[p] = uint32_t(offsets[p + 1] - offsets[p]);
+    }
+    const size_t cap = size_t(numEntries ? numEntries : 1);
+    std::vector<uint32_t> split(cap * 5);
+    for (uint64_t i = 0; i < numEntries; i++) {
+        if (entries[5 * i + 4] == LV_PPLL_DEAD) return lv_fail(ctx, LV_E_INVALID, "entry %llu: depth bits 0xFFFFFFFF are reserved", (unsigned long long)i);
+        for (int k = 0; k < 4; k++) split[4 * i + k] = entries[5 * i + k];
+        split[4 * cap + i] = entries[5 * i + 4];
+    }
+    LvUniforms U;
+    lv_fill_uniforms(ctx, U);
+    U.width = w; U.height = h;
+    U.ppllTileW = 1u; U.ppllTileH = 1u; U.ppllPaddedW = w; U.ppllPaddedH = h;   // address = y * w + x
+    hipStream_t st = ctx->stream;
+    int rc;
+    const size_t momBytes = size_t(numPixels) * (1 + N) * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, cap * 20))) return rc;
+    if (outMoments && (rc = lv_buf_reserve(ctx, ctx->ppllScratch, momBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, size_t(numPixels) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, split.data(), cap * 20, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    const uint32_t txy[2] = {0u, 0u};
+    ctx->tilesUploaded = false; // tilesDev is overwritten below
+    LV_HIP(ctx, hipMemcpyAsync(ctx->tilesDev.ptr, txy, 8, hipMemcpyHostToDevice, st));
+    LvTiles T{};
+    T.tilesXY = (const uint32_t*)ctx->tilesDev.ptr;
+    T.numTiles = 1; T.tileW = w; T.tileH = h;
+    T.blocksX = ((w + 63u) / 64u) * 4u; T.blocksY = ((h + 63u) / 64u) * 4u;
+    const uint32_t numGroups = (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;
+    const uint32_t noBox[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    LvMboitParams M = lv_mboit_params(ctx, U, noBox, ctx->opt.collectStats);
+    M.logDepthMin = logDepthMin;
+    M.logDepthMax = logDepthMax;
+    if ((rc = lv_mboit_resolve(ctx, U, T, M, numGroups, uint32_t(cap), nullptr, (uint32_t*)ctx->outDev.ptr,
+                               outMoments ? (float*)ctx->ppllScratch.ptr : nullptr, (LvDevCounters*)ctx->counters.ptr)))
+        return rc;
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(numPixels) * 4, hipMemcpyDeviceToHost, st));
+    if (outMoments) LV_HIP(ctx, hipMemcpyAsync(outMoments, ctx->ppllScratch.ptr, momBytes, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));   // (also: start / count / split are host vectors of this call)
     return LV_OK;
 }
 

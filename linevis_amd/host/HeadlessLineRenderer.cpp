@@ -31,6 +31,8 @@ void HeadlessLineRenderer::createRenderer(RenderingMode mode) {
         lineRenderer.reset(new HipPerPixelLinkedListLineRenderer(&sceneData, transferFunctionWindow));
     else if (mode == RENDERING_MODE_MLAB)
         lineRenderer.reset(new HipMLABRenderer(&sceneData, transferFunctionWindow));
+    else if (mode == RENDERING_MODE_MBOIT)
+        lineRenderer.reset(new HipMBOITRenderer(&sceneData, transferFunctionWindow));
     else
         lineRenderer.reset(new HipRayTracer(&sceneData, transferFunctionWindow));
     lineRenderer->initialize();

@@ -75,6 +75,32 @@ inline void getTestModesMlab(std::vector<InternalState>& states, InternalState s
     states.push_back(state);
 }
 
+/// getTestModesMboit, src/Utils/InternalState.cpp:90-135: 4 and 8 moments x {No Sync, Spinlock, Unordered Interlock, Ordered
+/// Interlock, Render Targets} of the MBOIT renderer (rendering mode 6).  Not part of getTestModes().
+inline void getTestModesMboit(std::vector<InternalState>& states, InternalState state) {
+    state.renderingMode = 6;
+    for (int i = 4; i <= 8; i += 4) {
+        const std::string n = std::to_string(i);
+        state.name = "MBOIT (" + n + " Moments, No Sync)";
+        state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"numMoments", n}, {"syncMode", "0"}, {"useRenderTargets", "false"}});
+        states.push_back(state);
+        state.name = "MBOIT (" + n + " Moments, Spinlock)";
+        state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"numMoments", n}, {"syncMode", "2"}, {"useRenderTargets", "false"}});
+        states.push_back(state);
+        state.name = "MBOIT (" + n + " Moments, Unordered Interlock)";
+        state.rendererSettings = SettingsMap(std::map<std::string, std::string>{
+                {"numMoments", n}, {"syncMode", "1"}, {"useOrderedFragmentShaderInterlock", "false"}, {"useRenderTargets", "false"}});
+        states.push_back(state);
+        state.name = "MBOIT (" + n + " Moments, Ordered Interlock)";
+        state.rendererSettings = SettingsMap(std::map<std::string, std::string>{
+                {"numMoments", n}, {"syncMode", "1"}, {"useOrderedFragmentShaderInterlock", "true"}, {"useRenderTargets", "false"}});
+        states.push_back(state);
+        state.name = "MBOIT (" + n + " Moments, Render Targets)";
+        state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"numMoments", n}, {"useRenderTargets", "true"}});
+        states.push_back(state);
+    }
+}
+
 /// The hot-path subset of getTestModes() (InternalState.cpp:641-644 -> getTestModesOIT, :149-214): 1920 x 1080, PPLL + the ray tracer
 /// states, every state twice for the error measure.
 inline std::vector<InternalState> getTestModes(bool runStatesTwoTimesForErrorMeasure = true) {

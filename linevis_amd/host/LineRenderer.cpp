@@ -714,6 +714,69 @@ bool HipMLABRenderer::setNewSettings(const SettingsMap& settings) {
     return r;
 }
 
+HipMBOITRenderer::HipMBOITRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Moment-Based Order Independent Transparency", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipMBOITRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipMBOITRenderer::setNewState(const InternalState& newState) {
+    const SettingsMap& m = newState.rendererSettings;
+    bool power = true;
+    std::string format = "Float";
+    int moments = numMoments;
+    refusedKey.clear();
+    if (m.getValueOpt("usePowerMoments", power) && !power) { refusedKey = "mboit_use_power_moments"; refusedValue = "false"; }
+    else if (m.getValueOpt("pixelFormat", format) && format != "Float") { refusedKey = "mboit_pixel_format"; refusedValue = format; }
+    else if (m.getValueOpt("numMoments", moments) && moments != 4 && moments != 6 && moments != 8) {
+        refusedKey = "mboit_num_moments"; refusedValue = std::to_string(moments);
+    }
+    if (!refusedKey.empty()) return;   // the previous state stays; render() reports the error
+    if (refusalReported) { lastError.clear(); refusalReported = false; }   // (an accepted state ends the refusal's error)
+    currentStateName = newState.name;
+    numMoments = moments;
+    m.getValueOpt("USE_R_RG_RGBA_FOR_MBOIT6", USE_R_RG_RGBA_FOR_MBOIT6);
+    if (!m.getValueOpt("overestimationBeta", overestimationBeta)) overestimationBeta = 0.1f;   // MBOITRenderer.cpp:293-300
+    m.getValueOpt("useRenderTargets", useRenderTargets);
+    m.getValueOpt("useOrderedFragmentShaderInterlock", useOrderedFragmentShaderInterlock);
+    m.getValueOpt("syncMode", syncMode);
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipMBOITRenderer::render() {
+    if (!refusedKey.empty()) {
+        setOption(refusedKey.c_str(), refusedValue);   // LV_E_INVALID: lastError names the family that is not built
+        refusalReported = true;
+        return;
+    }
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    setOption("mboit_num_moments", std::to_string(numMoments));
+    setOption("mboit_overestimation", std::to_string(overestimationBeta));
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_MBOIT); // depth range -> gather -> moments, reconstruction and blend
+}
+
+bool HipMBOITRenderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    bool power = true;
+    std::string format = "Float";
+    if ((settings.getValueOpt("usePowerMoments", power) && !power) || (settings.getValueOpt("pixelFormat", format) && format != "Float"))
+        return r;   // (the map of a state setNewState refused: its renderer keys are not applied)
+    int moments = numMoments;
+    if (settings.getValueOpt("numMoments", moments) && (moments == 4 || moments == 6 || moments == 8)) numMoments = moments;
+    settings.getValueOpt("overestimationBeta", overestimationBeta);
+    for (const char* key : {"ppll_expected_avg_depth_complexity", "ppll_tile_width", "ppll_tile_height", "ppll_fragment_source",
+                            "ppll_fragment_colour", "ppll_prism_rasteriser", "mboit_moment_bias"}) {
+        std::string s;
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
 void HipPerPixelLinkedListLineRenderer::computeStatistics(uint64_t& totalNumFragments, uint32_t& maxComplexity) {
     lv_stats s = getStatistics();
     totalNumFragments = s.fragments;

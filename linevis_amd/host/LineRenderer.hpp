@@ -26,6 +26,7 @@ enum RenderingMode : int32_t {
     RENDERING_MODE_NONE = -1,
     RENDERING_MODE_PER_PIXEL_LINKED_LIST = 2,
     RENDERING_MODE_MLAB = 3,
+    RENDERING_MODE_MBOIT = 6,
     RENDERING_MODE_VULKAN_RAY_TRACER = 11,
 };
 
@@ -347,6 +348,45 @@ private:
     int numLayers = 8;                              // MLABRenderer.hpp:133
     int syncMode = 1;                               // SYNC_FRAGMENT_SHADER_INTERLOCK (SyncMode.hpp:38-40), .hpp:134
     bool useOrderedFragmentShaderInterlock = true;  // .hpp:135
+};
+
+/// "Moment-Based Order-Independent Transparency" plugin (src/Renderers/OIT/MBOITRenderer.hpp) re-hosted on HIP (rendering mode
+/// 6): power moments stored as float32 over the fragments of the PPLL plugin's rasterised prism.
+class HipMBOITRenderer : public LineRenderer {
+public:
+    HipMBOITRenderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_MBOIT; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    /// MBOITRenderer::setNewState (MBOITRenderer.cpp:283-340): numMoments, pixelFormat, USE_R_RG_RGBA_FOR_MBOIT6, usePowerMoments,
+    /// overestimationBeta, useRenderTargets, syncMode, useOrderedFragmentShaderInterlock.  A key is applied only when the state
+    /// carries it (the reference reads pixelFormat and usePowerMoments of states without these keys as UNORM / false); the storage
+    /// layout and synchronisation keys are stored and change nothing (integer sums have no order).  A state that asks for
+    /// usePowerMoments = false or a pixelFormat other than "Float" is refused: the previous state stays and the next render()
+    /// reports the error of the C ABI.
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    bool setNewSettings(const SettingsMap& settings) override;
+    bool getUseAnalyticEllipticTubes() const override { return true; }
+    int getNumMoments() const { return numMoments; }
+    float getOverestimationBeta() const { return overestimationBeta; }
+    int getSyncMode() const { return syncMode; }
+    bool getUseOrderedFragmentShaderInterlock() const { return useOrderedFragmentShaderInterlock; }
+    bool getUseRenderTargets() const { return useRenderTargets; }
+    bool getUseRRgRgbaForMboit6() const { return USE_R_RG_RGBA_FOR_MBOIT6; }
+
+private:
+    std::string currentStateName;
+    int numMoments = 4;                             // MBOITRenderer.hpp / .cpp:41
+    bool usePowerMoments = true;                    // .cpp:43
+    std::string pixelFormat = "Float";              // MBOIT_PIXEL_FORMAT_FLOAT_32, .cpp:42
+    bool USE_R_RG_RGBA_FOR_MBOIT6 = true;           // .cpp:44
+    float overestimationBeta = 0.1f;                // .cpp:45
+    bool useRenderTargets = false;
+    int syncMode = 1;                               // SYNC_FRAGMENT_SHADER_INTERLOCK (SyncMode.hpp:38-40)
+    bool useOrderedFragmentShaderInterlock = true;
+    std::string refusedKey, refusedValue;           // the option a refused state asked for (reported by render())
+    bool refusalReported = false;                   // lastError holds that report
 };
 
 } // namespace lv

@@ -467,6 +467,36 @@ int lvh_renderer_mlab_state(void* r, int32_t* out3) {   // {numLayers, syncMode,
     out3[0] = m->getNumLayers(); out3[1] = m->getSyncMode(); out3[2] = m->getUseOrderedFragmentShaderInterlock() ? 1 : 0;
     return 0;
 }
+uint32_t lvh_test_modes_mboit_count() {
+    std::vector<InternalState> states;
+    getTestModesMboit(states, InternalState());
+    return uint32_t(states.size());
+}
+uint32_t lvh_test_mode_mboit(uint32_t index, char* buf, uint32_t capacity) {
+    std::vector<InternalState> states;
+    InternalState state;
+    state.windowResolution[0] = 1920;
+    state.windowResolution[1] = 1080;
+    getTestModesMboit(states, state);
+    if (index >= states.size()) return 0;
+    const InternalState& s = states[index];
+    std::string out = s.name + "\n" + std::to_string(s.renderingMode) + "\n" + std::to_string(s.windowResolution[0]) + "\n" +
+                      std::to_string(s.windowResolution[1]) + "\n";
+    for (const auto& kv : s.rendererSettings.getMap()) out += kv.first + "=" + kv.second + "\n";
+    if (buf && capacity > out.size()) memcpy(buf, out.c_str(), out.size() + 1);
+    return uint32_t(out.size());
+}
+// {numMoments, syncMode, useOrderedFragmentShaderInterlock, useRenderTargets, USE_R_RG_RGBA_FOR_MBOIT6} and overestimationBeta of a
+// mode-6 plugin
+int lvh_renderer_mboit_state(void* r, int32_t* out5, float* outBeta) {
+    HeadlessLineRenderer* h = static_cast<HeadlessLineRenderer*>(r);
+    const HipMBOITRenderer* m = dynamic_cast<const HipMBOITRenderer*>(h->getLineRenderer());
+    if (!m) return -1;
+    out5[0] = m->getNumMoments(); out5[1] = m->getSyncMode(); out5[2] = m->getUseOrderedFragmentShaderInterlock() ? 1 : 0;
+    out5[3] = m->getUseRenderTargets() ? 1 : 0; out5[4] = m->getUseRRgRgbaForMboit6() ? 1 : 0;
+    *outBeta = m->getOverestimationBeta();
+    return 0;
+}
 void lvh_renderer_destroy(void* r) { delete static_cast<HeadlessLineRenderer*>(r); }
 void lvh_renderer_set_resolution(void* r, uint32_t w, uint32_t h) { static_cast<HeadlessLineRenderer*>(r)->setRenderingResolution(w, h); }
 void lvh_renderer_set_line_data(void* r, void* flow, int isNewData) {

@@ -83,6 +83,9 @@ def load():
         "lvh_test_modes_mlab_count": (u32, []),
         "lvh_test_mode_mlab": (u32, [u32, vp, u32]),
         "lvh_renderer_mlab_state": (i32, [vp, vp]),
+        "lvh_test_modes_mboit_count": (u32, []),
+        "lvh_test_mode_mboit": (u32, [u32, vp, u32]),
+        "lvh_renderer_mboit_state": (i32, [vp, vp, vp]),
         "lvh_renderer_destroy": (None, [vp]),
         "lvh_renderer_set_resolution": (None, [vp, u32, u32]),
         "lvh_renderer_set_line_data": (None, [vp, vp, i32]),
@@ -498,8 +501,21 @@ def get_test_modes_mlab():
     return out
 
 
+def get_test_modes_mboit():
+    """The ten states of the MBOIT renderer (lv::getTestModesMboit = InternalState.cpp:90-135), same tuple form as get_test_modes;
+    not part of get_test_modes."""
+    L = load()
+    out = []
+    for i in range(L.lvh_test_modes_mboit_count()):
+        n = L.lvh_test_mode_mboit(i, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        L.lvh_test_mode_mboit(i, buf, n + 1)
+        out.append(_parse_test_mode(buf.value.decode()))
+    return out
+
+
 class HeadlessLineRenderer:
-    """lv::HeadlessLineRenderer: fixed-camera harness around one renderer plugin (mode 11, 2 or 3)."""
+    """lv::HeadlessLineRenderer: fixed-camera harness around one renderer plugin (mode 11, 2, 3 or 6)."""
 
     def __init__(self, mode=capi.MODE_RAY_TRACER, device=0, devices=None, transport="rccl"):
         """devices = [d0, d1, ...]: the plugin drives one context per device (SceneData::deviceOrdinals -> lv_create_multi)."""
@@ -597,6 +613,15 @@ class HeadlessLineRenderer:
         if self.L.lvh_renderer_mlab_state(self.h, _p(v)) != 0:
             return None
         return {"numLayers": int(v[0]), "syncMode": int(v[1]), "useOrderedFragmentShaderInterlock": bool(v[2])}
+
+    def mboit_state(self):
+        """the state of the mode-6 plugin (None for the other plugins)"""
+        v = np.zeros(5, dtype=np.int32)
+        beta = np.zeros(1, dtype=np.float32)
+        if self.L.lvh_renderer_mboit_state(self.h, _p(v), _p(beta)) != 0:
+            return None
+        return {"numMoments": int(v[0]), "syncMode": int(v[1]), "useOrderedFragmentShaderInterlock": bool(v[2]),
+                "useRenderTargets": bool(v[3]), "USE_R_RG_RGBA_FOR_MBOIT6": bool(v[4]), "overestimationBeta": float(beta[0])}
 
     def needs_re_render(self):
         return bool(self.L.lvh_renderer_needs_re_render(self.h))
