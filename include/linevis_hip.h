@@ -394,7 +394,9 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value);
 
 /* LineData::getRayTracingTubeAabbTopLevelAS (LineData.cpp:1057-1075) + getTubeAabbBottomLevelAS (:879-907):
  * builds the LBVH over segment AABBs min(p0,p1)-r .. max(p0,p1)+r (LineDataFlow.cpp:2230-2233) on the GPU.
- * Called implicitly by lv_render* when lines or line_width changed. */
+ * Called implicitly by lv_render* when lines or line_width changed.  The tube mesh and its triangle LBVH are built along
+ * with it only while the current options use them (RTAO on triangle tubes, the prebaker, geometry_mode "Triangle Mesh");
+ * every other frame that needs them later builds them itself. */
 int lv_build_accel(lv_ctx* ctx);
 
 /* LineRenderer::render() (LineRenderer.hpp:112) for mode 11 (VulkanRayTracer::render, VulkanRayTracer.cpp:131-154:

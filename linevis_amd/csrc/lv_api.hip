@@ -112,7 +112,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
-            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
+            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
@@ -692,7 +692,10 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         else if (strcmp(value, "exact") == 0) o.fastShading = false;
         else return bad();
     } else if (k == "overlap_primary_passes") {
-        o.overlapPrimaryPasses = strcmp(value, "auto") == 0 ? 2 : (parseBool(value) ? 1 : 0);
+        if (strcmp(value, "auto") == 0) o.overlapPrimaryPasses = 2;
+        else if (strcmp(value, "true") == 0 || strcmp(value, "1") == 0) o.overlapPrimaryPasses = 1;
+        else if (strcmp(value, "false") == 0 || strcmp(value, "0") == 0) o.overlapPrimaryPasses = 0;
+        else return bad();
     } else if (k == "tube_num_subdivisions") {
         if (!parseUint(value, u) || u < 3) return bad();
         o.tubeNumSubdivisions = u;
@@ -840,9 +843,14 @@ int lv_build_accel(lv_ctx* ctx) {
     int rc = lv_ensure_line_points(ctx);
     if (rc) return rc;
     if ((rc = lv_bvh_build(ctx))) return rc;
-    // LineData::getRayTracingTubeTriangleTopLevelAS (LineData.cpp:986-1013): the triangle LBVH of the tube mesh, if there is one
-    if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
-    if (ctx->triMeshSet && (rc = lv_bvh_build_triangles(ctx))) return rc;
+    // LineData::getRayTracingTubeTriangleTopLevelAS (LineData.cpp:986-1013): the tube mesh and its triangle LBVH, if the current
+    // options have a consumer for them (lv_frame_render builds them lazily for every other frame): the RTAO pass on triangle tubes, the
+    // prebaker, or the "Triangle Mesh" geometry mode.  Band / helicity trajectories in frames that never touch triangles build nothing here.
+    const bool needTriangles = (ctx->opt.useAmbientOcclusion && (ctx->opt.aoPrebaked || lv_ao_triangle_tubes(ctx))) || ctx->opt.rtTriangleMesh;
+    if (needTriangles) {
+        if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
+        if (ctx->triMeshSet && (rc = lv_bvh_build_triangles(ctx))) return rc;
+    }
     return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_build_accel(p); });
 }
 

@@ -841,6 +841,7 @@ int lv_flow_trace_max_helicity_first(lv_ctx* ctx, const float* helicityField, co
             if (have > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_CAPACITY, "more than 2^31 finished points");
             if (have > ctx->flowPointsCapacity) {
                 size_t cap = std::max<size_t>(have * 2, 1u << 16);
+                ctx->flowPointsCapacity = 0;   // a reserve that fails has freed its buffer
                 if ((rc = lv_buf_reserve(ctx, ctx->flowPoints, cap * 12))) return rc;
                 if ((rc = lv_buf_reserve(ctx, ctx->flowPointsNext, cap * 4))) return rc;
                 ctx->flowPointsCapacity = cap;

@@ -581,6 +581,15 @@ int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const fl
         return lv_fail(ctx, LV_E_INVALID, "max_helicity must be finite (<= 0: reduced on the device)");
     (void)hipSetDevice(ctx->device);
     lv_invalidate_bake(ctx);
+    // from here on the buffers of the previous data set are rewritten: it is gone whether or not this call gets to its end (a call
+    // that fails below leaves an empty scene, not counts and an LBVH over reallocated buffers); the new values are committed at the end
+    ctx->trajSet = false;
+    ctx->accelValid = false;
+    ctx->numPoints = ctx->numSegs = 0;
+    ctx->triMeshSet = false;
+    ctx->triMeshFromTraj = false;
+    ctx->triAccelValid = false;
+    ctx->evLinePointsValid = false;
     hipStream_t st = ctx->stream;
     int rc;
     if ((rc = lv_buf_reserve(ctx, ctx->trajPos, size_t(numPoints) * 12))) return rc;
@@ -606,11 +615,12 @@ int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const fl
     ctx->trajHasAttr = attribute != nullptr;
     ctx->trajHasRibbons = ribbon != nullptr;
     ctx->trajHasHelicity = helicity != nullptr;
-    ctx->trajSet = false;
     if ((rc = lv_write_line_points(ctx))) return rc;   // (synchronises: the host arrays were borrowed for the call only)
-    if (helicity && ctx->numPoints) {
+    const uint32_t numRecords = ctx->numPoints, numSegs = ctx->numSegs;
+    ctx->numPoints = ctx->numSegs = 0;                 // held back until the last kernel of this call has run
+    ctx->evLinePointsValid = false;
+    if (helicity && numRecords) {
         // the mesh table's rotation runs on across all lines and depends on nothing a tessellation changes: once per data set
-        const uint32_t numRecords = ctx->numPoints;
         if ((rc = lv_buf_reserve(ctx, ctx->trajMeshRot, size_t(numRecords) * 4))) return rc;
         k_mesh_rot_inc<<<nblk(numRecords), LV_BLOCK, 0, st>>>((const float*)ctx->trajPos.ptr, (const float*)ctx->trajHelicity.ptr,
                                                                (const float*)ctx->trajMaxHelicity.ptr, (const uint32_t*)ctx->trajRecLine.ptr,
@@ -620,10 +630,10 @@ int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const fl
         LV_HIP(ctx, hipGetLastError());
         LV_HIP(ctx, hipStreamSynchronize(st));
     }
-    ctx->trajSet = true;
-    ctx->triMeshSet = false;     // tessellated on demand (lv_ensure_tube_mesh)
-    ctx->triMeshFromTraj = false;
-    ctx->triAccelValid = false;
+    ctx->numPoints = numRecords;
+    ctx->numSegs = numSegs;
+    ctx->evLinePointsValid = true;
+    ctx->trajSet = true;         // (the tube mesh is tessellated on demand: lv_ensure_tube_mesh)
     ctx->aoGlobalFrameNumber = 0;   // VulkanRayTracedAmbientOcclusionPass::setLineData (.cpp:437-460), as lv_set_lines
     ctx->lastFrameViewProjValid = false;
     return lv_forward_to_ranks(ctx, [&](lv_ctx* p) {

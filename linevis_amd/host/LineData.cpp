@@ -234,10 +234,15 @@ bool loadFlowTrajectoriesFromFile(const std::string& filename, Trajectories& tra
 }
 
 // ---------------------------------------------------------------- LineData
+uint64_t LineData::nextDataGeneration() {
+    static std::atomic<uint64_t> counter{0};
+    return ++counter;
+}
+
 void LineData::setSelectedAttributeIndex(int idx) {
     if (idx != selectedAttributeIndex) {
         selectedAttributeIndex = idx;
-        dataGeneration++;
+        dataGeneration = nextDataGeneration();
         setTriangleRepresentationDirty();
     }
 }
@@ -456,7 +461,7 @@ void LineDataFlow::setTrajectoryData(const Trajectories& newTrajectories, const 
     modelBoundingBox = computeTrajectoriesAABB3(trajectories);
     cachedAabbDataValid = false;
     cachedTriangleDataValid = false;
-    dataGeneration++;
+    dataGeneration = nextDataGeneration();
     dirty = true;
 }
 

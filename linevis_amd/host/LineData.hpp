@@ -13,6 +13,7 @@
 // Accessors return host-side POD arrays (byte-identical record layouts) instead of sgl::vk::BufferPtr.
 #pragma once
 
+#include <atomic>
 #include <memory>
 #include <string>
 #include <vector>
@@ -176,7 +177,9 @@ protected:
     bool useHalos = true;
     int tubeNumSubdivisions = 6;     // LineData.cpp:52
     bool dirty = false;
-    uint64_t dataGeneration = 1;     // bumped by new trajectories / another selected attribute
+    /// process-wide: no two states of any two objects share a value, so (address, generation) of a freed object never matches a new one
+    static uint64_t nextDataGeneration();
+    uint64_t dataGeneration = nextDataGeneration(); // renewed by new trajectories / another selected attribute
     bool cachedAabbDataValid = false;
     bool cachedTriangleDataValid = false;
 };

@@ -364,6 +364,7 @@ bool LineRenderer::setNewSettings(const SettingsMap& settings) {
 void LineRenderer::updateNewLineData(LineDataPtr& newLineData, bool isNewData) {
     lineData = newLineData;
     linesDirty = true;
+    if (isNewData) uploadedTrajectoryData = nullptr;   // another data set: whatever the context holds was not uploaded from it
     if (useAmbientOcclusion && ambientOcclusionBaker) ambientOcclusionBaker->startAmbientOcclusionBaking(lineData, isNewData);
     dirty = false;
     reRender = true;

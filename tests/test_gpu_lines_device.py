@@ -139,6 +139,7 @@ def test_config3_geometry_on_the_device(hip_lib):
         assert len(mesh[0]) == 12060000
         for a, b in zip(mesh, hm):
             assert zlib.crc32(np.ascontiguousarray(a).view(np.uint8)) == zlib.crc32(np.ascontiguousarray(b).view(np.uint8))
+    ctx.set_option("geometry_mode", "Triangle Mesh")         # a consumer of the tube mesh: lv_build_accel builds what the options use
     ctx.build_accel()
     ctx.set_option("line_width", 0.0025)
     t0 = time.perf_counter()

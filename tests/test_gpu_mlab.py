@@ -182,9 +182,8 @@ def test_host_plugin_states_match_the_c_abi_frame(hip_lib):
     assert rc == 0 and np.array_equal(raw, frames[0])
 
 
-def _stacked_case(**settings):
+def _stacked_case(n=3000, width=48, height=40, **settings):
     """thousands of segments stacked through the same pixels (parallel lines along the view axis): runs of > 1000 fragments"""
-    n = 3000
     pos, off = [], [0]
     rng = np.random.default_rng(5)
     for i in range(n):
@@ -197,7 +196,7 @@ def _stacked_case(**settings):
     pts, seg, _ = lvo.build_tube_aabb_render_data(pos, attr, np.array(off, np.uint32), 0.02)
     from common import Case
     from linevis_amd import transfer_function as tfm
-    return Case(pts, seg, tfm.standard_transparent(), 48, 40, 0.02, **settings)
+    return Case(pts, seg, tfm.standard_transparent(), width, height, 0.02, **settings)
 
 
 def test_long_runs_and_pool_growth(hip_lib):

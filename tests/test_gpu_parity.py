@@ -520,7 +520,8 @@ def test_option_errors(hip_lib):
     c = small_case(width=32, height=32)
     ctx = c.hip_context()
     for key, val in [("no_such_key", "1"), ("num_accumulated_frames", 0), ("ambient_occlusion_mode", "SSAO"),
-                     ("line_width", -1.0), ("geometry_mode", "Curved Swept Spheres"), ("mlat_num_nodes", 3)]:
+                     ("line_width", -1.0), ("geometry_mode", "Curved Swept Spheres"), ("mlat_num_nodes", 3),
+                     ("overlap_primary_passes", "Auto"), ("overlap_primary_passes", "on"), ("overlap_primary_passes", "")]:
         with pytest.raises(capi.LineVisError):
             ctx.set_option(key, val)
     with pytest.raises(capi.LineVisError):
