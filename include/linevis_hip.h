@@ -573,6 +573,22 @@ int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_e
  * floats, b_0 then the normalised b_1 ... b_N of each pixel, zeros where b_0 is under the threshold. */
 int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                              uint32_t h, float log_depth_min, float log_depth_max, float* out_moments, uint8_t* out_rgba8);
+/* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
+ * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
+ * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =
+ * 4 floats {flow x, flow y, depth fwidth, unused}.  The three history images are read and overwritten with this call's: color_history
+ * = 1 float (colour after the first a-trous pass, or the filtered colour with 0 iterations), moments_history = 4 floats {m1, m2, history
+ * length, 0}, normal_depth_history = 4 floats.  out = 1 float per pixel, the denoised image.  The thresholds come from the options
+ * svgf_denoiser_allowed_z_dist / svgf_denoiser_allowed_normal_dist.  The renderer's own SVGF history is not touched.
+ * Where SVGF.glsl leaves a result open, the rules are: texel fetches outside the image return 0; the moments filter reads the image
+ * the reprojection pass wrote; `out` parameters the callee did not write keep 0 (moments) or the colour history at the pixel itself
+ * (colour; it then enters with weight 0); max / min return the other operand of a NaN; pow(x, 128) is seven squarings; a reprojected
+ * position ((0.5 + pixel) - flow or (0.01 + pixel) - flow) that is not finite or outside the int range fails
+ * load_moments_and_history_length and is never converted to int; a non-finite depth fwidth drops the depth term of compute_weight.
+ * LV_E_INVALID for a null pointer or an extent outside the range. */
+int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_depth,
+                            const float* flow_fwidth, float* color_history, float* moments_history, float* normal_depth_history,
+                            float* out);
 /* LBVH export for structural tests: compressed 4-wide nodes of 16 uint32/float words (64 B) each -- words 0-2 grid
  * origin xyz, words 3-5 grid scale xyz (floats), words 6-8 qmin x/y/z and words 9-11 qmax x/y/z (byte k = child slot
  * k; decoded plane = origin + q * scale), words 12-15 child references (bit 31 = leaf, 0xFFFFFFFF = empty slot);

@@ -104,7 +104,7 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -176,6 +176,7 @@ def load():
         ("lv_ppll_resolve_buffers", [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp]),
         ("lv_mlab_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp]),
         ("lv_mboit_resolve_buffers", [vp, vp, u64, vp, u32, u32, C.c_float, C.c_float, vp, vp]),
+        ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
         ("lv_set_trajectories", [vp, vp, vp, vp, u32]),
@@ -574,6 +575,25 @@ class Context:
         self._ck(self.L.lv_mboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, float(log_depth_min), float(log_depth_max),
                                                  _p(mom), _p(out)))
         return out, mom
+
+    def svgf_denoise(self, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history):
+        """One SVGF denoise() on caller-supplied images (lv_svgf_denoise_buffers): noisy (h, w), normal_depth (h, w, 4), flow_fwidth
+        (h, w, 4) {flow x, flow y, depth fwidth, unused}; the history images color_history (h, w), moments_history (h, w, 4) and
+        normal_depth_history (h, w, 4) must be C-contiguous float32 arrays and are updated in place.  Returns the denoised (h, w)
+        image.  Iterations and thresholds are the context's svgf_denoiser_* options."""
+        a = np.ascontiguousarray(noisy, dtype=np.float32)
+        h, w = a.shape
+        nd = np.ascontiguousarray(normal_depth, dtype=np.float32)
+        ff = np.ascontiguousarray(flow_fwidth, dtype=np.float32)
+        if nd.shape != (h, w, 4) or ff.shape != (h, w, 4):
+            raise ValueError("normal_depth and flow_fwidth must be (h, w, 4)")
+        for arr, shape in ((color_history, (h, w)), (moments_history, (h, w, 4)), (normal_depth_history, (h, w, 4))):
+            if arr.dtype != np.float32 or arr.shape != shape or not arr.flags.c_contiguous:
+                raise ValueError("history images must be C-contiguous float32 arrays of the viewport's shape")
+        out = np.zeros((h, w), dtype=np.float32)
+        self._ck(self.L.lv_svgf_denoise_buffers(self.h, w, h, _p(a), _p(nd), _p(ff), _p(color_history), _p(moments_history),
+                                                _p(normal_depth_history), _p(out)))
+        return out
 
     def get_accel(self, num_nodes, num_leaves):
         nodes = np.zeros((max(num_nodes, 1), 16), dtype=np.uint32)

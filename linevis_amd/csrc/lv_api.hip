@@ -111,7 +111,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->depthMinMax, &ctx->ao, &ctx->aoAlt, &ctx->featNormal, &ctx->featNormalAlt, &ctx->featPosition, &ctx->featPositionAlt,
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
-            &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
+            &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
             &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
@@ -1356,6 +1356,17 @@ int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_
     if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
     (void)hipSetDevice(ctx->device);
     return lv_frame_mboit_resolve_only(ctx, entries, num_entries, offsets, w, h, log_depth_min, log_depth_max, out_moments, out);
+}
+
+int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_depth,
+                            const float* flow_fwidth, float* color_history, float* moments_history, float* normal_depth_history,
+                            float* out) {
+    if (!ctx) return LV_E_INVALID;
+    if (!noisy || !normal_depth || !flow_fwidth || !color_history || !moments_history || !normal_depth_history || !out)
+        return lv_fail(ctx, LV_E_INVALID, "null array");
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u) return lv_fail(ctx, LV_E_INVALID, "extent %u x %u (1 ... 16384 each)", w, h);
+    (void)hipSetDevice(ctx->device);
+    return lv_svgf_denoise_given(ctx, w, h, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history, out);
 }
 
 int lv_get_accel(lv_ctx* ctx, void* out_nodes, uint64_t max_nodes, uint32_t* out_leaf_segment, uint64_t max_leaves) {

@@ -209,6 +209,7 @@ struct lv_ctx {
     const float* aoResult = nullptr;          // what the colour pass samples: ao (raw) or the denoised image
     bool aoRestart = false;                   // the denoiser changed: a progressive RTAO accumulation may only continue from frame 0
     LvSvgfState svgf;
+    LvDeviceBuffer svgfGiven;                 // every image of one lv_svgf_denoise_buffers call (lv_svgf_denoise_given)
     LvDeviceBuffer fullFrameTile;             // one tile origin (0, 0): the SVGF chain always covers the viewport
     uint32_t aoGlobalFrameNumber = 0;         // RTAO iterations since lv_set_lines (globalFrameNumber, ...AmbientOcclusion.cpp:582)
     float lastFrameViewProj[16] = {};         // projection * view at the previous RTAO iteration (:456,631)
@@ -383,7 +384,9 @@ void lv_fill_uniforms(const lv_ctx* ctx, LvUniforms& U);
 bool lv_ppll_prism_source(const lv_ctx* ctx);
 // lv_svgf.hip
 int lv_svgf_prepare(lv_ctx* ctx);
-int lv_svgf_denoise(lv_ctx* ctx, const float* noisy);
+int lv_svgf_denoise(lv_ctx* ctx, LvSvgfState& V, uint32_t width, uint32_t height, const float* noisy);
+int lv_svgf_denoise_given(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normalDepth, const float* flowFwidth,
+                          float* colorHistory, float* momentsHistory, float* normalDepthHistory, float* out);
 // lv_flow.hip
 int lv_flow_set_grid(lv_ctx* ctx, const float* vectorField, uint32_t xs, uint32_t ys, uint32_t zs, float dx, float dy,
                      float dz, const float* const* scalarFields, uint32_t numScalarFields);

@@ -3133,7 +3133,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         if (eaw) { std::swap(ctx->featNormal, ctx->featNormalAlt); std::swap(ctx->featPosition, ctx->featPositionAlt); }
         // temporal denoiser: denoise() belongs to every _render (VulkanRayTracedAmbientOcclusion.cpp:633-651), its history advances
         // with every RTAO iteration
-        if (svgf && (rc = lv_svgf_denoise(ctx, (const float*)ctx->ao.ptr))) return rc;
+        if (svgf && (rc = lv_svgf_denoise(ctx, ctx->svgf, ctx->width, ctx->height, (const float*)ctx->ao.ptr))) return rc;
     }
     if (iterEnd > iterBegin || !ctx->aoResult) ctx->aoResult = svgf ? (const float*)ctx->svgf.result.ptr : (const float*)ctx->ao.ptr;
     if (eaw && iterEnd > iterBegin) {

@@ -19,7 +19,9 @@
 // Where the reference leaves the result open, the build defines it:
 // texel fetches outside the image return 0; the moments filter reads the image the reprojection pass wrote (the reference
 // filters temp_accum in place, a data race between invocations); unwritten `out` parameters are 0; pow(x, 128) is seven
-// squarings.
+// squarings; a reprojected position that is not finite or lies outside the int range fails load_moments_and_history_length
+// (tested before any float -> int conversion, whose result for such a value differs between targets); a non-finite
+// depth_fwidth drops the depth term of compute_weight (fmaxf returns the other operand of a NaN, x / inf = 0).
 #include <cmath>
 #include <cstring>
 
@@ -55,6 +57,9 @@ struct LvSvgfImages {
     float2* tempAccum;                // out {colour, variance}
 };
 
+// true where int(v) is defined: finite and inside [-2^31, 2^31) (false for a NaN)
+__device__ __forceinline__ bool svgf_in_int_range(float v) { return v >= -2147483648.0f && v < 2147483648.0f; }
+
 // is_reprj_valid, SVGF.glsl:72-86 (bounds first: history texels of rejected coordinates are never fetched)
 __device__ __forceinline__ bool svgf_reprj_valid(const LvSvgfImages& I, int W, int H, int cx, int cy, const float4 nd,
                                                  float allowedZDist, float allowedNormalDist) {
@@ -73,8 +78,15 @@ __global__ __launch_bounds__(256) void k_svgf_reproject(const LvSvgfImages I, in
     const size_t ci = size_t(y) * W + x;
     const float4 ff = I.flowFwidth[ci];
     float prevM0 = 0.0f, prevM1 = 0.0f, historyLength = 0.0f;
-    const int ipx = int((0.5f + float(x)) - ff.x), ipy = int((0.5f + float(y)) - ff.y);
-    bool success = !(ipx < 0 || ipy < 0 || ipx >= W || ipy >= H); // load_moments_and_history_length, :186-199
+    const float fpx = (0.5f + float(x)) - ff.x, fpy = (0.5f + float(y)) - ff.y;
+    const float ppx = (0.01f + float(x)) - ff.x, ppy = (0.01f + float(y)) - ff.y;
+    // build-owned: positions that are not finite or outside the int range fail the load and are never converted
+    bool success = svgf_in_int_range(fpx) && svgf_in_int_range(fpy) && svgf_in_int_range(ppx) && svgf_in_int_range(ppy);
+    int ipx = 0, ipy = 0;
+    if (success) {
+        ipx = int(fpx); ipy = int(fpy);
+        success = !(ipx < 0 || ipy < 0 || ipx >= W || ipy >= H); // load_moments_and_history_length, :186-199
+    }
     if (success) {
         const float4 mh = I.momentsHistory[size_t(ipy) * W + ipx];
         prevM0 = mh.x; prevM1 = mh.y; historyLength = mh.z;
@@ -82,7 +94,6 @@ __global__ __launch_bounds__(256) void k_svgf_reproject(const LvSvgfImages I, in
     const float color = I.noisy[ci];
     float colorLastFrame = I.colorHistory[ci];
     if (success) {
-        const float ppx = (0.01f + float(x)) - ff.x, ppy = (0.01f + float(y)) - ff.y;
         const int qx = int(ppx), qy = int(ppy);
         const float4 nd = I.normalDepth[ci];
         // try_2x2_tap, :88-139: offsets {(0,0), (0,1), (1,0), (1,1)} with the weights in the order the reference lists them
@@ -254,13 +265,12 @@ int lv_svgf_prepare(lv_ctx* ctx) {
     return LV_OK;
 }
 
-// One SVGFDenoiser::denoise() on the raw AO image `noisy` (full viewport); the result is ctx->svgf.result.
-int lv_svgf_denoise(lv_ctx* ctx, const float* noisy) {
-    LvSvgfState& V = ctx->svgf;
+// One SVGFDenoiser::denoise() of the state V (width x height) on the raw AO image `noisy` (full viewport); the result is V.result.
+int lv_svgf_denoise(lv_ctx* ctx, LvSvgfState& V, uint32_t width, uint32_t height, const float* noisy) {
     hipStream_t st = ctx->stream;
-    const int W = int(ctx->width), H = int(ctx->height);
+    const int W = int(width), H = int(height);
     const size_t n = size_t(W) * H;
-    const dim3 grid(nblocks2(ctx->width), nblocks2(ctx->height));
+    const dim3 grid(nblocks2(width), nblocks2(height));
     LvSvgfImages I;
     I.noisy = noisy;
     I.normalDepth = (const float4*)V.normalDepth.ptr;
@@ -291,5 +301,39 @@ int lv_svgf_denoise(lv_ctx* ctx, const float* noisy) {
     std::swap(V.normalDepth, V.normalDepthHistory);
     std::swap(V.moments, V.momentsHistory);
     LV_HIP(ctx, hipGetLastError());
+    return LV_OK;
+}
+
+// lv_svgf_denoise_buffers: one denoise() on the caller's maps and history images.  The state is a local one whose images are
+// slices of ctx->svgfGiven (16-byte images first, so every slice keeps its alignment); the renderer's own ctx->svgf is not touched.
+int lv_svgf_denoise_given(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normalDepth, const float* flowFwidth,
+                          float* colorHistory, float* momentsHistory, float* normalDepthHistory, float* out) {
+    const size_t n = size_t(w) * h;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->svgfGiven, n * 124))) return rc;
+    char* base = (char*)ctx->svgfGiven.ptr;
+    size_t off = 0;
+    auto slice = [&](size_t bytes) { LvDeviceBuffer b; b.ptr = base + off; b.bytes = bytes; off += bytes; return b; };
+    LvSvgfState V;
+    V.normalDepth = slice(n * 16); V.normalDepthHistory = slice(n * 16); V.flowFwidth = slice(n * 16);
+    V.moments = slice(n * 16); V.momentsHistory = slice(n * 16);
+    V.tempAccum = slice(n * 8); V.tempAccumFiltered = slice(n * 8); V.ping = slice(n * 8); V.pong = slice(n * 8);
+    V.colorHistory = slice(n * 4); V.result = slice(n * 4);
+    const LvDeviceBuffer raw = slice(n * 4);
+    V.width = w; V.height = h; V.historyValid = true;
+    hipStream_t st = ctx->stream;
+    LV_HIP(ctx, hipMemcpyAsync(V.normalDepth.ptr, normalDepth, n * 16, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(V.normalDepthHistory.ptr, normalDepthHistory, n * 16, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(V.flowFwidth.ptr, flowFwidth, n * 16, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(V.momentsHistory.ptr, momentsHistory, n * 16, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(V.colorHistory.ptr, colorHistory, n * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(raw.ptr, noisy, n * 4, hipMemcpyHostToDevice, st));
+    if ((rc = lv_svgf_denoise(ctx, V, w, h, (const float*)raw.ptr))) return rc;
+    // lv_svgf_denoise has swapped current and previous: the *History members are this call's images
+    LV_HIP(ctx, hipMemcpyAsync(normalDepthHistory, V.normalDepthHistory.ptr, n * 16, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipMemcpyAsync(momentsHistory, V.momentsHistory.ptr, n * 16, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipMemcpyAsync(colorHistory, V.colorHistory.ptr, n * 4, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipMemcpyAsync(out, V.result.ptr, n * 4, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
     return LV_OK;
 }

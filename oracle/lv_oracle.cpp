@@ -2642,6 +2642,11 @@ void lvo_mat4_mul(const float* A, const float* B, float* out) {
 //     invocation reads the image as the reprojection pass left it;
 //   * `out` parameters the callee did not write (prev_moments when load_moments_and_history_length fails) are 0;
 //   * pow(x, 128) of compute_weight is seven squarings (exact products instead of exp2(128 log2 x)).
+//   * a reprojected position ((0.5 + pos) - flow or (0.01 + pos) - flow) that is not finite or lies outside the int range
+//     fails load_moments_and_history_length; it is tested before any float -> int conversion (GLSL leaves that conversion
+//     undefined, x86 gives INT_MIN, other targets saturate);
+//   * a non-finite depth_fwidth drops the depth term of compute_weight: max(NaN, 0) is 0 (fmaxf returns the other operand),
+//     and x / inf is 0.
 namespace {
 inline float svgfPow128(float x) { for (int i = 0; i < 7; i++) x = x * x; return x; }
 // svgf_common.glsl:28-40
@@ -2673,6 +2678,8 @@ void lvo_svgf_denoise(uint32_t width, uint32_t height, const float* noisy, const
         if (sqrtf((dx * dx + dy * dy) + dz * dz) > allowedNormalDist) return false;
         return true;
     };
+    // true where int(v) is defined: finite and inside [-2^31, 2^31) (false for a NaN)
+    auto inIntRange = [](float v) { return v >= -2147483648.0f && v < 2147483648.0f; };
     // ---- Compute-Reproject, SVGF.glsl:201-261
 #pragma omp parallel for schedule(dynamic, 8)
     for (int64_t yy = 0; yy < int64_t(H); yy++) {
@@ -2681,8 +2688,15 @@ void lvo_svgf_denoise(uint32_t width, uint32_t height, const float* noisy, const
             const size_t ci = size_t(y) * width + x;
             const float mx = flowMap[2 * ci], my = flowMap[2 * ci + 1];
             float prevM0 = 0.0f, prevM1 = 0.0f, historyLength = 0.0f;
-            const int ipx = int((0.5f + float(x)) - mx), ipy = int((0.5f + float(y)) - my);
-            bool success = !(ipx < 0 || ipy < 0 || ipx >= W || ipy >= H); // load_moments_and_history_length, :186-199
+            const float fpx = (0.5f + float(x)) - mx, fpy = (0.5f + float(y)) - my;
+            const float ppx = (0.01f + float(x)) - mx, ppy = (0.01f + float(y)) - my;
+            // build-owned: positions that are not finite or outside the int range fail the load and are never converted
+            bool success = inIntRange(fpx) && inIntRange(fpy) && inIntRange(ppx) && inIntRange(ppy);
+            int ipx = 0, ipy = 0;
+            if (success) {
+                ipx = int(fpx); ipy = int(fpy);
+                success = !(ipx < 0 || ipy < 0 || ipx >= W || ipy >= H); // load_moments_and_history_length, :186-199
+            }
             if (success) {
                 const float* mh = momentsHistory + 4 * (size_t(ipy) * width + ipx);
                 prevM0 = mh[0]; prevM1 = mh[1]; historyLength = mh[2];
@@ -2690,7 +2704,6 @@ void lvo_svgf_denoise(uint32_t width, uint32_t height, const float* noisy, const
             const float color = noisy[ci];
             float colorLastFrame = colorHistory[ci];
             if (success) {
-                const float ppx = (0.01f + float(x)) - mx, ppy = (0.01f + float(y)) - my;
                 const int qx = int(ppx), qy = int(ppy);
                 const float depth = depthMap[ci];
                 const float* normal = normalMap + 4 * ci;

@@ -4,6 +4,7 @@ over frame sequences -- SVGF is temporal, so parity means the same images after 
 import numpy as np
 import pytest
 
+import cameras
 from common import Case, small_case, max_lsb_diff
 from linevis_amd import camera
 from oracle import lvo
@@ -173,3 +174,112 @@ def test_svgf_full_size_sequence(hip_lib):
         assert max_lsb_diff(img, sc.render_rt(P, ao=ao_ref, use_bvh=True)) <= 2, "frame %d" % f
     assert (ao_ref < 0.95).sum() > 100000
     ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------- sequences that actually move
+# camera_path() above moves the eye by 0.01 a frame: flows under 2 px, no failed load, history lengths up to 6.  The paths below are
+# (eye, target) pairs at 96 x 72; before anything runs on the device the oracle's own state is classified (the float64 statement of
+# test_svgf_restatement.py, fed the oracle's maps, tells which pixels load and which keep a history) and each test asserts the branch
+# its path is meant for.
+def orbit_path(frames, degrees, radius=0.8, height=0.1):
+    a = [np.deg2rad(degrees * k) for k in range(frames)]
+    return [((float(radius * np.sin(t)), height, float(radius * np.cos(t))), (0.0, 0.0, 0.0)) for t in a]
+
+
+def moving_case(width=96, height=72, **kw):
+    s = dict(RTAO, use_jittered_primary_rays=True)
+    s.update(kw)
+    return small_case(width=width, height=height, n_lines=6, pts_per_line=30, line_width=0.25, **s)
+
+
+def oracle_moving_sequence(c, poses):
+    """The oracle along (eye, target) poses: per frame the AO image, the frame, and the classification of the reprojection."""
+    from test_svgf_restatement import Svgf64
+    its = int(c.settings.get("svgf_denoiser_iterations", 5))
+    th = (float(c.settings.get("svgf_denoiser_allowed_z_dist", 0.002)), float(c.settings.get("svgf_denoiser_allowed_normal_dist", 0.02)))
+    sc = c.oracle_scene()
+    sv = lvo.Svgf(c.width, c.height, iterations=its, allowed_z_dist=th[0], allowed_normal_dist=th[1])
+    st = Svgf64(c.width, c.height, its, *th)
+    frames = []
+    for eye, target in poses:
+        cameras.apply_camera(c, dict(eye=eye, target=target))
+        P = c.oracle_params(sc)
+        ao_ref = sv.step(lambda: sc.render_ao(P), P)
+        st.step(sv.raw, sv.normal, sv.depth, sv.fwidth, sv.flow)
+        length = sv.moments_history[..., 2].copy()
+        assert np.array_equal(st.length_history, length)          # the classifier decides as the oracle does
+        hit = sv.depth < 50.0
+        flow = np.abs(sv.flow).max(axis=-1)
+        frames.append(dict(ao=ao_ref, ref=sc.render_rt(P, ao=ao_ref), hit=int(hit.sum()), flow_over_10=int((hit & (flow > 10.0)).sum()),
+                           load_failed=int((hit & ~st.masks["load"]).sum()), kept=int((hit & st.masks["success"]).sum()),
+                           length_32=int((length == 32).sum()), hit_below_32=int((hit & (length < 32)).sum())))
+    return frames
+
+
+def compare_moving_sequence(c, poses, frames):
+    ctx = c.hip_context()
+    for f, ((eye, target), want) in enumerate(zip(poses, frames)):
+        cameras.apply_camera(c, dict(eye=eye, target=target))
+        ctx.set_camera(c.view, c.proj, c.fovy, c.near, c.far, c.width, c.height)
+        img = ctx.render(11)
+        assert np.abs(ctx.get_ao() - want["ao"]).max() < 3e-5, "frame %d" % f
+        assert max_lsb_diff(img, want["ref"]) <= 2, "frame %d" % f
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_svgf_orbit_of_15_degrees_per_frame(hip_lib):
+    c, poses = moving_case(), orbit_path(5, 15.0)
+    frames = oracle_moving_sequence(c, poses)
+    assert all(fr["flow_over_10"] >= 20 for fr in frames[1:]), [fr["flow_over_10"] for fr in frames]
+    compare_moving_sequence(c, poses, frames)
+
+
+@pytest.mark.gpu
+def test_svgf_fast_dolly_in(hip_lib):
+    c, poses = moving_case(), [((0.0, 0.0, z), (0.0, 0.0, 0.0)) for z in (1.2, 1.2, 1.0, 0.8, 0.6, 0.45)]
+    frames = oracle_moving_sequence(c, poses)
+    assert frames[-1]["flow_over_10"] >= 20 and frames[-2]["flow_over_10"] >= 20 and frames[-1]["hit"] > 3 * frames[0]["hit"]
+    compare_moving_sequence(c, poses, frames)
+
+
+@pytest.mark.gpu
+def test_svgf_cut_to_the_opposite_side(hip_lib):
+    c = moving_case()
+    poses = [((0.0, 0.0, 0.8), (0.0, 0.0, 0.0))] * 3 + [((0.1, 0.05, -0.8), (0.0, 0.0, 0.0))] * 2
+    frames = oracle_moving_sequence(c, poses)
+    # of the pixels that hit the data, a fifth and more keep a history while the camera rests and under 5 % across the cut
+    assert frames[2]["kept"] > 0.2 * frames[2]["hit"] and frames[3]["kept"] < 0.05 * frames[3]["hit"] and frames[4]["kept"] > 0.2 * frames[4]["hit"]
+    compare_moving_sequence(c, poses, frames)
+
+
+@pytest.mark.gpu
+def test_svgf_pan_off_the_screen_and_back(hip_lib):
+    c = moving_case()
+    poses = [((0.0, 0.0, 0.8), (x, 0.0, 0.0)) for x in (0.0, 0.0, 0.25, 0.5, 0.25, 0.0)]
+    frames = oracle_moving_sequence(c, poses)
+    assert frames[3]["hit"] < 0.75 * frames[0]["hit"]                      # a third of the data has left the picture ...
+    assert frames[4]["load_failed"] >= 20 and frames[5]["load_failed"] >= 20   # ... and what returns finds no history to load
+    compare_moving_sequence(c, poses, frames)
+
+
+@pytest.mark.gpu
+def test_svgf_36_static_frames_reach_the_history_cap(hip_lib):
+    c = moving_case(48, 36, use_jittered_primary_rays=False, svgf_denoiser_iterations=1)
+    poses = [((0.0, 0.0, 1.0), (0.0, 0.0, 0.0))] * 36       # from 1.0 the data stays off row 0, where no pixel builds a history
+    frames = oracle_moving_sequence(c, poses)
+    assert frames[30]["length_32"] == 0 and frames[31]["length_32"] >= 20 and frames[-1]["length_32"] >= 20
+    assert frames[-1]["hit"] > 300 and frames[-1]["hit_below_32"] == 0
+    compare_moving_sequence(c, poses, frames)
+
+
+@pytest.mark.gpu
+def test_svgf_orbit_with_wide_thresholds(hip_lib):
+    """allowed_z_dist = 0.02, allowed_normal_dist = 0.2 on an orbit of 3 degrees a frame: nearly every pixel keeps its history, where
+    the default thresholds (same maps, classified here) drop most of them."""
+    c = moving_case(svgf_denoiser_allowed_z_dist=0.02, svgf_denoiser_allowed_normal_dist=0.2)
+    poses = orbit_path(4, 3.0)
+    frames = oracle_moving_sequence(c, poses)
+    narrow = oracle_moving_sequence(moving_case(), poses)
+    assert all(fr["kept"] > 0.9 * fr["hit"] for fr in frames[1:]) and all(fr["kept"] < 0.5 * fr["hit"] for fr in narrow[1:])
+    compare_moving_sequence(c, poses, frames)
