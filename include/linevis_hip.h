@@ -294,6 +294,25 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   mboit_moment_bias: "auto" (default; 5e-7 / 5e-6 / 5e-5 for 4 / 6 / 8 moments, MBOITRenderer.cpp:136-145) or a float in (0, 0.1]
  *   mboit_use_power_moments ("true" only), mboit_pixel_format ("Float" only): trigonometric moments and the 16-bit quantised
  *   storage are not built; "false" / "UNORM" return LV_E_INVALID
+ *   mboit_fragment_storage: "pool" (default) | "streamed"; any other value is LV_E_INVALID and leaves the old value in force; modes
+ *   other than 6 ignore it.  "streamed" keeps no fragment pool: as the reference's MBOITRenderer the frame rasterises and shades
+ *   the geometry twice and accumulates per pixel with 64-bit integer atomics on the fixed-point terms above -- first the moment
+ *   sums, then the colour sums --, then blends.  The frame, the statistics and lv_mboit_get_moments equal the pooled frame's bit
+ *   for bit (same terms, integer addition).  Memory: (1 + N + 4) * 8 bytes of accumulators per pixel of the viewport padded to
+ *   ppll_tile_width x ppll_tile_height, plus the two 4-byte per-pixel words of mode 2; nothing grows with the number of
+ *   fragments (the pool costs 12 + 20 = 32 bytes per fragment: break-even at 2.25 / 2.75 / 3.25 fragments per pixel for N = 4 /
+ *   6 / 8).  The pool options ppll_expected_avg_depth_complexity, ppll_max_num_frags and sorting_mode have no effect.  No host
+ *   synchronisation per frame and no second run of the front end; the line points' box is read back once per acceleration
+ *   structure build.  ppll_prism_rasteriser = lbvh and ppll_fragment_source = capsule_entry return LV_E_INVALID at render time
+ *   (the context stays usable).  Statistics (collect_stats): every counter of lv_get_stats equals the pooled frame's except
+ *   ppll_pool_nodes (0) and device_bytes; rays_traced, prims_tested, hits_shaded and fragments are counted in the moments pass
+ *   only.  Timers: LV_KERNEL_PPLL_RASTER times the two pass launches (2 launches per frame, the first with the tile marking and
+ *   segment culling of a sharded frame), LV_KERNEL_PPLL_RESOLVE the blend, LV_KERNEL_PPLL_SHADE has no launch.  Limit: the
+ *   per-pixel count is 32 bits and the sums are exact for up to 2^63 / (1024 * 2^36) = 131071 kept fragments on a pixel (the
+ *   pool's limit is 65534); the blend flags a pixel with more.  lv_render reads the flag with the frame and returns
+ *   LV_E_CAPACITY; lv_render_device / lv_render_tiles_device stay asynchronous and the flag stays with the frame: the next
+ *   host-synchronous call that reads anything of that frame -- lv_get_stats, lv_mboit_get_moments -- returns LV_E_CAPACITY.  A
+ *   later successful frame clears it.
  *   use_capped_tubes, use_halos, tube_num_subdivisions                  (LineData.cpp:87-181)
  *   max_depth_complexity                                                (VulkanRayTracer.hpp:139)
  *   ppll_max_num_frags, ppll_expected_avg_depth_complexity, ppll_tile_width, ppll_tile_height
@@ -573,6 +592,12 @@ int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_e
  * floats, b_0 then the normalised b_1 ... b_N of each pixel, zeros where b_0 is under the threshold. */
 int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                              uint32_t h, float log_depth_min, float log_depth_max, float* out_moments, uint8_t* out_rgba8);
+/* The moments of the last frame when that was a mode-6 frame with mboit_fragment_storage = streamed over the whole viewport:
+ * width * height * (1 + N) floats, row-major, in the layout of out_moments above (b_0, then the normalised b_1 ... b_N, zeros
+ * where b_0 is under the threshold).  LV_E_STATE when the last frame was anything else (pooled storage, another mode, a tile list
+ * that does not cover the viewport, a multi-device handle); LV_E_INVALID for a null pointer or capacity_floats below that size;
+ * LV_E_CAPACITY when a pixel of that frame holds more than 131071 kept fragments.  Synchronises the context's stream. */
+int lv_mboit_get_moments(lv_ctx* ctx, float* out, uint64_t capacity_floats);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

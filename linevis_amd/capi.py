@@ -104,7 +104,7 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -176,6 +176,7 @@ def load():
         ("lv_ppll_resolve_buffers", [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp]),
         ("lv_mlab_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp]),
         ("lv_mboit_resolve_buffers", [vp, vp, u64, vp, u32, u32, C.c_float, C.c_float, vp, vp]),
+        ("lv_mboit_get_moments", [vp, vp, u64]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -364,6 +365,8 @@ class Context:
 
     def set_option(self, key, value):
         self._ck(self.L.lv_set_option(self.h, key.encode(), _fmt(value).encode()))
+        if key == "mboit_num_moments":
+            self._mboit_num_moments = int(value)
 
     def set_options(self, settings):
         """LineRenderer::setNewSettings(const SettingsMap&): a dict of string keys."""
@@ -575,6 +578,15 @@ class Context:
         self._ck(self.L.lv_mboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, float(log_depth_min), float(log_depth_max),
                                                  _p(mom), _p(out)))
         return out, mom
+
+    def mboit_moments(self):
+        """The moments of the last mode-6 frame rendered with mboit_fragment_storage = streamed over the whole viewport
+        (lv_mboit_get_moments): (height, width, 1 + mboit_num_moments) float32, b_0 then the normalised b_1 ... b_N, zeros where b_0
+        is under the threshold."""
+        n = getattr(self, "_mboit_num_moments", 4)
+        mom = np.zeros((self.height, self.width, 1 + n), dtype=np.float32)
+        self._ck(self.L.lv_mboit_get_moments(self.h, _p(mom), mom.size))
+        return mom
 
     def svgf_denoise(self, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history):
         """One SVGF denoise() on caller-supplied images (lv_svgf_denoise_buffers): noisy (h, w), normal_depth (h, w, 4), flow_fwidth

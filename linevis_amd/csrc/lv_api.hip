@@ -112,7 +112,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
-            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
+            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
@@ -669,6 +669,11 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
             if (!parseFloat(value, f) || !(f > 0.0f && f <= 0.1f)) return bad();
             o.mboitMomentBias = f;
         }
+    } else if (k == "mboit_fragment_storage") {
+        // "pool" (default): the fragment pool of modes 2 and 3; "streamed": two rasterise-and-accumulate passes, no pool
+        if (strcmp(value, "pool") == 0) o.mboitStreamed = false;
+        else if (strcmp(value, "streamed") == 0) o.mboitStreamed = true;
+        else return bad();
     } else if (k == "mboit_use_power_moments") {
         if (strcmp(value, "true") != 0 && strcmp(value, "1") != 0)
             return lv_fail(ctx, LV_E_INVALID, "mboit_use_power_moments = '%s': trigonometric moments are not built (power moments only)", value);
@@ -915,6 +920,15 @@ int lv_render(lv_ctx* ctx, int mode, uint32_t x0, uint32_t y0, uint32_t w, uint3
     if ((rc = lv_render_device(ctx, mode, x0, y0, w, h, ctx->outDev.ptr))) return rc;
     LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(w) * h * 4, hipMemcpyDeviceToHost, ctx->stream));
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // mboit_fragment_storage = streamed: the blend's overflow flag (the frame is synchronised anyway)
+    for (int r = 0; r < lv_multi_num_ranks(ctx); r++) {
+        lv_ctx* c = lv_multi_rank(ctx, r);
+        if (!c->mboitStreamLast) continue;
+        (void)hipSetDevice(c->device);
+        rc = lv_mboit_stream_overflow(c);
+        (void)hipSetDevice(ctx->device);
+        if (rc) return c == ctx ? rc : lv_fail(ctx, rc, "rank %d: %s", r, c->lastError.c_str());
+    }
     return LV_OK;
 }
 
@@ -970,6 +984,8 @@ static int lv_get_stats_impl(lv_ctx* ctx, lv_stats* out, bool aggregate) {
         s.ao_prim_may_axis = hc.aoPrimMayAxis;
         s.ao_prim_may_both = hc.aoPrimMayBoth;
         s.mboit_degenerate_pixels = hc.mboitDegenerate;
+        if (ctx->mboitStreamLast && hc.mboitOverflow)
+            return lv_fail(ctx, LV_E_CAPACITY, "MBOIT (streamed): a pixel of the last frame is covered by more than 131071 kept fragments");
         for (int k = 0; k < 3; k++) { s.ao_phase_iterations[k] = hc.aoPhaseIters[k]; s.ao_phase_lanes[k] = hc.aoPhaseLanes[k]; }
     }
     for (int k = 0; k < 8; k++) { s.ms_kernel_avg[k] = 0.0f; s.kernel_launches[k] = 0; }
@@ -1348,6 +1364,14 @@ int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_e
     if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
     (void)hipSetDevice(ctx->device);
     return lv_frame_mlab_resolve_only(ctx, entries, num_entries, offsets, w, h, out);
+}
+
+int lv_mboit_get_moments(lv_ctx* ctx, float* out, uint64_t capacity_floats) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out) return lv_fail(ctx, LV_E_INVALID, "lv_mboit_get_moments: null output");
+    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_mboit_get_moments: a multi-device handle keeps no moments of the whole viewport");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_mboit_stream_moments(ctx, out, capacity_floats);
 }
 
 int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,

@@ -129,6 +129,7 @@ struct LvDevCounters {
     uint32_t mlabSaturated;      // MLAB, MBOIT: 1 when a pixel's 16-bit fragment count saturated (the rasteriser dropped fragments)
     uint32_t mboitDegenerate;    // MBOIT (collect_stats): pixels with b_0 over the threshold that end as background (a_sum == 0)
     uint32_t mboitBoxOrd[6];     // MBOIT: lv_f2ord of max(-x), max(-y), max(-z), max(x), max(y), max(z) over the line points
+    uint32_t mboitOverflow;      // MBOIT, streamed storage: 1 when a pixel holds more kept fragments than its 64-bit sums are exact for
 };
 
 struct f3 { float x, y, z; };

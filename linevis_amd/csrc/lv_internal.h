@@ -81,6 +81,7 @@ struct LvOptions {
     uint32_t mboitNumMoments = 4;             // mboit_num_moments: 4 | 6 | 8 power moments of rendering mode 6 (MBOITRenderer.cpp:41-45)
     float mboitOverestimation = 0.1f;         // mboit_overestimation: overestimationBeta in [0, 1] (MBOITRenderer.cpp:45,609)
     float mboitMomentBias = 0.0f;             // mboit_moment_bias: 0 = auto (5e-7 / 5e-6 / 5e-5 for 4 / 6 / 8, MBOITRenderer.cpp:136-145), else (0, 0.1]
+    bool mboitStreamed = false;               // mboit_fragment_storage: false = "pool" (default), true = "streamed" (k_mboit_stream_pass: no fragment pool)
     // EAW denoiser of the RTAO pass (ambient_occlusion_denoiser; AO defaults of createDenoiserObject, Denoiser.cpp:54-62)
     bool eawEnabled = false;
     uint32_t eawIterations = 3;               // eaw_denoiser_iterations (GUI range 0..5, EAWDenoiser.cpp:437)
@@ -239,6 +240,9 @@ struct lv_ctx {
     uint64_t mlabPoolSlots = 0;               // modes 3 and 6: fragment slots the largest frame so far needed (the pool never drops one)
     uint32_t mboitBoxOrd[6] = {0, 0, 0, 0, 0, 0};   // mode 6: k_mboit_points_box's result for the current line points (lv_bvh_build resets)
     bool mboitBoxValid = false;
+    LvDeviceBuffer mboitAccum;                // mode 6, streamed storage: 1 + N moment sums and 4 colour sums of 8 B per padded pixel (addressed like ppllCount)
+    bool mboitStreamLast = false, mboitStreamFull = false;   // the last frame was a streamed mode-6 frame / one over the whole viewport
+    uint32_t mboitStreamW = 0, mboitStreamH = 0, mboitStreamN = 0, mboitStreamTile[2] = {0, 0};   // that frame's viewport, moment count and ppll tile
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
     LvDeviceBuffer accum;                     // rgba8 of the previous accumulated frame (full viewport)
@@ -376,6 +380,8 @@ inline void lv_invalidate_bake(lv_ctx* ctx) {
 int lv_frame_depth_range(lv_ctx* ctx);
 int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
                                uint32_t h, uint8_t* out);
+int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloats);
+int lv_mboit_stream_overflow(lv_ctx* ctx);
 int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
                                 uint32_t h, float logDepthMin, float logDepthMax, float* outMoments, uint8_t* out);
 int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numNodes, const uint32_t* start,

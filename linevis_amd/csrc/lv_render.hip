@@ -2507,6 +2507,362 @@ __global__ __launch_bounds__(LV_BLOCK) void k_mboit_points_box(const lv_line_poi
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// mboit_fragment_storage = streamed: mode 6 without a fragment pool.  As the reference's MBOITRenderer the frame draws the geometry
+// twice and accumulates with atomics -- here 64-bit integer atomics on the fixed-point terms of lv_mboit.h, so every sum is the sum
+// the pooled sweeps form and the frame equals the pooled one byte for byte.  Per padded pixel (addressed like ppllCount) the
+// accumulators hold 1 + N moment sums and 4 colour sums of 8 bytes each; ppllCount is the full 32-bit count of kept fragments.
+//   k_mboit_stream_pass   the segment rasteriser (stages A and B of k_ppll_raster_prism, same work list and requested-pixel mask)
+//                         and the fragment stage in one launch: covered triangles go to a second wave-local LDS queue as
+//                         (pixel, leaf | triangle << 26) and stage C shades 64 of them at a time, one lane each, exactly as
+//                         k_ppll_shade_prism<..., LV_ENTRY_MBOIT> does.  colourPass = 0: the fragment's moment terms (and 1 on the
+//                         pixel's count); colourPass = 1: the pixel's moment sums are complete, the fragment adds its colour terms.
+//   k_mboit_stream_blend  the cells and groups of k_mboit_resolve over the frame's tile list: lv_mboit_blend, the degenerate-pixel
+//                         counter, the maximum count and the overflow flag (a count above LV_MBOIT_STREAM_MAX_COUNT)
+// The sums are exact while |sum| < 2^63: terms saturate at 1024 * 2^36 = 2^46, so for up to 2^17 - 1 kept fragments per pixel.
+#define LV_MBOIT_STREAM_MAX_COUNT 131071u
+#ifndef LV_MBOIT_STREAM_MIN_WAVES
+#define LV_MBOIT_STREAM_MIN_WAVES 2   // the fragment stage alone holds 164 VGPRs (LV_PRISM_SHADE_MIN_WAVES)
+#endif
+#define LV_MBOIT_STREAM_QUEUE 128u   // fragments a wave holds between stages B and C (>= 2 * LV_WAVE, power of two)
+
+template <int N>
+__device__ __forceinline__ void lv_mboit_stream_moments(unsigned long long* a, float alpha, float viewDepth, const LvMboitParams& M) {
+    long long s[1 + N];
+#pragma unroll
+    for (int k = 0; k <= N; k++) s[k] = 0;
+    lv_mboit_moments<N>(alpha, viewDepth, M, s);
+#pragma unroll
+    for (int k = 0; k <= N; k++)
+        if (s[k] != 0) atomicAdd(a + k, (unsigned long long)s[k]);
+}
+template <int N>
+__device__ __forceinline__ void lv_mboit_stream_colour(unsigned long long* a, const f4& color, float viewDepth, const LvMboitParams& M) {
+    long long s[1 + N];
+#pragma unroll
+    for (int k = 0; k <= N; k++) s[k] = (long long)a[k];   // complete: the moments launch has finished
+    float b_0, nb[N];
+    LvMboitPixel<N> X;
+    if (!lv_mboit_pixel<N>(s, M, b_0, nb, X)) return;
+    long long c[4] = {0, 0, 0, 0};
+    lv_mboit_colour<N>(color, viewDepth, b_0, X, M, c);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (c[k] != 0) atomicAdd(a + 1 + N + k, (unsigned long long)c[k]);
+}
+
+template <int NT, int SHADE, int FAST>
+__global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_mboit_stream_pass(const LvUniforms U, const LvSceneDev S,
+                                                                   const LvMboitParams M, const uint32_t* __restrict__ startOffset,
+                                                                   uint32_t* __restrict__ fragCount, unsigned long long* acc,
+                                                                   LvDevCounters* dc, uint32_t allRequested,
+                                                                   const uint32_t* __restrict__ leafList, uint32_t numMoments,
+                                                                   uint32_t colourPass) {
+    __shared__ uint32_t s_qLeaf[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE], s_qPix[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE];
+    __shared__ uint32_t s_fFrag[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE], s_fPix[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE];
+    __shared__ float s_seg[LV_BLOCK / LV_WAVE][20][LV_WAVE];
+    __shared__ float s_prismRing[4 * LV_PRISM_MAX_SUBDIV];
+    // what stages A and B keep per lane, parked here while stage C runs: the fragment stage needs the registers (with them live
+    // across it the kernel spilled to scratch at two waves per SIMD)
+    __shared__ uint32_t s_park[19][LV_BLOCK];
+    if (threadIdx.x < LV_PRISM_MAX_SUBDIV) {
+        s_prismRing[threadIdx.x] = S.prism.c[threadIdx.x];
+        s_prismRing[LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.s[threadIdx.x];
+        s_prismRing[2 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.cp[threadIdx.x];
+        s_prismRing[3 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.sn[threadIdx.x];
+    }
+    __syncthreads();
+    const LvPrismDev& R = S.prism;
+    const uint32_t N = NT > 0 ? uint32_t(NT) : R.n;
+    const unsigned lane = lv_lane();
+    uint32_t* qLeaf = s_qLeaf[threadIdx.x >> 6];
+    uint32_t* qPix = s_qPix[threadIdx.x >> 6];
+    uint32_t* fFrag = s_fFrag[threadIdx.x >> 6];
+    uint32_t* fPix = s_fPix[threadIdx.x >> 6];
+    float (*segLds)[LV_WAVE] = s_seg[threadIdx.x >> 6];
+    const f3 o = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
+    float mx[4], my[4], mw[4];
+    lv_clip_rows(U, mx, my, mw);
+    const float halfW = 0.5f * float(U.width), halfH = 0.5f * float(U.height);
+    const float wEps = 1e-3f * U.nearDist;
+    const float tLo = 0.0001f, tHi = __uint_as_float(__float_as_uint(1000.0f) + 1u);
+    const size_t accStride = 1u + numMoments + 4u;
+    const bool count = colourPass == 0u, stats = M.stats != 0u && count;   // the statistics are the moments launch's
+    unsigned qHead = 0u, qCount = 0u;   // (pixel, segment) pairs (wave-uniform)
+    unsigned fHead = 0u, fCount = 0u;   // covered triangles (wave-uniform)
+    unsigned long long tests = 0, hits = 0;
+    uint32_t keptSum = 0u;
+    // stage A's walk over the lane's segment: candidate rectangle, position in it, oriented box
+    uint32_t leafA = 0u;
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1, px = 0, py = 0;
+    float ax = 1.0f, ay = 0.0f, cx0 = 0.0f, cy0 = 0.0f, aMid = 0.0f, aHalf = 3.0e38f, nMid = 0.0f, nHalf = 3.0e38f;
+    bool more = false;
+
+    // stage C on the m <= 64 oldest fragments of the queue.  (Both stages are lambdas with ONE call site each: a second site keeps
+    // the compiler from inlining them, and their by-reference captures -- U and S among them -- then live in scratch.)
+    auto fragmentStage = [&](unsigned m) __attribute__((always_inline)) {
+        if (lane < m) {
+            const unsigned q = (fHead + lane) & (LV_MBOIT_STREAM_QUEUE - 1u);
+            const uint32_t w0 = fPix[q], w1 = fFrag[q];
+            const uint32_t px = w0 & 0xFFFFu, py = w0 >> 16;
+            const uint32_t leaf = w1 & 0x03FFFFFFu, tt = w1 >> 26;
+            const float aoTexel = (U.useAmbientOcclusion && !U.aoPrebaked) ? S.ao[size_t(py) * U.width + px] : 1.0f;
+            f3 oo, d;
+            lv_primary_ray(U, px, py, 0.5f, 0.5f, oo, d);
+            const LvRasterQuad rq = lv_make_raster_quad(U, px, py);
+            bool kept;
+            float depth;
+            const f4 color = lv_shade_prism<SHADE, FAST>(S, U, s_prismRing, aoTexel, o, d, tLo, tHi, leaf, tt, rq, U.ppllRasterColour != 0u, depth, kept);
+            if (kept) {   // (only the `kept` rules discard in mode 6)
+                const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+                const float z = lv_view_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
+                unsigned long long* a = acc + size_t(addr) * accStride;
+                if (count) {
+                    if (numMoments == 4u) lv_mboit_stream_moments<4>(a, color.w, z, M);
+                    else if (numMoments == 6u) lv_mboit_stream_moments<6>(a, color.w, z, M);
+                    else lv_mboit_stream_moments<8>(a, color.w, z, M);
+                    atomicAdd(&fragCount[addr], 1u);
+                    keptSum++;
+                    if (stats) hits++;
+                } else {
+                    if (numMoments == 4u) lv_mboit_stream_colour<4>(a, color, z, M);
+                    else if (numMoments == 6u) lv_mboit_stream_colour<6>(a, color, z, M);
+                    else lv_mboit_stream_colour<8>(a, color, z, M);
+                }
+            }
+        }
+        fHead = (fHead + m) & (LV_MBOIT_STREAM_QUEUE - 1u);
+        fCount -= m;
+    };
+
+    // stage B on the m <= 64 oldest pairs of the queue (k_ppll_raster_prism's, the covered triangles queued instead of recorded);
+    // flush: the wave's last batch -- stage C also takes what is left in its queue
+    auto coverageStage = [&](unsigned m, bool flush) __attribute__((always_inline)) {
+        unsigned mask = 0u;
+        uint32_t leaf = 0u, pix = 0u;
+        if (lane < m) {
+            const unsigned q = (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u);
+            leaf = qLeaf[q];
+            pix = qPix[q];
+            const uint32_t px = pix & 0xFFFFu, py = pix >> 16;
+            const f3 d = lv_prism_cov_dir(R, px, py);
+            const uint32_t sl = leaf >> 26;
+            leaf &= 0x03FFFFFFu;
+            LvPrismPoint pt[2];
+            uint32_t pi[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                pt[e].centre = mk3(segLds[9 * e + 0][sl], segLds[9 * e + 1][sl], segLds[9 * e + 2][sl]);
+                pt[e].normal = mk3(segLds[9 * e + 3][sl], segLds[9 * e + 4][sl], segLds[9 * e + 5][sl]);
+                pt[e].binormal = mk3(segLds[9 * e + 6][sl], segLds[9 * e + 7][sl], segLds[9 * e + 8][sl]);
+                pi[e] = __float_as_uint(segLds[18 + e][sl]);
+            }
+            mask = lv_prism_coverage_pts<NT>(R, pt, pi, R.radius, o, d);
+            if (stats) tests++;
+        }
+        while (true) {
+            const bool hit = mask != 0u;
+            const unsigned long long hm = __ballot(hit);
+            if (hm == 0ull && !(flush && fCount > 0u)) break;
+            if (hit) {
+                const unsigned tt = unsigned(__ffs(int(mask))) - 1u;
+                mask &= mask - 1u;
+                const unsigned q = (fHead + fCount + unsigned(__popcll(hm & ((1ull << lane) - 1ull)))) & (LV_MBOIT_STREAM_QUEUE - 1u);
+                fPix[q] = pix;
+                fFrag[q] = leaf | (tt << 26);
+            }
+            fCount += unsigned(__popcll(hm));
+            if (fCount >= LV_WAVE || hm == 0ull) {
+                uint32_t* park = &s_park[0][threadIdx.x];
+                const float pf[8] = {ax, ay, cx0, cy0, aMid, aHalf, nMid, nHalf};
+                const uint32_t pu[11] = {mask, leaf, pix, leafA, uint32_t(x0), uint32_t(x1), uint32_t(y0), uint32_t(y1), uint32_t(px),
+                                         uint32_t(py), more ? 1u : 0u};
+#pragma unroll
+                for (int i = 0; i < 8; i++) park[i * LV_BLOCK] = __float_as_uint(pf[i]);
+#pragma unroll
+                for (int i = 0; i < 11; i++) park[(8 + i) * LV_BLOCK] = pu[i];
+                fragmentStage(fCount < LV_WAVE ? fCount : LV_WAVE);
+                ax = __uint_as_float(park[0]); ay = __uint_as_float(park[LV_BLOCK]); cx0 = __uint_as_float(park[2 * LV_BLOCK]);
+                cy0 = __uint_as_float(park[3 * LV_BLOCK]); aMid = __uint_as_float(park[4 * LV_BLOCK]); aHalf = __uint_as_float(park[5 * LV_BLOCK]);
+                nMid = __uint_as_float(park[6 * LV_BLOCK]); nHalf = __uint_as_float(park[7 * LV_BLOCK]);
+                mask = park[8 * LV_BLOCK]; leaf = park[9 * LV_BLOCK]; pix = park[10 * LV_BLOCK]; leafA = park[11 * LV_BLOCK];
+                x0 = int(park[12 * LV_BLOCK]); x1 = int(park[13 * LV_BLOCK]); y0 = int(park[14 * LV_BLOCK]); y1 = int(park[15 * LV_BLOCK]);
+                px = int(park[16 * LV_BLOCK]); py = int(park[17 * LV_BLOCK]); more = park[18 * LV_BLOCK] != 0u;
+            }
+        }
+        qHead = (qHead + m) & (LV_PRISM_RASTER_QUEUE - 1u);
+        qCount -= m;
+    };
+
+    const uint32_t waveId = blockIdx.x * (LV_BLOCK / LV_WAVE) + (threadIdx.x >> 6), numWaves = gridDim.x * (LV_BLOCK / LV_WAVE);
+    const uint32_t numItems = leafList ? dc->prismListCount : S.numSegs;
+    for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
+        // stage A: k_ppll_raster_prism's, statement for statement (the candidate set decides nothing, the coverage test does)
+        const bool valid = itemBase + lane < numItems;
+        const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
+        leafA = leaf;
+        x0 = 0; x1 = -1; y0 = 0; y1 = -1;
+        ax = 1.0f; ay = 0.0f; cx0 = 0.0f; cy0 = 0.0f; aMid = 0.0f; aHalf = 3.0e38f; nMid = 0.0f; nHalf = 3.0e38f;
+        if (valid) {
+            const float4 pa = S.segs[2 * size_t(leaf)], pb = S.segs[2 * size_t(leaf) + 1];
+            uint32_t pi[2];
+            LvPrismPoint pt[2];
+            lv_prism_frames(S, leaf, pa, pb, pt, pi);
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                segLds[9 * e + 0][lane] = pt[e].centre.x; segLds[9 * e + 1][lane] = pt[e].centre.y; segLds[9 * e + 2][lane] = pt[e].centre.z;
+                segLds[9 * e + 3][lane] = pt[e].normal.x; segLds[9 * e + 4][lane] = pt[e].normal.y; segLds[9 * e + 5][lane] = pt[e].normal.z;
+                segLds[9 * e + 6][lane] = pt[e].binormal.x; segLds[9 * e + 7][lane] = pt[e].binormal.y; segLds[9 * e + 8][lane] = pt[e].binormal.z;
+                segLds[18 + e][lane] = __uint_as_float(pi[e]);
+            }
+            bool axisOk = true;
+            float wcx[2], wcy[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const f3 v = pt[e].centre;
+                const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
+                const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
+                const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
+                axisOk = axisOk && cw > wEps;
+                wcx[e] = (ccx / cw + 1.0f) * halfW;
+                wcy[e] = (ccy / cw + 1.0f) * halfH;
+            }
+            if (axisOk) {
+                const float dx = wcx[1] - wcx[0], dy = wcy[1] - wcy[0], l2 = dx * dx + dy * dy;
+                if (l2 > 1e-12f && l2 < 1e30f) { const float il = 1.0f / sqrtf(l2); ax = dx * il; ay = dy * il; }
+                cx0 = wcx[0]; cy0 = wcy[0];
+            }
+            float lox = 3.0e38f, hix = -3.0e38f, loy = 3.0e38f, hiy = -3.0e38f;
+            float loa = 3.0e38f, hia = -3.0e38f, lon = 3.0e38f, hin = -3.0e38f;
+            bool anyFront = false, anyBehind = false;
+            for (uint32_t k = 0; k < N; k++) {
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const f3 v = lv_prism_pos(pt[e], lv_prism_dir(pt[e], R.cp[k], R.s[k]), R.radius);
+                    const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
+                    if (cw > wEps) {
+                        const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
+                        const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
+                        const float wx = (ccx / cw + 1.0f) * halfW, wy = (ccy / cw + 1.0f) * halfH;
+                        lox = fminf(lox, wx); hix = fmaxf(hix, wx); loy = fminf(loy, wy); hiy = fmaxf(hiy, wy);
+                        const float ta = (wx - cx0) * ax + (wy - cy0) * ay, tn = (wy - cy0) * ax - (wx - cx0) * ay;
+                        loa = fminf(loa, ta); hia = fmaxf(hia, ta); lon = fminf(lon, tn); hin = fmaxf(hin, tn);
+                        anyFront = true;
+                    } else anyBehind = true;
+                }
+            }
+            if (anyFront) {
+                if (anyBehind) { lox = 0.0f; loy = 0.0f; hix = float(U.width); hiy = float(U.height); }
+                else if (axisOk) {
+                    aMid = 0.5f * (loa + hia); aHalf = 0.5f * (hia - loa) + LV_PRISM_BBOX_MARGIN;
+                    nMid = 0.5f * (lon + hin); nHalf = 0.5f * (hin - lon) + LV_PRISM_BBOX_MARGIN;
+                }
+                const float fx0 = fmaxf(ceilf(lox - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
+                const float fy0 = fmaxf(ceilf(loy - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
+                const float fx1 = fminf(floorf(hix + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.width) - 1.0f);
+                const float fy1 = fminf(floorf(hiy + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.height) - 1.0f);
+                if (fx0 <= fx1 && fy0 <= fy1) { x0 = int(fx0); x1 = int(fx1); y0 = int(fy0); y1 = int(fy1); }
+            }
+        }
+        px = x0; py = y0;
+        more = valid && x1 >= x0 && y1 >= y0;
+        const bool lastItem = itemBase + numWaves * LV_WAVE >= numItems;   // (overflow: numItems < 2^26)
+        while (true) {
+            const bool drain = !__any(more);   // every rectangle walked: the rest of the pairs, 64 at a time
+            bool cand = false;
+            if (more) {
+                const float qx = (float(px) + 0.5f) - cx0, qy = (float(py) + 0.5f) - cy0;
+                cand = fabsf((qx * ax + qy * ay) - aMid) <= aHalf && fabsf((qy * ax - qx * ay) - nMid) <= nHalf;
+                if (cand && !allRequested)
+                    cand = startOffset[lv_ppll_addr(uint32_t(px), uint32_t(py), U.ppllPaddedW, U.ppllTileW, U.ppllTileH)] == 0u;
+            }
+            const unsigned long long cm = __ballot(cand);
+            if (cand) {
+                const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
+                qLeaf[q] = leafA | (lane << 26);
+                qPix[q] = uint32_t(px) | (uint32_t(py) << 16);
+            }
+            qCount += unsigned(__popcll(cm));
+            if (qCount >= LV_WAVE || drain) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE, lastItem && drain && qCount <= LV_WAVE);
+            if (drain && qCount == 0u) break;   // (the next 64 segments replace the frames in LDS)
+            if (more) {
+                if (++px > x1) { px = x0; more = ++py <= y1; }
+            }
+        }
+    }
+    if (count) {
+#pragma unroll
+        for (int ofs = 32; ofs > 0; ofs >>= 1) keptSum += (uint32_t)__shfl_xor(keptSum, ofs, 64);
+        if (lane == 0u && keptSum > 0u) atomicAdd(&dc->fragCounter, keptSum);   // fragCounter of the reference: every kept fragment
+    }
+    if (stats) {
+        tests = lv_wave_sum_u64(tests);
+        hits = lv_wave_sum_u64(hits);
+        if (lane == 0u && tests) atomicAdd(&dc->prims, tests);
+        if (lane == 0u && hits) atomicAdd(&dc->hits, hits);
+    }
+}
+
+// One lane per pixel, one wave per workgroup, the cells and groups of k_mboit_resolve
+__global__ __launch_bounds__(LV_WAVE) void k_mboit_stream_blend(const LvUniforms U, const LvTiles T, const LvMboitParams M,
+                                                                const unsigned long long* __restrict__ acc,
+                                                                const uint32_t* __restrict__ fragCount, uint32_t* __restrict__ out,
+                                                                uint32_t numGroups, uint32_t numMoments, LvDevCounters* dc) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t maxCount = 0u, degenerate = 0u;
+    const size_t accStride = 1u + numMoments + 4u;
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        const bool inTile = lx < T.tileW && ly < T.tileH;
+        if (!__any(inTile)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        const uint32_t outIndex = (tile * T.tileH + ly) * T.tileW + lx;
+        long long c[4] = {0, 0, 0, 0};
+        float b_0 = 0.0f;
+        if (inTile && x < U.width && y < U.height) {
+            const uint32_t addr = lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+            maxCount = max(maxCount, fragCount[addr]);
+            const unsigned long long* a = acc + size_t(addr) * accStride;
+            b_0 = lv_mboit_unfixed((long long)a[0]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) c[k] = (long long)a[1u + numMoments + k];
+        }
+        const bool covered = !(b_0 < LV_MBOIT_B0_MIN);   // lv_mboit_pixel's threshold
+        if (covered && c[3] == 0) degenerate++;
+        const uint32_t packed = lv_mboit_blend(U, covered, b_0, c);
+        if (inTile) out[outIndex] = packed;
+    }
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) {
+        maxCount = max(maxCount, (uint32_t)__shfl_xor(maxCount, ofs, 64));
+        degenerate += (uint32_t)__shfl_xor(degenerate, ofs, 64);
+    }
+    if (lane == 0 && maxCount > 0u) atomicMax(&dc->maxDepthComplexity, maxCount);
+    if (lane == 0 && maxCount > LV_MBOIT_STREAM_MAX_COUNT) atomicOr(&dc->mboitOverflow, 1u);
+    if (M.stats && lane == 0 && degenerate > 0u) atomicAdd(&dc->mboitDegenerate, degenerate);
+}
+
+// lv_mboit_get_moments: b_0 and the normalised b_1 ... b_N of every pixel of the viewport, row-major, zeros under the threshold
+// (the expressions of lv_mboit_pixel on the frame's moment sums)
+__global__ __launch_bounds__(LV_BLOCK) void k_mboit_stream_moments(const unsigned long long* __restrict__ acc, uint32_t width,
+                                                                  uint32_t height, uint32_t paddedW, uint32_t tileW, uint32_t tileH,
+                                                                  uint32_t numMoments, float* __restrict__ out) {
+    const size_t p = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (p >= size_t(width) * height) return;
+    const uint32_t x = uint32_t(p % width), y = uint32_t(p / width);
+    const unsigned long long* a = acc + size_t(lv_ppll_addr(x, y, paddedW, tileW, tileH)) * (1u + numMoments + 4u);
+    float* o = out + p * (1u + numMoments);
+    const float b_0 = lv_mboit_unfixed((long long)a[0]);
+    const bool covered = !(b_0 < LV_MBOIT_B0_MIN);
+    o[0] = covered ? b_0 : 0.0f;
+    for (uint32_t k = 0; k < numMoments; k++) o[1u + k] = covered ? lv_mboit_unfixed((long long)a[1u + k]) / b_0 : 0.0f;
+}
+
 // ================================================================ depth range
 __global__ __launch_bounds__(LV_BLOCK) void k_depth_minmax(const LvUniforms U, const lv_line_point* __restrict__ points,
                                                            uint32_t numPoints, LvDevCounters* dc) {
@@ -3281,6 +3637,144 @@ static int lv_mboit_resolve(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, 
     return LV_OK;
 }
 
+// A mode-6 frame with mboit_fragment_storage = streamed: clear, the two launches of k_mboit_stream_pass, the blend.  No record pool,
+// no fragment pool, no scan, no regrowth; the only host synchronisation is the read-back of the line points' box, once per
+// acceleration-structure build.  The blend's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
+#ifndef LV_MBOIT_STREAM_BLOCKS_PER_CU
+#define LV_MBOIT_STREAM_BLOCKS_PER_CU 2   // four waves per workgroup, LV_MBOIT_STREAM_MIN_WAVES per SIMD
+#endif
+static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t numTiles, uint32_t gridTiles,
+                                 bool stats, uint32_t* out, LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (!lv_ppll_prism_source(ctx) || (ctx->opt.useRibbons && ctx->opt.helicityBands))
+        return lv_fail(ctx, LV_E_INVALID, "mboit_fragment_storage = streamed: band data with rotating helicity bands has no prism fragment stage");
+    if (ctx->opt.ppllPrismLbvhWalk)
+        return lv_fail(ctx, LV_E_INVALID, "mboit_fragment_storage = streamed runs the segment rasteriser: ppll_prism_rasteriser = lbvh "
+                                          "is not supported");
+    lv_fill_prism(ctx, U, S.prism);
+    const uint32_t N = ctx->opt.mboitNumMoments;
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
+    const size_t accBytes = padded4 * 4 * size_t(1u + N + 4u) * 8;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->mboitAccum, accBytes))) return rc;
+    ctx->ppllPoolNodes = 0;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    if (!ctx->mboitBoxValid) {
+        // first frame on these line points: their box for the log depth range (words 2 ... 7 of the pinned block)
+        if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
+        if (ctx->numPoints)
+            k_mboit_points_box<<<std::min(nblocks(ctx->numPoints), 256u), LV_BLOCK, 0, st>>>(S.points, ctx->numPoints, dc);
+        LV_HIP(ctx, hipMemcpyAsync((void*)(ctx->pinned + 2), dc->mboitBoxOrd, 24, hipMemcpyDeviceToHost, st));
+        LV_HIP(ctx, hipStreamSynchronize(st));
+        for (int k = 0; k < 6; k++) ctx->mboitBoxOrd[k] = ctx->pinned[2 + k];
+        ctx->mboitBoxValid = true;
+    }
+    const LvMboitParams M = lv_mboit_params(ctx, U, ctx->mboitBoxOrd, stats);
+    const bool allRequested = ctx->tilesCoverViewport;
+    k_ppll_clear<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
+            (uint4*)ctx->ppllStart.ptr, (uint4*)ctx->ppllCount.ptr, padded4, dc, allRequested ? 0u : 0xFFFFFFFFu,
+            (allRequested && stats) ? (unsigned long long)U.width * U.height : 0ull);
+    LV_HIP(ctx, hipMemsetAsync(ctx->mboitAccum.ptr, 0, accBytes, st));
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    uint32_t* coarse = nullptr;
+    if (!allRequested) {
+        const size_t cells = size_t((U.width + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE) * ((U.height + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE);
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllCoarse, cells * 4))) return rc;
+        coarse = (uint32_t*)ctx->ppllCoarse.ptr;
+        LV_HIP(ctx, hipMemsetAsync(coarse, 0, cells * 4, st));
+    }
+    uint32_t* leafList = nullptr;
+    // LV_KERNEL_PPLL_RASTER: one launch per pass, the first with what a sharded frame runs in front of it (as in pooled storage)
+    const bool rasterTimed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) != 0u;
+    if (rasterTimed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
+    if (allRequested) {}   // (k_ppll_clear marked every pixel)
+    else if (stats) k_ppll_mark_tiles<true><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
+    else k_ppll_mark_tiles<false><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
+    if (!allRequested && S.numSegs != 0) {
+        if ((rc = lv_buf_reserve(ctx, ctx->prismLeafList, size_t(S.numSegs) * 4))) return rc;
+        leafList = (uint32_t*)ctx->prismLeafList.ptr;
+        const uint32_t cullGrid = (S.numSegs + LV_CULL_PER_BLOCK - 1u) / LV_CULL_PER_BLOCK;
+        k_ppll_cull_segments<<<cullGrid, LV_BLOCK, 0, st>>>(U, S, coarse, leafList, dc);
+    }
+    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
+    // the variants lv_frame_render selects for the pooled fragment stage; shading_numerics = fast: plain tubes with the raster colour
+    const bool fastShade = ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
+#define LV_LAUNCH_STREAM(NT, SH, FA)                                                                                            \
+    k_mboit_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, M, (const uint32_t*)ctx->ppllStart.ptr,               \
+            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->mboitAccum.ptr, dc, allRequested ? 1u : 0u, leafList, N, pass)
+#define LV_LAUNCH_STREAM2(NT)                                                        \
+    do {                                                                             \
+        if (fastShade) LV_LAUNCH_STREAM(NT, LV_SHADE_PLAIN, 2);                      \
+        else if (S.prism.bands) LV_LAUNCH_STREAM(NT, LV_SHADE_BANDS, 0);             \
+        else if (U.useHelicityBands) LV_LAUNCH_STREAM(NT, LV_SHADE_HELICITY, 0);     \
+        else LV_LAUNCH_STREAM(NT, LV_SHADE_PLAIN, 0);                                \
+    } while (0)
+    for (uint32_t pass = 0u; pass < 2u; pass++) {
+        if (rasterTimed && pass) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
+        if (S.numSegs != 0) {
+            if (S.prism.n == 6u) LV_LAUNCH_STREAM2(6); else LV_LAUNCH_STREAM2(0);
+        }
+        if (rasterTimed) {
+            LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
+            ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
+        }
+    }
+#undef LV_LAUNCH_STREAM2
+#undef LV_LAUNCH_STREAM
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
+    const uint64_t groups64 = uint64_t(numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;   // 8 x 8 cells of the 64 x 64 groups
+    if (groups64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(groups64);
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_mboit_stream_blend<<<numGroups, LV_WAVE, 0, st>>>(
+            U, T, M, (const unsigned long long*)ctx->mboitAccum.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, N, dc)));
+    ctx->mboitStreamLast = true;
+    ctx->mboitStreamFull = allRequested;
+    ctx->mboitStreamW = U.width;
+    ctx->mboitStreamH = U.height;
+    ctx->mboitStreamN = N;
+    ctx->mboitStreamTile[0] = U.ppllTileW;
+    ctx->mboitStreamTile[1] = U.ppllTileH;
+    return LV_OK;
+}
+
+// the overflow flag of the last frame when that was a streamed mode-6 frame (host-synchronous)
+int lv_mboit_stream_overflow(lv_ctx* ctx) {
+    if (!ctx->mboitStreamLast || !ctx->counters.ptr) return LV_OK;
+    uint32_t flag = 0u;
+    LV_HIP(ctx, hipMemcpy(&flag, &((const LvDevCounters*)ctx->counters.ptr)->mboitOverflow, 4, hipMemcpyDeviceToHost));
+    if (flag)
+        return lv_fail(ctx, LV_E_CAPACITY, "MBOIT (streamed): a pixel is covered by more than %u kept fragments (the 64-bit sums are "
+                                           "exact up to that count)", LV_MBOIT_STREAM_MAX_COUNT);
+    return LV_OK;
+}
+
+// lv_mboit_get_moments
+int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloats) {
+    if (!ctx->mboitStreamLast || !ctx->mboitStreamFull || !ctx->mboitAccum.ptr || ctx->mboitStreamW != ctx->width ||
+        ctx->mboitStreamH != ctx->height)
+        return lv_fail(ctx, LV_E_STATE, "lv_mboit_get_moments: the last frame was not a mode-6 frame with mboit_fragment_storage = "
+                                        "streamed over the whole viewport");
+    const uint64_t need = uint64_t(ctx->mboitStreamW) * ctx->mboitStreamH * (1u + ctx->mboitStreamN);
+    if (capacityFloats < need)
+        return lv_fail(ctx, LV_E_INVALID, "lv_mboit_get_moments: out holds %llu floats, need %llu", (unsigned long long)capacityFloats,
+                       (unsigned long long)need);
+    int rc;
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, size_t(need) * 4))) return rc;
+    const uint64_t pixels = uint64_t(ctx->mboitStreamW) * ctx->mboitStreamH;
+    k_mboit_stream_moments<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
+            (const unsigned long long*)ctx->mboitAccum.ptr, ctx->mboitStreamW, ctx->mboitStreamH, ctx->ppllPaddedW, ctx->mboitStreamTile[0],
+            ctx->mboitStreamTile[1], ctx->mboitStreamN, (float*)ctx->scratchRays.ptr);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(out, ctx->scratchRays.ptr, size_t(need) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LV_OK;
+}
+
 int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
                     uint32_t tileH, void* outDevice) {
     if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
@@ -3289,6 +3783,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
     const bool mboit = mode == LV_RENDERING_MODE_MBOIT;
     const bool mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
+    ctx->mboitStreamLast = false;   // (set again at the end of a streamed mode-6 frame)
+    ctx->mboitStreamFull = false;
     const char* const poolName = mboit ? "MBOIT" : "MLAB";
     if (mlab && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
@@ -3546,6 +4042,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
 #undef LV_LAUNCH_RT_PRE
 #undef LV_LAUNCH_RT
         }
+    } else if (mboit && ctx->opt.mboitStreamed) {
+        if ((rc = lv_mboit_stream_frame(ctx, U, S, T, numTiles, gridTiles, stats, out, dc))) return rc;
     } else {
         // reallocateFragmentBuffer, PerPixelLinkedListLineRenderer.cpp:251-357
         // gather(): fragments of the rasterised programmable-pull prism (the reference's geometry, default) or capsule entry hits

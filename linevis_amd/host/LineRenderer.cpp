@@ -771,7 +771,7 @@ bool HipMBOITRenderer::setNewSettings(const SettingsMap& settings) {
     if (settings.getValueOpt("numMoments", moments) && (moments == 4 || moments == 6 || moments == 8)) numMoments = moments;
     settings.getValueOpt("overestimationBeta", overestimationBeta);
     for (const char* key : {"ppll_expected_avg_depth_complexity", "ppll_tile_width", "ppll_tile_height", "ppll_fragment_source",
-                            "ppll_fragment_colour", "ppll_prism_rasteriser", "mboit_moment_bias"}) {
+                            "ppll_fragment_colour", "ppll_prism_rasteriser", "mboit_moment_bias", "mboit_fragment_storage"}) {
         std::string s;
         if (settings.getValueOpt(key, s)) setOption(key, s);
     }
