@@ -349,6 +349,13 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   kernel after the RTAO pass shades them; "false" = one pass after the other as in VulkanRayTracer::render (VulkanRayTracer.cpp:
  *   131-154); "auto" = overlapped while the tile list is at most half a 1920 x 1080 frame (a sharded frame's rank), one after the
  *   other for a whole frame on one GPU, where both passes are throughput-bound.  The frame is byte-identical either way,
+ *   ao_ray_generation (build-owned, no counterpart): "per_pixel" (default: with ambient_occlusion_samples_per_frame a multiple of 64 a
+ *   batch of 64 AO rays is 64 samples of one pixel, and the sample kernel looks that pixel up once per batch) | "per_ray" (every ray
+ *   looks its pixel up; always the path of other sample counts, of collect_stats and of the prebaker); the AO image is bit-identical,
+ *   traversal_reciprocal (build-owned, no counterpart; lv_trace_rays and lv_trace_rays_triangles only): "ieee" (default) | "hardware" =
+ *   the node steps of these two entry points use the hardware reciprocal of the direction, as the RTAO sample kernel always does; the
+ *   hits are bit-identical (the slab test's margins cover the <= 1 ulp; leaf tests divide by IEEE rules) -- a way to put arbitrary rays,
+ *   axis-parallel and denormal directions among them, through that arithmetic,
  *   dispatch_order (build-owned, no counterpart): "cost" (default: the tile kernels start their 64x64-pixel groups heaviest-of-
  *   the-previous-frame first, see lv_get_dispatch_order) | "as_numbered" (tile-list order); the image is the same,
  *   rtao_prebaker_iterations (128), rtao_prebaker_samples_per_frame (4), rtao_prebaker_num_tube_subdivisions (8): the

@@ -701,6 +701,14 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         else if (strcmp(value, "true") == 0 || strcmp(value, "1") == 0) o.overlapPrimaryPasses = 1;
         else if (strcmp(value, "false") == 0 || strcmp(value, "0") == 0) o.overlapPrimaryPasses = 0;
         else return bad();
+    } else if (k == "traversal_reciprocal") {
+        if (strcmp(value, "ieee") == 0) o.traceRaysHardwareInv = false;
+        else if (strcmp(value, "hardware") == 0) o.traceRaysHardwareInv = true;
+        else return bad();
+    } else if (k == "ao_ray_generation") {
+        if (strcmp(value, "per_pixel") == 0) o.aoPixelGeneration = true;
+        else if (strcmp(value, "per_ray") == 0) o.aoPixelGeneration = false;
+        else return bad();
     } else if (k == "tube_num_subdivisions") {
         if (!parseUint(value, u) || u < 3) return bad();
         o.tubeNumSubdivisions = u;

@@ -55,6 +55,8 @@ struct LvOptions {
     int overlapPrimaryPasses = 2;             // overlap_primary_passes: 0 = false, 1 = true, 2 = auto -- the colour pass' hit traces in one launch with the RTAO primaries (k_primary_pair)
     bool dispatchByCost = true;               // dispatch_order = cost | as_numbered (tile kernels: heaviest 64x64 group of the last frame first)
     bool aoJitterPrimary = true;              // :153
+    bool traceRaysHardwareInv = false;        // traversal_reciprocal = ieee (default) | hardware: lv_trace_rays / lv_trace_rays_triangles descend with lv_traversal_inv, the reciprocals of k_ao_rays (inspection of that path with arbitrary rays)
+    bool aoPixelGeneration = true;            // ao_ray_generation = per_pixel (default: k_ao_rays sets up a batch of 64 AO rays per pixel when spp is a multiple of 64) | per_ray (the general path, forced)
     uint32_t numSamplesPerFrame = 1;          // VulkanRayTracer.hpp:137 has 2 (interactive); offline default 1
     uint32_t numAccumulatedFrames = 1;        // :142 (32 interactive); > 1: the caller renders frame_number = 0, 1, ...
     uint32_t frameNumber = 0;                 // accumulatedFramesCounter, VulkanRayTracer.cpp:141

@@ -428,6 +428,58 @@ __device__ __forceinline__ size_t lv_ao_slot(const uint32_t* __restrict__ tileBa
     return lv_ao_group_base(tileCapacity, lo) + (ordinal - tileBase[lo]);
 }
 
+// Best hit of an AO ray in LDS, merged with one atomicMin per hit.  The AO value is t / aoRadius or 0 / 1: it never reads which
+// primitive was hit, and the primitive index in a (t, primitive) key only orders hits of EQUAL t, which give equal output.  So the
+// key is the bit pattern of t alone (t >= 0: the patterns order like the values); "no hit" is the pattern one above aoRadius's, which
+// no accepted hit (t <= aoRadius) can reach, so a hit at exactly aoRadius still differs from a miss.  As a float that pattern is the
+// next value above aoRadius: the culling interval of a ray without a hit is one ulp wider than aoRadius, which is conservative.
+// The wave-cooperative routines of the tile kernels keep 64-bit keys: they return the primitive.
+// LV_AO_KEY64=1 (measurement knob): the 64-bit key (t bits << 32 | primitive) of the earlier rounds.
+#ifndef LV_AO_KEY64
+#define LV_AO_KEY64 0
+#endif
+#if LV_AO_KEY64
+typedef unsigned long long lv_ao_key;
+__device__ __forceinline__ lv_ao_key lv_ao_key_none(float aoRadius) { return ((unsigned long long)__float_as_uint(aoRadius) << 32) | 0xFFFFFFFFull; }
+__device__ __forceinline__ lv_ao_key lv_ao_key_hit(float t, unsigned low) { return ((unsigned long long)__float_as_uint(t) << 32) | low; }
+__device__ __forceinline__ float lv_ao_key_t(lv_ao_key key) { return __uint_as_float(unsigned(key >> 32)); }
+#else
+typedef unsigned lv_ao_key;
+__device__ __forceinline__ lv_ao_key lv_ao_key_none(float aoRadius) { return __float_as_uint(aoRadius) + 1u; }
+__device__ __forceinline__ lv_ao_key lv_ao_key_hit(float t, unsigned) { return __float_as_uint(t); }
+__device__ __forceinline__ float lv_ao_key_t(lv_ao_key key) { return __uint_as_float(key); }
+#endif
+
+// One AO sample ray from its pixel's G-buffer entry and its sample index (sampleHemisphere + the frame transform,
+// VulkanRayTracedAmbientOcclusion.glsl:151-156,288-306): {o.xy}{o.z, d.x}{d.yz} into gen[0 .. 2].
+template <bool BAKE>
+__device__ __forceinline__ void lv_ao_generate_ray(const LvUniforms& U, float4 g0, float4 g1, float4 g2, uint32_t smpIdx, uint32_t spp,
+                                                   const uint2* __restrict__ lcgSkip, float2* gen) {
+    const uint32_t pix = __float_as_uint(g1.w);
+    const f3 pos = mk3(g0.x, g0.y, g0.z), T = mk3(g1.x, g1.y, g1.z), N = mk3(g2.x, g2.y, g2.z);
+    const f3 B = cross3(N, T);
+    uint32_t seed;
+    if (BAKE) {
+        const uint32_t sub = __float_as_uint(g2.w);
+        const uint2 skip = lcgSkip[2u * (sub * spp + smpIdx)];
+        seed = skip.x * lv_tea(pix /* = vertex */, U.aoFrameNumber) + skip.y;
+    } else {
+        seed = lv_tea(pix, U.aoGlobalFrameNumber * spp + smpIdx);
+    }
+    const float xi0 = lv_rnd(seed), xi1 = lv_rnd(seed);
+    float sn, cs;
+    lv_sincos2pi(xi1, sn, cs); // sampleHemisphere, glsl:151-156
+    const float rs = sqrtf(1.0f - xi0 * xi0);
+    const f3 smp = mk3(cs * rs, sn * rs, xi0);
+    const f3 dirU = mk3((T.x * smp.x + B.x * smp.y) + N.x * smp.z, (T.y * smp.x + B.y * smp.y) + N.y * smp.z,
+                        (T.z * smp.x + B.z * smp.y) + N.z * smp.z);
+    const f3 d = norm3(dirU);
+    const f3 o = BAKE ? pos : pos + d * g0.w;
+    gen[0] = make_float2(o.x, o.y);
+    gen[1] = make_float2(o.z, d.x);
+    gen[2] = make_float2(d.y, d.z);
+}
+
 // AO sample rays: PERSISTENT waves that keep three kinds of work apart and run each of them with (nearly) all
 // 64 lanes busy.  AO ray r belongs to compacted pixel r / spp, sample r % spp.
 //
@@ -440,32 +492,34 @@ __device__ __forceinline__ size_t lv_ao_slot(const uint32_t* __restrict__ tileBa
 //             appended to a wave-local FIFO in LDS (ballot + prefix popcount, no atomics).
 //   test      as soon as 64 pairs wait, all 64 lanes take one pair each, read the owner's ray from LDS, run the
 //             capsule test (8 IEEE divisions + 4 square roots, ~350 instructions) and merge into the owner's best hit
-//             with one 64-bit LDS atomicMin on the key (t bits << 32 | original segment): exactly "closest hit, ties
-//             to the lowest segment index".  The leaf test is the expensive phase; with one ray per thread it ran at
+//             with one 32-bit LDS atomicMin on the bits of t (lv_ao_key: AO never reads the primitive).  The leaf test is the expensive phase; with one ray per thread it ran at
 //             17-27 % lane utilisation (measured), here at ~100 %.
 // A finished ray is retired (samples[r] written, lane idle) once the FIFO head has passed its last queued leaf.
 // Scheduling inside a wave: test when >= 64 pairs wait; refill when >= LV_REFILL_THRESHOLD lanes are idle; otherwise
 // descend; flush partial batches only when nothing else can make progress.  Once the global queue is empty (drain) the
 // rays left in a wave are finished together: nobody retires early, idle lanes take over stacked subtrees of busy ones.
-// Resources: 31 KB LDS and <= 96 VGPRs -> 5 workgroups = 20 waves per CU; the kernel is VALU-issue-bound and needs that
+// Resources: 30 KB LDS and <= 96 VGPRs -> 5 workgroups = 20 waves per CU; the kernel is VALU-issue-bound and needs that
 // occupancy to hide the dependent node fetches (12 -> 16 -> 20 waves per CU: -16 %, -7 %).
 // BAKE: the static prebaker's rays (VulkanAmbientOcclusionBaker.glsl:230-281).  G-buffer slot = parametrisation vertex *
 // numTubeSubdivisions + subdivision with g0 = {ray origin, -}, g1 = {tangent, vertex}, g2 = {surface normal, subdivision};
 // the reference draws the (subdivision, ray) samples of a vertex from ONE LCG stream seeded with tea(vertex, frame), so
 // sample j starts from the stream advanced by 2 j steps: seed_j = A_j * seed_0 + C_j (lcgSkip[j] = {A_j, C_j}).
-template <bool STATS, bool ANY_HIT, int PRIM, bool BAKE = false, bool LIT = false>
+// PIXEL_GEN (host: spp % 64 == 0, not BAKE, ao_ray_generation = per_pixel): the generate phase looks its pixel up once per batch on
+// scalar registers instead of once per lane; same rays, same order, same scheduling.
+template <bool STATS, bool ANY_HIT, int PRIM, bool BAKE = false, bool LIT = false, bool PIXEL_GEN = false>
 __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const LvUniforms U, const LvSceneDev S,
                                                          const float4* __restrict__ gbuf, float* __restrict__ samples,
                                                          LvDevCounters* dc, const uint32_t* __restrict__ tileBase,
                                                          uint32_t numTiles, const LvAoLayout tileCapacity,
                                                          const uint2* __restrict__ lcgSkip = nullptr) {
     __shared__ unsigned s_stack[LV_AO_STACK_LDS * LV_AO_BLOCK];
-    // LDS budget: 15 KB + 6 + 6 + 2 + 2 = 31 KB per workgroup -> 5 workgroups (20 waves) per CU; the kernel hides the
+    // LDS budget: 15 KB + 6 + 6 + 2 + 1 = 30 KB per workgroup -> 5 workgroups (20 waves) per CU; the kernel hides the
     // latency of its dependent node fetches with occupancy (measured: 12 -> 16 waves/CU -16 %, 16 -> 20 another -7 %)
     __shared__ float2 s_ray[3 * LV_AO_BLOCK];              // current ray of every lane: {o.xy}{o.z, d.x}{d.yz} (24 B)
     __shared__ float2 s_gen[3 * LV_AO_BLOCK];              // generated rays waiting for a lane
     __shared__ unsigned s_queue[LV_AO_BLOCK / LV_WAVE][LV_AO_QCAP];
-    __shared__ unsigned long long s_key[LV_AO_BLOCK];      // best hit of every lane's ray
+    __shared__ lv_ao_key s_key[LV_AO_BLOCK];               // best hit of every lane's ray
+    __shared__ uint4 s_genState[PIXEL_GEN ? LV_AO_BLOCK / LV_WAVE : 1]; // PIXEL_GEN: {genLo, genHi, genSlot0, -} of every wave (generate phase)
 
     const uint32_t spp = U.aoSamplesPerFrame;
     const unsigned long long total = (unsigned long long)(dc->aoCount) * spp;
@@ -481,8 +535,10 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
     float2* rayW = &s_ray[3 * LV_WAVE * w];
     float2* genW = &s_gen[3 * LV_WAVE * w];
     unsigned* queueW = s_queue[w];
-    unsigned long long* keyW = &s_key[LV_WAVE * w];
-    const unsigned long long keyInit = ((unsigned long long)__float_as_uint(U.aoRadius) << 32) | 0xFFFFFFFFull;
+    lv_ao_key* keyW = &s_key[LV_WAVE * w];
+    uint4* genStateW = &s_genState[PIXEL_GEN ? w : 0];
+    if (PIXEL_GEN && lane == 0) genStateW[0] = make_uint4(0u, 0u, 0u, 0u);
+    const lv_ao_key keyInit = lv_ao_key_none(U.aoRadius);
     // literal roots: cull against best + r / |d| (AO directions are normalised: |d| = 1 to rounding, 1.001 covers it)
     // elliptic tubelets: bandWidth / |d| (lv_intersect_elliptic_tube's own-box rule)
     const float litSlack = PRIM == LV_PRIM_ELLIPTIC ? S.ellBandWidth * 1.001f : (PRIM == LV_PRIM_CAPSULE && LIT) ? radius * 1.001f : 0.0f;
@@ -537,9 +593,9 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
         const bool drain = !canRefill;
         // ---- retire rays whose traversal is finished and whose queued leaves have all been tested
         if (!drain && hasRay && cur == LV_INVALID && (!enq || int(head - lastSeq) > 0)) {
-            const unsigned long long key = keyW[lane];
+            const lv_ao_key key = keyW[lane];
             float occ = 1.0f;
-            if (key != keyInit) occ = U.aoUseDistance ? __uint_as_float(unsigned(key >> 32)) / U.aoRadius : 0.0f;
+            if (key != keyInit) occ = U.aoUseDistance ? lv_ao_key_t(key) / U.aoRadius : 0.0f;
             samples[r] = occ;
             hasRay = false;
         }
@@ -562,7 +618,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                 if (lv_leaf_test<PRIM, LIT ? 1 : 0>(S, leaf, mk3(r0.x, r0.y, r1.x), mk3(r1.y, r2.x, r2.y), radius, capped, t, low, 0.0f,
                                                     U.aoRadius)) {
                     if (t >= 0.0f && t <= U.aoRadius) { // traceAoRay: closest hit in [0, aoRadius], glsl:158-175
-                        atomicMin(&keyW[owner], ((unsigned long long)__float_as_uint(t) << 32) | low);
+                        atomicMin(&keyW[owner], lv_ao_key_hit(t, low));
                         if (STATS) primHits++;
                     }
                 }
@@ -578,8 +634,8 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             head += n;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             {
-                const unsigned long long key = keyW[owner];
-                best = __uint_as_float(unsigned(key >> 32)); // shrinks the slab interval of the following node steps
+                const lv_ao_key key = keyW[owner];
+                best = lv_ao_key_t(key); // shrinks the slab interval of the following node steps
                 if (ANY_HIT && key != keyInit) { cur = LV_INVALID; st.sp = 0; }
             }
             continue;
@@ -587,9 +643,9 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
         if (drain) {
             if (nNode == 0) { // FIFO empty (q == 0 here), nobody descends: the wave is done
                 if (hasRay) {
-                    const unsigned long long key = keyW[lane];
+                    const lv_ao_key key = keyW[lane];
                     float occ = 1.0f;
-                    if (key != keyInit) occ = U.aoUseDistance ? __uint_as_float(unsigned(key >> 32)) / U.aoRadius : 0.0f;
+                    if (key != keyInit) occ = U.aoUseDistance ? lv_ao_key_t(key) / U.aoRadius : 0.0f;
                     samples[r] = occ;
                 }
                 break;
@@ -612,9 +668,9 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                             cur = __float_as_uint(x.x);
                             owner = __float_as_uint(x.y);
                             const float2 r0 = rayW[3 * owner], r1 = rayW[3 * owner + 1], r2 = rayW[3 * owner + 2];
-                            inv = mk3(1.0f / r1.y, 1.0f / r2.x, 1.0f / r2.y);
+                            inv = lv_traversal_inv(mk3(r1.y, r2.x, r2.y));
                             oi = mk3(r0.x * inv.x, r0.y * inv.y, r1.x * inv.z);
-                            best = __uint_as_float(unsigned(keyW[owner] >> 32));
+                            best = lv_ao_key_t(keyW[owner]);
                             st.sp = 0;
                         }
                     }
@@ -637,34 +693,41 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                 const unsigned long long left = chunkEnd - chunkNext;
                 const unsigned n = left < LV_WAVE ? unsigned(left) : LV_WAVE;
                 if (STATS && lane == 0 && n) { phIt[0]++; phLn[0] += n; }
-                if (lane < n) {
+                if (PIXEL_GEN) {
+                    // spp is a multiple of 64 and so is every chunk start: the 64 rays of this batch are samples [genSmp0, genSmp0 + 64) of
+                    // ONE pixel.  Its ordinal, its group and its G-buffer slot are wave-uniform (scalar registers, scalar loads); per lane
+                    // only the sample index differs.  The same integers and the same float operations as below: the same rays, bit for bit.
+                    if (n) {
+                        // batch number -> (pixel ordinal, first sample): 32 bits (the host checks the launch's size), no division at spp = 64
+                        const uint32_t b = __builtin_amdgcn_readfirstlane(uint32_t(chunkNext / LV_WAVE)), bpp = spp / LV_WAVE;
+                        const uint32_t genOrdinal = bpp == 1u ? b : __builtin_amdgcn_readfirstlane(b / bpp);
+                        const uint32_t genSmp0 = (b - genOrdinal * bpp) * LV_WAVE;
+                        // the group the wave's previous batch was found in: its ordinals [genLo, genHi) and its first G-buffer slot.  Kept in
+                        // LDS, not in registers: the kernel has no scalar register to spare across its main loop
+                        const uint4 gs = genStateW[0];
+                        uint32_t genLo = __builtin_amdgcn_readfirstlane(gs.x), genHi = __builtin_amdgcn_readfirstlane(gs.y);
+                        uint32_t genSlot0 = __builtin_amdgcn_readfirstlane(gs.z);
+                        if (genOrdinal - genLo >= genHi - genLo) { // left that group (or the first batch: 0 >= 0)
+                            uint32_t lo = 0, hi = numTiles;        // lv_ao_slot's search, once per group a wave passes through
+                            while (hi - lo > 1u) {
+                                const uint32_t mid = (lo + hi) >> 1;
+                                if (tileBase[mid] <= genOrdinal) lo = mid; else hi = mid;
+                            }
+                            genLo = __builtin_amdgcn_readfirstlane(tileBase[lo]);
+                            genHi = __builtin_amdgcn_readfirstlane(tileBase[lo + 1u]);
+                            genSlot0 = __builtin_amdgcn_readfirstlane(uint32_t(lv_ao_group_base(tileCapacity, lo)));
+                            if (lane == 0) genStateW[0] = make_uint4(genLo, genHi, genSlot0, 0u);
+                        }
+                        const size_t slot = size_t(genSlot0) + (genOrdinal - genLo);
+                        const float4 g0 = gbuf[3 * slot + 0], g1 = gbuf[3 * slot + 1], g2 = gbuf[3 * slot + 2];
+                        lv_ao_generate_ray<false>(U, g0, g1, g2, genSmp0 + lane, spp, lcgSkip, &genW[3 * lane]);
+                    }
+                } else if (lane < n) {
                     const unsigned long long rr = chunkNext + lane;
                     const uint32_t smpIdx = uint32_t(rr % spp);
                     const size_t slot = lv_ao_slot(tileBase, numTiles, tileCapacity, uint32_t(rr / spp));
                     const float4 g0 = gbuf[3 * slot + 0], g1 = gbuf[3 * slot + 1], g2 = gbuf[3 * slot + 2];
-                    const uint32_t pix = __float_as_uint(g1.w);
-                    const f3 pos = mk3(g0.x, g0.y, g0.z), T = mk3(g1.x, g1.y, g1.z), N = mk3(g2.x, g2.y, g2.z);
-                    const f3 B = cross3(N, T);
-                    uint32_t seed;
-                    if (BAKE) {
-                        const uint32_t sub = __float_as_uint(g2.w);
-                        const uint2 skip = lcgSkip[2u * (sub * spp + smpIdx)];
-                        seed = skip.x * lv_tea(pix /* = vertex */, U.aoFrameNumber) + skip.y;
-                    } else {
-                        seed = lv_tea(pix, U.aoGlobalFrameNumber * spp + smpIdx);
-                    }
-                    const float xi0 = lv_rnd(seed), xi1 = lv_rnd(seed);
-                    float sn, cs;
-                    lv_sincos2pi(xi1, sn, cs); // sampleHemisphere, glsl:151-156
-                    const float rs = sqrtf(1.0f - xi0 * xi0);
-                    const f3 smp = mk3(cs * rs, sn * rs, xi0);
-                    const f3 dirU = mk3((T.x * smp.x + B.x * smp.y) + N.x * smp.z, (T.y * smp.x + B.y * smp.y) + N.y * smp.z,
-                                        (T.z * smp.x + B.z * smp.y) + N.z * smp.z);
-                    const f3 d = norm3(dirU);
-                    const f3 o = BAKE ? pos : pos + d * g0.w;
-                    genW[3 * lane] = make_float2(o.x, o.y);
-                    genW[3 * lane + 1] = make_float2(o.z, d.x);
-                    genW[3 * lane + 2] = make_float2(d.y, d.z);
+                    lv_ao_generate_ray<BAKE>(U, g0, g1, g2, smpIdx, spp, lcgSkip, &genW[3 * lane]);
                 }
                 genBase = chunkNext;
                 chunkNext += n;
@@ -683,7 +746,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                     rayW[3 * lane + 1] = r1;
                     rayW[3 * lane + 2] = r2;
                     keyW[lane] = keyInit;
-                    inv = mk3(1.0f / r1.y, 1.0f / r2.x, 1.0f / r2.y);
+                    inv = lv_traversal_inv(mk3(r1.y, r2.x, r2.y));
                     oi = mk3(r0.x * inv.x, r0.y * inv.y, r1.x * inv.z);
                     best = U.aoRadius;
                     r = genBase + gs;
@@ -2903,7 +2966,7 @@ __global__ void k_depth_finalize(const LvDevCounters* dc, float* out) {
 }
 
 // ================================================================ arbitrary rays (parity inspection)
-template <int PRIM>
+template <int PRIM, bool FAST_INV = false>
 __global__ __launch_bounds__(LV_BLOCK) void k_trace_rays(const LvSceneDev S, float radius, uint32_t capped,
                                                          const float* __restrict__ org, const float* __restrict__ dir,
                                                          float tMin, float tMax, uint32_t n, float* __restrict__ outT,
@@ -2917,14 +2980,15 @@ __global__ __launch_bounds__(LV_BLOCK) void k_trace_rays(const LvSceneDev S, flo
     const uint32_t j = valid ? i : 0u;
     f3 o = mk3(org[3 * j], org[3 * j + 1], org[3 * j + 2]);
     f3 d = mk3(dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
-    LvHit h = lv_trace_closest<false, false, PRIM>(S, radius, capped != 0, valid, o, d, tMin, tMax,
-                                                   lv_stack_mem(s_stack, S.stackOverflow), cm, cnt);
+    LvHit h = lv_trace_closest<false, false, PRIM, FAST_INV>(S, radius, capped != 0, valid, o, d, tMin, tMax,
+                                                             lv_stack_mem(s_stack, S.stackOverflow), cm, cnt);
     if (!valid) return;
     outT[i] = h.found ? h.t : tMax;
     outSeg[i] = h.found ? S.leafSeg[h.leaf] : 0xFFFFFFFFu;
     outKind[i] = h.found ? uint32_t(h.kind) : 0u;
 }
 
+template <bool FAST_INV>
 __global__ __launch_bounds__(LV_BLOCK) void k_trace_rays_tri(const LvSceneDev S, const float* __restrict__ org,
                                                              const float* __restrict__ dir, float tMin, float tMax,
                                                              uint32_t n, float* __restrict__ outT,
@@ -2938,8 +3002,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_trace_rays_tri(const LvSceneDev S,
     const uint32_t j = valid ? i : 0u;
     f3 o = mk3(org[3 * j], org[3 * j + 1], org[3 * j + 2]);
     f3 d = mk3(dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
-    LvHit h = lv_trace_closest<false, false, LV_PRIM_TRIANGLE>(S, 0.0f, false, valid, o, d, tMin, tMax,
-                                                               lv_stack_mem(s_stack, S.stackOverflow), cm, cnt);
+    LvHit h = lv_trace_closest<false, false, LV_PRIM_TRIANGLE, FAST_INV>(S, 0.0f, false, valid, o, d, tMin, tMax,
+                                                                         lv_stack_mem(s_stack, S.stackOverflow), cm, cnt);
     if (!valid) return;
     float t = tMax, u = 0.0f, v = 0.0f;
     if (h.found) {
@@ -3453,27 +3517,31 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
             LV_TIMED_LAUNCH(ctx, LV_KERNEL_AO_PRIMARY, (k_ao_primary<ST, PR><<<gridTiles, LV_BLOCK, 0, st>>>(  \
                     U, SA, T, aoIn, ao, (float4*)ctx->aoGbuf.ptr, tileCount, dc, fnIn, fnOut, fpIn, fpOut, SF))); \
     } while (0)
-#define LV_LAUNCH_AO(ST, AH, PR) \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_AO_RAYS, (k_ao_rays<ST, AH, PR><<<grid, LV_AO_BLOCK, 0, st>>>(U, SA, g, smp, dc, tileBase, numGroups, tileCap)))
-#define LV_LAUNCH_AO_LIT(ST, AH) \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_AO_RAYS, (k_ao_rays<ST, AH, LV_PRIM_CAPSULE, false, true><<<grid, LV_AO_BLOCK, 0, st>>>( \
+#define LV_LAUNCH_AO(ST, AH, PR, LI, PG) \
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_AO_RAYS, (k_ao_rays<ST, AH, PR, false, LI, PG><<<grid, LV_AO_BLOCK, 0, st>>>( \
             U, SA, g, smp, dc, tileBase, numGroups, tileCap)))
-#define LV_LAUNCH_AO2(ST, AH)                                          \
+#define LV_LAUNCH_AO3(ST, AH, PG)                                      \
     do {                                                               \
-        if (tri) LV_LAUNCH_AO(ST, AH, LV_PRIM_TRIANGLE);               \
-        else if (U.useEllipticTubes) LV_LAUNCH_AO(ST, AH, LV_PRIM_ELLIPTIC); \
-        else if (lv_literal_intersection(ctx)) LV_LAUNCH_AO_LIT(ST, AH); \
-        else LV_LAUNCH_AO(ST, AH, LV_PRIM_CAPSULE);                    \
+        if (tri) LV_LAUNCH_AO(ST, AH, LV_PRIM_TRIANGLE, false, PG);    \
+        else if (U.useEllipticTubes) LV_LAUNCH_AO(ST, AH, LV_PRIM_ELLIPTIC, false, PG); \
+        else if (lv_literal_intersection(ctx)) LV_LAUNCH_AO(ST, AH, LV_PRIM_CAPSULE, true, PG); \
+        else LV_LAUNCH_AO(ST, AH, LV_PRIM_CAPSULE, false, PG);         \
     } while (0)
+#define LV_LAUNCH_AO2(ST, AH) \
+    do { if (!ST && pixelGen) LV_LAUNCH_AO3(ST, AH, !ST); else LV_LAUNCH_AO3(ST, AH, false); } while (0)
         const bool ell = U.useEllipticTubes != 0u;
         if (stats) { if (tri) LV_LAUNCH_AOP(true, LV_PRIM_TRIANGLE); else if (ell) LV_LAUNCH_AOP(true, LV_PRIM_ELLIPTIC); else LV_LAUNCH_AOP(true, LV_PRIM_CAPSULE); }
         else { if (tri) LV_LAUNCH_AOP(false, LV_PRIM_TRIANGLE); else if (ell) LV_LAUNCH_AOP(false, LV_PRIM_ELLIPTIC); else LV_LAUNCH_AOP(false, LV_PRIM_CAPSULE); }
         k_ao_tile_scan<<<1, LV_BLOCK, 0, st>>>(tileCount, numGroups, tileBase, dc);
         const bool anyHit = !U.aoUseDistance;
+        // ao_ray_generation = per_pixel: a batch of 64 rays is 64 samples of one pixel whenever spp and both chunk sizes are multiples of
+        // 64 (k_ao_rays, PIXEL_GEN); batch numbers and G-buffer slots must fit 32 bits.  The collect_stats instantiations generate per ray.
+        const bool pixelGen = ctx->opt.aoPixelGeneration && spp % LV_WAVE == 0u && LV_AO_CHUNK % LV_WAVE == 0u &&
+                              LV_AO_CHUNK_SMALL % LV_WAVE == 0u && maxPixels < (1ull << 32) && maxPixels * spp < (1ull << 38);
         if (stats) { if (anyHit) LV_LAUNCH_AO2(true, true); else LV_LAUNCH_AO2(true, false); }
         else { if (anyHit) LV_LAUNCH_AO2(false, true); else LV_LAUNCH_AO2(false, false); }
 #undef LV_LAUNCH_AO2
-#undef LV_LAUNCH_AO_LIT
+#undef LV_LAUNCH_AO3
 #undef LV_LAUNCH_AO
 #undef LV_LAUNCH_AOP
 #undef LV_LAUNCH_PAIR
@@ -4321,6 +4389,9 @@ int lv_frame_trace_rays(lv_ctx* ctx, const float* o, const float* d, float tMin,
     if (ctx->opt.useRibbons && ctx->opt.ellipticTubes) // the elliptic tubelets of the band data (kind = 0)
         k_trace_rays<LV_PRIM_ELLIPTIC><<<nblocks(n), LV_BLOCK, 0, st>>>(S, ctx->opt.lineWidth * 0.5f, ctx->opt.useCappedTubes, dO,
                                                                         dD, tMin, tMax, n, dT, dS, dK);
+    else if (ctx->opt.traceRaysHardwareInv) // traversal_reciprocal = hardware: the node steps' reciprocals as in k_ao_rays (lv_traversal_inv)
+        k_trace_rays<LV_PRIM_CAPSULE, true><<<nblocks(n), LV_BLOCK, 0, st>>>(S, ctx->opt.lineWidth * 0.5f, ctx->opt.useCappedTubes, dO,
+                                                                             dD, tMin, tMax, n, dT, dS, dK);
     else
         k_trace_rays<LV_PRIM_CAPSULE><<<nblocks(n), LV_BLOCK, 0, st>>>(S, ctx->opt.lineWidth * 0.5f, ctx->opt.useCappedTubes, dO,
                                                                        dD, tMin, tMax, n, dT, dS, dK);
@@ -4521,7 +4592,8 @@ int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, f
     LV_HIP(ctx, hipMemcpyAsync(dD, d, rb, hipMemcpyHostToDevice, st));
     LvSceneDev S = sceneDevTriangles(ctx);
     if ((rc = lv_prepare_overflow(ctx, S, nblocks(n), LV_STACK_LDS, true))) return rc;
-    k_trace_rays_tri<<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
+    if (ctx->opt.traceRaysHardwareInv) k_trace_rays_tri<true><<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
+    else k_trace_rays_tri<false><<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(outT, dT, size_t(n) * 4, hipMemcpyDeviceToHost, st));
     LV_HIP(ctx, hipMemcpyAsync(outTri, dS, size_t(n) * 4, hipMemcpyDeviceToHost, st));

@@ -301,6 +301,35 @@ __device__ __forceinline__ bool lv_slab_q(uint32_t nearX, uint32_t nearY, uint32
     return tn <= __builtin_fmaf(tf, 1.00001f, 4e-7f);
 }
 
+// Per-ray reciprocals for lv_node_step ONLY (inv, and through it oi = o * inv): the hardware reciprocal, <= 1 ulp, in place of
+// the ~10-instruction IEEE division.  Why no hit can depend on it: every plane parameter of lv_slab_q is t = q * (scale * inv) +
+// (origin * inv - o * inv), so an inv that is off by a factor (1 + e) is the slab test of the same planes with every t scaled by
+// (1 + e_axis) -- the correctly rounded quotient has |e| <= 2^-24, the hardware one |e| <= 2^-23 + 2^-24 < 1.8e-7.  A point of the
+// ray at parameter t >= 0 inside a (padded) box has tn <= t (1 + 1.8e-7) and tf >= t (1 - 1.8e-7) per axis, and the interval ends
+// tMin <= t <= tMax are exact: tn <= tf * (1 + 3.6e-7 + ...) stays far inside the test's tn <= tf * 1.00001 + 4e-7, whose relative
+// margin is 28 times larger.  The rounding of the products and of the fma is the same in both forms.  So the boxes visited are a
+// superset of those an exact test visits, as before; what decides a hit (lv_leaf_test, the own-box rules, the literal roots) reads
+// o and d and divides by IEEE rules.  Only node-visit counters can move, by a few boxes at the margin.
+// Zero, -0 and denormal components: 1 / (+-0) = +-inf by both rules.  v_rcp_f32 treats a denormal as a zero of its sign and
+// returns +-inf, where the division gives a finite value only for |d| >= 2^-128 (else +-inf as well).  With inv = +-inf the axis'
+// planes are q * inf + (origin * inf - o * inf).  That is NaN whenever a 0 * inf or an inf - inf occurs (q = 0, o = 0, origin = 0,
+// o and origin of one sign, or o > 0 > origin), and fmaxf / fminf drop a NaN: the axis does not take part, which is always
+// conservative.  The one other outcome is +inf for both planes, when o < 0 < origin along that axis (mirrored for -inf): tn = inf,
+// the child is culled -- rightly: the coordinate of such a ray moves by less than tMax * 2^-126, the box lies wholly on the
+// other side of zero, and its primitives are at least the builder's pad (>= 1e-6) inside it.  A denormal therefore takes exactly
+// the path that a zero of its sign takes today (tests/test_gpu_ao_sample_overhead.py runs such rays against brute force).
+// LV_TRAVERSAL_INV_IEEE=1 (measurement knob) restores the division.
+#ifndef LV_TRAVERSAL_INV_IEEE
+#define LV_TRAVERSAL_INV_IEEE 0
+#endif
+__device__ __forceinline__ f3 lv_traversal_inv(f3 d) {
+#if LV_TRAVERSAL_INV_IEEE
+    return mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+#else
+    return mk3(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
+#endif
+}
+
 // ORDERED: 0 = children pushed as they come (all-hits), 1 = nearest hit child first, the rest as they come (closest hit:
 // measured as fast as a full sort, fewer instructions), 2 = all hit children in front-to-back order (MLAT: how early the
 // transmittance rule closes the ray interval depends on meeting the near layers first).
@@ -638,7 +667,9 @@ struct LvHitQueue {
 // So the expensive test (8 IEEE divisions + 4 square roots, ~350 instructions) always runs at full width, and a single
 // long ray that meets hundreds of leaves -- the tail that bounded the one-ray-per-thread kernels -- has them tested 64
 // at a time by the lanes that already finished.  ANY_HIT: gl_RayFlagsTerminateOnFirstHitEXT.
-template <bool STATS, bool ANY_HIT, int PRIM = LV_PRIM_CAPSULE>
+// FAST_INV: the node steps use lv_traversal_inv (the ray-trace entry points under traversal_reciprocal = hardware: arbitrary rays
+// through the reciprocals k_ao_rays descends with); the frame kernels keep the division.
+template <bool STATS, bool ANY_HIT, int PRIM = LV_PRIM_CAPSULE, bool FAST_INV = false>
 __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float radius, bool capped, bool active, f3 o, f3 d,
                                                   float tMin, float tMax, const LvStackMem& sm, const LvCoopMem& cm,
                                                   LvCounters& cnt) {
@@ -651,7 +682,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
     if (STATS && active) cnt.rays++;
     // the ray this lane currently descends for: its own at first, later possibly a subtree handed over by a busy lane
     unsigned owner = lane;
-    f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    f3 inv = FAST_INV ? lv_traversal_inv(d) : mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     f3 oi = mk3(o.x * inv.x, o.y * inv.y, o.z * inv.z);
     LvStack st;
     st.init(sm.lds, sm.ovf, sm.ovfStride);
@@ -727,7 +758,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
                         cur = x.x;
                         owner = x.y;
                         const float4 ro = cm.ray[2 * owner], rd = cm.ray[2 * owner + 1];
-                        inv = mk3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+                        inv = FAST_INV ? lv_traversal_inv(mk3(rd.x, rd.y, rd.z)) : mk3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
                         oi = mk3(ro.x * inv.x, ro.y * inv.y, ro.z * inv.z);
                         tMin = ro.w;
                         best = __uint_as_float(unsigned(cm.key[owner] >> 32));

@@ -39,7 +39,10 @@ for W in "$@"; do
     rm -rf $OUT/$W.p$i
     timeout 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$W.p$i -o p -- \
         python $R/bench.py --workload $W --steps 2 --warmup 1 --no-cpu-baseline > $OUT/$W.p$i.out 2> $OUT/$W.p$i.err
-    echo "pass $i ($C): rc $?" >> $OUT/$W.log
+    rc=$?
+    echo "pass $i ($C): rc $rc" >> $OUT/$W.log
+    # a pass that failed, faulted or ran into its limit ends the collection: nothing more is started on that GPU
+    if [ $rc -ne 0 ]; then echo "pass $i of $W: rc $rc -- stopping" | tee -a $OUT/$W.log; exit $rc; fi
   done
   python - <<PY
 import csv, collections, glob, json, os

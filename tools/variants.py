@@ -4,8 +4,9 @@
   python tools/variants.py build name1:-DFOO=1,-DBAR=2 name2:...     (here: cross-compiles lv_render.hip + lv_mlat.hip with
                                                                        the extra flags, links with the other objects of the
                                                                        regular build -> linevis_amd/_lib/variants/<name>.so)
-  python tools/variants.py run [--workload c3] [--steps 30] name1 name2 ...   (on the GPU box: bench.py per variant through
-                                                                       LV_LIB_PATH, prints ms/frame and per-kernel ms)
+  python tools/variants.py run [--workload c3] [--steps 30] [--set KEY=VALUE] name1 name2 ...   (on the GPU box: bench.py per
+                                                                       variant through LV_LIB_PATH, prints ms/frame and per-kernel ms)
+A name without flags that PRESETS knows is built with that row's flags.
 """
 import json
 import os
@@ -18,6 +19,13 @@ from linevis_amd import build as B  # noqa: E402
 
 OUT = os.path.join(B.OUT_DIR, "variants")
 RECOMPILE = ["lv_render.hip", "lv_mlat.hip"]   # the translation units that instantiate lv_trace.h
+# named rows: the build-time switches of k_ao_rays' per-ray overhead (the third part, per-pixel generation, is the run-time option
+# ao_ray_generation: run --set ao_ray_generation=per_ray base)
+PRESETS = {
+    "inv_ieee": "-DLV_TRAVERSAL_INV_IEEE=1",                       # node-step reciprocals by IEEE division
+    "key64": "-DLV_AO_KEY64=1",                                    # 64-bit (t, primitive) hit keys in k_ao_rays
+    "inv_ieee_key64": "-DLV_TRAVERSAL_INV_IEEE=1,-DLV_AO_KEY64=1",
+}
 
 
 def build(specs):
@@ -26,6 +34,7 @@ def build(specs):
     procs = []
     for spec in specs:
         name, _, flags = spec.partition(":")
+        flags = flags or PRESETS.get(name, "")
         flags = [f for f in flags.split(",") if f]
         objs = []
         for s, oname, extra in B.SOURCES:
@@ -54,13 +63,15 @@ def build(specs):
 
 
 def run(args):
-    workload, steps, names = "c3c", "30", []
+    workload, steps, names, sets = "c3c", "30", [], []
     it = iter(args)
     for a in it:
         if a == "--workload":
             workload = next(it)
         elif a == "--steps":
             steps = next(it)
+        elif a == "--set":
+            sets += ["--set", next(it)]
         else:
             names.append(a)
     for v in names:
@@ -68,7 +79,7 @@ def run(args):
         if v != "base":
             env["LV_LIB_PATH"] = os.path.join(OUT, v + ".so")
         r = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--workload", workload, "--steps", steps, "--warmup", "3",
-                            "--no-cpu-baseline"], env=env, capture_output=True, text=True)
+                            "--no-cpu-baseline"] + sets, env=env, capture_output=True, text=True)
         try:
             j = json.loads(r.stdout.strip().splitlines()[-1])
             print("%-14s %8.4f ms/frame  %s  nodes %d prims %d" % (v, j["ms_per_step"], j["kernels_ms"], j["counters_rank0"]["ao_nodes_visited"],
