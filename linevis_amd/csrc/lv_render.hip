@@ -1579,6 +1579,127 @@ __device__ __forceinline__ void lv_clip_rows(const LvUniforms& U, float mx[4], f
         }
     }
 }
+// a world position through those rows: clip w, x and y
+struct LvClipPoint { float cw, ccx, ccy; };
+__device__ __forceinline__ LvClipPoint lv_clip_point(const float mx[4], const float my[4], const float mw[4], const f3& v) {
+    LvClipPoint c;
+    c.cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
+    c.ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
+    c.ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
+    return c;
+}
+// Stage A of the segment rasteriser, one statement for k_ppll_raster_prism and k_mboit_stream_pass (pooled and streamed frames are
+// equal byte for byte): a lane's walk over the candidate pixels of its segment
+struct LvSegWalk {
+    int x0, x1, y0, y1;   // the screen rectangle (none: x1 < x0)
+    // oriented box: |(pixel centre - c) . a - aMid| <= aHalf and |(pixel centre - c) . n - nMid| <= nHalf, n = (-a.y, a.x)
+    float ax, ay, cx0, cy0, aMid, aHalf, nMid, nHalf;
+};
+// the set-up per segment: its frames ({centre, normal, binormal} x 2 + the two point indices) into the wave's block of LDS, where
+// stage B reads them, then rectangle and oriented box of the projected ring vertices
+__device__ __forceinline__ LvSegWalk lv_seg_walk_setup(const LvUniforms& U, const LvSceneDev& S, float (*segLds)[LV_WAVE], const float mx[4],
+                                                       const float my[4], const float mw[4], float halfW, float halfH, float wEps,
+                                                       uint32_t N, bool valid, uint32_t leaf, unsigned lane) {
+    const LvPrismDev& R = S.prism;
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+    float ax = 1.0f, ay = 0.0f, cx0 = 0.0f, cy0 = 0.0f, aMid = 0.0f, aHalf = 3.0e38f, nMid = 0.0f, nHalf = 3.0e38f;
+    if (valid) {
+        const float4 pa = S.segs[2 * size_t(leaf)], pb = S.segs[2 * size_t(leaf) + 1];
+        uint32_t pi[2];
+        LvPrismPoint pt[2];
+        lv_prism_frames(S, leaf, pa, pb, pt, pi);
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            segLds[9 * e + 0][lane] = pt[e].centre.x; segLds[9 * e + 1][lane] = pt[e].centre.y; segLds[9 * e + 2][lane] = pt[e].centre.z;
+            segLds[9 * e + 3][lane] = pt[e].normal.x; segLds[9 * e + 4][lane] = pt[e].normal.y; segLds[9 * e + 5][lane] = pt[e].normal.z;
+            segLds[9 * e + 6][lane] = pt[e].binormal.x; segLds[9 * e + 7][lane] = pt[e].binormal.y; segLds[9 * e + 8][lane] = pt[e].binormal.z;
+            segLds[18 + e][lane] = __uint_as_float(pi[e]);
+        }
+        // axis of the oriented box: the projected centres (any direction gives a valid box; this one gives a tight one)
+        bool axisOk = true;
+        float wcx[2], wcy[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const auto [cw, ccx, ccy] = lv_clip_point(mx, my, mw, pt[e].centre);
+            axisOk = axisOk && cw > wEps;
+            wcx[e] = (ccx / cw + 1.0f) * halfW;
+            wcy[e] = (ccy / cw + 1.0f) * halfH;
+        }
+        if (axisOk) {
+            const float dx = wcx[1] - wcx[0], dy = wcy[1] - wcy[0], l2 = dx * dx + dy * dy;
+            if (l2 > 1e-12f && l2 < 1e30f) { const float il = 1.0f / sqrtf(l2); ax = dx * il; ay = dy * il; }
+            cx0 = wcx[0]; cy0 = wcy[0];
+        }
+        float lox = 3.0e38f, hix = -3.0e38f, loy = 3.0e38f, hiy = -3.0e38f;
+        float loa = 3.0e38f, hia = -3.0e38f, lon = 3.0e38f, hin = -3.0e38f;
+        bool anyFront = false, anyBehind = false;
+        for (uint32_t k = 0; k < N; k++) {
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const f3 v = lv_prism_pos(pt[e], lv_prism_dir(pt[e], R.cp[k], R.s[k]), R.radius);
+                const auto [cw, ccx, ccy] = lv_clip_point(mx, my, mw, v);
+                if (cw > wEps) {
+                    const float wx = (ccx / cw + 1.0f) * halfW, wy = (ccy / cw + 1.0f) * halfH;
+                    lox = fminf(lox, wx); hix = fmaxf(hix, wx); loy = fminf(loy, wy); hiy = fmaxf(hiy, wy);
+                    const float ta = (wx - cx0) * ax + (wy - cy0) * ay, tn = (wy - cy0) * ax - (wx - cx0) * ay;
+                    loa = fminf(loa, ta); hia = fmaxf(hia, ta); lon = fminf(lon, tn); hin = fmaxf(hin, tn);
+                    anyFront = true;
+                } else anyBehind = true;
+            }
+        }
+        if (anyFront) {   // (all vertices behind the camera plane: no viewing ray meets the prism at a positive depth)
+            if (anyBehind) { lox = 0.0f; loy = 0.0f; hix = float(U.width); hiy = float(U.height); }   // straddles the camera plane
+            else if (axisOk) {
+                // (the projected coordinates carry a relative rounding error of a few ulp: the margin also covers the box's own arithmetic)
+                aMid = 0.5f * (loa + hia); aHalf = 0.5f * (hia - loa) + LV_PRISM_BBOX_MARGIN;
+                nMid = 0.5f * (lon + hin); nHalf = 0.5f * (hin - lon) + LV_PRISM_BBOX_MARGIN;
+            }
+            // pixel x is a candidate iff its centre x + 0.5 lies in [lo - margin, hi + margin]
+            const float fx0 = fmaxf(ceilf(lox - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
+            const float fy0 = fmaxf(ceilf(loy - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
+            const float fx1 = fminf(floorf(hix + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.width) - 1.0f);
+            const float fy1 = fminf(floorf(hiy + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.height) - 1.0f);
+            if (fx0 <= fx1 && fy0 <= fy1) { x0 = int(fx0); x1 = int(fx1); y0 = int(fy0); y1 = int(fy1); }
+        }
+    }
+    return LvSegWalk{x0, x1, y0, y1, ax, ay, cx0, cy0, aMid, aHalf, nMid, nHalf};
+}
+// is the walk's pixel a candidate: inside the oriented box and, in a frame that leaves tiles out, requested
+__device__ __forceinline__ bool lv_seg_walk_candidate(const LvUniforms& U, const LvSegWalk& w, int px, int py, uint32_t allRequested,
+                                                      const uint32_t* __restrict__ startOffset) {
+    const float qx = (float(px) + 0.5f) - w.cx0, qy = (float(py) + 0.5f) - w.cy0;
+    bool cand = fabsf((qx * w.ax + qy * w.ay) - w.aMid) <= w.aHalf && fabsf((qy * w.ax - qx * w.ay) - w.nMid) <= w.nHalf;
+    if (cand && !allRequested)
+        cand = startOffset[lv_ppll_addr(uint32_t(px), uint32_t(py), U.ppllPaddedW, U.ppllTileW, U.ppllTileH)] == 0u;
+    return cand;
+}
+// the next pixel of the rectangle, row by row; false after the last
+__device__ __forceinline__ bool lv_seg_walk_advance(const LvSegWalk& w, int& px, int& py) {
+    if (++px > w.x1) { px = w.x0; return ++py <= w.y1; }
+    return true;
+}
+// The front of stage B, again one statement for both kernels: the (pixel, segment) pair in slot q of the wave's queue and the coverage
+// mask of the pixel-centre viewing ray over the segment's triangles, the frames read back from the wave's block of LDS
+// (no requested-tile test here: a whole-viewport frame requests every pixel, a rank of a sharded frame filters in stage A)
+template <int NT>
+__device__ __forceinline__ unsigned lv_seg_pair_coverage(const LvPrismDev& R, const float (*segLds)[LV_WAVE], const uint32_t* qLeaf,
+                                                         const uint32_t* qPix, unsigned q, const f3& o, uint32_t& leaf, uint32_t& pix) {
+    leaf = qLeaf[q];
+    pix = qPix[q];
+    const f3 d = lv_prism_cov_dir(R, pix & 0xFFFFu, pix >> 16);   // the pixel's coverage direction (unnormalised, lv_prism.h)
+    const uint32_t sl = leaf >> 26;   // the pair's segment among the wave's 64 = the lane that queued it
+    leaf &= 0x03FFFFFFu;
+    LvPrismPoint pt[2];
+    uint32_t pi[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        pt[e].centre = mk3(segLds[9 * e + 0][sl], segLds[9 * e + 1][sl], segLds[9 * e + 2][sl]);
+        pt[e].normal = mk3(segLds[9 * e + 3][sl], segLds[9 * e + 4][sl], segLds[9 * e + 5][sl]);
+        pt[e].binormal = mk3(segLds[9 * e + 6][sl], segLds[9 * e + 7][sl], segLds[9 * e + 8][sl]);
+        pi[e] = __float_as_uint(segLds[18 + e][sl]);
+    }
+    return lv_prism_coverage_pts<NT>(R, pt, pi, R.radius, o, d);
+}
 // Sharded frame (a rank renders a tile list): ONE pass per frame over the segments' 32-B records decides which of them can touch a
 // requested pixel at all and appends those to a list; k_ppll_raster_prism then walks the list, so that the segments of the other ranks'
 // tiles cost this rank 32 B and ~60 instructions each instead of a slot of the rasteriser's waves (frames, oriented box, an empty
@@ -1616,11 +1737,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_ppll_cull_segments(const LvUniform
             bool decided = true;
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                const f3 v = centre[e];
-                const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
+                const auto [cw, ccx, ccy] = lv_clip_point(mx, my, mw, centre[e]);
                 if (!(cw > 4.0f * R.radius + wEps)) { decided = false; continue; }
-                const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
-                const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
                 const float sx = (ccx / cw + 1.0f) * halfW, sy = (ccy / cw + 1.0f) * halfH;
                 // |d screen| <= f r / (w - r) (1 + |x / w|) for a point within r of the centre: tangent of the off-axis angle from the
                 // centre's own clip coordinates, 25 % and 2 pixels on top.  With a lens shift (proj[8], proj[9] != 0: clip.x = proj[0] x
@@ -1697,25 +1815,8 @@ __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_RASTER_MIN_WAVES) void k_ppll_ra
         unsigned mask = 0u;
         uint32_t addr = 0u, leaf = 0u, pix = 0u;
         if (lane < m) {
-            const unsigned q = (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u);
-            leaf = qLeaf[q];
-            pix = qPix[q];
-            const uint32_t px = pix & 0xFFFFu, py = pix >> 16;
-            addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
-            // (no requested-tile test here: a whole-viewport frame requests every pixel, a rank of a sharded frame filters in stage A)
-            const f3 d = lv_prism_cov_dir(R, px, py);   // the pixel's coverage direction (unnormalised, lv_prism.h)
-            const uint32_t sl = leaf >> 26;   // the pair's segment among the wave's 64 = the lane that queued it
-            leaf &= 0x03FFFFFFu;
-            LvPrismPoint pt[2];
-            uint32_t pi[2];
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                pt[e].centre = mk3(segLds[9 * e + 0][sl], segLds[9 * e + 1][sl], segLds[9 * e + 2][sl]);
-                pt[e].normal = mk3(segLds[9 * e + 3][sl], segLds[9 * e + 4][sl], segLds[9 * e + 5][sl]);
-                pt[e].binormal = mk3(segLds[9 * e + 6][sl], segLds[9 * e + 7][sl], segLds[9 * e + 8][sl]);
-                pi[e] = __float_as_uint(segLds[18 + e][sl]);
-            }
-            mask = lv_prism_coverage_pts<NT>(R, pt, pi, R.radius, o, d);
+            mask = lv_seg_pair_coverage<NT>(R, segLds, qLeaf, qPix, (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u), o, leaf, pix);
+            addr = lv_ppll_addr(pix & 0xFFFFu, pix >> 16, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
             if (STATS) tests++;
         }
         while (__any(mask != 0u)) {
@@ -1772,83 +1873,11 @@ __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_RASTER_MIN_WAVES) void k_ppll_ra
     for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
         const bool valid = itemBase + lane < numItems;
         const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
-        int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-        // oriented box: |(pixel centre - c) . a - aMid| <= aHalf and |(pixel centre - c) . n - nMid| <= nHalf, n = (-a.y, a.x)
-        float ax = 1.0f, ay = 0.0f, cx0 = 0.0f, cy0 = 0.0f, aMid = 0.0f, aHalf = 3.0e38f, nMid = 0.0f, nHalf = 3.0e38f;
-        if (valid) {
-            const float4 pa = S.segs[2 * size_t(leaf)], pb = S.segs[2 * size_t(leaf) + 1];
-            uint32_t pi[2];
-            LvPrismPoint pt[2];
-            lv_prism_frames(S, leaf, pa, pb, pt, pi);
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                segLds[9 * e + 0][lane] = pt[e].centre.x; segLds[9 * e + 1][lane] = pt[e].centre.y; segLds[9 * e + 2][lane] = pt[e].centre.z;
-                segLds[9 * e + 3][lane] = pt[e].normal.x; segLds[9 * e + 4][lane] = pt[e].normal.y; segLds[9 * e + 5][lane] = pt[e].normal.z;
-                segLds[9 * e + 6][lane] = pt[e].binormal.x; segLds[9 * e + 7][lane] = pt[e].binormal.y; segLds[9 * e + 8][lane] = pt[e].binormal.z;
-                segLds[18 + e][lane] = __uint_as_float(pi[e]);
-            }
-            // axis of the oriented box: the projected centres (any direction gives a valid box; this one gives a tight one)
-            bool axisOk = true;
-            float wcx[2], wcy[2];
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const f3 v = pt[e].centre;
-                const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
-                const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
-                const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
-                axisOk = axisOk && cw > wEps;
-                wcx[e] = (ccx / cw + 1.0f) * halfW;
-                wcy[e] = (ccy / cw + 1.0f) * halfH;
-            }
-            if (axisOk) {
-                const float dx = wcx[1] - wcx[0], dy = wcy[1] - wcy[0], l2 = dx * dx + dy * dy;
-                if (l2 > 1e-12f && l2 < 1e30f) { const float il = 1.0f / sqrtf(l2); ax = dx * il; ay = dy * il; }
-                cx0 = wcx[0]; cy0 = wcy[0];
-            }
-            float lox = 3.0e38f, hix = -3.0e38f, loy = 3.0e38f, hiy = -3.0e38f;
-            float loa = 3.0e38f, hia = -3.0e38f, lon = 3.0e38f, hin = -3.0e38f;
-            bool anyFront = false, anyBehind = false;
-            for (uint32_t k = 0; k < N; k++) {
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const f3 v = lv_prism_pos(pt[e], lv_prism_dir(pt[e], R.cp[k], R.s[k]), R.radius);
-                    const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
-                    if (cw > wEps) {
-                        const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
-                        const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
-                        const float wx = (ccx / cw + 1.0f) * halfW, wy = (ccy / cw + 1.0f) * halfH;
-                        lox = fminf(lox, wx); hix = fmaxf(hix, wx); loy = fminf(loy, wy); hiy = fmaxf(hiy, wy);
-                        const float ta = (wx - cx0) * ax + (wy - cy0) * ay, tn = (wy - cy0) * ax - (wx - cx0) * ay;
-                        loa = fminf(loa, ta); hia = fmaxf(hia, ta); lon = fminf(lon, tn); hin = fmaxf(hin, tn);
-                        anyFront = true;
-                    } else anyBehind = true;
-                }
-            }
-            if (anyFront) {   // (all vertices behind the camera plane: no viewing ray meets the prism at a positive depth)
-                if (anyBehind) { lox = 0.0f; loy = 0.0f; hix = float(U.width); hiy = float(U.height); }   // straddles the camera plane
-                else if (axisOk) {
-                    // (the projected coordinates carry a relative rounding error of a few ulp: the margin also covers the box's own arithmetic)
-                    aMid = 0.5f * (loa + hia); aHalf = 0.5f * (hia - loa) + LV_PRISM_BBOX_MARGIN;
-                    nMid = 0.5f * (lon + hin); nHalf = 0.5f * (hin - lon) + LV_PRISM_BBOX_MARGIN;
-                }
-                // pixel x is a candidate iff its centre x + 0.5 lies in [lo - margin, hi + margin]
-                const float fx0 = fmaxf(ceilf(lox - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
-                const float fy0 = fmaxf(ceilf(loy - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
-                const float fx1 = fminf(floorf(hix + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.width) - 1.0f);
-                const float fy1 = fminf(floorf(hiy + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.height) - 1.0f);
-                if (fx0 <= fx1 && fy0 <= fy1) { x0 = int(fx0); x1 = int(fx1); y0 = int(fy0); y1 = int(fy1); }
-            }
-        }
-        int px = x0, py = y0;
-        bool more = valid && x1 >= x0 && y1 >= y0;
+        const LvSegWalk w = lv_seg_walk_setup(U, S, segLds, mx, my, mw, halfW, halfH, wEps, N, valid, leaf, lane);
+        int px = w.x0, py = w.y0;
+        bool more = valid && w.x1 >= w.x0 && w.y1 >= w.y0;
         while (__any(more)) {
-            bool cand = false;
-            if (more) {
-                const float qx = (float(px) + 0.5f) - cx0, qy = (float(py) + 0.5f) - cy0;
-                cand = fabsf((qx * ax + qy * ay) - aMid) <= aHalf && fabsf((qy * ax - qx * ay) - nMid) <= nHalf;
-                if (cand && !allRequested)
-                    cand = startOffset[lv_ppll_addr(uint32_t(px), uint32_t(py), U.ppllPaddedW, U.ppllTileW, U.ppllTileH)] == 0u;
-            }
+            const bool cand = more && lv_seg_walk_candidate(U, w, px, py, allRequested, startOffset);
             const unsigned long long cm = __ballot(cand);
             if (cand) {
                 const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
@@ -1857,9 +1886,7 @@ __global__ __launch_bounds__(LV_BLOCK, LV_PRISM_RASTER_MIN_WAVES) void k_ppll_ra
             }
             qCount += unsigned(__popcll(cm));
             if (qCount >= LV_WAVE) coverageStage(LV_WAVE);
-            if (more) {
-                if (++px > x1) { px = x0; more = ++py <= y1; }
-            }
+            if (more) more = lv_seg_walk_advance(w, px, py);
         }
         while (qCount > 0u) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE);   // (the next 64 segments replace the frames in LDS)
     }
@@ -2655,10 +2682,10 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_mboit_s
     unsigned fHead = 0u, fCount = 0u;   // covered triangles (wave-uniform)
     unsigned long long tests = 0, hits = 0;
     uint32_t keptSum = 0u;
-    // stage A's walk over the lane's segment: candidate rectangle, position in it, oriented box
+    // stage A's walk over the lane's segment: candidate rectangle and oriented box, position in it
     uint32_t leafA = 0u;
-    int x0 = 0, x1 = -1, y0 = 0, y1 = -1, px = 0, py = 0;
-    float ax = 1.0f, ay = 0.0f, cx0 = 0.0f, cy0 = 0.0f, aMid = 0.0f, aHalf = 3.0e38f, nMid = 0.0f, nHalf = 3.0e38f;
+    LvSegWalk w = {};
+    int px = 0, py = 0;
     bool more = false;
 
     // stage C on the m <= 64 oldest fragments of the queue.  (Both stages are lambdas with ONE call site each: a second site keeps
@@ -2704,23 +2731,7 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_mboit_s
         unsigned mask = 0u;
         uint32_t leaf = 0u, pix = 0u;
         if (lane < m) {
-            const unsigned q = (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u);
-            leaf = qLeaf[q];
-            pix = qPix[q];
-            const uint32_t px = pix & 0xFFFFu, py = pix >> 16;
-            const f3 d = lv_prism_cov_dir(R, px, py);
-            const uint32_t sl = leaf >> 26;
-            leaf &= 0x03FFFFFFu;
-            LvPrismPoint pt[2];
-            uint32_t pi[2];
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                pt[e].centre = mk3(segLds[9 * e + 0][sl], segLds[9 * e + 1][sl], segLds[9 * e + 2][sl]);
-                pt[e].normal = mk3(segLds[9 * e + 3][sl], segLds[9 * e + 4][sl], segLds[9 * e + 5][sl]);
-                pt[e].binormal = mk3(segLds[9 * e + 6][sl], segLds[9 * e + 7][sl], segLds[9 * e + 8][sl]);
-                pi[e] = __float_as_uint(segLds[18 + e][sl]);
-            }
-            mask = lv_prism_coverage_pts<NT>(R, pt, pi, R.radius, o, d);
+            mask = lv_seg_pair_coverage<NT>(R, segLds, qLeaf, qPix, (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u), o, leaf, pix);
             if (stats) tests++;
         }
         while (true) {
@@ -2737,19 +2748,19 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_mboit_s
             fCount += unsigned(__popcll(hm));
             if (fCount >= LV_WAVE || hm == 0ull) {
                 uint32_t* park = &s_park[0][threadIdx.x];
-                const float pf[8] = {ax, ay, cx0, cy0, aMid, aHalf, nMid, nHalf};
-                const uint32_t pu[11] = {mask, leaf, pix, leafA, uint32_t(x0), uint32_t(x1), uint32_t(y0), uint32_t(y1), uint32_t(px),
-                                         uint32_t(py), more ? 1u : 0u};
+                const float pf[8] = {w.ax, w.ay, w.cx0, w.cy0, w.aMid, w.aHalf, w.nMid, w.nHalf};
+                const uint32_t pu[11] = {mask, leaf, pix, leafA, uint32_t(w.x0), uint32_t(w.x1), uint32_t(w.y0), uint32_t(w.y1),
+                                         uint32_t(px), uint32_t(py), more ? 1u : 0u};
 #pragma unroll
                 for (int i = 0; i < 8; i++) park[i * LV_BLOCK] = __float_as_uint(pf[i]);
 #pragma unroll
                 for (int i = 0; i < 11; i++) park[(8 + i) * LV_BLOCK] = pu[i];
                 fragmentStage(fCount < LV_WAVE ? fCount : LV_WAVE);
-                ax = __uint_as_float(park[0]); ay = __uint_as_float(park[LV_BLOCK]); cx0 = __uint_as_float(park[2 * LV_BLOCK]);
-                cy0 = __uint_as_float(park[3 * LV_BLOCK]); aMid = __uint_as_float(park[4 * LV_BLOCK]); aHalf = __uint_as_float(park[5 * LV_BLOCK]);
-                nMid = __uint_as_float(park[6 * LV_BLOCK]); nHalf = __uint_as_float(park[7 * LV_BLOCK]);
+                w.ax = __uint_as_float(park[0]); w.ay = __uint_as_float(park[LV_BLOCK]); w.cx0 = __uint_as_float(park[2 * LV_BLOCK]);
+                w.cy0 = __uint_as_float(park[3 * LV_BLOCK]); w.aMid = __uint_as_float(park[4 * LV_BLOCK]); w.aHalf = __uint_as_float(park[5 * LV_BLOCK]);
+                w.nMid = __uint_as_float(park[6 * LV_BLOCK]); w.nHalf = __uint_as_float(park[7 * LV_BLOCK]);
                 mask = park[8 * LV_BLOCK]; leaf = park[9 * LV_BLOCK]; pix = park[10 * LV_BLOCK]; leafA = park[11 * LV_BLOCK];
-                x0 = int(park[12 * LV_BLOCK]); x1 = int(park[13 * LV_BLOCK]); y0 = int(park[14 * LV_BLOCK]); y1 = int(park[15 * LV_BLOCK]);
+                w.x0 = int(park[12 * LV_BLOCK]); w.x1 = int(park[13 * LV_BLOCK]); w.y0 = int(park[14 * LV_BLOCK]); w.y1 = int(park[15 * LV_BLOCK]);
                 px = int(park[16 * LV_BLOCK]); py = int(park[17 * LV_BLOCK]); more = park[18 * LV_BLOCK] != 0u;
             }
         }
@@ -2760,85 +2771,16 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_mboit_s
     const uint32_t waveId = blockIdx.x * (LV_BLOCK / LV_WAVE) + (threadIdx.x >> 6), numWaves = gridDim.x * (LV_BLOCK / LV_WAVE);
     const uint32_t numItems = leafList ? dc->prismListCount : S.numSegs;
     for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
-        // stage A: k_ppll_raster_prism's, statement for statement (the candidate set decides nothing, the coverage test does)
         const bool valid = itemBase + lane < numItems;
         const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
         leafA = leaf;
-        x0 = 0; x1 = -1; y0 = 0; y1 = -1;
-        ax = 1.0f; ay = 0.0f; cx0 = 0.0f; cy0 = 0.0f; aMid = 0.0f; aHalf = 3.0e38f; nMid = 0.0f; nHalf = 3.0e38f;
-        if (valid) {
-            const float4 pa = S.segs[2 * size_t(leaf)], pb = S.segs[2 * size_t(leaf) + 1];
-            uint32_t pi[2];
-            LvPrismPoint pt[2];
-            lv_prism_frames(S, leaf, pa, pb, pt, pi);
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                segLds[9 * e + 0][lane] = pt[e].centre.x; segLds[9 * e + 1][lane] = pt[e].centre.y; segLds[9 * e + 2][lane] = pt[e].centre.z;
-                segLds[9 * e + 3][lane] = pt[e].normal.x; segLds[9 * e + 4][lane] = pt[e].normal.y; segLds[9 * e + 5][lane] = pt[e].normal.z;
-                segLds[9 * e + 6][lane] = pt[e].binormal.x; segLds[9 * e + 7][lane] = pt[e].binormal.y; segLds[9 * e + 8][lane] = pt[e].binormal.z;
-                segLds[18 + e][lane] = __uint_as_float(pi[e]);
-            }
-            bool axisOk = true;
-            float wcx[2], wcy[2];
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const f3 v = pt[e].centre;
-                const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
-                const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
-                const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
-                axisOk = axisOk && cw > wEps;
-                wcx[e] = (ccx / cw + 1.0f) * halfW;
-                wcy[e] = (ccy / cw + 1.0f) * halfH;
-            }
-            if (axisOk) {
-                const float dx = wcx[1] - wcx[0], dy = wcy[1] - wcy[0], l2 = dx * dx + dy * dy;
-                if (l2 > 1e-12f && l2 < 1e30f) { const float il = 1.0f / sqrtf(l2); ax = dx * il; ay = dy * il; }
-                cx0 = wcx[0]; cy0 = wcy[0];
-            }
-            float lox = 3.0e38f, hix = -3.0e38f, loy = 3.0e38f, hiy = -3.0e38f;
-            float loa = 3.0e38f, hia = -3.0e38f, lon = 3.0e38f, hin = -3.0e38f;
-            bool anyFront = false, anyBehind = false;
-            for (uint32_t k = 0; k < N; k++) {
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const f3 v = lv_prism_pos(pt[e], lv_prism_dir(pt[e], R.cp[k], R.s[k]), R.radius);
-                    const float cw = ((mw[0] * v.x + mw[1] * v.y) + mw[2] * v.z) + mw[3];
-                    if (cw > wEps) {
-                        const float ccx = ((mx[0] * v.x + mx[1] * v.y) + mx[2] * v.z) + mx[3];
-                        const float ccy = ((my[0] * v.x + my[1] * v.y) + my[2] * v.z) + my[3];
-                        const float wx = (ccx / cw + 1.0f) * halfW, wy = (ccy / cw + 1.0f) * halfH;
-                        lox = fminf(lox, wx); hix = fmaxf(hix, wx); loy = fminf(loy, wy); hiy = fmaxf(hiy, wy);
-                        const float ta = (wx - cx0) * ax + (wy - cy0) * ay, tn = (wy - cy0) * ax - (wx - cx0) * ay;
-                        loa = fminf(loa, ta); hia = fmaxf(hia, ta); lon = fminf(lon, tn); hin = fmaxf(hin, tn);
-                        anyFront = true;
-                    } else anyBehind = true;
-                }
-            }
-            if (anyFront) {
-                if (anyBehind) { lox = 0.0f; loy = 0.0f; hix = float(U.width); hiy = float(U.height); }
-                else if (axisOk) {
-                    aMid = 0.5f * (loa + hia); aHalf = 0.5f * (hia - loa) + LV_PRISM_BBOX_MARGIN;
-                    nMid = 0.5f * (lon + hin); nHalf = 0.5f * (hin - lon) + LV_PRISM_BBOX_MARGIN;
-                }
-                const float fx0 = fmaxf(ceilf(lox - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
-                const float fy0 = fmaxf(ceilf(loy - LV_PRISM_BBOX_MARGIN - 0.5f), 0.0f);
-                const float fx1 = fminf(floorf(hix + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.width) - 1.0f);
-                const float fy1 = fminf(floorf(hiy + LV_PRISM_BBOX_MARGIN - 0.5f), float(U.height) - 1.0f);
-                if (fx0 <= fx1 && fy0 <= fy1) { x0 = int(fx0); x1 = int(fx1); y0 = int(fy0); y1 = int(fy1); }
-            }
-        }
-        px = x0; py = y0;
-        more = valid && x1 >= x0 && y1 >= y0;
+        w = lv_seg_walk_setup(U, S, segLds, mx, my, mw, halfW, halfH, wEps, N, valid, leaf, lane);
+        px = w.x0; py = w.y0;
+        more = valid && w.x1 >= w.x0 && w.y1 >= w.y0;
         const bool lastItem = itemBase + numWaves * LV_WAVE >= numItems;   // (overflow: numItems < 2^26)
         while (true) {
             const bool drain = !__any(more);   // every rectangle walked: the rest of the pairs, 64 at a time
-            bool cand = false;
-            if (more) {
-                const float qx = (float(px) + 0.5f) - cx0, qy = (float(py) + 0.5f) - cy0;
-                cand = fabsf((qx * ax + qy * ay) - aMid) <= aHalf && fabsf((qy * ax - qx * ay) - nMid) <= nHalf;
-                if (cand && !allRequested)
-                    cand = startOffset[lv_ppll_addr(uint32_t(px), uint32_t(py), U.ppllPaddedW, U.ppllTileW, U.ppllTileH)] == 0u;
-            }
+            const bool cand = more && lv_seg_walk_candidate(U, w, px, py, allRequested, startOffset);
             const unsigned long long cm = __ballot(cand);
             if (cand) {
                 const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
@@ -2848,9 +2790,7 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_mboit_s
             qCount += unsigned(__popcll(cm));
             if (qCount >= LV_WAVE || drain) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE, lastItem && drain && qCount <= LV_WAVE);
             if (drain && qCount == 0u) break;   // (the next 64 segments replace the frames in LDS)
-            if (more) {
-                if (++px > x1) { px = x0; more = ++py <= y1; }
-            }
+            if (more) more = lv_seg_walk_advance(w, px, py);
         }
     }
     if (count) {
@@ -3705,6 +3645,36 @@ static int lv_mboit_resolve(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, 
     return LV_OK;
 }
 
+// What the segment rasteriser's frame runs in front of it, for k_ppll_raster_prism and k_mboit_stream_pass alike: the opening event
+// of LV_KERNEL_PPLL_RASTER and -- a frame that leaves tiles out -- the coarse grid, the requested pixels (k_ppll_mark_tiles) and the
+// list of the segments that can touch them (k_ppll_cull_segments; k_ppll_clear zeroed the list's counter).  LV_KERNEL_PPLL_RASTER
+// times the rasteriser WITH these: a rank's rasteriser cost is the three together.  leafList: the list, or nullptr =
+// every segment
+static int lv_segment_raster_front(lv_ctx* ctx, const LvUniforms& U, const LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats,
+                                   bool allRequested, LvDevCounters* dc, uint32_t*& leafList) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    uint32_t* coarse = nullptr;
+    if (!allRequested) {
+        const size_t cells = size_t((U.width + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE) * ((U.height + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE);
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllCoarse, cells * 4))) return rc;
+        coarse = (uint32_t*)ctx->ppllCoarse.ptr;
+        LV_HIP(ctx, hipMemsetAsync(coarse, 0, cells * 4, st));
+    }
+    leafList = nullptr;
+    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
+    if (allRequested) {}   // (k_ppll_clear marked every pixel)
+    else if (stats) k_ppll_mark_tiles<true><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
+    else k_ppll_mark_tiles<false><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
+    if (!allRequested && S.numSegs != 0) {
+        if ((rc = lv_buf_reserve(ctx, ctx->prismLeafList, size_t(S.numSegs) * 4))) return rc;
+        leafList = (uint32_t*)ctx->prismLeafList.ptr;
+        const uint32_t cullGrid = (S.numSegs + LV_CULL_PER_BLOCK - 1u) / LV_CULL_PER_BLOCK;
+        k_ppll_cull_segments<<<cullGrid, LV_BLOCK, 0, st>>>(U, S, coarse, leafList, dc);
+    }
+    return LV_OK;
+}
+
 // A mode-6 frame with mboit_fragment_storage = streamed: clear, the two launches of k_mboit_stream_pass, the blend.  No record pool,
 // no fragment pool, no scan, no regrowth; the only host synchronisation is the read-back of the line points' box, once per
 // acceleration-structure build.  The blend's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
@@ -3747,26 +3717,10 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
             (allRequested && stats) ? (unsigned long long)U.width * U.height : 0ull);
     LV_HIP(ctx, hipMemsetAsync(ctx->mboitAccum.ptr, 0, accBytes, st));
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
-    uint32_t* coarse = nullptr;
-    if (!allRequested) {
-        const size_t cells = size_t((U.width + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE) * ((U.height + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE);
-        if ((rc = lv_buf_reserve(ctx, ctx->ppllCoarse, cells * 4))) return rc;
-        coarse = (uint32_t*)ctx->ppllCoarse.ptr;
-        LV_HIP(ctx, hipMemsetAsync(coarse, 0, cells * 4, st));
-    }
-    uint32_t* leafList = nullptr;
     // LV_KERNEL_PPLL_RASTER: one launch per pass, the first with what a sharded frame runs in front of it (as in pooled storage)
     const bool rasterTimed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) != 0u;
-    if (rasterTimed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
-    if (allRequested) {}   // (k_ppll_clear marked every pixel)
-    else if (stats) k_ppll_mark_tiles<true><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
-    else k_ppll_mark_tiles<false><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
-    if (!allRequested && S.numSegs != 0) {
-        if ((rc = lv_buf_reserve(ctx, ctx->prismLeafList, size_t(S.numSegs) * 4))) return rc;
-        leafList = (uint32_t*)ctx->prismLeafList.ptr;
-        const uint32_t cullGrid = (S.numSegs + LV_CULL_PER_BLOCK - 1u) / LV_CULL_PER_BLOCK;
-        k_ppll_cull_segments<<<cullGrid, LV_BLOCK, 0, st>>>(U, S, coarse, leafList, dc);
-    }
+    uint32_t* leafList;
+    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
     const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
     // the variants lv_frame_render selects for the pooled fragment stage; shading_numerics = fast: plain tubes with the raster colour
     const bool fastShade = ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
@@ -4184,32 +4138,13 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     } while (0)
         if (segmentRaster) {
             // the segment rasteriser (k_ppll_raster_prism): requested pixels marked, then one lane per segment
-            uint32_t* coarse = nullptr;
-            if (!allRequested) {
-                const size_t cells = size_t((U.width + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE) * ((U.height + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE);
-                if ((rc = lv_buf_reserve(ctx, ctx->ppllCoarse, cells * 4))) return rc;
-                coarse = (uint32_t*)ctx->ppllCoarse.ptr;
-                LV_HIP(ctx, hipMemsetAsync(coarse, 0, cells * 4, st));
-            }
 #define LV_LAUNCH_RASTER(ST, NT)                                                                                              \
     k_ppll_raster_prism<ST, NT><<<rasterGrid, LV_BLOCK, 0, st>>>(                                                             \
             U, S, gatherPool, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots,                \
             allRequested ? 1u : 0u, leafList)
-            uint32_t* leafList = nullptr;
-            // LV_KERNEL_PPLL_RASTER times the rasteriser WITH what a sharded frame runs in front of it (k_ppll_mark_tiles,
-            // k_ppll_cull_segments): a rank's rasteriser cost is the three together
             const bool rasterTimed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) != 0u;
-            if (rasterTimed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
-            if (allRequested) {}   // (k_ppll_clear marked every pixel)
-            else if (stats) k_ppll_mark_tiles<true><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
-            else k_ppll_mark_tiles<false><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, coarse, dc);
-            if (!allRequested && S.numSegs != 0) {
-                // the segments that can touch this tile list (k_ppll_clear zeroed the list's counter)
-                if ((rc = lv_buf_reserve(ctx, ctx->prismLeafList, size_t(S.numSegs) * 4))) return rc;
-                leafList = (uint32_t*)ctx->prismLeafList.ptr;
-                const uint32_t cullGrid = (S.numSegs + LV_CULL_PER_BLOCK - 1u) / LV_CULL_PER_BLOCK;
-                k_ppll_cull_segments<<<cullGrid, LV_BLOCK, 0, st>>>(U, S, coarse, leafList, dc);
-            }
+            uint32_t* leafList;
+            if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
             if (S.numSegs != 0) {
                 if (S.prism.n == 6u) { if (stats) LV_LAUNCH_RASTER(true, 6); else LV_LAUNCH_RASTER(false, 6); }
                 else { if (stats) LV_LAUNCH_RASTER(true, 0); else LV_LAUNCH_RASTER(false, 0); }
