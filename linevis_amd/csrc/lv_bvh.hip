@@ -55,7 +55,11 @@ __global__ __launch_bounds__(LV_BLOCK) void k_seg_boxes(const lv_line_point* __r
         const float* p1 = points[segIdx[2 * s + 1]].linePosition;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const float lo = (fminf(p0[k], p1[k]) - radius) - pad, hi = (fmaxf(p0[k], p1[k]) + radius) + pad;
+            // the pad grows with the coordinate: lv_node_step's planes carry a rounding error of about 2 * 2^-24 * |plane| in position
+            // space (lv_trace.h, lv_traversal_inv), and lo0 itself rounds to the float32 grid of |x|.  2^-21 |x| is four times that
+            // and exceeds the absolute pad (>= 1e-6) only for |x| > 2.09: boxes of normalised scenes are what they were
+            const float lo0 = fminf(p0[k], p1[k]) - radius, hi0 = fmaxf(p0[k], p1[k]) + radius;
+            const float lo = lo0 - fmaxf(pad, fabsf(lo0) * 0x1p-21f), hi = hi0 + fmaxf(pad, fabsf(hi0) * 0x1p-21f);
             boxOrig[6 * size_t(s) + k] = lo;
             boxOrig[6 * size_t(s) + 3 + k] = hi;
             mn[k] = fminf(mn[k], lo);
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(LV_BLOCK) void k_leaves(const lv_line_point* __rest
     for (int k = 0; k < 6; k++) leafBox[6 * size_t(i) + k] = boxOrig[6 * size_t(s) + k];
 }
 
-// triangle tubes: padded AABB of every triangle (the same box the ray-triangle test clips t against)
+// triangle tubes: padded AABB of every triangle (inside the unit box the same box the ray-triangle test clips t against)
 // Leaves of the triangle LBVH are GROUPS of `group` consecutive triangles of the input order (the tessellator emits the two
 // triangles of a tube face, then the next face, then the next segment: consecutive triangles are neighbours): box of group g =
 // union of the padded boxes of its triangles.  A tree over N / 4 leaves is one wide level lower and a quarter the size of a tree
@@ -141,12 +145,16 @@ __global__ __launch_bounds__(LV_BLOCK) void k_tri_boxes(const lv_tube_vertex* __
             const float* c = verts[triIdx[3 * size_t(s) + 2]].vertexPosition;
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-                lo[k] = fminf(lo[k], fminf(fminf(a[k], b[k]), c[k]) - pad);
-                hi[k] = fmaxf(hi[k], fmaxf(fmaxf(a[k], b[k]), c[k]) + pad);
+                lo[k] = fminf(lo[k], fminf(fminf(a[k], b[k]), c[k]));
+                hi[k] = fmaxf(hi[k], fmaxf(fmaxf(a[k], b[k]), c[k]));
             }
         }
+        // the group box is padded like a segment box (k_seg_boxes): by `pad`, or by 2^-21 of the coordinate where that is more.  The
+        // own-box rule of lv_ray_triangle keeps the plain pad (ctx->triPad): that one is part of the hit's definition
 #pragma unroll
         for (int k = 0; k < 3; k++) {
+            lo[k] = lo[k] - fmaxf(pad, fabsf(lo[k]) * 0x1p-21f);
+            hi[k] = hi[k] + fmaxf(pad, fabsf(hi[k]) * 0x1p-21f);
             boxOrig[6 * size_t(g) + k] = lo[k];
             boxOrig[6 * size_t(g) + 3 + k] = hi[k];
             mn[k] = fminf(mn[k], lo[k]);

@@ -316,8 +316,15 @@ __device__ __forceinline__ bool lv_slab_q(uint32_t nearX, uint32_t nearY, uint32
 // o and origin of one sign, or o > 0 > origin), and fmaxf / fminf drop a NaN: the axis does not take part, which is always
 // conservative.  The one other outcome is +inf for both planes, when o < 0 < origin along that axis (mirrored for -inf): tn = inf,
 // the child is culled -- rightly: the coordinate of such a ray moves by less than tMax * 2^-126, the box lies wholly on the
-// other side of zero, and its primitives are at least the builder's pad (>= 1e-6) inside it.  A denormal therefore takes exactly
-// the path that a zero of its sign takes today (tests/test_gpu_ao_sample_overhead.py runs such rays against brute force).
+// other side of zero, and its primitives are at least the builder's pad (max(r * 1e-3 + 1e-6, 2^-21 |x|), k_seg_boxes / k_tri_boxes)
+// inside it.  A denormal therefore takes exactly the path that a zero of its sign takes today (tests/test_gpu_ao_sample_overhead.py
+// runs such rays against brute force).
+// What the factor 1.00001 does NOT cover is the cancellation in origin * inv - o * inv: both terms are about |plane| * |inv|, each
+// rounds by up to 2^-24 of itself, and the difference keeps that error while t itself may be small -- every plane of the axis is
+// displaced by about 2 * 2^-24 * |plane| in position space, whatever t is.  That error is relative to the COORDINATE, so the pad that
+// absorbs it is too: the builders pad every box by at least 2^-21 of its coordinate (four times the displacement;
+// tests/test_gpu_culling_grazing.py runs rays that graze the box faces at |x| up to 1000 against brute force).  Supported range: a
+// radius of at least 64 ulp of the largest coordinate (numerics contract).
 // LV_TRAVERSAL_INV_IEEE=1 (measurement knob) restores the division.
 #ifndef LV_TRAVERSAL_INV_IEEE
 #define LV_TRAVERSAL_INV_IEEE 0

@@ -1539,8 +1539,11 @@ void lvo_scene_build_bvh(lvo_scene* sc, float lineWidth) {
         V3 p0, p1; segPoints(*sc, s, p0, p1);
         const float a[3] = {p0.x, p0.y, p0.z}, b[3] = {p1.x, p1.y, p1.z};
         for (int k = 0; k < 3; k++) {
-            boxes[s].mn[k] = fminf(a[k], b[k]) - r - pad;
-            boxes[s].mx[k] = fmaxf(a[k], b[k]) + r + pad;
+            // the pad grows with the coordinate (the library's rule, k_seg_boxes): lo0 and the subtraction below round to the float32
+            // grid of |x|, which is coarser than r * 1e-3 + 1e-6 once |x| passes about 16 -- the box then ended inside the capsule
+            const float lo0 = fminf(a[k], b[k]) - r, hi0 = fmaxf(a[k], b[k]) + r;
+            boxes[s].mn[k] = lo0 - fmaxf(pad, fabsf(lo0) * 0x1p-21f);
+            boxes[s].mx[k] = hi0 + fmaxf(pad, fabsf(hi0) * 0x1p-21f);
             smn[k] = fminf(smn[k], boxes[s].mn[k]);
             smx[k] = fmaxf(smx[k], boxes[s].mx[k]);
         }

@@ -522,7 +522,14 @@ void lvo_tri_scene_build_bvh(lvo_tri_scene* sc) {
     for (uint32_t t = 0; t < n; t++) {
         V3 a, b, c; triVerts(*sc, t, a, b, c);
         float* bx = &sc->leafBoxes[6 * size_t(t)];
-        triBox(a, b, c, sc->pad, bx, bx + 3);
+        triBox(a, b, c, 0.0f, bx, bx + 3);
+        // leaf boxes of the tree: the pad grows with the coordinate, as in the library (k_tri_boxes).  rayTriangle's own-box rule
+        // keeps sc->pad: that one is part of the hit's definition
+        for (int k = 0; k < 3; k++) {
+            const float lo0 = bx[k], hi0 = bx[3 + k];
+            bx[k] = lo0 - fmaxf(sc->pad, fabsf(lo0) * 0x1p-21f);
+            bx[3 + k] = hi0 + fmaxf(sc->pad, fabsf(hi0) * 0x1p-21f);
+        }
         for (int k = 0; k < 3; k++) { smn[k] = fminf(smn[k], bx[k]); smx[k] = fmaxf(smx[k], bx[3 + k]); }
     }
     std::vector<uint64_t> keys(n);
