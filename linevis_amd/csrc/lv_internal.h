@@ -370,7 +370,8 @@ int lv_frame_trace_rays(lv_ctx* ctx, const float* o, const float* d, float tMin,
                         uint32_t* outSeg, uint32_t* outKind);
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,
                                   float* outT, uint32_t* outTri, float* outUV);
-int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async = false);
+// inFrame: called by lv_frame_render, which reserved the traversal-stack slab for the bake too (nothing inside a frame moves it)
+int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async = false, bool inFrame = false);
 int lv_bake_poll(lv_ctx* ctx, bool wait);
 // everything that changes what a baked table depends on: a running asynchronous bake still reads the old inputs, so it is waited for
 // (and its result discarded: the generation no longer matches)

@@ -3184,18 +3184,102 @@ int lv_frame_depth_range(lv_ctx* ctx) {
     return LV_OK;
 }
 
-// bytes of the global part of the traversal stacks for one launch geometry (0: the LDS-staged part holds the whole stack)
-static size_t lv_overflow_bytes(const lv_ctx* ctx, uint64_t gridBlocks, uint32_t ldsEntries, bool triangles) {
-    const uint64_t maxEntries = 3ull * uint64_t(triangles ? ctx->triWideDepth : ctx->wideDepth) + 2;
-    if (maxEntries <= ldsEntries) return 0;
-    return size_t(gridBlocks) * LV_BLOCK * (maxEntries - ldsEntries) * 4;
+// ---------------------------------------------------------------- launch geometry of a tile list (the host side of lv_block_pixel)
+// numTiles tiles of tileW x tileH pixels, each in 16x16-pixel blocks that fill whole 64x64 groups
+static LvTiles lv_tiles(const uint32_t* tilesXY, uint32_t numTiles, uint32_t tileW, uint32_t tileH) {
+    LvTiles T{};
+    T.tilesXY = tilesXY; T.numTiles = numTiles; T.tileW = tileW; T.tileH = tileH;
+    T.blocksX = ((tileW + 63u) / 64u) * 4u; T.blocksY = ((tileH + 63u) / 64u) * 4u;
+    return T;
 }
+static uint64_t lv_tiles_blocks(const LvTiles& T) { return uint64_t(T.numTiles) * T.blocksX * T.blocksY; }
+// workgroups of a tile kernel: a multiple of 8 XCDs x LV_XCD_GROUP (a launch bounds the blocks by 0x7FFFFFF0 first)
+static uint64_t lv_tiles_grid(const LvTiles& T) { return (lv_tiles_blocks(T) + 127u) / 128u * 128u; }
+static uint64_t lv_tiles_groups(const LvTiles& T) { return uint64_t(T.numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u); }   // 64 x 64 pixels
+static uint64_t lv_tiles_cells(const LvTiles& T) { return lv_tiles_groups(T) * 64u; }   // 8 x 8 pixels: one wave of a resolve each
+static uint64_t lv_tiles_pixels(const LvTiles& T) { return uint64_t(T.numTiles) * T.tileW * T.tileH; }
 
 // persistent grid of k_ao_rays: enough workgroups to fill every CU at the kernel's LDS-limited residency
 static uint64_t lv_ao_grid(const lv_ctx* ctx, uint64_t maxRays) {
     uint64_t gridRays = uint64_t(ctx->numCUs) * LV_AO_BLOCKS_PER_CU;
     if (gridRays > (maxRays + LV_AO_BLOCK - 1) / LV_AO_BLOCK) gridRays = (maxRays + LV_AO_BLOCK - 1) / LV_AO_BLOCK;
     return gridRays ? gridRays : 1;
+}
+
+// Launch geometry of a frame's RTAO pass (lv_run_ao) for the colour pass' tiles Tcolour.  The pass runs on those tiles dilated by
+// haloPx pixels: 1 when the colour rays are jittered (the AO lookup blends the four texels around the projected hit,
+// AmbientOcclusion.glsl:84-99), plus the 2 * (2^iterations - 1) pixels the EAW denoiser reads around every pixel it filters (a-trous
+// passes with step widths 1, 2, 4, ...).  SVGF is temporal -- its history is read at reprojected positions anywhere in the picture --
+// so with it the pass covers the whole viewport as one tile at the origin, no halo, whatever tiles the call renders.
+struct LvAoGeometry {
+    bool svgf;
+    uint32_t haloPx, numTiles, tileW, tileH;
+    uint64_t maxPixels;
+    // workgroups of k_ao_primary, of k_ao_rays, and of k_primary_pair (the RTAO primaries' and the colour pass' in one launch)
+    uint64_t gridTiles, gridRays, gridPair;
+};
+static LvAoGeometry lv_ao_geometry(const lv_ctx* ctx, const LvUniforms& U, const LvTiles& Tcolour) {
+    LvAoGeometry G;
+    const bool eaw = ctx->opt.eawEnabled && ctx->opt.eawIterations > 0u;
+    G.svgf = ctx->opt.svgfEnabled;
+    G.haloPx = G.svgf ? 0u : (U.aoProjectLookup ? 1u : 0u) + (eaw ? 2u * ((1u << ctx->opt.eawIterations) - 1u) : 0u);
+    G.numTiles = G.svgf ? 1u : Tcolour.numTiles;
+    G.tileW = G.svgf ? ctx->width : Tcolour.tileW + 2u * G.haloPx;
+    G.tileH = G.svgf ? ctx->height : Tcolour.tileH + 2u * G.haloPx;
+    const LvTiles T = lv_tiles(nullptr, G.numTiles, G.tileW, G.tileH);
+    G.gridTiles = lv_tiles_grid(T);
+    G.maxPixels = lv_tiles_pixels(T);
+    G.gridRays = lv_ao_grid(ctx, G.maxPixels * U.aoSamplesPerFrame);
+    G.gridPair = G.gridTiles + lv_tiles_grid(Tcolour);
+    return G;
+}
+
+// ---------------------------------------------------------------- the global part of the traversal stacks
+// Bytes of the slab for one launch, one column of entries per thread (0: the LDS-staged part holds the whole stack, the tree is not
+// higher than that): a step of the 4-wide tree pushes at most 3 references per level
+static size_t lv_overflow_bytes(const lv_ctx* ctx, uint64_t gridBlocks, uint32_t ldsEntries, bool triangles) {
+    const uint64_t maxEntries = 3ull * uint64_t(triangles ? ctx->triWideDepth : ctx->wideDepth) + 2;
+    return maxEntries > ldsEntries ? size_t(gridBlocks) * LV_BLOCK * (maxEntries - ldsEntries) * 4 : 0;
+}
+// ... for every launch of a frame: lv_frame_render reserves ctx->stackOverflow once, BEFORE it builds a scene view, because a later,
+// larger request would free the slab under the views built before it.  Same geometries as the launches: lv_ao_geometry.
+static size_t lv_frame_overflow_bytes(const lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, int mode, bool pairPrimaries) {
+    const uint64_t gridTiles = lv_tiles_grid(T);
+    size_t need = lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, false);
+    if (ctx->opt.rtTriangleMesh && mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER)
+        need = std::max(need, lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, true));
+    if (U.useAmbientOcclusion && !U.aoPrebaked) {
+        const LvAoGeometry G = lv_ao_geometry(ctx, U, T);
+        const bool tri = lv_ao_triangle_tubes(ctx);
+        need = std::max(need, lv_overflow_bytes(ctx, std::max(G.gridRays, G.gridTiles), LV_AO_STACK_LDS, tri));
+        if (pairPrimaries) {   // one slab for both halves of the launch, for the deeper of the two trees
+            need = std::max(need, lv_overflow_bytes(ctx, G.gridPair, LV_STACK_LDS, false));
+            if (tri) need = std::max(need, lv_overflow_bytes(ctx, G.gridPair, LV_STACK_LDS, true));
+        }
+    }
+    if (U.aoPrebaked && !ctx->bakeValid)   // the synchronous bake (lv_bake_ambient_occlusion)
+        need = std::max(need, lv_overflow_bytes(ctx, uint64_t(ctx->numCUs) * LV_AO_BLOCKS_PER_CU, LV_AO_STACK_LDS, true));
+    return need;
+}
+// Points a scene view of a frame at the slab.  Nothing inside a frame moves it: a launch the reservation did not cover is an error.
+static int lv_prepare_overflow(lv_ctx* ctx, LvSceneDev& S, const char* launch, uint64_t gridBlocks, uint32_t ldsEntries = LV_STACK_LDS,
+                               bool triangles = false) {
+    S.stackOverflow = nullptr;
+    const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, triangles);
+    if (bytes == 0) return LV_OK;
+    if (!ctx->stackOverflow.ptr || ctx->stackOverflow.bytes < bytes)
+        return lv_fail(ctx, LV_E_CAPACITY, "%s: the traversal stacks need %llu bytes, the frame reserved %llu", launch,
+                       (unsigned long long)bytes, (unsigned long long)ctx->stackOverflow.bytes);
+    S.stackOverflow = (unsigned*)ctx->stackOverflow.ptr;
+    return LV_OK;
+}
+// ... of an entry point outside a frame, which reserves for its one launch
+static int lv_reserve_overflow(lv_ctx* ctx, LvSceneDev& S, const char* launch, uint64_t gridBlocks, uint32_t ldsEntries = LV_STACK_LDS,
+                               bool triangles = false) {
+    const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, triangles);
+    int rc;
+    if (bytes && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, bytes))) return rc;
+    return lv_prepare_overflow(ctx, S, launch, gridBlocks, ldsEntries, triangles);
 }
 
 // ---------------------------------------------------------------- dispatch order of the tile kernels
@@ -3253,7 +3337,7 @@ static int lv_group_order_prepare(lv_ctx* ctx, LvTiles& T, int which) {
     T.groupCost = nullptr;
     lv_ctx::GroupOrder& G = ctx->groupOrder[which];
     G.active = false;
-    const uint64_t n64 = uint64_t(T.numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u);
+    const uint64_t n64 = lv_tiles_groups(T);
     if (!ctx->opt.dispatchByCost || n64 < 2u || n64 > LV_ORDER_MAX_GROUPS) { G.n = 0; return LV_OK; }
     const uint32_t n = uint32_t(n64);
     int rc;
@@ -3286,60 +3370,29 @@ static int lv_group_order_sort(lv_ctx* ctx) {
     return LV_OK;
 }
 
-// the global part of the traversal stacks: only when the tree is higher than the LDS-staged part.  lv_frame_render
-// reserves the largest slab any kernel of the frame needs BEFORE it builds a scene view, so that the reserve below never
-// reallocates under a pointer an earlier view still holds.
-static int lv_prepare_overflow(lv_ctx* ctx, LvSceneDev& S, uint64_t gridBlocks, uint32_t ldsEntries = LV_STACK_LDS,
-                               bool triangles = false) {
-    S.stackOverflow = nullptr;
-    // a step of the 4-wide tree pushes at most 3 references per level
-    const uint64_t maxEntries = 3ull * uint64_t(triangles ? ctx->triWideDepth : ctx->wideDepth) + 2;
-    if (maxEntries <= ldsEntries) return LV_OK;
-    const uint64_t extra = maxEntries - ldsEntries;
-    int rc = lv_buf_reserve(ctx, ctx->stackOverflow, size_t(gridBlocks) * LV_BLOCK * extra * 4);
-    if (rc) return rc;
-    S.stackOverflow = (unsigned*)ctx->stackOverflow.ptr;
-    return LV_OK;
-}
-
 // pairColour: the colour pass' scene view when its first-hit trace rides along with the RTAO primaries of the first iteration
 // (k_primary_pair; lv_frame_render decides) -- the hits land in ctx->firstHit, *paired says whether the launch happened
-static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& Tcolour, uint32_t gridTilesColour,
-                     uint64_t maxPixelsColour, const LvSceneDev* pairColour = nullptr, bool* paired = nullptr) {
+static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& Tcolour, const LvSceneDev* pairColour = nullptr,
+                     bool* paired = nullptr) {
     hipStream_t st = ctx->stream;
     LvDevCounters* dc = (LvDevCounters*)ctx->counters.ptr;
     const uint32_t spp = U.aoSamplesPerFrame;
     int rc;
-    // With jittered colour rays the AO lookup blends the four texels around the projected hit (AmbientOcclusion.glsl:84-99), so
-    // the AO image needs a 1-pixel halo around every rendered tile: the AO pass runs on the tiles dilated by one pixel
-    // (origins - 1, modulo 2^32: pixels left of / above the viewport fail the inView test; size + 2).  Rings of adjacent tiles
-    // overlap -- those pixels are simply computed twice, which is why the running mean below reads the previous pass' image
-    // (ping-pong) instead of updating in place.
-    LvTiles T = Tcolour;
-    uint32_t gridTiles = gridTilesColour;
-    uint64_t maxPixels = maxPixelsColour;
-    // ... and the EAW denoiser (ambient_occlusion_denoiser) reads 2 * (2^iterations - 1) pixels around every pixel it filters
-    // (a-trous passes with step widths 1, 2, 4, ...): the same mechanism with a wider halo.
+    // The tiles of the pass (lv_ao_geometry): the colour pass', dilated by the halo -- origins - haloPx, modulo 2^32: pixels left of /
+    // above the viewport fail the inView test.  Rings of adjacent tiles overlap -- those pixels are simply computed twice, which is
+    // why the running mean below reads the previous pass' image (ping-pong) instead of updating in place.  Or the whole viewport.
+    const LvAoGeometry G = lv_ao_geometry(ctx, U, Tcolour);
     const bool eaw = ctx->opt.eawEnabled && ctx->opt.eawIterations > 0u;
-    // ... and SVGF is temporal: its history is read at reprojected positions anywhere in the picture, so the RTAO pass and the
-    // denoiser always cover the whole viewport (one tile at the origin, no halo needed), whatever tiles the call renders.
-    const bool svgf = ctx->opt.svgfEnabled;
-    const uint32_t haloPx = svgf ? 0u : (U.aoProjectLookup ? 1u : 0u) + (eaw ? 2u * ((1u << ctx->opt.eawIterations) - 1u) : 0u);
-    const bool halo = haloPx != 0u;
+    const bool svgf = G.svgf, halo = G.haloPx != 0u;
+    const uint32_t haloPx = G.haloPx, gridTiles = uint32_t(G.gridTiles), gridTilesColour = uint32_t(lv_tiles_grid(Tcolour));
+    const uint64_t maxPixelsColour = lv_tiles_pixels(Tcolour), maxPixels = G.maxPixels;
+    LvTiles T = Tcolour;
     if (svgf) {
         if (!ctx->fullFrameTile.ptr) {
             if ((rc = lv_buf_reserve(ctx, ctx->fullFrameTile, 8))) return rc;
             LV_HIP(ctx, hipMemsetAsync(ctx->fullFrameTile.ptr, 0, 8, st));
         }
-        T.tilesXY = (const uint32_t*)ctx->fullFrameTile.ptr;
-        T.numTiles = 1;
-        T.tileW = ctx->width;
-        T.tileH = ctx->height;
-        T.blocksX = ((T.tileW + 63u) / 64u) * 4u;
-        T.blocksY = ((T.tileH + 63u) / 64u) * 4u;
-        const uint64_t nb = uint64_t(T.blocksX) * T.blocksY;
-        gridTiles = uint32_t((nb + 127u) / 128u) * 128u;
-        maxPixels = uint64_t(T.tileW) * T.tileH;
+        T = lv_tiles((const uint32_t*)ctx->fullFrameTile.ptr, G.numTiles, G.tileW, G.tileH);
         if ((rc = lv_svgf_prepare(ctx))) return rc;
     }
     if (halo) {
@@ -3353,15 +3406,8 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
             ctx->tilesHaloUploaded = true;
             ctx->tilesHalo = haloPx;
         }
-        T.tilesXY = (const uint32_t*)ctx->tilesHaloDev.ptr;
-        T.tileW = Tcolour.tileW + 2u * haloPx;
-        T.tileH = Tcolour.tileH + 2u * haloPx;
-        T.blocksX = ((T.tileW + 63u) / 64u) * 4u;
-        T.blocksY = ((T.tileH + 63u) / 64u) * 4u;
-        const uint64_t nb = uint64_t(n) * T.blocksX * T.blocksY;
-        if (nb > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-        gridTiles = uint32_t((nb + 127u) / 128u) * 128u;
-        maxPixels = uint64_t(n) * T.tileW * T.tileH;
+        T = lv_tiles((const uint32_t*)ctx->tilesHaloDev.ptr, G.numTiles, G.tileW, G.tileH);
+        if (lv_tiles_blocks(T) > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
         if ((rc = lv_buf_reserve(ctx, ctx->aoAlt, size_t(ctx->width) * ctx->height * 4))) return rc;
     }
     const size_t numPix = size_t(ctx->width) * ctx->height;
@@ -3372,9 +3418,8 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         if ((rc = lv_buf_reserve(ctx, ctx->eawPong, numPix * 4))) return rc;
     }
     // G-buffer: one segment of 4096 slots per 64x64-pixel group of the launch (k_ao_primary); samples: compact
-    const uint64_t numGroups64 = uint64_t(T.numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u);
-    if (numGroups64 > 0x000FFFFFull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(numGroups64);
+    if (lv_tiles_groups(T) > 0x000FFFFFull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_groups(T));
     // dispatch order: the colour pass' (same launch geometry: both passes add to one cost array) or, on dilated tiles / the
     // whole viewport, one of its own
     if ((svgf || halo) && (rc = lv_group_order_prepare(ctx, T, 1))) return rc;
@@ -3386,19 +3431,17 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
     uint32_t* tileCount = (uint32_t*)ctx->aoList.ptr;
     uint32_t* tileBase = tileCount + numGroups;
     ctx->aoNumGroups = svgf ? 0u : numGroups; // whole-viewport pass: no per-tile costs of the caller's tile list (lv_get_ao_tile_costs)
-    ctx->aoGroupsPerTile = (T.blocksX / 4u) * (T.blocksY / 4u);
-    const uint64_t gridRays = lv_ao_grid(ctx, maxPixels * spp);
-    const uint64_t gridMax = gridRays > gridTiles ? gridRays : gridTiles;
+    ctx->aoGroupsPerTile = tileCap.groupsPerTile;
     const bool tri = lv_ao_triangle_tubes(ctx);
     // RTAO geometry: the capsules of the colour pass, or the reference's triangle tubes (own LBVH, own scene view)
     LvSceneDev SA = tri ? sceneDevTriangles(ctx) : S;
-    if ((rc = lv_prepare_overflow(ctx, SA, gridMax, LV_AO_STACK_LDS, tri))) return rc;
-    // the paired launch: gridTiles + gridTilesColour workgroups share one slab (columns are indexed by the launch's global thread id);
-    // lv_frame_render reserved it for that grid and for the deeper of the two trees
+    if ((rc = lv_prepare_overflow(ctx, SA, "RTAO pass", std::max(G.gridRays, G.gridTiles), LV_AO_STACK_LDS, tri))) return rc;
+    // the paired launch: gridTiles + gridTilesColour workgroups share one slab (columns are indexed by the launch's global thread id)
     LvSceneDev SCpair = pairColour ? *pairColour : S;
-    if (pairColour) SCpair.stackOverflow = ctx->stackOverflow.ptr ? (unsigned*)ctx->stackOverflow.ptr : nullptr;
     LvSceneDev SApair = SA;
-    if (pairColour) SApair.stackOverflow = SCpair.stackOverflow;
+    if (pairColour && ((rc = lv_prepare_overflow(ctx, SCpair, "paired primaries (colour rays)", G.gridPair)) ||
+                       (rc = lv_prepare_overflow(ctx, SApair, "paired primaries (RTAO rays)", G.gridPair, LV_STACK_LDS, tri))))
+        return rc;
     const bool stats = ctx->opt.collectStats;
     // progressive mode (num_accumulated_frames > 1): one RTAO iteration per rendered frame while frame_number <
     // ambient_occlusion_iterations (ambientOcclusionBaker->updateIterative(), LineRenderer.cpp:257-264), accumulated in ctx->ao
@@ -3431,7 +3474,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         }
         ctx->aoGlobalFrameNumber++;
         LV_HIP(ctx, hipMemsetAsync(tileCount, 0, size_t(numGroups) * 4, st));
-        const uint32_t grid = uint32_t(gridRays);
+        const uint32_t grid = uint32_t(G.gridRays);
         const float4* g = (const float4*)ctx->aoGbuf.ptr;
         // halo: read the previous pass' image, write the other buffer, swap; otherwise update in place
         const float* aoIn = (const float*)ctx->ao.ptr;
@@ -3509,7 +3552,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         E.phiNormal = ctx->opt.eawPhiNormal * 1.0f;
         E.useColor = ctx->opt.eawColorWeights; E.usePosition = ctx->opt.eawPositionWeights; E.useNormal = ctx->opt.eawNormalWeights;
         E.stepWidth = 1;
-        const uint64_t threads = uint64_t(T.numTiles) * T.tileW * T.tileH;
+        const uint64_t threads = lv_tiles_pixels(T);
         const float* src = (const float*)ctx->ao.ptr;
         float* bufs[2] = {(float*)ctx->eawPing.ptr, (float*)ctx->eawPong.ptr};
         for (uint32_t i = 0; i < ctx->opt.eawIterations; i++) {
@@ -3536,9 +3579,8 @@ static int lv_mlab_fold(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, uint
                         uint2* scratch, LvDevCounters* dc) {
     hipStream_t st = ctx->stream;
     // the long list holds one entry per (tile, pixel) pair of the tile list: repeated or overlapping tiles list a pixel more than once
-    const uint64_t longCap64 = uint64_t(T.numTiles) * T.tileW * T.tileH;
-    if (longCap64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t longCap = uint32_t(longCap64);
+    if (lv_tiles_pixels(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t longCap = uint32_t(lv_tiles_pixels(T));
     int rc;
     if ((rc = lv_buf_reserve(ctx, ctx->mlabLong, size_t(longCap) * 8))) return rc;
     const uint32_t K = ctx->opt.mlabNumLayers;
@@ -3615,14 +3657,40 @@ static LvMboitParams lv_mboit_params(const lv_ctx* ctx, const LvUniforms& U, con
     return M;
 }
 
+// Mode 6, first frame on these line points: their box for the log depth range.  Queues k_mboit_points_box and the copy of its six
+// values into words 2 ... 7 of the pinned block; lv_mboit_box_adopt takes them over once the caller has synchronised the stream.
+static int lv_mboit_box_queue(lv_ctx* ctx, const LvSceneDev& S, LvDevCounters* dc) {
+    if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
+    if (ctx->numPoints)
+        k_mboit_points_box<<<std::min(nblocks(ctx->numPoints), 256u), LV_BLOCK, 0, ctx->stream>>>(S.points, ctx->numPoints, dc);
+    LV_HIP(ctx, hipMemcpyAsync((void*)(ctx->pinned + 2), dc->mboitBoxOrd, 24, hipMemcpyDeviceToHost, ctx->stream));
+    return LV_OK;
+}
+static void lv_mboit_box_adopt(lv_ctx* ctx) {
+    for (int k = 0; k < 6; k++) ctx->mboitBoxOrd[k] = ctx->pinned[2 + k];
+    ctx->mboitBoxValid = true;
+}
+
+// clear(): LinkedListClear.glsl:46-55 + fragmentCounterBuffer->fill(0); allRequested: every pixel is marked as requested right away
+static void lv_ppll_clear(lv_ctx* ctx, const LvUniforms& U, size_t padded4, bool allRequested, bool stats, LvDevCounters* dc) {
+    k_ppll_clear<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
+            (uint4*)ctx->ppllStart.ptr, (uint4*)ctx->ppllCount.ptr, padded4, dc, allRequested ? 0u : 0xFFFFFFFFu,
+            (allRequested && stats) ? (unsigned long long)U.width * U.height : 0ull);
+}
+
+// shading_numerics = fast in the prism fragment stage: the plain tubes with the raster colour (the only variant whose alpha cannot
+// follow the halo coordinate); every other variant keeps the exact arithmetic
+static bool lv_prism_fast_shade(const lv_ctx* ctx, const LvUniforms& U, const LvSceneDev& S, bool stats) {
+    return ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
+}
+
 // The two sweeps of mode 6 over the runs in ctx->ppllNodes (colours, then the view depths depthBase entries in) / ppllStart
 // (+ blockBase) / ppllCount: k_mboit_resolve, then the listed long runs
 static int lv_mboit_resolve(lv_ctx* ctx, const LvUniforms& U, const LvTiles& T, const LvMboitParams& M, uint32_t numGroups,
                             uint32_t depthBase, const uint32_t* blockBase, uint32_t* out, float* moments, LvDevCounters* dc) {
     hipStream_t st = ctx->stream;
-    const uint64_t longCap64 = uint64_t(T.numTiles) * T.tileW * T.tileH;   // one entry per (tile, pixel) pair, as lv_mlab_fold
-    if (longCap64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t longCap = uint32_t(longCap64);
+    if (lv_tiles_pixels(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t longCap = uint32_t(lv_tiles_pixels(T));   // one entry per (tile, pixel) pair, as lv_mlab_fold
     int rc;
     if ((rc = lv_buf_reserve(ctx, ctx->mlabLong, size_t(longCap) * 8))) return rc;
     const uint4* rgba = (const uint4*)ctx->ppllNodes.ptr;
@@ -3681,8 +3749,8 @@ static int lv_segment_raster_front(lv_ctx* ctx, const LvUniforms& U, const LvSce
 #ifndef LV_MBOIT_STREAM_BLOCKS_PER_CU
 #define LV_MBOIT_STREAM_BLOCKS_PER_CU 2   // four waves per workgroup, LV_MBOIT_STREAM_MIN_WAVES per SIMD
 #endif
-static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t numTiles, uint32_t gridTiles,
-                                 bool stats, uint32_t* out, LvDevCounters* dc) {
+static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats,
+                                 uint32_t* out, LvDevCounters* dc) {
     hipStream_t st = ctx->stream;
     int rc;
     if (!lv_ppll_prism_source(ctx) || (ctx->opt.useRibbons && ctx->opt.helicityBands))
@@ -3701,20 +3769,13 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
     ctx->ppllPaddedW = U.ppllPaddedW;
     ctx->ppllPaddedH = U.ppllPaddedH;
     if (!ctx->mboitBoxValid) {
-        // first frame on these line points: their box for the log depth range (words 2 ... 7 of the pinned block)
-        if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
-        if (ctx->numPoints)
-            k_mboit_points_box<<<std::min(nblocks(ctx->numPoints), 256u), LV_BLOCK, 0, st>>>(S.points, ctx->numPoints, dc);
-        LV_HIP(ctx, hipMemcpyAsync((void*)(ctx->pinned + 2), dc->mboitBoxOrd, 24, hipMemcpyDeviceToHost, st));
+        if ((rc = lv_mboit_box_queue(ctx, S, dc))) return rc;
         LV_HIP(ctx, hipStreamSynchronize(st));
-        for (int k = 0; k < 6; k++) ctx->mboitBoxOrd[k] = ctx->pinned[2 + k];
-        ctx->mboitBoxValid = true;
+        lv_mboit_box_adopt(ctx);
     }
     const LvMboitParams M = lv_mboit_params(ctx, U, ctx->mboitBoxOrd, stats);
     const bool allRequested = ctx->tilesCoverViewport;
-    k_ppll_clear<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
-            (uint4*)ctx->ppllStart.ptr, (uint4*)ctx->ppllCount.ptr, padded4, dc, allRequested ? 0u : 0xFFFFFFFFu,
-            (allRequested && stats) ? (unsigned long long)U.width * U.height : 0ull);
+    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
     LV_HIP(ctx, hipMemsetAsync(ctx->mboitAccum.ptr, 0, accBytes, st));
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
     // LV_KERNEL_PPLL_RASTER: one launch per pass, the first with what a sharded frame runs in front of it (as in pooled storage)
@@ -3722,8 +3783,7 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
     uint32_t* leafList;
     if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
     const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
-    // the variants lv_frame_render selects for the pooled fragment stage; shading_numerics = fast: plain tubes with the raster colour
-    const bool fastShade = ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
+    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);   // the variants lv_frame_render selects for the pooled fragment stage
 #define LV_LAUNCH_STREAM(NT, SH, FA)                                                                                            \
     k_mboit_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, M, (const uint32_t*)ctx->ppllStart.ptr,               \
             (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->mboitAccum.ptr, dc, allRequested ? 1u : 0u, leafList, N, pass)
@@ -3747,9 +3807,8 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
 #undef LV_LAUNCH_STREAM2
 #undef LV_LAUNCH_STREAM
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-    const uint64_t groups64 = uint64_t(numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;   // 8 x 8 cells of the 64 x 64 groups
-    if (groups64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(groups64);
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_mboit_stream_blend<<<numGroups, LV_WAVE, 0, st>>>(
             U, T, M, (const unsigned long long*)ctx->mboitAccum.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, N, dc)));
     ctx->mboitStreamLast = true;
@@ -3899,20 +3958,13 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     }
     LV_HIP(ctx, hipMemsetAsync(dc, 0, sizeof(LvDevCounters), st));
 
-    LvTiles T{};
-    T.tilesXY = (const uint32_t*)ctx->tilesDev.ptr;
-    T.numTiles = numTiles;
-    T.tileW = tileW;
-    T.tileH = tileH;
-    T.blocksX = ((tileW + 63u) / 64u) * 4u; // 16x16-pixel blocks, in whole 64x64 groups (lv_block_pixel)
-    T.blocksY = ((tileH + 63u) / 64u) * 4u;
-    const uint64_t nb = uint64_t(numTiles) * T.blocksX * T.blocksY;
-    if (nb > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    LvTiles T = lv_tiles((const uint32_t*)ctx->tilesDev.ptr, numTiles, tileW, tileH);
+    if (lv_tiles_blocks(T) > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
     ctx->groupOrderSorted = false;
     ctx->groupOrder[1].active = false;
     if ((rc = lv_group_order_prepare(ctx, T, 0))) return rc;
-    const uint32_t gridTiles = uint32_t((nb + 127u) / 128u) * 128u; // multiple of 8 XCDs x LV_XCD_GROUP (lv_block_pixel)
-    const uint64_t maxPixels = uint64_t(numTiles) * tileW * tileH;
+    const uint32_t gridTiles = uint32_t(lv_tiles_grid(T));
+    const uint64_t maxPixels = lv_tiles_pixels(T);
     const bool stats = ctx->opt.collectStats;
     // overlap_primary_passes (default on): the colour pass' first-hit trace rides along with the RTAO primaries (k_primary_pair) and the
     // colour kernel after the RTAO pass only shades.  Where it applies: the ray tracer on the analytic capsules, one sample per pixel
@@ -3924,42 +3976,11 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
                                !U.aoPrebaked && !ctx->opt.useMlat && !ctx->opt.rtTriangleMesh && !U.useEllipticTubes &&
                                !ctx->opt.svgfEnabled && (U.useJitteredRays ? U.numSamplesPerFrame : 1u) == 1u && ctx->numSegs > 0u &&
                                (ctx->opt.numAccumulatedFrames <= 1u || ctx->opt.frameNumber < ctx->opt.aoIterations);
-    {
-        // one reservation for every launch geometry of this frame (a later, larger request would free the slab under the
-        // scene views built before it)
-        const bool aoRun = U.useAmbientOcclusion && !U.aoPrebaked, aoBake = U.aoPrebaked && !ctx->bakeValid;
-        const bool triColour = ctx->opt.rtTriangleMesh && mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER;
-        size_t need = lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, false);
-        if (triColour) need = std::max(need, lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, true));
-        if (aoRun) {
-            // with the AO halo the AO pass runs on tiles of (tileW + 2) x (tileH + 2) pixels (lv_run_ao)
-            const uint32_t haloPx = (U.aoProjectLookup ? 1u : 0u) +
-                                    ((ctx->opt.eawEnabled && ctx->opt.eawIterations) ? 2u * ((1u << ctx->opt.eawIterations) - 1u) : 0u);
-            // ... and under SVGF on the whole viewport
-            const bool svgf = ctx->opt.svgfEnabled;
-            const uint64_t tw = svgf ? ctx->width : tileW + 2u * haloPx, th = svgf ? ctx->height : tileH + 2u * haloPx;
-            const uint64_t nAo = svgf ? 1u : numTiles;
-            const uint64_t nbAo = nAo * (((tw + 63u) / 64u) * 4u) * (((th + 63u) / 64u) * 4u);
-            const uint64_t gridAo = ((nbAo + 127u) / 128u) * 128u;
-            need = std::max(need, lv_overflow_bytes(ctx, std::max<uint64_t>(lv_ao_grid(ctx, nAo * tw * th * U.aoSamplesPerFrame), gridAo),
-                                                    LV_AO_STACK_LDS, lv_ao_triangle_tubes(ctx)));
-        }
-        if (aoBake)
-            need = std::max(need, lv_overflow_bytes(ctx, uint64_t(ctx->numCUs) * LV_AO_BLOCKS_PER_CU, LV_AO_STACK_LDS, true));
-        if (pairPrimaries) {
-            // k_primary_pair: the RTAO primaries' workgroups and the colour rays' share one launch and one slab
-            const uint32_t haloPx = (U.aoProjectLookup ? 1u : 0u) +
-                                    ((ctx->opt.eawEnabled && ctx->opt.eawIterations) ? 2u * ((1u << ctx->opt.eawIterations) - 1u) : 0u);
-            const uint64_t tw = tileW + 2u * haloPx, th = tileH + 2u * haloPx;
-            const uint64_t nbAo = uint64_t(numTiles) * (((tw + 63u) / 64u) * 4u) * (((th + 63u) / 64u) * 4u);
-            const uint64_t gridPair = ((nbAo + 127u) / 128u) * 128u + gridTiles;
-            need = std::max(need, lv_overflow_bytes(ctx, gridPair, LV_STACK_LDS, false));
-            if (lv_ao_triangle_tubes(ctx)) need = std::max(need, lv_overflow_bytes(ctx, gridPair, LV_STACK_LDS, true));
-        }
-        if (need && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, need))) return rc;
-    }
+    // one reservation for every launch of this frame: no view built below can move the slab
+    const size_t need = lv_frame_overflow_bytes(ctx, U, T, mode, pairPrimaries);
+    if (need && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, need))) return rc;
     LvSceneDev S = sceneDev(ctx);
-    if ((rc = lv_prepare_overflow(ctx, S, gridTiles))) return rc;
+    if ((rc = lv_prepare_overflow(ctx, S, "colour pass", gridTiles))) return rc;
 
     // LineRenderer::renderBase: depth range, LineRenderer.cpp:248-256
     if (U.useDepthCues) {
@@ -3979,7 +4000,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             if (U.lssGeometry) SP.literalIntersection = 0u; // as the colour pass below
             if ((rc = lv_buf_reserve(ctx, ctx->firstHit, size_t(maxPixels) * 8 * LV_PRE_HITS))) return rc;
         }
-        if ((rc = lv_run_ao(ctx, U, S, T, gridTiles, maxPixels, pairPrimaries ? &SP : nullptr, &firstHitsTraced))) return rc;
+        if ((rc = lv_run_ao(ctx, U, S, T, pairPrimaries ? &SP : nullptr, &firstHitsTraced))) return rc;
     }
     if (U.aoPrebaked && !ctx->bakeValid && ctx->bakeAsyncPending) {
         // a bake is running on the second stream (lv_bake_ao_start): adopt its table if it has finished; otherwise this frame is
@@ -3990,8 +4011,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     if (U.aoPrebaked) {
         // static prebaker: view independent, (re)baked only when geometry or baking settings changed
         if (!ctx->bakeValid) {
-            if ((rc = lv_bake_ambient_occlusion(ctx))) return rc;
-            if ((rc = lv_prepare_overflow(ctx, S, gridTiles))) return rc; // the bake may have regrown the overflow slab
+            if ((rc = lv_bake_ambient_occlusion(ctx, false, true))) return rc;
         }
         S.bakedAo = (const float*)ctx->bakedAo.ptr;
         S.bakedBlendingWeights = (const float*)ctx->bakeBlendingWeights.ptr;
@@ -4026,13 +4046,13 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             LvSceneDev SM = tri ? sceneDevTriangles(ctx) : S;
             SM.accum = S.accum;
             if (U.lssGeometry) SM.literalIntersection = 0u; // the hardware primitive has no intersection shader
-            if (tri && (rc = lv_prepare_overflow(ctx, SM, gridTiles, LV_STACK_LDS, true))) return rc;
+            if (tri && (rc = lv_prepare_overflow(ctx, SM, "MLAT pass", gridTiles, LV_STACK_LDS, true))) return rc;
             if ((rc = lv_mlat_render(ctx, U, SM, T, gridTiles, out, dc, tri))) return rc;
         } else {
         LvSceneDev SC = tri ? sceneDevTriangles(ctx) : S;
         SC.accum = S.accum;
         if (U.lssGeometry) SC.literalIntersection = 0u; // the hardware primitive has no intersection shader
-        if (tri && (rc = lv_prepare_overflow(ctx, SC, gridTiles, LV_STACK_LDS, true))) return rc;
+        if (tri && (rc = lv_prepare_overflow(ctx, SC, "colour pass (triangle mesh)", gridTiles, LV_STACK_LDS, true))) return rc;
 #define LV_LAUNCH_RT(ST, PR, BA) \
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_RENDER_RT, (k_render_rt<ST, PR, BA><<<gridTiles, LV_BLOCK, 0, st>>>(U, SC, T, out, dc)))
 #define LV_LAUNCH_RT_PRE(ST, BA) \
@@ -4065,7 +4085,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
 #undef LV_LAUNCH_RT
         }
     } else if (mboit && ctx->opt.mboitStreamed) {
-        if ((rc = lv_mboit_stream_frame(ctx, U, S, T, numTiles, gridTiles, stats, out, dc))) return rc;
+        if ((rc = lv_mboit_stream_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else {
         // reallocateFragmentBuffer, PerPixelLinkedListLineRenderer.cpp:251-357
         // gather(): fragments of the rasterised programmable-pull prism (the reference's geometry, default) or capsule entry hits
@@ -4118,11 +4138,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         ctx->ppllPoolNodes = poolSlots;
         ctx->ppllPaddedW = U.ppllPaddedW;
         ctx->ppllPaddedH = U.ppllPaddedH;
-        // clear(): LinkedListClear.glsl:46-55 + fragmentCounterBuffer->fill(0)
         const bool allRequested = segmentRaster && ctx->tilesCoverViewport;
-        k_ppll_clear<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
-                (uint4*)ctx->ppllStart.ptr, (uint4*)ctx->ppllCount.ptr, padded4, dc, allRequested ? 0u : 0xFFFFFFFFu,
-                (allRequested && stats) ? (unsigned long long)U.width * U.height : 0ull);
+        lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
         if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
 #define LV_LAUNCH_GATHER(ST, PR, BA)                                                                             \
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_GATHER, (k_ppll_gather<ST, PR, BA><<<gridTiles * numSlices, LV_BLOCK, 0, st>>>( \
@@ -4169,18 +4186,9 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             LV_HIP(ctx, hipMemcpyAsync((void*)pin, &dc->fragAlloc, 4, hipMemcpyDeviceToHost, st));
             LV_HIP(ctx, hipMemcpyAsync((void*)(pin + 1), &dc->mlabSaturated, 4, hipMemcpyDeviceToHost, st));
             const bool readBox = mboit && !ctx->mboitBoxValid;
-            if (readBox) {
-                // mode 6, first frame on these line points: their box for the log depth range, read back with the same
-                // synchronisation (words 2 ... 7 of the pinned block)
-                if (ctx->numPoints)
-                    k_mboit_points_box<<<std::min(nblocks(ctx->numPoints), 256u), LV_BLOCK, 0, st>>>(S.points, ctx->numPoints, dc);
-                LV_HIP(ctx, hipMemcpyAsync((void*)(ctx->pinned + 2), dc->mboitBoxOrd, 24, hipMemcpyDeviceToHost, st));
-            }
+            if (readBox && (rc = lv_mboit_box_queue(ctx, S, dc))) return rc;   // read back with the same synchronisation
             LV_HIP(ctx, hipStreamSynchronize(st));
-            if (readBox) {
-                for (int k = 0; k < 6; k++) ctx->mboitBoxOrd[k] = ctx->pinned[2 + k];
-                ctx->mboitBoxValid = true;
-            }
+            if (readBox) lv_mboit_box_adopt(ctx);
             const uint32_t need = pin[0], saturated = pin[1];
             if (saturated)
                 return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than 65534 fragments (16-bit per-pixel count)", poolName);
@@ -4213,37 +4221,24 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
             k_ppll_scan_bases<<<1, LV_BLOCK, 0, st>>>(blockTotals, blockBase, scanBlocks);
             ctx->ppllScanBlocks = scanBlocks;
             const uint32_t shadeGrid = uint32_t(ctx->numCUs) * LV_PRISM_SHADE_BLOCKS_PER_CU;
-#define LV_LAUNCH_SHADE(ST, ML)                                                                                                 \
-    if (S.prism.bands)                                                                                                          \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_BANDS, 0, ML><<<shadeGrid, LV_BLOCK, 0, st>>>(  \
-            U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
-            blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)));                                                         \
-    else if (U.useHelicityBands)                                                                                                \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_HELICITY, 0, ML><<<shadeGrid, LV_BLOCK, 0, st>>>( \
-            U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
-            blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)));                                                         \
-    else                                                                                                                        \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, LV_SHADE_PLAIN, 0, ML><<<shadeGrid, LV_BLOCK, 0, st>>>(  \
+#define LV_LAUNCH_SHADE(ST, BA, FA, ML)                                                                                         \
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, BA, FA, ML><<<shadeGrid, LV_BLOCK, 0, st>>>(             \
             U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
             blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)))
-#define LV_LAUNCH_SHADE_FAST(ML)                                                                                                \
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<false, LV_SHADE_PLAIN, 2, ML><<<shadeGrid, LV_BLOCK, 0, st>>>( \
-            U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
-            blockBase, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots)))
-            // shading_numerics = fast: the plain-tube fragment stage with the raster colour (the only variant whose alpha cannot follow
-            // the halo coordinate); every other variant keeps the exact arithmetic
-            const bool fastShade = ctx->opt.fastShading && !stats && !S.prism.bands && !U.useHelicityBands && U.ppllRasterColour;
-            if (mboit) {
-                if (fastShade) LV_LAUNCH_SHADE_FAST(LV_ENTRY_MBOIT);
-                else if (stats) LV_LAUNCH_SHADE(true, LV_ENTRY_MBOIT); else LV_LAUNCH_SHADE(false, LV_ENTRY_MBOIT);
-            } else if (mlab) {
-                if (fastShade) LV_LAUNCH_SHADE_FAST(LV_ENTRY_MLAB);
-                else if (stats) LV_LAUNCH_SHADE(true, LV_ENTRY_MLAB); else LV_LAUNCH_SHADE(false, LV_ENTRY_MLAB);
-            } else {
-                if (fastShade) LV_LAUNCH_SHADE_FAST(LV_ENTRY_PPLL);
-                else if (stats) LV_LAUNCH_SHADE(true, LV_ENTRY_PPLL); else LV_LAUNCH_SHADE(false, LV_ENTRY_PPLL);
-            }
-#undef LV_LAUNCH_SHADE_FAST
+#define LV_LAUNCH_SHADE2(ST, ML)                                                     \
+    do {                                                                             \
+        if (fastShade) LV_LAUNCH_SHADE(false, LV_SHADE_PLAIN, 2, ML);                \
+        else if (S.prism.bands) LV_LAUNCH_SHADE(ST, LV_SHADE_BANDS, 0, ML);          \
+        else if (U.useHelicityBands) LV_LAUNCH_SHADE(ST, LV_SHADE_HELICITY, 0, ML);  \
+        else LV_LAUNCH_SHADE(ST, LV_SHADE_PLAIN, 0, ML);                             \
+    } while (0)
+#define LV_LAUNCH_SHADE3(ML) do { if (stats) LV_LAUNCH_SHADE2(true, ML); else LV_LAUNCH_SHADE2(false, ML); } while (0)
+            const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);
+            if (mboit) LV_LAUNCH_SHADE3(LV_ENTRY_MBOIT);
+            else if (mlab) LV_LAUNCH_SHADE3(LV_ENTRY_MLAB);
+            else LV_LAUNCH_SHADE3(LV_ENTRY_PPLL);
+#undef LV_LAUNCH_SHADE3
+#undef LV_LAUNCH_SHADE2
 #undef LV_LAUNCH_SHADE
             // the listed pixels: their nearest ppllMaxNumFrags fragments to the front of the run
             if (!mlab) k_ppll_select_nearest<<<uint32_t(ctx->numCUs) * 16u, LV_WAVE, 0, st>>>(
@@ -4253,9 +4248,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
         // resolve()
         const uint32_t* prismCount = prismSource ? (const uint32_t*)ctx->ppllCount.ptr : nullptr; // (kept fragments per pixel -> max depth complexity)
-        const uint64_t groups64 = uint64_t(numTiles) * (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;   // 8 x 8 cells of the 64 x 64 groups
-        if (groups64 > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-        const uint32_t numGroups = uint32_t(groups64);
+        if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+        const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
         if (mlab) {
             // the fold: k_mlab_resolve, then the pixels with long runs (k_mlab_resolve_long); both in the LV_KERNEL_PPLL_RESOLVE slot
             const bool timed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RESOLVE) & 1u) != 0u;
@@ -4320,7 +4314,7 @@ int lv_frame_trace_rays(lv_ctx* ctx, const float* o, const float* d, float tMin,
     LV_HIP(ctx, hipMemcpyAsync(dO, o, rb, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(dD, d, rb, hipMemcpyHostToDevice, st));
     LvSceneDev S = sceneDev(ctx);
-    if ((rc = lv_prepare_overflow(ctx, S, nblocks(n)))) return rc;
+    if ((rc = lv_reserve_overflow(ctx, S, "lv_trace_rays", nblocks(n)))) return rc;
     if (ctx->opt.useRibbons && ctx->opt.ellipticTubes) // the elliptic tubelets of the band data (kind = 0)
         k_trace_rays<LV_PRIM_ELLIPTIC><<<nblocks(n), LV_BLOCK, 0, st>>>(S, ctx->opt.lineWidth * 0.5f, ctx->opt.useCappedTubes, dO,
                                                                         dD, tMin, tMax, n, dT, dS, dK);
@@ -4336,6 +4330,64 @@ int lv_frame_trace_rays(lv_ctx* ctx, const float* o, const float* d, float tMin,
     LV_HIP(ctx, hipMemcpyAsync(outKind, dK, size_t(n) * 4, hipMemcpyDeviceToHost, st));
     LV_HIP(ctx, hipStreamSynchronize(st));
     return LV_OK;
+}
+
+// ---------------------------------------------------------------- the *_resolve_only entry points: the caller's runs through a resolve
+// The one tile (txy, w x h) they resolve, uploaded into ctx->tilesDev (reserved by the caller; txy outlives the call's last
+// synchronisation), and the grid of its resolve
+static int lv_single_tile(lv_ctx* ctx, const uint32_t* txy, uint32_t w, uint32_t h, LvTiles& T, uint32_t& numGroups) {
+    ctx->tilesUploaded = false; // tilesDev is overwritten below
+    LV_HIP(ctx, hipMemcpyAsync(ctx->tilesDev.ptr, txy, 8, hipMemcpyHostToDevice, ctx->stream));
+    T = lv_tiles((const uint32_t*)ctx->tilesDev.ptr, 1, w, h);
+    numGroups = uint32_t(lv_tiles_cells(T));
+    return LV_OK;
+}
+// ... and the resolved rectangle (ctx->outDev), with mode 6's moments (ctx->ppllScratch) when asked for, back to the caller
+static int lv_resolve_read_back(lv_ctx* ctx, uint8_t* out, size_t numPixels, float* outMoments = nullptr, size_t momBytes = 0) {
+    hipStream_t st = ctx->stream;
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, numPixels * 4, hipMemcpyDeviceToHost, st));
+    if (outMoments) LV_HIP(ctx, hipMemcpyAsync(outMoments, ctx->ppllScratch.ptr, momBytes, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));   // (also: the host arrays of the call were sources of asynchronous uploads)
+    return LV_OK;
+}
+// Pixel p owns entries [offsets[p], offsets[p + 1]): the runs' starts and lengths, at most maxCount entries per pixel
+static int lv_runs_from_offsets(lv_ctx* ctx, const uint64_t* offsets, uint64_t numPixels, uint64_t numEntries, uint32_t maxCount,
+                                std::vector<uint32_t>& start, std::vector<uint32_t>& count) {
+    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
+    start.resize(numPixels); count.resize(numPixels);
+    for (uint64_t p = 0; p < numPixels; p++) {
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > maxCount)
+            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most %u entries per pixel", (unsigned long long)p, maxCount);
+        start[p] = uint32_t(offsets[p]);
+        count[p] = uint32_t(offsets[p + 1] - offsets[p]);
+    }
+    return LV_OK;
+}
+// Modes 3 and 6: the buffers of a w x h rectangle behind the caller's own (ppllNodes, ppllScratch), the uploads of the entries
+// (entryBytes of them; 0: none) and the runs, zeroed counters, the tile at the origin and its grid
+static int lv_upload_runs(lv_ctx* ctx, const uint32_t* entries, size_t entryBytes, const std::vector<uint32_t>& start,
+                          const std::vector<uint32_t>& count, uint32_t w, uint32_t h, LvTiles& T, uint32_t& numGroups) {
+    static const uint32_t txy[2] = {0u, 0u};
+    hipStream_t st = ctx->stream;
+    const size_t numPixels = start.size();
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, numPixels * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, numPixels * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, numPixels * 4))) return rc;
+    if (entryBytes) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, entryBytes, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), numPixels * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), numPixels * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    return lv_single_tile(ctx, txy, w, h, T, numGroups);
+}
+// row-major addressing of a w x h rectangle: one 1 x 1-pixel tiling, address = y * w + x
+static void lv_row_major_uniforms(lv_ctx* ctx, LvUniforms& U, uint32_t w, uint32_t h) {
+    lv_fill_uniforms(ctx, U);
+    U.width = w; U.height = h;
+    U.ppllTileW = 1u; U.ppllTileH = 1u; U.ppllPaddedW = w; U.ppllPaddedH = h;
 }
 
 int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numNodes, const uint32_t* start,
@@ -4354,15 +4406,11 @@ int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numN
     if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(w) * h * 4))) return rc;
     if (numNodes) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, nodes, size_t(numNodes) * 12, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start, size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
-    uint32_t txy[2] = {x0, y0};
-    ctx->tilesUploaded = false; // tilesDev is overwritten below
-    LV_HIP(ctx, hipMemcpyAsync(ctx->tilesDev.ptr, txy, 8, hipMemcpyHostToDevice, st));
+    const uint32_t txy[2] = {x0, y0};
+    LvTiles T;
+    uint32_t numGroups;
+    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
     LV_HIP(ctx, hipStreamSynchronize(st));
-    LvTiles T{};
-    T.tilesXY = (const uint32_t*)ctx->tilesDev.ptr;
-    T.numTiles = 1; T.tileW = w; T.tileH = h;
-    T.blocksX = ((w + 63u) / 64u) * 4u; T.blocksY = ((h + 63u) / 64u) * 4u;
-    const uint32_t numGroups = (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;
     const size_t ldsBytes = size_t(U.ppllMaxNumFrags) * LV_WAVE * 8;
     const uint32_t* nd = (const uint32_t*)ctx->ppllNodes.ptr;
     const uint32_t* so = (const uint32_t*)ctx->ppllStart.ptr;
@@ -4378,10 +4426,7 @@ int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numN
         if (pq) k_ppll_resolve<false, true><<<grid, LV_WAVE, 0, st>>>(U, T, nd, so, od, sc, numGroups, nullptr, nullptr, nullptr);
         else k_ppll_resolve<false, false><<<grid, LV_WAVE, 0, st>>>(U, T, nd, so, od, sc, numGroups, nullptr, nullptr, nullptr);
     }
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(w) * h * 4, hipMemcpyDeviceToHost, st));
-    LV_HIP(ctx, hipStreamSynchronize(st));
-    return LV_OK;
+    return lv_resolve_read_back(ctx, out, size_t(w) * h);
 }
 
 // lv_mlab_resolve_buffers: the caller's runs (pixel p of the w x h rectangle owns entries [offsets[p], offsets[p + 1])) through the
@@ -4390,14 +4435,9 @@ int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
                                uint32_t h, uint8_t* out) {
     const uint64_t numPixels = uint64_t(w) * h;
     if (numEntries >= 0xFFFFFFF0ull || numPixels > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
-    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
-    std::vector<uint32_t> start(numPixels), count(numPixels);
-    for (uint64_t p = 0; p < numPixels; p++) {
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > 0xFFFFu)
-            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most 65535 entries per pixel", (unsigned long long)p);
-        start[p] = uint32_t(offsets[p]);
-        count[p] = uint32_t(offsets[p + 1] - offsets[p]);
-    }
+    int rc;
+    std::vector<uint32_t> start, count;
+    if ((rc = lv_runs_from_offsets(ctx, offsets, numPixels, numEntries, 0xFFFFu, start, count))) return rc;
     for (uint64_t i = 0; i < numEntries; i++)
         if (entries[3 * i + 2] == LV_MLAB_NO_KEY) return lv_fail(ctx, LV_E_INVALID, "entry %llu: key 0xFFFFFFFF is reserved", (unsigned long long)i);
     {   // keys unique within a pixel: the ordering ranks by key (a repeated key would leave a rank unwritten)
@@ -4411,37 +4451,16 @@ int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
         }
     }
     LvUniforms U;
-    lv_fill_uniforms(ctx, U);
-    U.width = w; U.height = h;
-    U.ppllTileW = 1u; U.ppllTileH = 1u; U.ppllPaddedW = w; U.ppllPaddedH = h;   // address = y * w + x
-    hipStream_t st = ctx->stream;
-    int rc;
+    lv_row_major_uniforms(ctx, U, w, h);
     if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(numEntries ? numEntries : 1) * 12))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, size_t(numEntries ? numEntries : 1) * 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, size_t(numPixels) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
-    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 12, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
-    const uint32_t txy[2] = {0u, 0u};
-    ctx->tilesUploaded = false; // tilesDev is overwritten below
-    LV_HIP(ctx, hipMemcpyAsync(ctx->tilesDev.ptr, txy, 8, hipMemcpyHostToDevice, st));
-    LvTiles T{};
-    T.tilesXY = (const uint32_t*)ctx->tilesDev.ptr;
-    T.numTiles = 1; T.tileW = w; T.tileH = h;
-    T.blocksX = ((w + 63u) / 64u) * 4u; T.blocksY = ((h + 63u) / 64u) * 4u;
-    const uint32_t numGroups = (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;
+    LvTiles T;
+    uint32_t numGroups;
+    if ((rc = lv_upload_runs(ctx, entries, size_t(numEntries) * 12, start, count, w, h, T, numGroups))) return rc;
     if ((rc = lv_mlab_fold(ctx, U, T, numGroups, nullptr, (uint32_t*)ctx->outDev.ptr, (uint2*)ctx->ppllScratch.ptr,
                            (LvDevCounters*)ctx->counters.ptr)))
         return rc;
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(numPixels) * 4, hipMemcpyDeviceToHost, st));
-    LV_HIP(ctx, hipStreamSynchronize(st));   // (also: start / count are host vectors of this call)
-    return LV_OK;
+    return lv_resolve_read_back(ctx, out, size_t(numPixels));
 }
 
 // lv_mboit_resolve_buffers: the caller's runs through the two sweeps of mode 6 (row-major addressing, absolute run starts, as
@@ -4451,14 +4470,9 @@ int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
     const uint64_t numPixels = uint64_t(w) * h;
     const uint32_t N = ctx->opt.mboitNumMoments;
     if (numEntries >= 0xFFFFFFF0ull / 5 || numPixels > 0x7FFFFFF0ull / (1 + N)) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
-    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
-    std::vector<uint32_t> start(numPixels), count(numPixels);
-    for (uint64_t p = 0; p < numPixels; p++) {
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > 0xFFFEu)
-            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most 65534 entries per pixel", (unsigned long long)p);
-        start[p] = uint32_t(offsets[p]);
-        count[p] = uint32_t(offsets[p + 1] - offsets[p]);
-    }
+    int rc;
+    std::vector<uint32_t> start, count;
+    if ((rc = lv_runs_from_offsets(ctx, offsets, numPixels, numEntries, 0xFFFEu, start, count))) return rc;
     const size_t cap = size_t(numEntries ? numEntries : 1);
     std::vector<uint32_t> split(cap * 5);
     for (uint64_t i = 0; i < numEntries; i++) {
@@ -4467,31 +4481,13 @@ int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
         split[4 * cap + i] = entries[5 * i + 4];
     }
     LvUniforms U;
-    lv_fill_uniforms(ctx, U);
-    U.width = w; U.height = h;
-    U.ppllTileW = 1u; U.ppllTileH = 1u; U.ppllPaddedW = w; U.ppllPaddedH = h;   // address = y * w + x
-    hipStream_t st = ctx->stream;
-    int rc;
+    lv_row_major_uniforms(ctx, U, w, h);
     const size_t momBytes = size_t(numPixels) * (1 + N) * 4;
     if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, cap * 20))) return rc;
     if (outMoments && (rc = lv_buf_reserve(ctx, ctx->ppllScratch, momBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, size_t(numPixels) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, split.data(), cap * 20, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), size_t(numPixels) * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
-    const uint32_t txy[2] = {0u, 0u};
-    ctx->tilesUploaded = false; // tilesDev is overwritten below
-    LV_HIP(ctx, hipMemcpyAsync(ctx->tilesDev.ptr, txy, 8, hipMemcpyHostToDevice, st));
-    LvTiles T{};
-    T.tilesXY = (const uint32_t*)ctx->tilesDev.ptr;
-    T.numTiles = 1; T.tileW = w; T.tileH = h;
-    T.blocksX = ((w + 63u) / 64u) * 4u; T.blocksY = ((h + 63u) / 64u) * 4u;
-    const uint32_t numGroups = (T.blocksX / 4u) * (T.blocksY / 4u) * 64u;
+    LvTiles T;
+    uint32_t numGroups;
+    if ((rc = lv_upload_runs(ctx, split.data(), cap * 20, start, count, w, h, T, numGroups))) return rc;
     const uint32_t noBox[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     LvMboitParams M = lv_mboit_params(ctx, U, noBox, ctx->opt.collectStats);
     M.logDepthMin = logDepthMin;
@@ -4499,11 +4495,7 @@ int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
     if ((rc = lv_mboit_resolve(ctx, U, T, M, numGroups, uint32_t(cap), nullptr, (uint32_t*)ctx->outDev.ptr,
                                outMoments ? (float*)ctx->ppllScratch.ptr : nullptr, (LvDevCounters*)ctx->counters.ptr)))
         return rc;
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(numPixels) * 4, hipMemcpyDeviceToHost, st));
-    if (outMoments) LV_HIP(ctx, hipMemcpyAsync(outMoments, ctx->ppllScratch.ptr, momBytes, hipMemcpyDeviceToHost, st));
-    LV_HIP(ctx, hipStreamSynchronize(st));   // (also: start / count / split are host vectors of this call)
-    return LV_OK;
+    return lv_resolve_read_back(ctx, out, size_t(numPixels), outMoments, momBytes);
 }
 
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,
@@ -4526,7 +4518,7 @@ int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, f
     LV_HIP(ctx, hipMemcpyAsync(dO, o, rb, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(dD, d, rb, hipMemcpyHostToDevice, st));
     LvSceneDev S = sceneDevTriangles(ctx);
-    if ((rc = lv_prepare_overflow(ctx, S, nblocks(n), LV_STACK_LDS, true))) return rc;
+    if ((rc = lv_reserve_overflow(ctx, S, "lv_trace_rays_triangles", nblocks(n), LV_STACK_LDS, true))) return rc;
     if (ctx->opt.traceRaysHardwareInv) k_trace_rays_tri<true><<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
     else k_trace_rays_tri<false><<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
     LV_HIP(ctx, hipGetLastError());
@@ -4545,7 +4537,7 @@ int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, f
 // async == true (lv_bake_ao_start; the reference's BakingMode::MULTI_THREADED, VulkanAmbientOcclusionBaker.cpp:266-346): on a second
 // stream, into a second table, with scratch buffers and counters of its own -- frames keep rendering on the context's stream (without
 // AO, or with the previous table's AO while that is still valid) until lv_bake_poll finds the stream finished and swaps the tables.
-int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async) {
+int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async, bool inFrame) {
     const LvOptions& o = ctx->opt;
     {
         const int rcMesh = lv_ensure_tube_mesh(ctx);
@@ -4602,15 +4594,16 @@ int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async) {
     if (async) {
         // stack overflow slab of its own (the frames' slab is in use on the other stream)
         SA.stackOverflow = nullptr;
-        const uint64_t maxEntries = 3ull * uint64_t(ctx->triWideDepth) + 2;
-        if (maxEntries > LV_AO_STACK_LDS) {
-            if ((rc = lv_buf_reserve(ctx, ctx->bakeOverflow, size_t(gridRays) * LV_BLOCK * (maxEntries - LV_AO_STACK_LDS) * 4))) return rc;
+        const size_t bytes = lv_overflow_bytes(ctx, gridRays, LV_AO_STACK_LDS, true);
+        if (bytes) {
+            if ((rc = lv_buf_reserve(ctx, ctx->bakeOverflow, bytes))) return rc;
             SA.stackOverflow = (unsigned*)ctx->bakeOverflow.ptr;
         }
         // everything queued on the context's stream so far (mesh upload, triangle LBVH) comes first
         LV_HIP(ctx, hipEventRecord(ctx->evBakePrereq, ctx->stream));
         LV_HIP(ctx, hipStreamWaitEvent(st, ctx->evBakePrereq, 0));
-    } else if ((rc = lv_prepare_overflow(ctx, SA, gridRays, LV_AO_STACK_LDS, true))) {
+    } else if ((rc = inFrame ? lv_prepare_overflow(ctx, SA, "RTAO prebaker", gridRays, LV_AO_STACK_LDS, true)
+                             : lv_reserve_overflow(ctx, SA, "RTAO prebaker", gridRays, LV_AO_STACK_LDS, true))) {
         return rc;
     }
     LV_HIP(ctx, hipMemcpyAsync(ctx->bakeLcgSkip.ptr, skip.data(), skip.size() * 4, hipMemcpyHostToDevice, st));
