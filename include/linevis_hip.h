@@ -576,6 +576,54 @@ int lv_get_mlat_trace(lv_ctx* ctx, uint32_t* out_records, uint64_t max_records, 
  * root; out_mismatches = number of arguments whose results differ in any bit (NaN results count as equal to each other),
  * out_first_argument = the bits of one of them. */
 int lv_selftest_rsqrt(lv_ctx* ctx, uint64_t* out_mismatches, uint32_t* out_first_argument);
+/* Parity instrument without a reference counterpart: one of the build-owned scalar definitions evaluated on the
+ * device for n arguments, by the same inline functions the render kernels call.  in_words / out_words are host arrays of bit
+ * patterns (a float travels as its 32 bits), element-major: n x arity words in, n x results words out.  Uploads, launches one
+ * kernel on the context's stream, synchronises and downloads.  LV_E_INVALID for a null pointer or an unknown id; n == 0 succeeds
+ * without a launch.  tests/test_gpu_math.py compares the words with the CPU checker's, bit for bit (two NaNs count as equal).
+ *
+ * id (arguments -> results) and the domain on which host and device are bound to agree; tests/math_args.py holds each excluded
+ * set as a named predicate:
+ *   LV_FN_SINCOS2PI (xi -> sin, cos)        all floats except finite |xi| >= 2^29 (math_args.sincos2pi_outside_domain): the quadrant
+ *                                           int(floor(4 xi)) does not fit an int there; callers pass [0, 1] or lv_sincos_rad's fraction
+ *   LV_FN_SINCOS_RAD (a -> sin, cos)        all floats (non-finite a: the angle 0)
+ *   LV_FN_ATAN2_DET (y, x -> angle)         all floats
+ *   LV_FN_POW_DET (x, y -> x^y)             all floats (x < 0, x NaN, x denormal: the x == 0 rule)
+ *   LV_FN_LOG2_DET (x -> log2 x)            all floats, bit for bit; a logarithm only for normal x > 0
+ *   LV_FN_EXP2_DET (p -> 2^p)               all floats
+ *   LV_FN_RSQRT_SHADE (x -> r(x))           all floats (lv_selftest_rsqrt)
+ *   LV_FN_TEA (val0, val1 -> word), LV_FN_RND (seed -> next seed, value in [0, 1))   all words
+ *   LV_FN_TRANSFER_FUNCTION (attribute -> rgba)   all floats and any range, attr_min == attr_max and infinite bounds included: the
+ *                                           position is clamped to [0, 1] before anything is converted, a NaN position counts as 0
+ *   LV_FN_TWIST_SAMPLE (u, dudx, dudy, use_grad != 0 -> rgba)   all floats: the texel coordinate goes through a saturating conversion
+ *                                           (NaN -> 0, beyond the int range -> INT_MIN / INT_MAX) before it is wrapped
+ *   LV_FN_PACK_UNORM4X8 (r, g, b, a -> word), LV_FN_UNPACK_UNORM4X8 (word -> r, g, b, a), LV_FN_STORE_RGBA8 (r, g, b, a -> the
+ *                                           frame's pixel word, no accumulation)   all floats / words (a NaN channel stores 0)
+ *   LV_FN_MBOIT_FIXED (term -> low, high word of the int64), LV_FN_MBOIT_UNFIXED (low, high -> float), LV_FN_MBOIT_SATURATE   all
+ *   LV_FN_RSQRT_FAST, LV_FN_DIV_FAST (a, b), LV_FN_POW_FAST (x, y)   shading_numerics = fast: no host twin, accuracy bars in DESIGN.md §4
+ * The transfer function and the twist sampler read the context's table, attribute range, texture and filtering mode (LV_E_STATE
+ * while none is set); no line data is needed. */
+#define LV_FN_SINCOS2PI 1
+#define LV_FN_SINCOS_RAD 2
+#define LV_FN_ATAN2_DET 3
+#define LV_FN_POW_DET 4
+#define LV_FN_LOG2_DET 5
+#define LV_FN_EXP2_DET 6
+#define LV_FN_RSQRT_SHADE 7
+#define LV_FN_TEA 8
+#define LV_FN_RND 9
+#define LV_FN_TRANSFER_FUNCTION 10
+#define LV_FN_TWIST_SAMPLE 11
+#define LV_FN_PACK_UNORM4X8 12
+#define LV_FN_UNPACK_UNORM4X8 13
+#define LV_FN_STORE_RGBA8 14
+#define LV_FN_MBOIT_FIXED 15
+#define LV_FN_MBOIT_UNFIXED 16
+#define LV_FN_MBOIT_SATURATE 17
+#define LV_FN_RSQRT_FAST 18
+#define LV_FN_DIV_FAST 19
+#define LV_FN_POW_FAST 20
+int lv_selftest_eval(lv_ctx* ctx, uint32_t function_id, const uint32_t* in_words, uint64_t n, uint32_t* out_words);
 /* PPLL buffers after the last mode-2 render: nodes = 3 uint32 {rgba8, depth bits, next} per node slot (slots are handed
  * out to waves in chunks, so unreferenced slots may lie between the stored fragments), start_offset = padded_w * padded_h
  * heads (0xFFFFFFFF = empty), frag_counter = number of fragments generated.  Either pointer may be NULL. */

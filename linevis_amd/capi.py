@@ -106,9 +106,16 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
            "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
-           "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt",
+           "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
            "lv_create_multi", "lv_multi_ranks", "lv_multi_rank_stats", "lv_multi_rebalance", "lv_multi_deal", "lv_tile_deal", "lv_make_tiles"]
+
+# function -> (LV_FN_* id, argument words, result words) of lv_selftest_eval
+SELFTEST_FUNCTIONS = {"sincos2pi": (1, 1, 2), "sincos_rad": (2, 1, 2), "atan2_det": (3, 2, 1), "pow_det": (4, 2, 1), "log2_det": (5, 1, 1),
+                      "exp2_det": (6, 1, 1), "rsqrt_shade": (7, 1, 1), "tea": (8, 2, 1), "rnd": (9, 1, 2), "transfer_function": (10, 1, 4),
+                      "twist_sample": (11, 4, 4), "pack_unorm4x8": (12, 4, 1), "unpack_unorm4x8": (13, 1, 4), "store_rgba8": (14, 4, 1),
+                      "mboit_fixed": (15, 1, 2), "mboit_unfixed": (16, 2, 1), "mboit_saturate": (17, 1, 1), "rsqrt_fast": (18, 1, 1),
+                      "div_fast": (19, 2, 1), "pow_fast": (20, 2, 1)}
 
 _lib = None
 
@@ -195,6 +202,7 @@ def load():
         ("lv_get_baked_ao", [vp, vp, u64]),
         ("lv_get_mlat_trace", [vp, vp, u64, C.POINTER(u64)]),
         ("lv_selftest_rsqrt", [vp, C.POINTER(u64), C.POINTER(u32)]),
+        ("lv_selftest_eval", [vp, u32, vp, u64, vp]),
     ]:
         fn = getattr(L, name)
         fn.restype = i32
@@ -494,6 +502,15 @@ class Context:
         bad, first = C.c_uint64(), C.c_uint32()
         self._ck(self.L.lv_selftest_rsqrt(self.h, C.byref(bad), C.byref(first)))
         return int(bad.value), int(first.value)
+
+    def selftest_eval(self, name, words):
+        """lv_selftest_eval: one build-owned scalar function (SELFTEST_FUNCTIONS) on (n, arity) uint32 bit patterns, evaluated on the
+        device by the inline functions the render kernels call -> (n, results) uint32."""
+        fid, arity, results = SELFTEST_FUNCTIONS[name]
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, arity)
+        out = np.empty((len(w), results), dtype=np.uint32)
+        self._ck(self.L.lv_selftest_eval(self.h, fid, _p(w), len(w), _p(out)))
+        return out
 
     def kernel_times(self, kernel_id):
         """Individual launch durations (ms) of one kernel since reset_timers(), oldest first (at most the last 512)."""

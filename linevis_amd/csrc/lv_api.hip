@@ -5,6 +5,8 @@
 #include <cstring>
 
 #include "lv_internal.h"
+#include "lv_trace.h"
+#include "lv_mboit.h"
 
 int lv_fail(lv_ctx* ctx, int code, const char* fmt, ...) {
     char buf[1024];
@@ -117,7 +119,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
             &ctx->bakeGbuf, &ctx->bakeSamples, &ctx->bakeOverflow, &ctx->mlatTrace, &ctx->buildArena, &ctx->firstHit,
-            &ctx->accum, &ctx->groupOrder[0].cost, &ctx->groupOrder[0].order, &ctx->groupOrder[1].cost, &ctx->groupOrder[1].order};
+            &ctx->accum, &ctx->selftestIn, &ctx->selftestOut, &ctx->groupOrder[0].cost, &ctx->groupOrder[0].order, &ctx->groupOrder[1].cost, &ctx->groupOrder[1].order};
 }
 
 namespace {
@@ -1332,6 +1334,99 @@ int lv_selftest_rsqrt(lv_ctx* ctx, uint64_t* out_mismatches, uint32_t* out_first
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out_mismatches = host[0];
     if (out_first_argument) *out_first_argument = uint32_t(host[1]);
+    return LV_OK;
+}
+
+namespace {
+// arity and result words per LV_FN_* id (0 = unknown id)
+void lv_selftest_shape(uint32_t fn, uint32_t& arity, uint32_t& results) {
+    switch (fn) {
+        case LV_FN_SINCOS2PI: case LV_FN_SINCOS_RAD: case LV_FN_RND: case LV_FN_MBOIT_FIXED: arity = 1; results = 2; break;
+        case LV_FN_ATAN2_DET: case LV_FN_POW_DET: case LV_FN_TEA: case LV_FN_MBOIT_UNFIXED: case LV_FN_DIV_FAST: case LV_FN_POW_FAST:
+            arity = 2; results = 1; break;
+        case LV_FN_LOG2_DET: case LV_FN_EXP2_DET: case LV_FN_RSQRT_SHADE: case LV_FN_MBOIT_SATURATE: case LV_FN_RSQRT_FAST:
+            arity = 1; results = 1; break;
+        case LV_FN_TRANSFER_FUNCTION: case LV_FN_UNPACK_UNORM4X8: arity = 1; results = 4; break;
+        case LV_FN_TWIST_SAMPLE: arity = 4; results = 4; break;
+        case LV_FN_PACK_UNORM4X8: case LV_FN_STORE_RGBA8: arity = 4; results = 1; break;
+        default: arity = 0; results = 0; break;
+    }
+}
+// one element per lane, grid-stride; every case calls the function the render kernels call, on bit patterns loaded from memory
+__global__ __launch_bounds__(256) void k_selftest_eval(uint32_t fn, uint32_t arity, uint32_t results, const uint32_t* __restrict__ in,
+                                                       uint64_t n, uint32_t* __restrict__ out, LvSceneDev S, LvUniforms U) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
+        const uint32_t* a = in + i * arity;
+        uint32_t* o = out + i * results;
+        const uint32_t a0 = a[0], a1 = arity > 1u ? a[1] : 0u, a2 = arity > 2u ? a[2] : 0u, a3 = arity > 3u ? a[3] : 0u;
+        const float x0 = __uint_as_float(a0), x1 = __uint_as_float(a1), x2 = __uint_as_float(a2), x3 = __uint_as_float(a3);
+        float r0 = 0.0f, r1 = 0.0f;
+        f4 c;
+        c.x = x0; c.y = x1; c.z = x2; c.w = x3;
+        switch (fn) {
+            case LV_FN_SINCOS2PI: lv_sincos2pi(x0, r0, r1); o[0] = __float_as_uint(r0); o[1] = __float_as_uint(r1); break;
+            case LV_FN_SINCOS_RAD: lv_sincos_rad(x0, r0, r1); o[0] = __float_as_uint(r0); o[1] = __float_as_uint(r1); break;
+            case LV_FN_ATAN2_DET: o[0] = __float_as_uint(lv_atan2_det(x0, x1)); break;
+            case LV_FN_POW_DET: o[0] = __float_as_uint(lv_pow_det(x0, x1)); break;
+            case LV_FN_LOG2_DET: o[0] = __float_as_uint(lv_log2_det(x0)); break;
+            case LV_FN_EXP2_DET: o[0] = __float_as_uint(lv_exp2_det(x0)); break;
+            case LV_FN_RSQRT_SHADE: o[0] = __float_as_uint(lv_rsqrt_shade(x0)); break;
+            case LV_FN_TEA: o[0] = lv_tea(a0, a1); break;
+            case LV_FN_RND: { uint32_t seed = a0; r0 = lv_rnd(seed); o[0] = seed; o[1] = __float_as_uint(r0); break; }
+            case LV_FN_TRANSFER_FUNCTION: c = lv_transfer_function(S, U, x0); break;
+            case LV_FN_TWIST_SAMPLE: c = lv_twist_sample(S, U, x0, x1, x2, a3 != 0u); break;
+            case LV_FN_PACK_UNORM4X8: o[0] = lv_pack_unorm4x8(c); break;
+            case LV_FN_UNPACK_UNORM4X8: c = lv_unpack_unorm4x8(a0); break;
+            case LV_FN_STORE_RGBA8: o[0] = lv_store_color(S, U, 0u, 0u, c); break;   // S.accum == nullptr: the frame's plain store
+            case LV_FN_MBOIT_FIXED: { const unsigned long long s = (unsigned long long)lv_mboit_fixed(x0); o[0] = uint32_t(s); o[1] = uint32_t(s >> 32); break; }
+            case LV_FN_MBOIT_UNFIXED: o[0] = __float_as_uint(lv_mboit_unfixed((long long)((unsigned long long)a0 | ((unsigned long long)a1 << 32)))); break;
+            case LV_FN_MBOIT_SATURATE: o[0] = __float_as_uint(lv_mboit_saturate(x0)); break;
+            case LV_FN_RSQRT_FAST: o[0] = __float_as_uint(lv_rsqrt_fast(x0)); break;
+            case LV_FN_DIV_FAST: o[0] = __float_as_uint(lv_div_fast(x0, x1)); break;
+            default: o[0] = __float_as_uint(lv_pow_fast(x0, x1)); break;   // LV_FN_POW_FAST (the host rejects every other id)
+        }
+        if (fn == LV_FN_TRANSFER_FUNCTION || fn == LV_FN_TWIST_SAMPLE || fn == LV_FN_UNPACK_UNORM4X8) {
+            o[0] = __float_as_uint(c.x); o[1] = __float_as_uint(c.y); o[2] = __float_as_uint(c.z); o[3] = __float_as_uint(c.w);
+        }
+    }
+}
+}   // namespace
+
+int lv_selftest_eval(lv_ctx* ctx, uint32_t function_id, const uint32_t* in_words, uint64_t n, uint32_t* out_words) {
+    if (!ctx) return LV_E_INVALID;
+    uint32_t arity, results;
+    lv_selftest_shape(function_id, arity, results);
+    if (!arity) return lv_fail(ctx, LV_E_INVALID, "lv_selftest_eval: unknown function id %u", function_id);
+    if (!in_words || !out_words) return lv_fail(ctx, LV_E_INVALID, "lv_selftest_eval: null array");
+    if (n == 0) return LV_OK;
+    if (n > (1ull << 28)) return lv_fail(ctx, LV_E_INVALID, "lv_selftest_eval: %llu elements (at most 2^28 per call)", (unsigned long long)n);
+    LvSceneDev S;
+    LvUniforms U;
+    memset(&S, 0, sizeof S);
+    memset(&U, 0, sizeof U);
+    if (function_id == LV_FN_TRANSFER_FUNCTION) {
+        if (!ctx->tf.ptr || ctx->tfN == 0) return lv_fail(ctx, LV_E_STATE, "lv_selftest_eval: no transfer function (lv_set_transfer_function first)");
+        S.tf = (const float4*)ctx->tf.ptr;
+        U.tfN = ctx->tfN; U.attrMin = ctx->attrMin; U.attrMax = ctx->attrMax;
+    }
+    if (function_id == LV_FN_TWIST_SAMPLE) {
+        if (!ctx->twistTex.ptr || ctx->twistLevels == 0) return lv_fail(ctx, LV_E_STATE, "lv_selftest_eval: no twist-line texture (lv_set_twist_line_texture first)");
+        S.twistTex = (const float4*)ctx->twistTex.ptr;
+        U.twistW = ctx->twistW; U.twistH = ctx->twistH; U.twistLevels = ctx->twistLevels;
+        U.twistFilterMode = ctx->opt.twistFilterMode;
+    }
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    const size_t inBytes = size_t(n) * arity * 4, outBytes = size_t(n) * results * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->selftestIn, inBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->selftestOut, outBytes))) return rc;
+    LV_HIP(ctx, hipMemcpyAsync(ctx->selftestIn.ptr, in_words, inBytes, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t blocks = (n + 255u) / 256u, maxBlocks = uint64_t(ctx->numCUs) * 16u;
+    k_selftest_eval<<<uint32_t(blocks < maxBlocks ? blocks : maxBlocks), 256, 0, ctx->stream>>>(
+        function_id, arity, results, (const uint32_t*)ctx->selftestIn.ptr, n, (uint32_t*)ctx->selftestOut.ptr, S, U);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(out_words, ctx->selftestOut.ptr, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LV_OK;
 }
 

@@ -149,6 +149,14 @@ __device__ __forceinline__ float len3(f3 a) { return sqrtf(dot3(a, a)); }
 __device__ __forceinline__ f3 norm3(f3 a) { float l = len3(a); return mk3(a.x / l, a.y / l, a.z / l); }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 __device__ __forceinline__ float mixf(float a, float b, float w) { return a * (1.0f - w) + b * w; }
+// float -> int where the value is not known to fit (a texture coordinate that comes from line data): NaN -> 0, values beyond the int
+// range saturate.  This is what v_cvt_i32_f32 does and what the plain cast compiled to, but C++ leaves the cast undefined there and
+// x86 answers INT_MIN for all three, so the rule is stated: the CPU checker's f2iSat is the same
+__device__ __forceinline__ int lv_f2i_sat(float f) {
+    if (!(f > -2147483648.0f)) return f != f ? 0 : (-2147483647 - 1);
+    if (f >= 2147483648.0f) return 2147483647;
+    return int(f);
+}
 __device__ __forceinline__ float smoothstepf(float e0, float e1, float x) {
     float t = clampf((x - e0) / (e1 - e0), 0.0f, 1.0f);
     return t * t * (3.0f - 2.0f * t);
@@ -452,7 +460,15 @@ __device__ __forceinline__ float lv_rsqrt_fast(float x) { return __builtin_amdgc
 __device__ __forceinline__ f3 norm3f(f3 a) { const float r = lv_rsqrt_fast(dot3(a, a)); return mk3(a.x * r, a.y * r, a.z * r); }
 template <bool FASTN>
 __device__ __forceinline__ f3 norm3q(f3 a) { return FASTN ? norm3f(a) : norm3s(a); }
-__device__ __forceinline__ float lv_div_fast(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+// a / b within one ulp: a * rcp(b) alone rounds twice (rcp <= 1 ulp, then the product: 1.98 ulp measured, tests/test_gpu_math.py), so
+// the quotient takes one residual step, q + (a - b q) rcp(b) in two fma.  Where that step has no value (b == 0, b infinite, an
+// overflowed q: inf - inf or 0 * inf) the plain product stands, which is what exact division answers there (inf, 0, inf)
+__device__ __forceinline__ float lv_div_fast(float a, float b) {
+    const float r = __builtin_amdgcn_rcpf(b);
+    const float q = a * r;
+    const float qc = __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
+    return qc == qc ? qc : q;
+}
 template <bool FASTN>
 __device__ __forceinline__ float lv_divq(float a, float b) { return FASTN ? lv_div_fast(a, b) : a / b; }
 __device__ __forceinline__ float lv_pow_fast(float x, float y) {

@@ -247,6 +247,7 @@ struct lv_ctx {
     uint32_t mboitStreamW = 0, mboitStreamH = 0, mboitStreamN = 0, mboitStreamTile[2] = {0, 0};   // that frame's viewport, moment count and ppll tile
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
+    LvDeviceBuffer selftestIn, selftestOut;   // lv_selftest_eval: argument and result words
     LvDeviceBuffer accum;                     // rgba8 of the previous accumulated frame (full viewport)
     uint32_t* pinned = nullptr;               // 64 B of pinned host memory for small read-backs (hipHostMalloc)
     LvDeviceBuffer buildArena;                // temporaries of the LBVH builds, kept between builds

@@ -1085,11 +1085,12 @@ __device__ __forceinline__ f4 lv_twist_level(const LvSceneDev& S, const LvUnifor
     const float4* __restrict__ T = S.twistTex + base;
     auto wrap = [](int i, uint32_t n) { int m = i % int(n); return uint32_t(m < 0 ? m + int(n) : m); };
     auto texel = [&](uint32_t i, uint32_t j) { const float4 t = T[size_t(j) * w + i]; f4 r; r.x = t.x; r.y = t.y; r.z = t.z; r.w = t.w; return r; };
-    if (!linear) return texel(wrap(int(floorf(u * float(w))), w), wrap(int(floorf(v * float(h))), h));
+    auto next = [](int i) { return int(uint32_t(i) + 1u); };   // i + 1 that wraps at INT_MAX (a saturated coordinate)
+    if (!linear) return texel(wrap(lv_f2i_sat(floorf(u * float(w))), w), wrap(lv_f2i_sat(floorf(v * float(h))), h));
     const float x = u * float(w) - 0.5f, y = v * float(h) - 0.5f;
     const float fx0 = floorf(x), fy0 = floorf(y);
     const float a = x - fx0, b = y - fy0;
-    const uint32_t i0 = wrap(int(fx0), w), i1 = wrap(int(fx0) + 1, w), j0 = wrap(int(fy0), h), j1 = wrap(int(fy0) + 1, h);
+    const uint32_t i0 = wrap(lv_f2i_sat(fx0), w), i1 = wrap(next(lv_f2i_sat(fx0)), w), j0 = wrap(lv_f2i_sat(fy0), h), j1 = wrap(next(lv_f2i_sat(fy0)), h);
     const f4 t00 = texel(i0, j0), t10 = texel(i1, j0), t01 = texel(i0, j1), t11 = texel(i1, j1);
     f4 r;
     r.x = mixf(mixf(t00.x, t10.x, a), mixf(t01.x, t11.x, a), b);

@@ -694,15 +694,16 @@ static void twistLevel(uint32_t level, float u, float v, bool linear, float out[
     for (uint32_t l = 0; l < level; l++) { base += size_t(w) * h * 4; w = std::max(w >> 1, 1u); h = std::max(h >> 1, 1u); }
     const float* T = g_twist.texels.data() + base;
     auto wrap = [](int i, uint32_t n) { int m = i % int(n); return uint32_t(m < 0 ? m + int(n) : m); };
+    auto next = [](int i) { return int(uint32_t(i) + 1u); };   // i + 1 that wraps at INT_MAX (a saturated coordinate)
     if (!linear) {
-        const uint32_t i = wrap(int(floorf(u * float(w))), w), j = wrap(int(floorf(v * float(h))), h);
+        const uint32_t i = wrap(f2iSat(floorf(u * float(w))), w), j = wrap(f2iSat(floorf(v * float(h))), h);
         for (int c = 0; c < 4; c++) out[c] = T[(size_t(j) * w + i) * 4 + c];
         return;
     }
     const float x = u * float(w) - 0.5f, y = v * float(h) - 0.5f;
     const float fx0 = floorf(x), fy0 = floorf(y);
     const float a = x - fx0, b = y - fy0;
-    const uint32_t i0 = wrap(int(fx0), w), i1 = wrap(int(fx0) + 1, w), j0 = wrap(int(fy0), h), j1 = wrap(int(fy0) + 1, h);
+    const uint32_t i0 = wrap(f2iSat(fx0), w), i1 = wrap(next(f2iSat(fx0)), w), j0 = wrap(f2iSat(fy0), h), j1 = wrap(next(f2iSat(fy0)), h);
     for (int c = 0; c < 4; c++)
         out[c] = mixf(mixf(T[(size_t(j0) * w + i0) * 4 + c], T[(size_t(j0) * w + i1) * 4 + c], a),
                       mixf(T[(size_t(j1) * w + i0) * 4 + c], T[(size_t(j1) * w + i1) * 4 + c], a), b);
@@ -712,7 +713,7 @@ static void twistSample(float u, float dudx, float dudy, bool useGrad, float out
     const bool linear = mode == 1u || mode == 3u || mode == 5u;
     const float v = 0.5f;
     if (mode < 2u || !useGrad || g_twist.levels <= 1u) { twistLevel(0u, u, v, linear, out); return; }
-    const float rho = fmaxf(fabsf(dudx), fabsf(dudy)) * float(g_twist.w);
+    const float rho = maxNum(fabsf(dudx), fabsf(dudy)) * float(g_twist.w);
     const float maxLevel = float(g_twist.levels - 1u);
     const float lambda = rho > 1.0f ? fminf(log2Det(rho), maxLevel) : 0.0f;
     if (mode == 2u || mode == 3u) {
@@ -2601,6 +2602,62 @@ void lvo_prebaked_ao_lookup_batch(const float* factors, const float* blendingWei
 }
 void lvo_pow_det(const float* x, const float* y, uint64_t n, float* out) {
     for (uint64_t i = 0; i < n; i++) out[i] = powDet(x[i], y[i]);
+}
+// Test hook: the host twin of the HIP library's lv_selftest_eval -- each function below is the statement the frame code of this file
+// calls, evaluated on bit patterns (element-major: n x arity words in, n x results words out).  Returns 0, or -1 for an unknown id.
+int lvo_eval_words(uint32_t fn, const uint32_t* in, uint64_t n, uint32_t* out, const float* tfRgba, uint32_t tfN, float attrMin,
+                   float attrMax) {
+    lvo_scene sc;
+    lvo_params P{};
+    if (fn == LVO_FN_TRANSFER_FUNCTION) {
+        if (!tfRgba || tfN == 0) return -1;
+        sc.tf.assign(tfRgba, tfRgba + 4 * size_t(tfN));
+        sc.tfN = tfN;
+        P.attrMin = attrMin; P.attrMax = attrMax;
+    }
+    if (fn == LVO_FN_TWIST_SAMPLE && !g_twist.use) return -1;
+    switch (fn) {
+        case LVO_FN_SINCOS2PI: case LVO_FN_SINCOS_RAD: case LVO_FN_ATAN2_DET: case LVO_FN_POW_DET: case LVO_FN_LOG2_DET:
+        case LVO_FN_EXP2_DET: case LVO_FN_RSQRT_SHADE: case LVO_FN_TEA: case LVO_FN_RND: case LVO_FN_TRANSFER_FUNCTION:
+        case LVO_FN_TWIST_SAMPLE: case LVO_FN_PACK_UNORM4X8: case LVO_FN_UNPACK_UNORM4X8: case LVO_FN_STORE_RGBA8: break;
+        default: return -1;
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < int64_t(n); i++) {
+        float r[4];
+        switch (fn) {
+            case LVO_FN_SINCOS2PI: sincos2pi(u2f(in[i]), r[0], r[1]); out[2 * i] = f2u(r[0]); out[2 * i + 1] = f2u(r[1]); break;
+            case LVO_FN_SINCOS_RAD: sincosRad(u2f(in[i]), r[0], r[1]); out[2 * i] = f2u(r[0]); out[2 * i + 1] = f2u(r[1]); break;
+            case LVO_FN_ATAN2_DET: out[i] = f2u(atan2Det(u2f(in[2 * i]), u2f(in[2 * i + 1]))); break;
+            case LVO_FN_POW_DET: out[i] = f2u(powDet(u2f(in[2 * i]), u2f(in[2 * i + 1]))); break;
+            case LVO_FN_LOG2_DET: out[i] = f2u(log2Det(u2f(in[i]))); break;
+            case LVO_FN_EXP2_DET: { const float p = u2f(in[i]); out[i] = f2u(p != p ? p : powDet(2.0f, p)); break; }   // lv_exp2_det
+            case LVO_FN_RSQRT_SHADE: out[i] = f2u(rsqrtShade(u2f(in[i]))); break;
+            case LVO_FN_TEA: out[i] = tea(in[2 * i], in[2 * i + 1]); break;
+            case LVO_FN_RND: { uint32_t s = in[i]; const float v = rnd(s); out[2 * i] = s; out[2 * i + 1] = f2u(v); break; }
+            case LVO_FN_TRANSFER_FUNCTION:
+                transferFunction(sc, P, u2f(in[i]), r);
+                for (int k = 0; k < 4; k++) out[4 * i + k] = f2u(r[k]);
+                break;
+            case LVO_FN_TWIST_SAMPLE:
+                twistSample(u2f(in[4 * i]), u2f(in[4 * i + 1]), u2f(in[4 * i + 2]), in[4 * i + 3] != 0u, r);
+                for (int k = 0; k < 4; k++) out[4 * i + k] = f2u(r[k]);
+                break;
+            case LVO_FN_PACK_UNORM4X8:
+                for (int k = 0; k < 4; k++) r[k] = u2f(in[4 * i + k]);
+                out[i] = packUnorm4x8(r);
+                break;
+            case LVO_FN_UNPACK_UNORM4X8:
+                unpackUnorm4x8(in[i], r);
+                for (int k = 0; k < 4; k++) out[4 * i + k] = f2u(r[k]);
+                break;
+            default:   // LVO_FN_STORE_RGBA8: the frame loops' px[k] = toUnorm8(fragmentColor[k]), bytes in memory order
+                out[i] = 0u;
+                for (int k = 0; k < 4; k++) out[i] |= uint32_t(toUnorm8(u2f(in[4 * i + k]))) << (8 * k);
+                break;
+        }
+    }
+    return 0;
 }
 void lvo_set_ppll_fragment_colour_variant(int rayTracerVariant) { g_rtFragmentColourInPpll = rayTracerVariant != 0; }
 void lvo_set_ppll_prebaked_ao(const float* factors, const float* blendingWeights, uint32_t numLineVertices,

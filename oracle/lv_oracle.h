@@ -418,6 +418,19 @@ void lvo_set_ppll_prebaked_ao(const float* factors, const float* blendingWeights
                               uint32_t numParametrizationVertices, uint32_t numAoTubeSubdivisions);
 /* the build-owned pow of the shading code (powDet = lv_pow_det of the HIP library) on n inputs */
 void lvo_pow_det(const float* x, const float* y, uint64_t n, float* out);
+/* Test hook: the build-owned scalar definitions on n arguments given as float32 / uint32 bit patterns -- the host twin of the HIP
+ * library's lv_selftest_eval (same ids, arities and element-major layout: n x arity words in, n x results words out), each one the
+ * statement the frame code calls.  The transfer function reads tfRgba / tfN / attrMin / attrMax, the twist sampler the texture and
+ * filtering mode of lvo_set_twist_line_texture.  The MBOIT fixed-point helpers and the fast forms have no statement in this library
+ * (tests/test_mboit_restatement.py states the former; the latter have no host twin).  Returns 0; -1 for an id without a statement
+ * here or a missing table. */
+enum {
+    LVO_FN_SINCOS2PI = 1, LVO_FN_SINCOS_RAD = 2, LVO_FN_ATAN2_DET = 3, LVO_FN_POW_DET = 4, LVO_FN_LOG2_DET = 5, LVO_FN_EXP2_DET = 6,
+    LVO_FN_RSQRT_SHADE = 7, LVO_FN_TEA = 8, LVO_FN_RND = 9, LVO_FN_TRANSFER_FUNCTION = 10, LVO_FN_TWIST_SAMPLE = 11,
+    LVO_FN_PACK_UNORM4X8 = 12, LVO_FN_UNPACK_UNORM4X8 = 13, LVO_FN_STORE_RGBA8 = 14
+};
+int lvo_eval_words(uint32_t fn, const uint32_t* in, uint64_t n, uint32_t* out, const float* tfRgba, uint32_t tfN, float attrMin,
+                   float attrMax);
 void lvo_prebaked_ao_lookup_batch(const float* factors, const float* blendingWeights, uint32_t numLineVertices,
                                   uint32_t numParametrizationVertices, uint32_t numAoTubeSubdivisions, const float* vertexId,
                                   const float* phi, uint64_t n, float* out);

@@ -43,7 +43,20 @@ inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 inline V3 cross(V3 a, V3 b) { return V3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 inline float length(V3 a) { return sqrtf(dot(a, a)); }
 inline V3 normalize(V3 a) { float l = length(a); return V3{a.x / l, a.y / l, a.z / l}; }
-inline float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+// max / min that return the other operand when one is a NaN -- quiet or signalling: what fmaxf / fminf compile to on gfx950.  glibc's
+// fmaxf / fminf answer NaN for a signalling NaN; the functions below that the HIP library states with fmaxf / fminf on arguments a
+// caller can hand over unprocessed (a colour channel, an attribute, a texture derivative) use these, so that both sides agree on every
+// bit pattern (tests/test_gpu_math.py).  For every other operand pair they are fmaxf / fminf.
+inline float maxNum(float a, float b) { return a != a ? b : (b != b ? a : fmaxf(a, b)); }
+inline float minNum(float a, float b) { return a != a ? b : (b != b ? a : fminf(a, b)); }
+inline float clampf(float x, float lo, float hi) { return minNum(maxNum(x, lo), hi); }
+// float -> int where the value is not known to fit (a texture coordinate that comes from line data): NaN -> 0, values beyond
+// the int range saturate -- what the HIP library's lv_f2i_sat states (C++ leaves the plain cast undefined there)
+inline int f2iSat(float f) {
+    if (!(f > -2147483648.0f)) return f != f ? 0 : std::numeric_limits<int>::min();
+    if (f >= 2147483648.0f) return std::numeric_limits<int>::max();
+    return int(f);
+}
 // pow(x, y) of the shading code as a build-owned float32 definition, bit-identical to lv_pow_det of the HIP library
 // (linevis_amd/csrc/lv_device.h): exp2(y * log2(x)), log2 through the exponent bits + an atanh series, exp2 through a 7th-order series.
 inline float powDet(float x, float y) {
@@ -91,11 +104,12 @@ inline float log2Det(float x) {
 // the range is counted (lvo_shade_normalize_out_of_range), and the parity tests assert that the scenes they compare never get there --
 // so "device == checker" on those scenes is also "device == the reference's normalize()".
 inline std::atomic<unsigned long long> g_shadeNormalizeOutOfRange{0ull};
+// r(x) of the rule (lv_rsqrt_shade of the HIP library); (NaN -> 2^-60: max / min return the other operand)
+inline float rsqrtShade(float x0) { return 1.0f / sqrtf(minNum(maxNum(x0, 0x1p-60f), 0x1p60f)); }
 inline V3 normalizeShade(V3 a) {
     const float x0 = dot(a, a);
     if (!(x0 >= 0x1p-60f && x0 <= 0x1p60f)) g_shadeNormalizeOutOfRange.fetch_add(1ull, std::memory_order_relaxed);
-    const float x = fminf(fmaxf(x0, 0x1p-60f), 0x1p60f);   // (NaN -> 2^-60: fmaxf / fminf return the other operand)
-    const float r = 1.0f / sqrtf(x);
+    const float r = rsqrtShade(x0);
     return V3{a.x * r, a.y * r, a.z * r};
 }
 
@@ -168,7 +182,7 @@ inline void sincosRad(float a, float& s, float& c) {
 }
 inline float atan2Det(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
+    const float mx = maxNum(ax, ay), mn = minNum(ax, ay);
     float r = 0.0f;
     if (mx > 0.0f) {
         float a = mn / mx;                                   // [0, 1]

@@ -115,6 +115,8 @@ def lib():
     L.lvo_set_ppll_fragment_colour_variant.argtypes = [i32]
     L.lvo_set_ppll_prebaked_ao.argtypes = [vp, vp, u32, u32, u32]
     L.lvo_pow_det.argtypes = [vp, vp, C.c_uint64, vp]
+    L.lvo_eval_words.restype = i32
+    L.lvo_eval_words.argtypes = [u32, vp, C.c_uint64, vp, vp, u32, f32, f32]
     L.lvo_prebaked_ao_lookup_batch.argtypes = [vp, vp, u32, u32, u32, vp, vp, C.c_uint64, vp]
     L.lvo_num_threads.restype = i32
     L.lvo_num_threads.argtypes = []
@@ -907,6 +909,26 @@ def pow_det(x, y):
     yy = np.ascontiguousarray(np.broadcast_to(np.asarray(y, dtype=np.float32), np.broadcast(x, y).shape), dtype=np.float32).reshape(-1)
     out = np.empty(len(xx), dtype=np.float32)
     lib().lvo_pow_det(_p(xx), _p(yy), len(xx), _p(out))
+    return out
+
+
+# function -> (id, argument words, result words) of lvo_eval_words (lv_oracle.h); the ids are those of the HIP library's LV_FN_*
+EVAL_FUNCTIONS = {"sincos2pi": (1, 1, 2), "sincos_rad": (2, 1, 2), "atan2_det": (3, 2, 1), "pow_det": (4, 2, 1), "log2_det": (5, 1, 1),
+                  "exp2_det": (6, 1, 1), "rsqrt_shade": (7, 1, 1), "tea": (8, 2, 1), "rnd": (9, 1, 2), "transfer_function": (10, 1, 4),
+                  "twist_sample": (11, 4, 4), "pack_unorm4x8": (12, 4, 1), "unpack_unorm4x8": (13, 1, 4), "store_rgba8": (14, 4, 1)}
+
+
+def eval_words(name, words, tf=None, attr_min=0.0, attr_max=1.0):
+    """The oracle's statement of one build-owned scalar function on (n, arity) uint32 bit patterns -> (n, results) uint32.
+    transfer_function: tf = (k, 4) float32 texels + the attribute range; twist_sample: inside a twist_line_texture context."""
+    fid, arity, results = EVAL_FUNCTIONS[name]
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, arity)
+    out = np.empty((len(w), results), dtype=np.uint32)
+    t = None if tf is None else np.ascontiguousarray(tf, dtype=np.float32).reshape(-1, 4)
+    rc = lib().lvo_eval_words(fid, _p(w), len(w), _p(out), None if t is None else _p(t), 0 if t is None else len(t), float(attr_min),
+                              float(attr_max))
+    if rc != 0:
+        raise ValueError("lvo_eval_words(%s): no statement or missing table" % name)
     return out
 
 

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import math_args as A
 from common import GOLDEN_DIR, Case, small_case, max_lsb_diff, scene_arrays
 from linevis_amd import scenes, transfer_function as tfm
 from oracle import lvo
@@ -402,6 +403,114 @@ def test_pow_det_against_float64():
     assert lvo.pow_det(np.float32(0.0), np.float32(1.7))[0] == 0.0 and lvo.pow_det(np.float32(0.0), np.float32(0.0))[0] == 1.0
     assert lvo.pow_det(np.float32(1.0), np.float32(30.0))[0] == 1.0
     assert lvo.pow_det(np.float32(1e-30), np.float32(30.0))[0] == 0.0
+
+
+# ---------------------------------------------------------------- float64 anchors of the function-level device tests
+# tests/test_gpu_math.py compares the device with the checker's statements over the sets of tests/math_args.py; here the same
+# statements run over the in-domain part of the same sets against numpy float64.
+def _f64(words):
+    with np.errstate(invalid="ignore"):   # (signalling NaNs in the sets)
+        return A.w2f(words).astype(np.float64)
+
+
+def test_argument_sets_and_their_exclusions():
+    """The only arguments the device tests leave out are those math_args.sincos2pi_outside_domain names: finite |xi| >= 2^29.  Its share
+    of the structured set follows from the float format alone, the call domain of lv_sincos2pi holds none of them, and nothing but
+    the predicate shapes the count (no isfinite mask: NaN and +-inf stay in)."""
+    s = A.structured_words()
+    assert len(s) == 1 << 21 and len(np.unique(s)) == 1 << 21 and (s & np.uint32(0x7FF) == 0).all()
+    assert int(A.sincos2pi_outside_domain(s).sum()) == A.structured_outside_sincos2pi_domain() == 811008
+    assert not A.sincos2pi_outside_domain(A.f2w(A.call_domain("sincos2pi"))).any()
+    w = A.unary_words("sincos2pi")
+    out = A.sincos2pi_outside_domain(w)
+    x = A.w2f(w)
+    with np.errstate(invalid="ignore"):
+        assert np.array_equal(out, (np.abs(x) >= 2.0 ** 29) & (np.abs(x) < np.inf))
+    assert np.isnan(x[~out]).any() and np.isinf(x[~out]).any()
+    assert not out[np.isin(w, A.neighbours([2.0 ** 29], 64)[:64])].any() and out[np.isin(w, A.neighbours([2.0 ** 29], 64)[64:])].all()
+    # the sets are what the tests say they are
+    assert len(A.atan2_axis()) == 2048 and len(np.unique(A.atan2_axis())) == 2048
+    k = (A.call_domain("sincos2pi")[:1 << 20].astype(np.float64) * (1 << 24))
+    assert np.array_equal(k, np.round(k)) and k.max() < (1 << 24)
+    for wh in A.TWIST_TEXTURES:
+        with np.errstate(invalid="ignore"):
+            u = A.w2f(A.twist_u(wh[0])).astype(np.float64) * wh[0]
+            assert (u >= 2.0 ** 31).any() and (u <= -2.0 ** 31).any() and np.isnan(u).any() and np.isinf(u).any()
+    t = A.mboit_tie_terms().astype(np.float64) * 2.0 ** 36
+    assert (np.abs(t - np.floor(t)) == 0.5).sum() >= 3 * 4096
+    assert np.abs(A.mboit_sums().view(np.int64)).max() == 1 << 62
+
+
+def test_sincos_2pi_against_float64():
+    """lvo sincos_2pi over the in-domain part of the device test's set (everything but finite |xi| >= 2^29) against sin / cos of
+    2 pi (xi mod 1) in float64 (the reduction is exact in float64).  Measured maximum absolute error on this set: 1.162e-7
+    (the larger of sin and cos); asserted: twice that, 2.324e-7.  The factor covers a
+    change of the argument set, not of the formula.  Non-finite xi: NaN."""
+    w = A.unary_words("sincos2pi")
+    w = w[~A.sincos2pi_outside_domain(w)]
+    got = lvo.eval_words("sincos2pi", w).view(np.float32).astype(np.float64)
+    x = _f64(w)
+    with np.errstate(invalid="ignore"):
+        r = x - np.floor(x)
+        want = np.stack([np.sin(2 * np.pi * r), np.cos(2 * np.pi * r)], axis=1)
+    fin = np.isfinite(x)
+    assert np.isnan(got[~fin]).all()
+    err = np.abs(got[fin] - want[fin])
+    print("sincos_2pi: max |error| %.3e over %d arguments" % (err.max(), fin.sum()))
+    assert err.max() <= 2.324e-7
+
+
+def test_log2_det_against_float64():
+    """lvo log2 over the part of the device test's set where it is a logarithm (normal x > 0: math_args.log2_det_is_a_logarithm) against
+    numpy float64.  Measured maximum of |error| / max(|log2 x|, 1) on this set: 1.011e-7; asserted: twice that, 2.022e-7.  The factor
+    covers a change of the argument set, not of the formula."""
+    w = A.unary_words("log2_det")
+    w = w[A.log2_det_is_a_logarithm(w)]
+    got = lvo.eval_words("log2_det", w).view(np.float32).astype(np.float64)[:, 0]
+    want = np.log2(_f64(w))
+    err = np.abs(got - want) / np.maximum(np.abs(want), 1.0)
+    print("log2_det: max scaled error %.3e over %d arguments" % (err.max(), len(w)))
+    assert len(w) > 1 << 20 and err.max() <= 2.022e-7
+
+
+def test_sincos_rad_atan2_exp2_and_pow_keep_their_bars_on_the_device_sets():
+    """The bars that exist, unchanged, over the in-domain part of the sets the device tests run: lv_sincos_rad below 1.5e-6 on
+    |a| <= 8 and lv_atan2_det below 5e-7 (tests/test_bands.py); exp2 and pow within 3e-6 relative where the result lies in
+    (1e-4, 1e4) and within 1e-9 absolute below 1e-4 (test_pow_det_against_float64, tests/test_mboit_restatement.py)."""
+    w = A.unary_words("sincos_rad")
+    w = w[A.sincos_rad_anchor_domain(w)]
+    got = lvo.eval_words("sincos_rad", w).view(np.float32).astype(np.float64)
+    a = _f64(w)
+    err = np.abs(got - np.stack([np.sin(a), np.cos(a)], axis=1)).max()
+    print("sincos_rad: max |error| %.3e over %d arguments" % (err, len(w)))
+    assert len(w) > 1 << 20 and err < 1.5e-6
+
+    w = A.atan2_words()
+    y, x = A.w2f(w[:, 0]), A.w2f(w[:, 1])
+    fin = A.atan2_det_anchor_domain(w)
+    got = lvo.eval_words("atan2_det", w[fin]).view(np.float32).astype(np.float64)[:, 0]
+    err = np.abs(got - np.arctan2(y[fin].astype(np.float64), x[fin].astype(np.float64))).max()
+    print("atan2_det: max |error| %.3e over %d pairs" % (err, fin.sum()))
+    assert err < 5e-7
+
+    def bars(name, got, want):
+        big = (want > 1e-4) & (want < 1e4)
+        small = want <= 1e-4
+        rel, ab = np.abs(got[big] / want[big] - 1.0).max(), np.abs(got[small] - want[small]).max()
+        print("%s: max relative error %.3e over %d results in (1e-4, 1e4), max |error| %.3e over %d below" % (name, rel, big.sum(), ab, small.sum()))
+        assert big.sum() > 1000 and rel < 3e-6 and ab < 1e-9
+
+    w = A.unary_words("exp2_det")
+    p = _f64(w)
+    w, p = w[np.isfinite(p)], p[np.isfinite(p)]
+    with np.errstate(over="ignore"):
+        bars("exp2_det", lvo.eval_words("exp2_det", w).view(np.float32).astype(np.float64)[:, 0], np.exp2(p))
+
+    w = A.pow_words()
+    w = w[A.pow_det_anchor_domain(w)]
+    x, y = _f64(w[:, 0]), _f64(w[:, 1])
+    with np.errstate(over="ignore", divide="ignore"):
+        bars("pow_det", lvo.eval_words("pow_det", w).view(np.float32).astype(np.float64)[:, 0], np.power(x, y))
 
 
 def test_shading_normalisations_of_the_test_scenes_stay_inside_the_clamp_range():
