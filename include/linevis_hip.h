@@ -323,6 +323,9 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   accel_build (build-owned; the reference builds its BLAS with VK_BUILD_ACCELERATION_STRUCTURE_PREFER_FAST_TRACE_BIT_KHR,
  *   LineData.cpp:740-741): "fast_trace" (default: LBVH whose subtrees of <= treelet_leaves leaves are rebuilt with a binned
  *   surface-area heuristic) | "fast_build" (the plain LBVH); treelet_leaves (3 ... 4096, default 512),
+ *   accel_partition (fast_trace only): "sah" (default: a binned-SAH partition of the whole scene chooses the leaf sets of the
+ *   treelets -- path-code bits in front of the Morton sort keys) | "morton" (runs of the Morton order do); same hits either way; accel_partition_min_leaves
+ *   (default 65536; 0 = always): builds of fewer leaves keep the Morton order under "sah" too,
  *   treelet_group_leaves (0 | 8 | 16, default 16), treelet_lane_leaves (0 | 2 ... 64, default 6; used when the former is 0),
  *   treelet_plane_eval ("scan" | "loop"), accel_collapse_top ("true" | "false"): build time only, the tree is the same -- the
  *   small ranges of a treelet are built by groups of 8 / 16 lanes (or one lane per range) instead of by the whole wave; the form

@@ -118,7 +118,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
-            &ctx->bakeGbuf, &ctx->bakeSamples, &ctx->bakeOverflow, &ctx->mlatTrace, &ctx->buildArena, &ctx->firstHit,
+            &ctx->bakeGbuf, &ctx->bakeSamples, &ctx->bakeOverflow, &ctx->mlatTrace, &ctx->buildArena, &ctx->partitionScratch, &ctx->firstHit,
             &ctx->accum, &ctx->selftestIn, &ctx->selftestOut, &ctx->groupOrder[0].cost, &ctx->groupOrder[0].order, &ctx->groupOrder[1].cost, &ctx->groupOrder[1].order};
 }
 
@@ -835,6 +835,21 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         else return bad();
         if (ft != o.accelFastTrace) { ctx->accelValid = false; ctx->triAccelValid = false; lv_invalidate_bake(ctx); }
         o.accelFastTrace = ft;
+    } else if (k == "accel_partition") {
+        // which leaves share a treelet of the fast_trace build: "sah" (default) = the clusters of a binned-SAH partition of the whole scene
+        // (path-code sort keys, lv_bvh.hip), "morton" = runs of the Morton order.  Closest hits do not depend on it; fast_build ignores it
+        bool sah;
+        if (std::string(value) == "sah") sah = true;
+        else if (std::string(value) == "morton") sah = false;
+        else return bad();
+        if (sah != o.accelPartitionSah) { ctx->accelValid = false; ctx->triAccelValid = false; lv_invalidate_bake(ctx); }
+        o.accelPartitionSah = sah;
+    } else if (k == "accel_partition_min_leaves") {
+        // accel_partition = sah applies to builds of at least this many leaves (default 65 536 = 128 treelets of 512); 0 = to every build
+        uint32_t t;
+        if (!parseUint(value, t)) return bad();
+        if (t != o.accelPartitionMinLeaves) { ctx->accelValid = false; ctx->triAccelValid = false; lv_invalidate_bake(ctx); }
+        o.accelPartitionMinLeaves = t;
     } else if (k == "dispatch_order") {
         // tile kernels: "cost" = the 64x64-pixel groups start in the order of what they cost in the previous frame, heaviest
         // first (default); "as_numbered" = in tile-list order (measurement knob; the image is the same)

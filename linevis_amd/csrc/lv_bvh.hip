@@ -9,6 +9,7 @@
 //   k_seg_boxes   segment AABBs (+ conservative pad) and scene bounds (wave reduce + 6 atomics per wave)
 //   k_morton      63-bit Morton keys of box centroids
 //   radix sort    rocprim::radix_sort_pairs (key, segment)
+//   k_part_*      accel_partition = sah: binned-SAH cuts of the clusters above treelet size -> path code || Morton keys, second sort
 //   k_leaves      32-byte segment records + leaf boxes written in Morton order
 //   k_karras      Karras 2012 topology: one thread per internal node
 //   k_refit_pass  bottom-up AABB + height, one pass per tree level (kernel boundaries are the synchronisation)
@@ -949,6 +950,300 @@ __global__ __launch_bounds__(64) void k_treelet_rebuild(const uint32_t* __restri
     if (nSmall || nMid) runSmall();
 }
 
+// ---------------------------------------------------------------- binned-SAH partition above the treelets (accel_partition = sah)
+// Morton order alone decides which leaves share a treelet, and the treelet pass cannot move a leaf across that boundary (rebuilding the
+// tree ABOVE fixed 512-leaf sets changed nothing, EXPERIMENTS.md 10).  This pass chooses the sets: all leaves start in one cluster, and
+// level by level every cluster of more than `treelet_leaves` leaves is cut by the cheapest of the 3 x 15 planes of a 16-bin surface-area
+// heuristic (the bins, cost expression and tie rule of k_treelet_rebuild; a bin also keeps the bounds of its leaves' centres, so the
+// parent's bins give a child cluster its centre bounds and no pass over the leaves is needed for them).  Nothing is moved: a leaf
+// appends one bit per cut to its PATH CODE, and the sort key becomes  path code || high Morton bits.  Karras' tree over these keys has the cuts at the top -- the first differing path bit of a
+// range is its cluster's plane -- and every final cluster is one key prefix, i.e. one Karras node of <= treelet_leaves leaves under a
+// larger parent: exactly a treelet root.  A cluster no plane separates (every centre in one bin on every axis), a cluster at or below
+// the limit, and whatever is left when the level cap (32 path bits) or the cluster table is full gets no further bits: its leaves stay
+// in Morton order, as in the plain build.  Bin boxes and counts are integer atomics (ordered float bits): the keys do not depend on the
+// order of execution, and neither does anything built from them.
+// Builds of fewer than accel_partition_min_leaves leaves (default 65 536) skip the pass: its levels cost two launches and a host round
+// trip each whatever the size, and what it gains is measured on scenes of 1 M and 6 M leaves (EXPERIMENTS.md 17).
+#define LV_PART_LEVELS 32u                 // path bits = levels of cuts
+#define LV_PART_MAX_CLUSTERS 65536u        // clusters of one level (156 MB of bins per table at 2496 B each)
+#define LV_PART_BIN_WORDS 13u              // {box min.xyz, max.xyz, count, min.xyz and max.xyz of twice the box centres}: floats as ordered bits
+#define LV_PART_WORD_IS_MIN(w) ((w) % LV_PART_BIN_WORDS < 3u || ((w) % LV_PART_BIN_WORDS >= 7u && (w) % LV_PART_BIN_WORDS < 10u))
+#define LV_PART_CLUSTER_WORDS (3u * LV_TREELET_BINS * LV_PART_BIN_WORDS)
+#define LV_PART_FINAL 0x80000000u          // leaf state: cluster | path length << 16 | FINAL
+
+__device__ __forceinline__ uint32_t lv_part_bin(float lo, float hi, float cmn, float scale) {
+    const int bi = int(((lo + hi) - cmn) * scale);
+    return uint32_t(bi < 0 ? 0 : (bi > int(LV_TREELET_BINS) - 1 ? int(LV_TREELET_BINS) - 1 : bi));
+}
+// bins of a cluster on one axis: twice the box centre against the bounds of that over the cluster (as in k_treelet_rebuild)
+__device__ __forceinline__ void lv_part_axis(const float* cen, int ax, float& cmn, float& scale) {
+    cmn = cen[ax];
+    const float ext = cen[3 + ax] - cmn;
+    scale = ext > 0.0f ? float(LV_TREELET_BINS) / ext : 0.0f;
+}
+
+// counters[level] = clusters of that level; words LV_PART_LEVELS + 1 ... + 6: the root cluster's centre bounds as ordered bits
+__global__ void k_part_init(uint32_t* __restrict__ bins, uint32_t* __restrict__ counters) {
+    const uint32_t t = threadIdx.x;
+    for (uint32_t w = t; w < LV_PART_CLUSTER_WORDS; w += blockDim.x) bins[w] = LV_PART_WORD_IS_MIN(w) ? 0xFFFFFFFFu : 0u;
+    if (t < LV_PART_LEVELS + 1u) counters[t] = t == 0u ? 1u : 0u;
+    if (t < 6u) counters[LV_PART_LEVELS + 1u + t] = t < 3u ? 0xFFFFFFFFu : 0u;
+}
+__global__ __launch_bounds__(LV_BLOCK) void k_part_root_centres(const float* __restrict__ boxOrig, uint32_t n, uint32_t* __restrict__ cenOrd) {
+    float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    for (uint32_t s = blockIdx.x * LV_BLOCK + threadIdx.x; s < n; s += gridDim.x * LV_BLOCK)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float c = boxOrig[6 * size_t(s) + k] + boxOrig[6 * size_t(s) + 3 + k];
+            mn[k] = fminf(mn[k], c);
+            mx[k] = fmaxf(mx[k], c);
+        }
+    lv_block_bounds(mn, mx, cenOrd);
+}
+__global__ void k_part_root(const uint32_t* __restrict__ cenOrd, float* __restrict__ clusterCen) {
+    if (threadIdx.x < 6u) clusterCen[threadIdx.x] = lv_ord2f(cenOrd[threadIdx.x]);
+}
+
+// One pass over the leaves per level: take the side of the cut the level before chose for the leaf's cluster (BIN = false: only that,
+// after the last level), then add the leaf to the bins of the cluster it is in now.  A global atomic per leaf and bin word is what the
+// pass would cost (13 x 3 per leaf), so the sums are merged twice on the way.  The pass walks the leaves in MORTON order (`order` = the values of a first sort by the plain Morton keys):
+// neighbours in that order are neighbours in space at every scale, so the leaves of a wave mostly share cluster and bin -- the lanes of
+// one (cluster, axis, bin) merge in the wave -- and a workgroup keeps the bins of its LV_PART_ITEMS x 256 consecutive leaves in a hashed
+// LDS table that it adds to the global bins once, at its end (a key that finds no slot goes to the global bins directly).  In input
+// order 64 consecutive segments of a line span a tenth of the scene and share nothing below the first levels: 14.3 instead of 8.9 ms
+// for the whole build of 1 M segments (the plain Morton build: 2.3).
+// state and path are indexed by the position in Morton order.
+#define LV_PART_ITEMS 8u
+#define LV_PART_SLOTS 512u
+#define LV_PART_PROBES 4u
+__device__ __forceinline__ void lv_part_add(uint32_t* w, const float mn[3], const float mx[3], const float cmn[3], const float cmx[3], uint32_t count) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        atomicMin(&w[k], lv_f2ord(mn[k]));
+        atomicMax(&w[3 + k], lv_f2ord(mx[k]));
+        atomicMin(&w[7 + k], lv_f2ord(cmn[k]));
+        atomicMax(&w[10 + k], lv_f2ord(cmx[k]));
+    }
+    atomicAdd(&w[6], count);
+}
+template <bool BIN>
+__global__ __launch_bounds__(LV_BLOCK) void k_part_level(const float* __restrict__ boxOrig, const uint32_t* __restrict__ order, uint32_t n, uint32_t first, uint32_t maxClusters,
+                                                         uint32_t* __restrict__ state, uint32_t* __restrict__ path,
+                                                         const uint32_t* __restrict__ splitPrev, const float* __restrict__ boxPrev,
+                                                         const float* __restrict__ boxCur, uint32_t* __restrict__ bins) {
+    __shared__ uint32_t s_tag[BIN ? LV_PART_SLOTS : 1u];                        // key = (cluster * 3 + axis) * 16 + bin, LV_INVALID = free
+    __shared__ uint32_t s_val[BIN ? LV_PART_SLOTS : 1u][LV_PART_BIN_WORDS];
+    if (BIN) {
+        for (uint32_t j = threadIdx.x; j < LV_PART_SLOTS; j += LV_BLOCK) {
+            s_tag[j] = LV_INVALID;
+#pragma unroll
+            for (uint32_t w = 0; w < LV_PART_BIN_WORDS; w++) s_val[j][w] = LV_PART_WORD_IS_MIN(w) ? 0xFFFFFFFFu : 0u;
+        }
+        __syncthreads();
+    }
+#pragma unroll 1
+    for (uint32_t it = 0; it < LV_PART_ITEMS; it++) {
+        const uint32_t s = (blockIdx.x * LV_PART_ITEMS + it) * LV_BLOCK + threadIdx.x;
+        bool active = s < n;
+        uint32_t st = 0u;
+        float b[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (active) {
+            st = first ? 0u : state[s];
+            active = !(st & LV_PART_FINAL);
+        }
+        if (active) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) b[k] = boxOrig[6 * size_t(order[s]) + k];
+            if (!first) {
+                const uint32_t c = st & 0xFFFFu, len = (st >> 16) & 0xFFu;
+                const uint32_t sp = splitPrev[3u * c];
+                if (sp == LV_INVALID) {
+                    st |= LV_PART_FINAL;             // no plane separates the cluster's centres
+                } else {
+                    const int ax = int(sp & 3u);
+                    float cmn, scale;
+                    lv_part_axis(boxPrev + 6 * size_t(c), ax, cmn, scale);
+                    const uint32_t side = lv_part_bin(b[ax], b[3 + ax], cmn, scale) >= (sp >> 2) ? 1u : 0u;
+                    const uint32_t child = splitPrev[3u * c + 1u + side];
+                    path[s] = (len ? path[s] << 1 : 0u) | side;
+                    st = (child < maxClusters ? child : LV_PART_FINAL) | ((len + 1u) << 16);
+                }
+                state[s] = st;
+                active = !(st & LV_PART_FINAL);
+            } else {
+                state[s] = 0u;
+                path[s] = 0u;
+            }
+        }
+        if (!BIN) continue;
+        const uint32_t c = st & 0xFFFFu;
+        uint32_t key[3] = {LV_INVALID, LV_INVALID, LV_INVALID};
+        if (active) {
+#pragma unroll
+            for (int ax = 0; ax < 3; ax++) {
+                float cmn, scale;
+                lv_part_axis(boxCur + 6 * size_t(c), ax, cmn, scale);
+                key[ax] = (c * 3u + uint32_t(ax)) * LV_TREELET_BINS + lv_part_bin(b[ax], b[3 + ax], cmn, scale);
+            }
+        }
+        // adds the union of the lanes `mine` to the bin `lk` (LDS table, or the global bins when the table has no slot for it)
+        auto merge = [&](bool mine, uint32_t lk, int leader, int numKeys, const uint32_t* lks) {
+            const unsigned long long m = __ballot(mine);
+            float mn[3], mx[3], cmn[3], cmx[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                mn[k] = lv_wave_min(mine ? b[k] : 3.0e38f);
+                mx[k] = lv_wave_max(mine ? b[3 + k] : -3.0e38f);
+                cmn[k] = lv_wave_min(mine ? b[k] + b[3 + k] : 3.0e38f);
+                cmx[k] = lv_wave_max(mine ? b[k] + b[3 + k] : -3.0e38f);
+            }
+            if (int(lv_lane()) == leader) {
+                for (int q = 0; q < numKeys; q++) {
+                    const uint32_t kq = numKeys == 1 ? lk : lks[q];
+                    uint32_t slot = (kq * 2654435761u) >> 23;   // 9 bits = LV_PART_SLOTS
+                    uint32_t* w = nullptr;
+                    for (uint32_t p = 0; p < LV_PART_PROBES && !w; p++, slot = (slot + 1u) & (LV_PART_SLOTS - 1u)) {
+                        const uint32_t prev = atomicCAS(&s_tag[slot], LV_INVALID, kq);
+                        if (prev == LV_INVALID || prev == kq) w = s_val[slot];
+                    }
+                    if (!w) w = bins + size_t(kq) * LV_PART_BIN_WORDS;
+                    lv_part_add(w, mn, mx, cmn, cmx, uint32_t(__popcll(m)));
+                }
+            }
+            return m;
+        };
+        const unsigned long long act = __ballot(active);
+        if (act == 0ull) continue;
+        const int first0 = __ffsll((long long)act) - 1;
+        const uint32_t lks[3] = {uint32_t(__shfl(int(key[0]), first0, 64)), uint32_t(__shfl(int(key[1]), first0, 64)),
+                                 uint32_t(__shfl(int(key[2]), first0, 64))};
+        if (__ballot(active && (key[0] != lks[0] || key[1] != lks[1] || key[2] != lks[2])) == 0ull) {
+            merge(active, 0u, first0, 3, lks);   // the usual case in Morton order: one cluster, one bin per axis for the whole wave
+            continue;
+        }
+#pragma unroll 1
+        for (int ax = 0; ax < 3; ax++) {
+            const uint32_t kx = ax == 0 ? key[0] : (ax == 1 ? key[1] : key[2]);
+            unsigned long long todo = act;
+            while (todo) {
+                const int leader = __ffsll((long long)todo) - 1;
+                const uint32_t lk = uint32_t(__shfl(int(kx), leader, 64));
+                todo &= ~merge(active && kx == lk, lk, leader, 1, lks);
+            }
+        }
+    }
+    if (!BIN) return;
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < LV_PART_SLOTS; j += LV_BLOCK) {
+        const uint32_t lk = s_tag[j];
+        if (lk == LV_INVALID) continue;
+        uint32_t* w = bins + size_t(lk) * LV_PART_BIN_WORDS;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            atomicMin(&w[k], s_val[j][k]);
+            atomicMax(&w[3 + k], s_val[j][3 + k]);
+            atomicMin(&w[7 + k], s_val[j][7 + k]);
+            atomicMax(&w[10 + k], s_val[j][10 + k]);
+        }
+        atomicAdd(&w[6], s_val[j][6]);
+    }
+}
+
+// One wave per cluster: lane (axis, plane) sums the bins on either side of its plane; the cheapest plane with leaves on both sides wins
+// (lowest cost, then lowest axis, lowest plane: k_treelet_rebuild's rule).  A side of more than maxLeaves leaves becomes a cluster of
+// the next level (centre bounds = the union of its bins', bins cleared here); counters[level + 1] counts them, also past the table's end.
+__global__ __launch_bounds__(64) void k_part_pick(uint32_t level, uint32_t maxLeaves, uint32_t maxClusters, const uint32_t* __restrict__ bins,
+                                                  uint32_t* __restrict__ split, float* __restrict__ boxNext, uint32_t* __restrict__ binsNext,
+                                                  uint32_t* __restrict__ counters) {
+    __shared__ uint32_t s_bin[3u * LV_TREELET_BINS][LV_PART_BIN_WORDS];
+    __shared__ uint32_t s_child[2];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t count = min(counters[level], maxClusters);
+    for (uint32_t c = blockIdx.x; c < count; c += gridDim.x) {
+        __syncthreads();
+        if (lane < 3u * LV_TREELET_BINS)
+            for (uint32_t k = 0; k < LV_PART_BIN_WORDS; k++) s_bin[lane][k] = bins[(size_t(c) * 3u * LV_TREELET_BINS + lane) * LV_PART_BIN_WORDS + k];
+        if (lane < 2u) s_child[lane] = LV_INVALID;
+        __syncthreads();
+        float mn[2][3], mx[2][3], cmn[2][3], cmx[2][3];
+        uint32_t cn[2] = {0u, 0u};
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) { mn[h][k] = cmn[h][k] = 3.0e38f; mx[h][k] = cmx[h][k] = -3.0e38f; }
+        unsigned long long key = ~0ull;
+        const uint32_t ax = lane / (LV_TREELET_BINS - 1u), plane = lane % (LV_TREELET_BINS - 1u) + 1u;
+        if (lane < 3u * (LV_TREELET_BINS - 1u)) {
+            for (uint32_t bn = 0; bn < LV_TREELET_BINS; bn++) {
+                const uint32_t* w = s_bin[ax * LV_TREELET_BINS + bn];
+                if (w[6] == 0u) continue;
+                const int h = bn < plane ? 0 : 1;
+                cn[h] += w[6];
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    mn[h][k] = fminf(mn[h][k], lv_ord2f(w[k]));
+                    mx[h][k] = fmaxf(mx[h][k], lv_ord2f(w[3 + k]));
+                    cmn[h][k] = fminf(cmn[h][k], lv_ord2f(w[7 + k]));
+                    cmx[h][k] = fmaxf(cmx[h][k], lv_ord2f(w[10 + k]));
+                }
+            }
+            if (cn[0] != 0u && cn[1] != 0u) {
+                float area[2];
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const float dx = mx[h][0] - mn[h][0], dy = mx[h][1] - mn[h][1], dz = mx[h][2] - mn[h][2];
+                    area[h] = dx * dy + dy * dz + dz * dx;
+                }
+                const float cost = area[0] * float(cn[0]) + area[1] * float(cn[1]);
+                if (cost >= 0.0f && cost < 3.0e38f) key = ((unsigned long long)__float_as_uint(cost) << 32) | lane;
+            }
+        }
+        unsigned long long best = key;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ok = (unsigned long long)__shfl_xor((long long)best, o, 64);
+            best = ok < best ? ok : best;
+        }
+        if (best == ~0ull) {
+            if (lane == 0u) split[3u * c] = LV_INVALID;
+            continue;
+        }
+        if (key == best) {   // the winning lane (keys are distinct: they carry the lane)
+            split[3u * c] = ax | (plane << 2);
+            for (int h = 0; h < 2; h++) {
+                uint32_t id = LV_INVALID;
+                if (cn[h] > maxLeaves) {
+                    id = atomicAdd(&counters[level + 1u], 1u);
+                    if (id < maxClusters) {
+#pragma unroll
+                        for (int k = 0; k < 3; k++) { boxNext[6 * size_t(id) + k] = cmn[h][k]; boxNext[6 * size_t(id) + 3 + k] = cmx[h][k]; }
+                    } else {
+                        id = LV_INVALID;
+                    }
+                }
+                split[3u * c + 1u + h] = id;
+                s_child[h] = id;
+            }
+        }
+        __syncthreads();
+        for (int h = 0; h < 2; h++) {
+            const uint32_t id = s_child[h];
+            if (id == LV_INVALID) continue;
+            for (uint32_t w = lane; w < LV_PART_CLUSTER_WORDS; w += 64u)
+                binsNext[size_t(id) * LV_PART_CLUSTER_WORDS + w] = LV_PART_WORD_IS_MIN(w) ? 0xFFFFFFFFu : 0u;
+        }
+    }
+}
+
+// sort key = path code || as many of the high Morton bits as still fit in the 63
+__global__ __launch_bounds__(LV_BLOCK) void k_part_keys(uint32_t n, const uint32_t* __restrict__ state, const uint32_t* __restrict__ path,
+                                                        uint64_t* __restrict__ keys) {
+    const uint32_t s = blockIdx.x * LV_BLOCK + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t len = (state[s] >> 16) & 0xFFu;
+    if (len) keys[s] = (uint64_t(path[s]) << (63u - len)) | (keys[s] >> len);
+}
+
 // Bottom-up boxes + heights in PASSES: in pass k every internal node whose two children were finished in an EARLIER pass
 // (leaves always are) computes its box and height and stamps itself with k.  The kernel boundary between passes is the only
 // synchronisation -- per-CU L1s and per-XCD L2s are not coherent, and the classic "second thread to arrive continues"
@@ -1289,6 +1584,46 @@ static int lv_bvh_build_core(lv_ctx* ctx, uint32_t n, LvDeviceBuffer& nodesOut, 
         size_t tmpBytes = sortBytes;
         LV_HIPF(rocprim::radix_sort_pairs(sortTmp.ptr, tmpBytes, (uint64_t*)keysA.ptr, (uint64_t*)keysB.ptr,
                                           (uint32_t*)valsA.ptr, (uint32_t*)valsB.ptr, n, 0, 63, st));
+    }
+    if (ctx->opt.accelFastTrace && ctx->opt.accelPartitionSah && n > ctx->opt.treeletLeaves && n >= ctx->opt.accelPartitionMinLeaves) {
+        // binned-SAH partition into clusters of <= treelet_leaves leaves: path code bits in front of the Morton keys (k_part_*)
+        const uint32_t maxLeaves = ctx->opt.treeletLeaves;
+        const uint32_t cap = std::min<uint32_t>(n / (maxLeaves + 1u) + 1u, LV_PART_MAX_CLUSTERS); // a cluster that is cut holds > maxLeaves leaves
+        auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const size_t oPath = al(size_t(n) * 4), oCount = oPath + al(size_t(n) * 4), oSplit = oCount + 256,
+                     oBox = oSplit + al(size_t(cap) * 12), oBins = oBox + 2 * al(size_t(cap) * 24),
+                     binBytes = al(size_t(cap) * LV_PART_CLUSTER_WORDS * 4);
+        LV_TRY(lv_buf_reserve(ctx, ctx->partitionScratch, oBins + 2 * binBytes));
+        char* base = (char*)ctx->partitionScratch.ptr;
+        uint32_t *state = (uint32_t*)base, *path = (uint32_t*)(base + oPath), *counters = (uint32_t*)(base + oCount),
+                 *split = (uint32_t*)(base + oSplit);
+        float* cbox[2] = {(float*)(base + oBox), (float*)(base + oBox + al(size_t(cap) * 24))};
+        uint32_t* bins[2] = {(uint32_t*)(base + oBins), (uint32_t*)(base + oBins + binBytes)};
+        k_part_init<<<1, LV_BLOCK, 0, st>>>(bins[0], counters);
+        k_part_root_centres<<<std::min(nblocks(n), 2048u), LV_BLOCK, 0, st>>>((const float*)boxOrig.ptr, n, counters + LV_PART_LEVELS + 1u);
+        k_part_root<<<1, 64, 0, st>>>(counters + LV_PART_LEVELS + 1u, cbox[0]);
+        const uint32_t partBlocks = uint32_t((uint64_t(n) + LV_PART_ITEMS * LV_BLOCK - 1) / (LV_PART_ITEMS * LV_BLOCK));
+        uint32_t level = 0, count = 1;
+        while (true) {   // ends at the level cap whatever the bins hold: what is not cut by then stays in Morton order
+            const uint32_t cur = level & 1u;
+            k_part_level<true><<<partBlocks, LV_BLOCK, 0, st>>>((const float*)boxOrig.ptr, (const uint32_t*)valsB.ptr, n, level == 0u ? 1u : 0u, cap, state, path, split,
+                                                                cbox[cur ^ 1u], cbox[cur], bins[cur]);
+            k_part_pick<<<std::min(count, 4096u), 64, 0, st>>>(level, maxLeaves, cap, bins[cur], split, cbox[cur ^ 1u], bins[cur ^ 1u], counters);
+            LV_HIPF(hipMemcpyAsync((void*)ctx->pinned, counters + level + 1u, 4, hipMemcpyDeviceToHost, st));
+            LV_HIPF(hipStreamSynchronize(st));
+            count = pin[0];
+            level++;
+            if (count == 0u || count > cap || level == LV_PART_LEVELS) break;
+        }
+        k_part_level<false><<<partBlocks, LV_BLOCK, 0, st>>>((const float*)boxOrig.ptr, (const uint32_t*)valsB.ptr, n, 0u, cap, state, path, split,
+                                                             cbox[(level & 1u) ^ 1u], cbox[level & 1u], bins[level & 1u]);
+        k_part_keys<<<nblocks(n), LV_BLOCK, 0, st>>>(n, state, path, (uint64_t*)keysB.ptr);
+        // second sort, by path code || Morton bits; stable, so equal keys stay in Morton order
+        size_t tmpBytes = sortBytes;
+        LV_HIPF(rocprim::radix_sort_pairs(sortTmp.ptr, tmpBytes, (uint64_t*)keysB.ptr, (uint64_t*)keysA.ptr,
+                                          (uint32_t*)valsB.ptr, (uint32_t*)valsA.ptr, n, 0, 63, st));
+        std::swap(keysA.ptr, keysB.ptr);
+        std::swap(valsA.ptr, valsB.ptr);
     }
     leaves((const uint32_t*)valsB.ptr, (const float*)boxOrig.ptr, (float*)leafBox.ptr);
     if (n == 1) {

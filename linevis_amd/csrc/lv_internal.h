@@ -51,6 +51,9 @@ struct LvOptions {
     bool collapseTop = true;                  // accel_collapse_top: the levels of the wide tree with <= 1024 nodes in one launch (k_collapse_top)
     bool treeletPlaneScan = true;             // treelet_plane_eval = scan (DPP prefix / suffix scans over the bins) | loop (round-3 form)
     bool accelFastTrace = true;               // accel_build = fast_trace (LBVH + SAH treelets, the reference's PREFER_FAST_TRACE) | fast_build (LBVH)
+    bool accelPartitionSah = true;            // accel_partition = sah (fast_trace only: a binned-SAH partition chooses the leaf sets of the treelets, k_part_* in lv_bvh.hip) | morton (Morton order does)
+    uint32_t accelPartitionMinLeaves = 65536; // accel_partition_min_leaves: builds of fewer leaves keep the Morton order under accel_partition = sah too (the partition's
+                                              // levels cost two launches and a host round trip each whatever the size; its gain is measured on 1 M and 6 M leaves)
     bool fastShading = false;                 // shading_numerics = fast: approximate hardware rsq / rcp / log2 / exp2 in colour-only arithmetic (lv_device.h)
     int overlapPrimaryPasses = 2;             // overlap_primary_passes: 0 = false, 1 = true, 2 = auto -- the colour pass' hit traces in one launch with the RTAO primaries (k_primary_pair)
     bool dispatchByCost = true;               // dispatch_order = cost | as_numbered (tile kernels: heaviest 64x64 group of the last frame first)
@@ -250,6 +253,7 @@ struct lv_ctx {
     LvDeviceBuffer selftestIn, selftestOut;   // lv_selftest_eval: argument and result words
     LvDeviceBuffer accum;                     // rgba8 of the previous accumulated frame (full viewport)
     uint32_t* pinned = nullptr;               // 64 B of pinned host memory for small read-backs (hipHostMalloc)
+    LvDeviceBuffer partitionScratch;          // accel_partition = sah: leaf states, path codes, cluster tables and bins of the build, kept between builds like buildArena
     LvDeviceBuffer buildArena;                // temporaries of the LBVH builds, kept between builds
     // dispatch order of the 64x64-pixel groups of the tile kernels (lv_group_order_prepare): [0] colour pass, [1] RTAO pass geometry
     struct GroupOrder {

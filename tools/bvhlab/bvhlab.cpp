@@ -219,8 +219,84 @@ static uint32_t countLeaves(const BTree& T, int32_t c, std::vector<uint32_t>& cn
     if (c < 0) return 1;
     return cnt[c] = countLeaves(T, T.nodes[c].l, cnt) + countLeaves(T, T.nodes[c].r, cnt);
 }
-static BTree buildHybrid(uint32_t K) {
-    BTree L = buildLbvh();
+static BTree buildHybridOver(const BTree& L, uint32_t K);
+static BTree buildHybrid(uint32_t K) { return buildHybridOver(buildLbvh(), K); }
+
+// keysah: the GPU build's accel_partition = sah, statement for statement (lv_bvh.hip, k_part_*).  All leaves start in one cluster; level
+// by level every cluster of more than K leaves is cut by the cheapest of the 3 x 15 planes of 16 bins over the bounds of its box centres (cost =
+// area * count per side, lowest axis and plane on ties, planes with an empty side skipped); a leaf appends one bit per cut to its path
+// code, at most 32.  Sort key = path code || high Morton bits, highest-differing-bit splits over the keys, SAH treelets of <= K below.
+static BTree buildKeySah(uint32_t K) {
+    const uint32_t n = numPrims();
+    Box sb; sb.reset();
+    for (auto& b : g_boxes) sb.grow(b);
+    std::vector<uint64_t> keys(n);
+    std::vector<uint32_t> order(n), path(n, 0), len(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        uint64_t q[3];
+        for (int k = 0; k < 3; k++) {
+            float c = 0.5f * (g_boxes[i].mn[k] + g_boxes[i].mx[k]);
+            float u = (c - sb.mn[k]) / std::max(sb.mx[k] - sb.mn[k], 1e-30f);
+            u = std::min(std::max(u, 0.0f), 1.0f);
+            q[k] = uint64_t(std::min(2097151.0f, u * 2097152.0f));
+        }
+        keys[i] = (expand21(q[0]) << 2) | (expand21(q[1]) << 1) | expand21(q[2]);
+        order[i] = i;
+    }
+    // (the GPU pass walks the leaves in Morton order and sorts a second time, stably: equal keys stay in Morton order)
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    struct Cluster { std::vector<uint32_t> ids; };
+    std::vector<Cluster> cur(1), next;
+    cur[0].ids = order;
+    uint32_t levels = 0, finals = 0, stuck = 0;
+    for (; levels < 32 && !cur.empty(); levels++) {
+        next.clear();
+        for (auto& C : cur) {
+            const int NB = 16;
+            auto binOf = [&](uint32_t i, int a, float cmn, float scale) {
+                int k = int(((g_boxes[i].mn[a] + g_boxes[i].mx[a]) - cmn) * scale); return std::min(std::max(k, 0), NB - 1); };
+            float cmn[3], scale[3];
+            Box cb; cb.reset();   // bounds of twice the box centres (the GPU build unites them from the parent's bins: the same numbers)
+            for (uint32_t i : C.ids) for (int a = 0; a < 3; a++) { const float c = g_boxes[i].mn[a] + g_boxes[i].mx[a]; cb.mn[a] = std::min(cb.mn[a], c); cb.mx[a] = std::max(cb.mx[a], c); }
+            for (int a = 0; a < 3; a++) { cmn[a] = cb.mn[a]; const float ext = cb.mx[a] - cmn[a]; scale[a] = ext > 0.0f ? float(NB) / ext : 0.0f; }
+            float bestCost = 3e38f; int bestAxis = -1, bestPlane = 0;
+            for (int a = 0; a < 3; a++) {
+                Box bb[16]; uint32_t cnt[16];
+                for (int k = 0; k < NB; k++) { bb[k].reset(); cnt[k] = 0; }
+                for (uint32_t i : C.ids) { const int k = binOf(i, a, cmn[a], scale[a]); bb[k].grow(g_boxes[i]); cnt[k]++; }
+                for (int pl = 1; pl < NB; pl++) {
+                    Box side[2]; uint32_t cn[2] = {0, 0}; side[0].reset(); side[1].reset();
+                    for (int k = 0; k < NB; k++) if (cnt[k]) { side[k < pl ? 0 : 1].grow(bb[k]); cn[k < pl ? 0 : 1] += cnt[k]; }
+                    if (!cn[0] || !cn[1]) continue;
+                    const float cost = side[0].halfArea() * float(cn[0]) + side[1].halfArea() * float(cn[1]);
+                    if (cost < bestCost) { bestCost = cost; bestAxis = a; bestPlane = pl; }
+                }
+            }
+            if (bestAxis < 0) { stuck++; continue; }
+            Cluster ch[2];
+            for (uint32_t i : C.ids) {
+                const uint32_t side = binOf(i, bestAxis, cmn[bestAxis], scale[bestAxis]) >= bestPlane ? 1u : 0u;
+                path[i] = (path[i] << 1) | side; len[i]++;
+                ch[side].ids.push_back(i);
+            }
+            for (int h = 0; h < 2; h++) { if (ch[h].ids.size() > K) next.push_back(std::move(ch[h])); else finals++; }
+        }
+        cur.swap(next);
+    }
+    uint32_t maxLen = 0; for (uint32_t i = 0; i < n; i++) maxLen = std::max(maxLen, len[i]);
+    printf("  keysah: %u levels of cuts, %u final clusters, %u clusters no plane separates, %zu clusters left at the level cap, longest path code %u bits\n",
+           levels, finals, stuck, cur.size(), maxLen);
+    for (uint32_t i = 0; i < n; i++) if (len[i]) keys[i] = (uint64_t(path[i]) << (63u - len[i])) | (keys[i] >> len[i]);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    std::vector<uint64_t> sk(n);
+    for (uint32_t i = 0; i < n; i++) sk[i] = keys[order[i]];
+    BTree L;
+    L.nodes.reserve(n);
+    L.root = lbvhRange(L, sk, order, 0, n);
+    return buildHybridOver(L, K);
+}
+
+static BTree buildHybridOver(const BTree& L, uint32_t K) {
     std::vector<uint32_t> cnt(L.nodes.size(), 0);
     countLeaves(L, L.root, cnt);
     BTree T; T.nodes.reserve(L.nodes.size());
@@ -547,6 +623,7 @@ int main(int argc, char** argv) {
         if (name == "lbvh") T = buildLbvh();
         else if (name == "sah") T = buildSah(1u << 14);
         else if (name == "sahbin") T = buildSah(0);
+        else if (name.rfind("keysah", 0) == 0) T = buildKeySah(name.size() > 6 ? uint32_t(atoi(name.c_str() + 6)) : 512u);
         else if (name.rfind("hyb", 0) == 0) T = buildHybrid(uint32_t(atoi(name.c_str() + 3)));
         else { fprintf(stderr, "unknown builder %s\n", name.c_str()); continue; }
         const double tb = now() - t0;
