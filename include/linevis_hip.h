@@ -42,6 +42,9 @@ extern "C" {
 /* Moment-based order-independent transparency (src/Renderers/OIT/MBOITRenderer.cpp) with power moments stored as float32, over the
  * fragments of mode 2's rasterised prism; see mboit_num_moments and lv_mboit_resolve_buffers below */
 #define LV_RENDERING_MODE_MBOIT 6
+/* Atomic Loop 64 (src/Renderers/OIT/AtomicLoop64Renderer.cpp): the K nearest fragments of mode 2's rasterised prism per pixel,
+ * exactly, in K * 8 bytes per pixel; see atomic_loop_num_layers, lv_atomic_loop_get_buffers and lv_atomic_loop_resolve_buffers below */
+#define LV_RENDERING_MODE_ATOMIC_LOOP_64 10
 #define LV_RENDERING_MODE_VULKAN_RAY_TRACER 11
 
 /* struct LinePointDataUnified, src/LineData/LineRenderData.hpp:99-106 -- byte-identical (48 B). */
@@ -279,6 +282,32 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   needed) and a frame whose pool cannot be allocated, or with a pixel covered by more than 65534 fragments, returns
  *   LV_E_CAPACITY.  ppll_fragment_source = capsule_entry is LV_E_INVALID in mode 3; ppll_max_num_frags and sorting_mode are
  *   ignored; the fold is timed as LV_KERNEL_PPLL_RESOLVE / ms_ppll_resolve.
+ *   atomic_loop_num_layers: numLayers K of rendering mode 10, 1 ... 64 (default 8)  (AtomicLoop64Renderer.hpp:112); out of range is
+ *   LV_E_INVALID and the old value stays.  Mode 10 keeps, per pixel, the K nearest of the fragments mode 2 keeps (the `kept` rules,
+ *   then alpha >= 0.001, AtomicLoop64Gather.glsl:56; RTAO, depth cues, band data and rotating helicity bands as in mode 2) and no
+ *   fragment pool.  A fragment is the 64-bit key (window depth bits << 32) | packUnorm4x8(straight colour), compared unsigned -- the
+ *   window depth is mode 3's --; a pixel owns K slots, cleared to 0xFFFFFFFFFFFFFFFF.  Insert (AtomicLoop64Gather.glsl:70-79): for
+ *   i = 0 ... K - 1: old = atomicMin(slot[i], v); stop if old is the clear value; if old > v then v = old.  Every exchange keeps the
+ *   multiset, so the slots end as the K smallest keys in ascending order whatever order the fragments arrive in, and a value still
+ *   carried after slot K - 1 is a TAIL fragment.  Rule this build owns: the reference blends a carried colour into
+ *   the framebuffer in the order of the racing invocations, which is not defined from run to run; here the tail is order
+ *   independent -- five 64-bit integer sums per pixel over the 8-bit channels of the carried keys, SA = sum a8, SR / SG / SB = sum
+ *   a8 * r8 / g8 / b8, SL = sum term(a8) with term(0) = 0, term(255) = fixed(1024) and term(a8) = fixed(-log(1 - a8 / 255))
+ *   otherwise (the 2^36 fixed point and the log of mode 6).  Tail alpha At = 1 - exp(-unfixed(SL)), tail colour (SR / SA) / 255 per
+ *   channel, SA = 0: no tail.  Resolve (AtomicLoop64Resolve.glsl:69-87, float32, one operation at a time): colour = 0, T = 1; per
+ *   non-empty slot colour.rgb += (T * a) * rgb, T *= 1 - a; alphaOut = 1 - T; the framebuffer under the layers is the clear colour,
+ *   or the tail blended over it (rgb = Ct * At + clear.rgb * (1 - At), a = At + clear.a * (1 - At)); alphaOut > 0: out.rgb = (colour
+ *   / alphaOut) * alphaOut + fb.rgb * (1 - alphaOut), out.a = alphaOut + fb.a * (1 - alphaOut), else out = fb.  A pixel with at most
+ *   K fragments is the reference's arithmetic bit for bit; frames, tile lists and shards are bit-reproducible.  Memory: (K + 5) * 8
+ *   bytes per pixel of the viewport padded to ppll_tile_width x ppll_tile_height plus the two 4-byte per-pixel words of mode 2;
+ *   nothing grows with the number of fragments.  One rasteriser launch per frame, no host synchronisation.  The pool options
+ *   (ppll_expected_avg_depth_complexity, ppll_max_num_frags, sorting_mode) have no effect; ppll_prism_rasteriser = lbvh,
+ *   ppll_fragment_source = capsule_entry and band data with rotating helicity bands return LV_E_INVALID at render time (the
+ *   context stays usable).  Statistics: fragments = the fragments past the discard, ppll_pool_nodes = 0.  Timers:
+ *   LV_KERNEL_PPLL_RASTER times the pass (with the tile marking and segment culling of a sharded frame), LV_KERNEL_PPLL_RESOLVE
+ *   the resolve.  Limit: the sums are exact for up to 131071 kept fragments on a pixel; a pixel with more sets the flag of
+ *   mboit_fragment_storage = streamed below, with the same contract (LV_E_CAPACITY from lv_render; the flag stays with the frame
+ *   for the asynchronous entry points; a later successful frame clears it).
  *   mboit_num_moments: 4 | 6 | 8 power moments of rendering mode 6 (default 4)   (MBOITRenderer.cpp:41-45).  Mode 6 sweeps, per
  *   pixel, ALL fragments the fragment stage of mode 2 produces (the alpha < 0.001 discard of modes 2 and 3 is not MBOIT's; its own
  *   rules are transmittance > 0.9999999 per fragment in the moment pass and b_0 < 0.00100050033 per pixel) twice: power moments of
@@ -656,6 +685,21 @@ int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_
  * that does not cover the viewport, a multi-device handle); LV_E_INVALID for a null pointer or capacity_floats below that size;
  * LV_E_CAPACITY when a pixel of that frame holds more than 131071 kept fragments.  Synchronises the context's stream. */
 int lv_mboit_get_moments(lv_ctx* ctx, float* out, uint64_t capacity_floats);
+/* K of the last frame when that was a mode-10 frame, else LV_E_STATE: the layer count lv_atomic_loop_get_buffers writes per pixel.  It
+ * is the frame's, not the option's current value -- size out_slots by it when the option may have changed since the frame. */
+int lv_atomic_loop_get_num_layers(lv_ctx* ctx, uint32_t* out_num_layers);
+/* The slots and tail sums of the last frame when that was a mode-10 frame over the whole viewport, row-major: out_slots = width *
+ * height * K keys (K = that frame's atomic_loop_num_layers, see lv_atomic_loop_get_num_layers; ascending, then 0xFFFFFFFFFFFFFFFF), out_tail = width * height * 5 sums
+ * {SA, SR, SG, SB, SL}.  LV_E_STATE when the last frame was anything else (another mode, a tile list that does not cover the
+ * viewport, a multi-device handle); LV_E_INVALID for a null pointer or capacity_pixels below width * height; LV_E_CAPACITY when a
+ * pixel of that frame holds more than 131071 kept fragments.  Synchronises the context's stream. */
+int lv_atomic_loop_get_buffers(lv_ctx* ctx, uint64_t* out_slots, uint64_t* out_tail, uint64_t capacity_pixels);
+/* Test entry point of mode 10's insert and resolve: pixel p = y * w + x of the w x h rectangle owns keys [offsets[p], offsets[p + 1])
+ * (offsets: w * h + 1 values from 0 to num_keys), at most 131071 per pixel, none 0xFFFFFFFFFFFFFFFF; equal keys are allowed.  The
+ * keys are inserted on the device, one lane per key with all lanes racing, then resolved over the background.  K =
+ * atomic_loop_num_layers.  out_slots (w * h * K) and out_tail (w * h * 5) may be NULL. */
+int lv_atomic_loop_resolve_buffers(lv_ctx* ctx, const uint64_t* keys, uint64_t num_keys, const uint64_t* offsets, uint32_t w,
+                                   uint32_t h, uint8_t* out_rgba8, uint64_t* out_slots, uint64_t* out_tail);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

@@ -17,6 +17,7 @@ LV_OK = 0
 MODE_PPLL = 2          # RENDERING_MODE_PER_PIXEL_LINKED_LIST, src/Renderers/RenderingModes.hpp:32-53
 MODE_MLAB = 3          # RENDERING_MODE_MLAB (Multi-Layer Alpha Blending over mode 2's fragments)
 MODE_MBOIT = 6         # RENDERING_MODE_MBOIT (moment-based OIT, power moments as float32, over mode 2's fragments)
+MODE_ATOMIC_LOOP_64 = 10   # RENDERING_MODE_ATOMIC_LOOP_64 (the K nearest fragments of mode 2 in 64-bit atomicMin slots)
 MODE_RAY_TRACER = 11   # RENDERING_MODE_VULKAN_RAY_TRACER
 
 LINE_POINT_DTYPE = np.dtype([("linePosition", "<f4", 3), ("lineAttribute", "<f4"),
@@ -104,7 +105,7 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_svgf_denoise_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -184,6 +185,9 @@ def load():
         ("lv_mlab_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp]),
         ("lv_mboit_resolve_buffers", [vp, vp, u64, vp, u32, u32, C.c_float, C.c_float, vp, vp]),
         ("lv_mboit_get_moments", [vp, vp, u64]),
+        ("lv_atomic_loop_get_num_layers", [vp, C.POINTER(u32)]),
+        ("lv_atomic_loop_get_buffers", [vp, vp, vp, u64]),
+        ("lv_atomic_loop_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp, vp]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -375,6 +379,8 @@ class Context:
         self._ck(self.L.lv_set_option(self.h, key.encode(), _fmt(value).encode()))
         if key == "mboit_num_moments":
             self._mboit_num_moments = int(value)
+        if key == "atomic_loop_num_layers":
+            self._atomic_loop_num_layers = int(value)
 
     def set_options(self, settings):
         """LineRenderer::setNewSettings(const SettingsMap&): a dict of string keys."""
@@ -604,6 +610,33 @@ class Context:
         mom = np.zeros((self.height, self.width, 1 + n), dtype=np.float32)
         self._ck(self.L.lv_mboit_get_moments(self.h, _p(mom), mom.size))
         return mom
+
+    def atomic_loop_buffers(self):
+        """The slots and tail sums of the last mode-10 frame over the whole viewport (lv_atomic_loop_get_buffers): ((height, width, K)
+        uint64 keys, ascending then 0xFFFFFFFFFFFFFFFF; (height, width, 5) uint64 {SA, SR, SG, SB, SL}), K = that frame's
+        atomic_loop_num_layers (lv_atomic_loop_get_num_layers), whatever the option has been set to since."""
+        k = C.c_uint32(0)
+        self._ck(self.L.lv_atomic_loop_get_num_layers(self.h, C.byref(k)))
+        k = int(k.value)
+        slots = np.zeros((self.height, self.width, k), dtype=np.uint64)
+        tail = np.zeros((self.height, self.width, 5), dtype=np.uint64)
+        self._ck(self.L.lv_atomic_loop_get_buffers(self.h, _p(slots), _p(tail), self.width * self.height))
+        return slots, tail
+
+    def atomic_loop_resolve(self, keys, offsets, w, h):
+        """Mode 10's insert and resolve of caller-supplied keys (lv_atomic_loop_resolve_buffers) with K = atomic_loop_num_layers:
+        keys = uint64 (depth bits << 32 | packed colour), pixel p = y * w + x owns keys[offsets[p]:offsets[p + 1]].  Returns ((h, w,
+        4) uint8, (h, w, K) uint64 slots, (h, w, 5) uint64 tail sums)."""
+        k = getattr(self, "_atomic_loop_num_layers", 8)
+        e = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if o.shape[0] != w * h + 1:
+            raise ValueError("offsets must hold w * h + 1 values")
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        slots = np.zeros((h, w, k), dtype=np.uint64)
+        tail = np.zeros((h, w, 5), dtype=np.uint64)
+        self._ck(self.L.lv_atomic_loop_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(slots), _p(tail)))
+        return out, slots, tail
 
     def svgf_denoise(self, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history):
         """One SVGF denoise() on caller-supplied images (lv_svgf_denoise_buffers): noisy (h, w), normal_depth (h, w, 4), flow_fwidth

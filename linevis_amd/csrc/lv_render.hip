@@ -23,6 +23,7 @@
 #include "lv_trace.h"
 #include "lv_tile.h"
 #include "lv_mboit.h"
+#include "lv_al64.h"
 
 namespace {
 
@@ -2866,6 +2867,254 @@ __global__ __launch_bounds__(LV_BLOCK) void k_mboit_stream_moments(const unsigne
     for (uint32_t k = 0; k < numMoments; k++) o[1u + k] = covered ? lv_mboit_unfixed((long long)a[1u + k]) / b_0 : 0.0f;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Atomic Loop 64 (rendering mode 10, AtomicLoop64Renderer): the K nearest fragments of every pixel exactly, the rest as a weighted
+// average behind them (lv_al64.h).  (K + 5) x 8 B per padded pixel (addressed like ppllCount), no fragment pool, no regrowth, no
+// read-back; ppllCount is the 32-bit count of the fragments past the discard.
+//   k_al64_stream_pass   the loop of k_mboit_stream_pass (stages A and B through the lv_seg_walk_* / lv_seg_pair_coverage helpers,
+//                        the second LDS queue, stage C one lane per fragment) with lv_al64_insert as the fragment's store; ONE
+//                        launch per frame.  The loop is a copy because k_mboit_stream_pass sits at the edge of its register budget
+//                        and must compile as it does; once that allows it, the two kernels should share one skeleton with
+//                        stage C as a parameter
+//   k_al64_resolve       the cells and groups of k_mboit_stream_blend over the frame's tile list: lv_al64_resolve_pixel, the maximum
+//                        count and the overflow flag (a count above LV_AL64_MAX_COUNT)
+// The buffer is cleared per frame and not by the resolve (as the reference does): a tile list may repeat or overlap pixels.
+__global__ __launch_bounds__(LV_BLOCK) void k_al64_clear(unsigned long long* __restrict__ buf, size_t numWords, uint32_t K) {
+    const uint32_t stride = K + LV_AL64_TAIL;
+    for (size_t i = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x; i < numWords; i += size_t(gridDim.x) * LV_BLOCK)
+        buf[i] = uint32_t(i % stride) < K ? LV_AL64_EMPTY : 0ull;
+}
+
+template <int NT, int SHADE, int FAST>
+__global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_al64_stream_pass(const LvUniforms U, const LvSceneDev S,
+                                                                   const uint32_t* __restrict__ startOffset,
+                                                                   uint32_t* __restrict__ fragCount, unsigned long long* buf,
+                                                                   LvDevCounters* dc, uint32_t allRequested,
+                                                                   const uint32_t* __restrict__ leafList, uint32_t K,
+                                                                   uint32_t collectStats) {
+    __shared__ uint32_t s_qLeaf[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE], s_qPix[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE];
+    __shared__ uint32_t s_fFrag[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE], s_fPix[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE];
+    __shared__ float s_seg[LV_BLOCK / LV_WAVE][20][LV_WAVE];
+    __shared__ float s_prismRing[4 * LV_PRISM_MAX_SUBDIV];
+    // what stages A and B keep per lane, parked here while stage C runs (as k_mboit_stream_pass, for the registers of stage C)
+    __shared__ uint32_t s_park[19][LV_BLOCK];
+    if (threadIdx.x < LV_PRISM_MAX_SUBDIV) {
+        s_prismRing[threadIdx.x] = S.prism.c[threadIdx.x];
+        s_prismRing[LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.s[threadIdx.x];
+        s_prismRing[2 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.cp[threadIdx.x];
+        s_prismRing[3 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.sn[threadIdx.x];
+    }
+    __syncthreads();
+    const LvPrismDev& R = S.prism;
+    const uint32_t N = NT > 0 ? uint32_t(NT) : R.n;
+    const unsigned lane = lv_lane();
+    // (the wave's index as a scalar: the five LDS bases and the item counter below then hold no vector registers either)
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t* qLeaf = s_qLeaf[wave];
+    uint32_t* qPix = s_qPix[wave];
+    uint32_t* fFrag = s_fFrag[wave];
+    uint32_t* fPix = s_fPix[wave];
+    float (*segLds)[LV_WAVE] = s_seg[wave];
+    const f3 o = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
+    // the frame's set-up constants are the same in every lane: kept in scalar registers, so that the 15 of them do not hold vector
+    // registers across stage C
+    auto uniform = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
+    float mx[4], my[4], mw[4];
+    lv_clip_rows(U, mx, my, mw);
+#pragma unroll
+    for (int c = 0; c < 4; c++) { mx[c] = uniform(mx[c]); my[c] = uniform(my[c]); mw[c] = uniform(mw[c]); }
+    const float halfW = uniform(0.5f * float(U.width)), halfH = uniform(0.5f * float(U.height));
+    const float wEps = uniform(1e-3f * U.nearDist);
+    const float tLo = 0.0001f, tHi = __uint_as_float(__float_as_uint(1000.0f) + 1u);
+    const size_t stride = size_t(K) + LV_AL64_TAIL;
+    const bool stats = collectStats != 0u;
+    unsigned qHead = 0u, qCount = 0u;   // (pixel, segment) pairs (wave-uniform)
+    unsigned fHead = 0u, fCount = 0u;   // covered triangles (wave-uniform)
+    // the frame's counters, per wave (ballots: wave-uniform values need no vector registers across the stages)
+    unsigned long long tests = 0, hits = 0;
+    uint32_t keptSum = 0u;
+    // stage A's walk over the lane's segment: candidate rectangle and oriented box, position in it
+    uint32_t leafA = 0u;
+    LvSegWalk w = {};
+    int px = 0, py = 0;
+    bool more = false;
+
+    // stage C on the m <= 64 oldest fragments of the queue: shaded as k_ppll_shade_prism<..., LV_ENTRY_MLAB> shades them (the `kept`
+    // rules, then the gather's discard, AtomicLoop64Gather.glsl:56), key = window depth bits << 32 | packUnorm4x8(colour), inserted.
+    // (One call site, as in k_mboit_stream_pass.)
+    auto fragmentStage = [&](unsigned m) __attribute__((always_inline)) {
+        bool hit = false, stored = false;
+        if (lane < m) {
+            const unsigned q = (fHead + lane) & (LV_MBOIT_STREAM_QUEUE - 1u);
+            const uint32_t w0 = fPix[q], w1 = fFrag[q];
+            const uint32_t px = w0 & 0xFFFFu, py = w0 >> 16;
+            const uint32_t leaf = w1 & 0x03FFFFFFu, tt = w1 >> 26;
+            const float aoTexel = (U.useAmbientOcclusion && !U.aoPrebaked) ? S.ao[size_t(py) * U.width + px] : 1.0f;
+            f3 oo, d;
+            lv_primary_ray(U, px, py, 0.5f, 0.5f, oo, d);
+            const LvRasterQuad rq = lv_make_raster_quad(U, px, py);
+            bool kept;
+            float depth;
+            const f4 color = lv_shade_prism<SHADE, FAST>(S, U, s_prismRing, aoTexel, o, d, tLo, tHi, leaf, tt, rq, U.ppllRasterColour != 0u, depth, kept);
+            hit = kept;
+            if (kept && color.w >= 0.001f) {
+                const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+                const float z = lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
+                const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | lv_pack_unorm4x8(color);
+                unsigned long long* slots = buf + size_t(addr) * stride;
+                lv_al64_insert(slots, K, key, slots + K);
+                atomicAdd(&fragCount[addr], 1u);
+                stored = true;
+            }
+        }
+        keptSum += uint32_t(__popcll(__ballot(stored)));
+        if (stats) hits += (unsigned long long)__popcll(__ballot(hit));
+        fHead = (fHead + m) & (LV_MBOIT_STREAM_QUEUE - 1u);
+        fCount -= m;
+    };
+
+    // stage B on the m <= 64 oldest pairs of the queue (k_mboit_stream_pass's: the covered triangles go to the second queue);
+    // flush: the wave's last batch -- stage C also takes what is left in its queue
+    auto coverageStage = [&](unsigned m, bool flush) __attribute__((always_inline)) {
+        unsigned mask = 0u;
+        uint32_t leaf = 0u, pix = 0u;
+        if (lane < m) {
+            mask = lv_seg_pair_coverage<NT>(R, segLds, qLeaf, qPix, (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u), o, leaf, pix);
+        }
+        if (stats) tests += m;
+        while (true) {
+            const bool hit = mask != 0u;
+            const unsigned long long hm = __ballot(hit);
+            if (hm == 0ull && !(flush && fCount > 0u)) break;
+            if (hit) {
+                const unsigned tt = unsigned(__ffs(int(mask))) - 1u;
+                mask &= mask - 1u;
+                const unsigned q = (fHead + fCount + unsigned(__popcll(hm & ((1ull << lane) - 1ull)))) & (LV_MBOIT_STREAM_QUEUE - 1u);
+                fPix[q] = pix;
+                fFrag[q] = leaf | (tt << 26);
+            }
+            fCount += unsigned(__popcll(hm));
+            if (fCount >= LV_WAVE || hm == 0ull) {
+                uint32_t* park = &s_park[0][threadIdx.x];
+                const float pf[8] = {w.ax, w.ay, w.cx0, w.cy0, w.aMid, w.aHalf, w.nMid, w.nHalf};
+                const uint32_t pu[11] = {mask, leaf, pix, leafA, uint32_t(w.x0), uint32_t(w.x1), uint32_t(w.y0), uint32_t(w.y1),
+                                         uint32_t(px), uint32_t(py), more ? 1u : 0u};
+#pragma unroll
+                for (int i = 0; i < 8; i++) park[i * LV_BLOCK] = __float_as_uint(pf[i]);
+#pragma unroll
+                for (int i = 0; i < 11; i++) park[(8 + i) * LV_BLOCK] = pu[i];
+                fragmentStage(fCount < LV_WAVE ? fCount : LV_WAVE);
+                w.ax = __uint_as_float(park[0]); w.ay = __uint_as_float(park[LV_BLOCK]); w.cx0 = __uint_as_float(park[2 * LV_BLOCK]);
+                w.cy0 = __uint_as_float(park[3 * LV_BLOCK]); w.aMid = __uint_as_float(park[4 * LV_BLOCK]); w.aHalf = __uint_as_float(park[5 * LV_BLOCK]);
+                w.nMid = __uint_as_float(park[6 * LV_BLOCK]); w.nHalf = __uint_as_float(park[7 * LV_BLOCK]);
+                mask = park[8 * LV_BLOCK]; leaf = park[9 * LV_BLOCK]; pix = park[10 * LV_BLOCK]; leafA = park[11 * LV_BLOCK];
+                w.x0 = int(park[12 * LV_BLOCK]); w.x1 = int(park[13 * LV_BLOCK]); w.y0 = int(park[14 * LV_BLOCK]); w.y1 = int(park[15 * LV_BLOCK]);
+                px = int(park[16 * LV_BLOCK]); py = int(park[17 * LV_BLOCK]); more = park[18 * LV_BLOCK] != 0u;
+            }
+        }
+        qHead = (qHead + m) & (LV_PRISM_RASTER_QUEUE - 1u);
+        qCount -= m;
+    };
+
+    const uint32_t waveId = blockIdx.x * (LV_BLOCK / LV_WAVE) + wave, numWaves = gridDim.x * (LV_BLOCK / LV_WAVE);
+    const uint32_t numItems = leafList ? dc->prismListCount : S.numSegs;
+    for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
+        const bool valid = itemBase + lane < numItems;
+        const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
+        leafA = leaf;
+        w = lv_seg_walk_setup(U, S, segLds, mx, my, mw, halfW, halfH, wEps, N, valid, leaf, lane);
+        px = w.x0; py = w.y0;
+        more = valid && w.x1 >= w.x0 && w.y1 >= w.y0;
+        const bool lastItem = itemBase + numWaves * LV_WAVE >= numItems;   // (overflow: numItems < 2^26)
+        while (true) {
+            const bool drain = !__any(more);   // every rectangle walked: the rest of the pairs, 64 at a time
+            const bool cand = more && lv_seg_walk_candidate(U, w, px, py, allRequested, startOffset);
+            const unsigned long long cm = __ballot(cand);
+            if (cand) {
+                const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
+                qLeaf[q] = leafA | (lane << 26);
+                qPix[q] = uint32_t(px) | (uint32_t(py) << 16);
+            }
+            qCount += unsigned(__popcll(cm));
+            if (qCount >= LV_WAVE || drain) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE, lastItem && drain && qCount <= LV_WAVE);
+            if (drain && qCount == 0u) break;   // (the next 64 segments replace the frames in LDS)
+            if (more) more = lv_seg_walk_advance(w, px, py);
+        }
+    }
+    if (lane == 0u && keptSum > 0u) atomicAdd(&dc->fragCounter, keptSum);   // every fragment past the discard
+    if (stats) {
+        if (lane == 0u && tests) atomicAdd(&dc->prims, tests);
+        if (lane == 0u && hits) atomicAdd(&dc->hits, hits);
+    }
+}
+
+// One lane per pixel, one wave per workgroup, the cells and groups of k_mboit_stream_blend
+__global__ __launch_bounds__(LV_WAVE) void k_al64_resolve(const LvUniforms U, const LvTiles T, const unsigned long long* __restrict__ buf,
+                                                          const uint32_t* __restrict__ fragCount, uint32_t* __restrict__ out,
+                                                          uint32_t numGroups, uint32_t K, LvDevCounters* dc) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t maxCount = 0u;
+    const size_t stride = size_t(K) + LV_AL64_TAIL;
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        const bool inTile = lx < T.tileW && ly < T.tileH;
+        if (!__any(inTile)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        const uint32_t outIndex = (tile * T.tileH + ly) * T.tileW + lx;
+        if (!inTile) continue;
+        uint32_t packed;
+        if (x < U.width && y < U.height) {
+            const uint32_t addr = lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+            maxCount = max(maxCount, fragCount[addr]);
+            const unsigned long long* slots = buf + size_t(addr) * stride;
+            packed = lv_al64_resolve_pixel(U, slots, K, slots + K);
+        } else {
+            f4 r;
+            r.x = U.background[0]; r.y = U.background[1]; r.z = U.background[2]; r.w = U.background[3];
+            packed = lv_pack_unorm4x8(r);
+        }
+        out[outIndex] = packed;
+    }
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) maxCount = max(maxCount, (uint32_t)__shfl_xor(maxCount, ofs, 64));
+    if (lane == 0 && maxCount > 0u) atomicMax(&dc->maxDepthComplexity, maxCount);
+    if (lane == 0 && maxCount > LV_AL64_MAX_COUNT) atomicOr(&dc->mboitOverflow, 1u);
+}
+
+// lv_atomic_loop_resolve_buffers: one lane per given key, all lanes racing; pixel = the run of `offsets` that holds the key (binary
+// search over the numPixels + 1 ascending offsets on the device)
+__global__ __launch_bounds__(LV_BLOCK) void k_al64_insert_given(const unsigned long long* __restrict__ keys, uint64_t numKeys,
+                                                               const unsigned long long* __restrict__ offsets, uint32_t numPixels,
+                                                               unsigned long long* buf, uint32_t* __restrict__ fragCount, uint32_t K) {
+    const uint64_t i = uint64_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (i >= numKeys) return;
+    uint32_t lo = 0u, hi = numPixels;   // the last p in [0, numPixels) with offsets[p] <= i  (offsets[0] = 0, offsets[numPixels] = numKeys > i)
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    unsigned long long* slots = buf + size_t(lo) * (size_t(K) + LV_AL64_TAIL);
+    lv_al64_insert(slots, K, keys[i], slots + K);
+    atomicAdd(&fragCount[lo], 1u);
+}
+
+// lv_atomic_loop_get_buffers: the slots and the tail sums of every pixel of the viewport, row-major
+__global__ __launch_bounds__(LV_BLOCK) void k_al64_read(const unsigned long long* __restrict__ buf, uint32_t width, uint32_t height,
+                                                       uint32_t paddedW, uint32_t tileW, uint32_t tileH, uint32_t K,
+                                                       unsigned long long* __restrict__ outSlots, unsigned long long* __restrict__ outTail) {
+    const size_t p = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (p >= size_t(width) * height) return;
+    const uint32_t x = uint32_t(p % width), y = uint32_t(p / width);
+    const unsigned long long* a = buf + size_t(lv_ppll_addr(x, y, paddedW, tileW, tileH)) * (size_t(K) + LV_AL64_TAIL);
+    for (uint32_t i = 0u; i < K; i++) outSlots[p * K + i] = a[i];
+    for (uint32_t i = 0u; i < LV_AL64_TAIL; i++) outTail[p * LV_AL64_TAIL + i] = a[K + i];
+}
+
 // ================================================================ depth range
 __global__ __launch_bounds__(LV_BLOCK) void k_depth_minmax(const LvUniforms U, const lv_line_point* __restrict__ points,
                                                            uint32_t numPoints, LvDevCounters* dc) {
@@ -3821,14 +4070,15 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
     return LV_OK;
 }
 
-// the overflow flag of the last frame when that was a streamed mode-6 frame (host-synchronous)
+// the overflow flag of the last frame when that was a streamed mode-6 frame or a mode-10 frame (host-synchronous)
 int lv_mboit_stream_overflow(lv_ctx* ctx) {
-    if (!ctx->mboitStreamLast || !ctx->counters.ptr) return LV_OK;
+    if ((!ctx->mboitStreamLast && !ctx->al64Last) || !ctx->counters.ptr) return LV_OK;
     uint32_t flag = 0u;
     LV_HIP(ctx, hipMemcpy(&flag, &((const LvDevCounters*)ctx->counters.ptr)->mboitOverflow, 4, hipMemcpyDeviceToHost));
     if (flag)
-        return lv_fail(ctx, LV_E_CAPACITY, "MBOIT (streamed): a pixel is covered by more than %u kept fragments (the 64-bit sums are "
-                                           "exact up to that count)", LV_MBOIT_STREAM_MAX_COUNT);
+        return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than %u kept fragments (the 64-bit sums are "
+                                           "exact up to that count)", ctx->al64Last ? "Atomic Loop 64" : "MBOIT (streamed)",
+                       LV_MBOIT_STREAM_MAX_COUNT);
     return LV_OK;
 }
 
@@ -3856,18 +4106,124 @@ int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloa
     return LV_OK;
 }
 
+// A mode-10 frame (Atomic Loop 64): clear, ONE launch of k_al64_stream_pass, the resolve.  No pool, no scan, no regrowth and no host
+// synchronisation; the resolve's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
+static void lv_al64_clear(lv_ctx* ctx, size_t numWords, uint32_t K) {
+    const size_t blocks = (numWords + LV_BLOCK - 1) / LV_BLOCK, maxBlocks = size_t(ctx->numCUs) * 32u;
+    k_al64_clear<<<uint32_t(std::max<size_t>(1, std::min(blocks, maxBlocks))), LV_BLOCK, 0, ctx->stream>>>(
+            (unsigned long long*)ctx->al64Buf.ptr, numWords, K);
+}
+static int lv_al64_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
+                         LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    // (use_ribbons with rotating_helicity_bands never gets here: lv_frame_render refuses that pair for every mode)
+    if (!lv_ppll_prism_source(ctx))
+        return lv_fail(ctx, LV_E_INVALID, "mode 10 (Atomic Loop 64) works on the fragments of the rasterised prism, which this line data does not have");
+    if (ctx->opt.ppllPrismLbvhWalk)
+        return lv_fail(ctx, LV_E_INVALID, "mode 10 (Atomic Loop 64) runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported");
+    lv_fill_prism(ctx, U, S.prism);
+    const uint32_t K = ctx->opt.al64NumLayers;
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
+    const size_t numWords = padded4 * 4 * size_t(K + LV_AL64_TAIL);
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->al64Buf, numWords * 8))) return rc;
+    ctx->ppllPoolNodes = 0;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    const bool allRequested = ctx->tilesCoverViewport;
+    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
+    lv_al64_clear(ctx, numWords, K);
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    // LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in modes 2, 3 and 6)
+    uint32_t* leafList;
+    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
+    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
+    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);   // the instances and the selection of the streamed MBOIT pass
+#define LV_LAUNCH_AL64(NT, SH, FA)                                                                                              \
+    k_al64_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr,                    \
+            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->al64Buf.ptr, dc, allRequested ? 1u : 0u, leafList, K,      \
+            stats ? 1u : 0u)
+#define LV_LAUNCH_AL64_2(NT)                                                         \
+    do {                                                                             \
+        if (fastShade) LV_LAUNCH_AL64(NT, LV_SHADE_PLAIN, 2);                        \
+        else if (S.prism.bands) LV_LAUNCH_AL64(NT, LV_SHADE_BANDS, 0);               \
+        else if (U.useHelicityBands) LV_LAUNCH_AL64(NT, LV_SHADE_HELICITY, 0);       \
+        else LV_LAUNCH_AL64(NT, LV_SHADE_PLAIN, 0);                                  \
+    } while (0)
+    if (S.numSegs != 0) {
+        if (S.prism.n == 6u) LV_LAUNCH_AL64_2(6); else LV_LAUNCH_AL64_2(0);
+    }
+    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
+        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
+        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
+    }
+#undef LV_LAUNCH_AL64_2
+#undef LV_LAUNCH_AL64
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_al64_resolve<<<numGroups, LV_WAVE, 0, st>>>(
+            U, T, (const unsigned long long*)ctx->al64Buf.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, K, dc)));
+    ctx->al64Last = true;
+    ctx->al64Full = allRequested;
+    ctx->al64W = U.width;
+    ctx->al64H = U.height;
+    ctx->al64K = K;
+    ctx->al64Tile[0] = U.ppllTileW;
+    ctx->al64Tile[1] = U.ppllTileH;
+    return LV_OK;
+}
+
+// lv_atomic_loop_get_num_layers: K of the last frame when that was a mode-10 frame (what lv_atomic_loop_get_buffers returns per pixel)
+int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out) {
+    if (!ctx->al64Last) return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_num_layers: the last frame was not a mode-10 frame");
+    *out = ctx->al64K;
+    return LV_OK;
+}
+
+// lv_atomic_loop_get_buffers
+int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, uint64_t capacityPixels) {
+    if (!ctx->al64Last || !ctx->al64Full || !ctx->al64Buf.ptr || ctx->al64W != ctx->width || ctx->al64H != ctx->height)
+        return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_buffers: the last frame was not a mode-10 frame over the whole viewport");
+    const uint64_t pixels = uint64_t(ctx->al64W) * ctx->al64H;
+    if (capacityPixels < pixels)
+        return lv_fail(ctx, LV_E_INVALID, "lv_atomic_loop_get_buffers: the arrays hold %llu pixels, need %llu",
+                       (unsigned long long)capacityPixels, (unsigned long long)pixels);
+    int rc;
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
+    const uint32_t K = ctx->al64K;
+    const size_t slotBytes = size_t(pixels) * K * 8, tailBytes = size_t(pixels) * LV_AL64_TAIL * 8;
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, slotBytes + tailBytes))) return rc;
+    unsigned long long* dSlots = (unsigned long long*)ctx->scratchRays.ptr;
+    unsigned long long* dTail = dSlots + size_t(pixels) * K;
+    k_al64_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
+            (const unsigned long long*)ctx->al64Buf.ptr, ctx->al64W, ctx->al64H, ctx->ppllPaddedW, ctx->al64Tile[0], ctx->al64Tile[1], K,
+            dSlots, dTail);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(outSlots, dSlots, slotBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipMemcpyAsync(outTail, dTail, tailBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LV_OK;
+}
+
 int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
                     uint32_t tileH, void* outDevice) {
     if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
-        mode != LV_RENDERING_MODE_MBOIT)
-        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 6 = MBOIT)", mode);
+        mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64)
+        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 6 = MBOIT, 10 = Atomic Loop 64)", mode);
     // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
     const bool mboit = mode == LV_RENDERING_MODE_MBOIT;
     const bool mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
+    const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64;   // (the prism's fragments too, but no pool: lv_al64_frame)
     ctx->mboitStreamLast = false;   // (set again at the end of a streamed mode-6 frame)
     ctx->mboitStreamFull = false;
-    const char* const poolName = mboit ? "MBOIT" : "MLAB";
-    if (mlab && ctx->opt.ppllFragmentSource == 1)
+    ctx->al64Last = false;          // (set again at the end of a mode-10 frame)
+    ctx->al64Full = false;
+    const char* const poolName = al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
+    if ((mlab || al64) && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
                                           "capsule_entry is not supported", mode, poolName);
     if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_set_camera has not been called");
@@ -3881,7 +4237,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         // tubes (rtao_geometry = triangle_tubes); MLAT over the same geometries; the PPLL gather over the analytic tubelets /
         // capsules.  The static prebaker bakes band data on the elliptic cross-section against the elliptic triangle tubes the caller
         // passed (VulkanAmbientOcclusionBaker.glsl:200-257) and is looked up with the band's own angle (phiLine of the tubelets).
-        if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab) && (ctx->opt.rtTriangleMesh || ctx->opt.rtLss))
+        if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab || al64) && (ctx->opt.rtTriangleMesh || ctx->opt.rtLss))
             return lv_fail(ctx, LV_E_INVALID, "use_ribbons: the PPLL gather of band data runs over the analytic tubelets / capsules "
                                               "(geometry_mode \"AABBs\")");
         if (ctx->opt.rtTriangleMesh && ctx->opt.ellipticTubes)
@@ -4019,7 +4375,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[7], st));
     // The colour pass of a raster_prism frame with the segment rasteriser has no tile kernel: only its resolve pass could use the
     // dispatch order, and measured it does not (config 4: 0.134 ms as numbered, 0.145 ms heaviest first + 11 us for k_group_order)
-    if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab) && lv_ppll_prism_source(ctx) && !ctx->opt.ppllPrismLbvhWalk &&
+    if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab || al64) && lv_ppll_prism_source(ctx) && !ctx->opt.ppllPrismLbvhWalk &&
         !ctx->groupOrderSorted) {
         T.groupOrder = nullptr;
         T.groupCost = nullptr;
@@ -4086,6 +4442,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         }
     } else if (mboit && ctx->opt.mboitStreamed) {
         if ((rc = lv_mboit_stream_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
+    } else if (al64) {
+        if ((rc = lv_al64_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else {
         // reallocateFragmentBuffer, PerPixelLinkedListLineRenderer.cpp:251-357
         // gather(): fragments of the rasterised programmable-pull prism (the reference's geometry, default) or capsule entry hits
@@ -4496,6 +4854,62 @@ int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
                                outMoments ? (float*)ctx->ppllScratch.ptr : nullptr, (LvDevCounters*)ctx->counters.ptr)))
         return rc;
     return lv_resolve_read_back(ctx, out, size_t(numPixels), outMoments, momBytes);
+}
+
+// lv_atomic_loop_resolve_buffers: the caller's keys (pixel p of the w x h rectangle owns keys [offsets[p], offsets[p + 1])) inserted
+// by k_al64_insert_given, one lane per key with all lanes racing, then k_al64_resolve with row-major addressing
+int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKeys, const uint64_t* offsets, uint32_t w, uint32_t h,
+                               uint8_t* out, uint64_t* outSlots, uint64_t* outTail) {
+    const uint64_t numPixels = uint64_t(w) * h;
+    const uint32_t K = ctx->opt.al64NumLayers;
+    if (numKeys >= 0xFFFFFFF0ull || numPixels > 0x7FFFFFF0ull / (K + LV_AL64_TAIL)) return lv_fail(ctx, LV_E_CAPACITY, "too many keys or pixels");
+    if (offsets[0] != 0 || offsets[numPixels] != numKeys) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_keys");
+    for (uint64_t p = 0; p < numPixels; p++)
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > LV_AL64_MAX_COUNT)
+            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most %u keys per pixel", (unsigned long long)p, LV_AL64_MAX_COUNT);
+    for (uint64_t i = 0; i < numKeys; i++)
+        if (keys[i] == LV_AL64_EMPTY) return lv_fail(ctx, LV_E_INVALID, "key %llu: 0xFFFFFFFFFFFFFFFF is the empty slot", (unsigned long long)i);
+    hipStream_t st = ctx->stream;
+    LvUniforms U;
+    lv_row_major_uniforms(ctx, U, w, h);
+    const size_t numWords = size_t(numPixels) * (K + LV_AL64_TAIL);
+    const size_t keyBytes = size_t(numKeys ? numKeys : 1) * 8, offBytes = size_t(numPixels + 1) * 8;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->al64Buf, numWords * 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, keyBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
+    ctx->al64Last = false;   // (the buffer no longer holds a frame)
+    ctx->mboitStreamLast = false;
+    if (numKeys) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, keys, size_t(numKeys) * 8, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, size_t(numPixels) * 4, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    lv_al64_clear(ctx, numWords, K);
+    if (numKeys)
+        k_al64_insert_given<<<uint32_t((numKeys + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
+                (const unsigned long long*)ctx->ppllNodes.ptr, numKeys, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels),
+                (unsigned long long*)ctx->al64Buf.ptr, (uint32_t*)ctx->ppllCount.ptr, K);
+    static const uint32_t txy[2] = {0u, 0u};
+    LvTiles T;
+    uint32_t numGroups;
+    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
+    k_al64_resolve<<<numGroups, LV_WAVE, 0, st>>>(U, T, (const unsigned long long*)ctx->al64Buf.ptr, (const uint32_t*)ctx->ppllCount.ptr,
+                                                  (uint32_t*)ctx->outDev.ptr, numGroups, K, (LvDevCounters*)ctx->counters.ptr);
+    if (outSlots || outTail) {
+        const size_t slotBytes = size_t(numPixels) * K * 8, tailBytes = size_t(numPixels) * LV_AL64_TAIL * 8;
+        if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, slotBytes + tailBytes))) return rc;
+        unsigned long long* dSlots = (unsigned long long*)ctx->scratchRays.ptr;
+        unsigned long long* dTail = dSlots + size_t(numPixels) * K;
+        k_al64_read<<<uint32_t((numPixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
+                (const unsigned long long*)ctx->al64Buf.ptr, w, h, w, 1u, 1u, K, dSlots, dTail);
+        if (outSlots) LV_HIP(ctx, hipMemcpyAsync(outSlots, dSlots, slotBytes, hipMemcpyDeviceToHost, st));
+        if (outTail) LV_HIP(ctx, hipMemcpyAsync(outTail, dTail, tailBytes, hipMemcpyDeviceToHost, st));
+    }
+    return lv_resolve_read_back(ctx, out, size_t(numPixels));
 }
 
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,

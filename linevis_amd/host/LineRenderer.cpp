@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 namespace lv {
@@ -772,6 +773,42 @@ bool HipMBOITRenderer::setNewSettings(const SettingsMap& settings) {
     settings.getValueOpt("overestimationBeta", overestimationBeta);
     for (const char* key : {"ppll_expected_avg_depth_complexity", "ppll_tile_width", "ppll_tile_height", "ppll_fragment_source",
                             "ppll_fragment_colour", "ppll_prism_rasteriser", "mboit_moment_bias", "mboit_fragment_storage"}) {
+        std::string s;
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
+HipAtomicLoop64Renderer::HipAtomicLoop64Renderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Atomic Loop 64 Renderer", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipAtomicLoop64Renderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipAtomicLoop64Renderer::setNewState(const InternalState& newState) {
+    currentStateName = newState.name;
+    newState.rendererSettings.getValueOpt("numLayers", numLayers);
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipAtomicLoop64Renderer::render() {
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    setOption("atomic_loop_num_layers", std::to_string(numLayers));
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_ATOMIC_LOOP_64); // clear -> rasterise, shade and insert -> resolve
+}
+
+bool HipAtomicLoop64Renderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    settings.getValueOpt("numLayers", numLayers);
+    std::string layers;
+    if (settings.getValueOpt("atomic_loop_num_layers", layers) && setOption("atomic_loop_num_layers", layers))
+        numLayers = std::atoi(layers.c_str());   // (a value the C ABI refuses leaves numLayers as it is)
+    for (const char* key : {"ppll_tile_width", "ppll_tile_height", "ppll_fragment_source", "ppll_fragment_colour", "ppll_prism_rasteriser"}) {
         std::string s;
         if (settings.getValueOpt(key, s)) setOption(key, s);
     }

@@ -27,6 +27,7 @@ enum RenderingMode : int32_t {
     RENDERING_MODE_PER_PIXEL_LINKED_LIST = 2,
     RENDERING_MODE_MLAB = 3,
     RENDERING_MODE_MBOIT = 6,
+    RENDERING_MODE_ATOMIC_LOOP_64 = 10,
     RENDERING_MODE_VULKAN_RAY_TRACER = 11,
 };
 
@@ -387,6 +388,26 @@ private:
     bool useOrderedFragmentShaderInterlock = true;
     std::string refusedKey, refusedValue;           // the option a refused state asked for (reported by render())
     bool refusalReported = false;                   // lastError holds that report
+};
+
+/// "Atomic Loop 64" plugin (src/Renderers/OIT/AtomicLoop64Renderer.hpp) re-hosted on HIP (rendering mode 10): the numLayers nearest
+/// fragments of the PPLL plugin's rasterised prism per pixel in 64-bit atomicMin slots, the rest as an order-independent tail.
+class HipAtomicLoop64Renderer : public LineRenderer {
+public:
+    HipAtomicLoop64Renderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_ATOMIC_LOOP_64; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    /// AtomicLoop64Renderer::setNewState (AtomicLoop64Renderer.cpp:104): numLayers
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    bool setNewSettings(const SettingsMap& settings) override;
+    bool getUseAnalyticEllipticTubes() const override { return true; }
+    int getNumLayers() const { return numLayers; }
+
+private:
+    std::string currentStateName;
+    int numLayers = 8;                              // AtomicLoop64Renderer.hpp:112
 };
 
 } // namespace lv

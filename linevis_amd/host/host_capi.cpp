@@ -497,6 +497,13 @@ int lvh_renderer_mboit_state(void* r, int32_t* out5, float* outBeta) {
     *outBeta = m->getOverestimationBeta();
     return 0;
 }
+int lvh_renderer_atomic_loop_state(void* r, int32_t* out1) {   // {numLayers} of a mode-10 plugin
+    HeadlessLineRenderer* h = static_cast<HeadlessLineRenderer*>(r);
+    const HipAtomicLoop64Renderer* m = dynamic_cast<const HipAtomicLoop64Renderer*>(h->getLineRenderer());
+    if (!m) return -1;
+    out1[0] = m->getNumLayers();
+    return 0;
+}
 void lvh_renderer_destroy(void* r) { delete static_cast<HeadlessLineRenderer*>(r); }
 void lvh_renderer_set_resolution(void* r, uint32_t w, uint32_t h) { static_cast<HeadlessLineRenderer*>(r)->setRenderingResolution(w, h); }
 void lvh_renderer_set_line_data(void* r, void* flow, int isNewData) {

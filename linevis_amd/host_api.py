@@ -86,6 +86,7 @@ def load():
         "lvh_test_modes_mboit_count": (u32, []),
         "lvh_test_mode_mboit": (u32, [u32, vp, u32]),
         "lvh_renderer_mboit_state": (i32, [vp, vp, vp]),
+        "lvh_renderer_atomic_loop_state": (i32, [vp, vp]),
         "lvh_renderer_destroy": (None, [vp]),
         "lvh_renderer_set_resolution": (None, [vp, u32, u32]),
         "lvh_renderer_set_line_data": (None, [vp, vp, i32]),
@@ -622,6 +623,13 @@ class HeadlessLineRenderer:
             return None
         return {"numMoments": int(v[0]), "syncMode": int(v[1]), "useOrderedFragmentShaderInterlock": bool(v[2]),
                 "useRenderTargets": bool(v[3]), "USE_R_RG_RGBA_FOR_MBOIT6": bool(v[4]), "overestimationBeta": float(beta[0])}
+
+    def atomic_loop_state(self):
+        """{numLayers} of the mode-10 plugin (None for the other plugins)"""
+        v = np.zeros(1, dtype=np.int32)
+        if self.L.lvh_renderer_atomic_loop_state(self.h, _p(v)) != 0:
+            return None
+        return {"numLayers": int(v[0])}
 
     def needs_re_render(self):
         return bool(self.L.lvh_renderer_needs_re_render(self.h))
