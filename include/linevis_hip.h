@@ -608,6 +608,27 @@ int lv_get_mlat_trace(lv_ctx* ctx, uint32_t* out_records, uint64_t max_records, 
  * root; out_mismatches = number of arguments whose results differ in any bit (NaN results count as equal to each other),
  * out_first_argument = the bits of one of them. */
 int lv_selftest_rsqrt(lv_ctx* ctx, uint64_t* out_mismatches, uint32_t* out_first_argument);
+/* Parity instrument without a reference counterpart: the traversal stack of the ray kernels (a window of LDS slots over a per-thread
+ * column of a global slab, spilled and refilled in blocks) run on scripts.  One workgroup of 256 threads with the window and stride
+ * of the RTAO sample kernel (LV_STACK_INST_AO) or of the tile kernels (LV_STACK_INST_TILE); thread t executes ops[t][0 .. ops_per_thread),
+ * four words per operation: {code | keep flags, c3, c2, c1}.  LV_STACK_OP_PUSH3 is a node step's push of c3, c2, c1 in that order, each
+ * kept only if its flag (bit 8, 9, 10) is set; LV_STACK_OP_POP appends the popped word (LV_INVALID: the stack is empty; only
+ * LV_STACK_OP_CLEAR may follow) to out_words[t][...]; LV_STACK_OP_CLEAR drops every entry; LV_STACK_OP_END does nothing.
+ * out_counts[t] = {words popped, blocks spilled, blocks refilled}.  The slab is sized by the routine that sizes it for a launch, for a
+ * tree of wide_levels levels (at most 3 * wide_levels + 2 entries): a script that goes deeper, or pushes a word that is no node or
+ * leaf reference (index < 2^26), is refused with LV_E_INVALID before anything runs.
+ * out_info (may be NULL) = {entries of the LDS window, entries per spilled block, slab entries per thread for wide_levels, bytes of
+ * slab the context's launches had reserved before this call, levels of the context's segment tree, of its triangle tree};
+ * ops_per_thread == 0 only fills out_info.  tests/test_gpu_stack_spill.py compares with a plain list. */
+#define LV_STACK_INST_AO 0
+#define LV_STACK_INST_TILE 1
+#define LV_STACK_OP_END 0
+#define LV_STACK_OP_PUSH3 1
+#define LV_STACK_OP_POP 2
+#define LV_STACK_OP_CLEAR 3
+int lv_selftest_stack(lv_ctx* ctx, uint32_t instantiation, uint32_t wide_levels, const uint32_t* ops /* 256 x ops_per_thread x 4 */,
+                      uint32_t ops_per_thread, uint32_t* out_words /* 256 x ops_per_thread */, uint32_t* out_counts /* 256 x 3 */,
+                      uint64_t* out_info /* 6 */);
 /* Parity instrument without a reference counterpart: one of the build-owned scalar definitions evaluated on the
  * device for n arguments, by the same inline functions the render kernels call.  in_words / out_words are host arrays of bit
  * patterns (a float travels as its 32 bits), element-major: n x arity words in, n x results words out.  Uploads, launches one

@@ -107,7 +107,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
            "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
-           "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval",
+           "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
            "lv_create_multi", "lv_multi_ranks", "lv_multi_rank_stats", "lv_multi_rebalance", "lv_multi_deal", "lv_tile_deal", "lv_make_tiles"]
 
@@ -207,6 +207,7 @@ def load():
         ("lv_get_mlat_trace", [vp, vp, u64, C.POINTER(u64)]),
         ("lv_selftest_rsqrt", [vp, C.POINTER(u64), C.POINTER(u32)]),
         ("lv_selftest_eval", [vp, u32, vp, u64, vp]),
+        ("lv_selftest_stack", [vp, u32, u32, vp, u32, vp, vp, vp]),
     ]:
         fn = getattr(L, name)
         fn.restype = i32
@@ -517,6 +518,24 @@ class Context:
         out = np.empty((len(w), results), dtype=np.uint32)
         self._ck(self.L.lv_selftest_eval(self.h, fid, _p(w), len(w), _p(out)))
         return out
+
+    def selftest_stack(self, instantiation, wide_levels, ops=None):
+        """lv_selftest_stack: the ray kernels' traversal stack on scripts.  instantiation 0 = the RTAO sample kernel's window, 1 = the
+        tile kernels'; ops = (256, n, 4) uint32 {code | keep flags << 8, c3, c2, c1} with code 1 = push3, 2 = pop, 3 = clear, 0 = nothing.
+        -> (popped words per thread as a list of uint32 arrays, (256, 3) {pops, spills, refills}, info dict); ops = None: info only."""
+        info = np.zeros(6, dtype=np.uint64)
+        if ops is None:
+            self._ck(self.L.lv_selftest_stack(self.h, int(instantiation), int(wide_levels), None, 0, None, None, _p(info)))
+            words, counts = [], np.zeros((256, 3), dtype=np.uint32)
+        else:
+            ops = np.ascontiguousarray(ops, dtype=np.uint32)
+            assert ops.ndim == 3 and ops.shape[0] == 256 and ops.shape[2] == 4
+            out = np.zeros((256, ops.shape[1]), dtype=np.uint32)
+            counts = np.zeros((256, 3), dtype=np.uint32)
+            self._ck(self.L.lv_selftest_stack(self.h, int(instantiation), int(wide_levels), _p(ops), ops.shape[1], _p(out), _p(counts), _p(info)))
+            words = [out[t, :counts[t, 0]] for t in range(256)]
+        keys = ("window", "block", "column_entries", "context_slab_bytes", "wide_levels", "triangle_wide_levels")
+        return words, counts, dict(zip(keys, (int(v) for v in info)))
 
     def kernel_times(self, kernel_id):
         """Individual launch durations (ms) of one kernel since reset_timers(), oldest first (at most the last 512)."""

@@ -20,7 +20,12 @@
 #ifndef LV_STACK_LDS
 #define LV_STACK_LDS 24
 #endif
-#define LV_STACK_SPILL 64   // further entries in a global overflow slab; 96 >= max LBVH height (63 key bits + 32)
+// The LDS entries are a window onto the top of the stack (slot 0 holds a sentinel, lv_trace.h): when a node step finds no room for
+// three references, the bottom LV_STACK_SPILL_BLOCK entries of the window move to the thread's column of a global slab, and come
+// back as a block when the window runs empty.
+#ifndef LV_STACK_SPILL_BLOCK
+#define LV_STACK_SPILL_BLOCK 4   // config 3: 4 / 8 / 12 = 5610 / 5565 / 5493 Mrays/s (a spill and the refill that follows move less; EXPERIMENTS.md section 18)
+#endif
 // minimum waves per SIMD the register allocator must leave room for (hipcc's second __launch_bounds__ argument)
 // k_render_rt: 4 waves per SIMD (<= 128 VGPRs instead of 146; with the 40-KB workgroups that is 4 workgroups per CU): -6 % on
 // config 3's colour pass, -4.5 % on config 2.  The instrumented and the elliptic-tube instantiations keep their registers.
@@ -55,7 +60,7 @@
 #define LV_AO_SMALL_CHUNKS 12u
 #endif
 #ifndef LV_AO_STACK_LDS
-#define LV_AO_STACK_LDS 15      // LDS-staged stack entries per thread in k_ao_rays (deeper entries: HBM overflow slab)
+#define LV_AO_STACK_LDS 16      // LDS stack slots per thread in k_ao_rays: the sentinel + a window of 15 entries (deeper entries: HBM slab)
 #endif
 #ifndef LV_AO_MIN_WAVES
 #define LV_AO_MIN_WAVES 5         // waves per SIMD k_ao_rays is compiled for (95 VGPRs; 6 would need <= 85 and 26 KB of LDS)
@@ -266,7 +271,7 @@ struct LvSceneDev {
     // tolerances (EllipticTubeRayTracing.glsl:186-270)
     float ellBandWidth, ellMinBandThickness, ellCamPos[3];
     const float* ao;            // full-viewport AO factors
-    unsigned* stackOverflow;    // null unless the LBVH is higher than LV_STACK_LDS
+    unsigned* stackOverflow;    // slab of the traversal stacks; null unless 3 * levels + 2 entries exceed the window (LDS slots - 1) of this launch's stacks
     uint32_t* accum;            // full-viewport rgba8 of the previous frame (num_accumulated_frames > 1), else null
     uint32_t numSegs;           // primitives under `nodes` (segments, or triangles in a triangle-tube scene view)
     uint32_t literalIntersection; // intersection_form = literal: the reference's textbook roots (lv_intersect_capsule_literal)

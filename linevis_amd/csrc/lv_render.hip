@@ -499,7 +499,7 @@ __device__ __forceinline__ void lv_ao_generate_ray(const LvUniforms& U, float4 g
 // Scheduling inside a wave: test when >= 64 pairs wait; refill when >= LV_REFILL_THRESHOLD lanes are idle; otherwise
 // descend; flush partial batches only when nothing else can make progress.  Once the global queue is empty (drain) the
 // rays left in a wave are finished together: nobody retires early, idle lanes take over stacked subtrees of busy ones.
-// Resources: 30 KB LDS and <= 96 VGPRs -> 5 workgroups = 20 waves per CU; the kernel is VALU-issue-bound and needs that
+// Resources: 31 KB LDS and <= 96 VGPRs -> 5 workgroups = 20 waves per CU; the kernel is VALU-issue-bound and needs that
 // occupancy to hide the dependent node fetches (12 -> 16 -> 20 waves per CU: -16 %, -7 %).
 // BAKE: the static prebaker's rays (VulkanAmbientOcclusionBaker.glsl:230-281).  G-buffer slot = parametrisation vertex *
 // numTubeSubdivisions + subdivision with g0 = {ray origin, -}, g1 = {tangent, vertex}, g2 = {surface normal, subdivision};
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                                                          uint32_t numTiles, const LvAoLayout tileCapacity,
                                                          const uint2* __restrict__ lcgSkip = nullptr) {
     __shared__ unsigned s_stack[LV_AO_STACK_LDS * LV_AO_BLOCK];
-    // LDS budget: 15 KB + 6 + 6 + 2 + 1 = 30 KB per workgroup -> 5 workgroups (20 waves) per CU; the kernel hides the
+    // LDS budget: 16 KB + 6 + 6 + 2 + 1 = 31 KB per workgroup -> 5 workgroups (20 waves) per CU; the kernel hides the
     // latency of its dependent node fetches with occupancy (measured: 12 -> 16 waves/CU -16 %, 16 -> 20 another -7 %)
     __shared__ float2 s_ray[3 * LV_AO_BLOCK];              // current ray of every lane: {o.xy}{o.z, d.x}{d.yz} (24 B)
     __shared__ float2 s_gen[3 * LV_AO_BLOCK];              // generated rays waiting for a lane
@@ -545,8 +545,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
     const float litSlack = PRIM == LV_PRIM_ELLIPTIC ? S.ellBandWidth * 1.001f : (PRIM == LV_PRIM_CAPSULE && LIT) ? radius * 1.001f : 0.0f;
 
     LvStackT<LV_AO_STACK_LDS, LV_AO_BLOCK> st;
-    st.init(&s_stack[threadIdx.x], S.stackOverflow ? S.stackOverflow + (size_t(blockIdx.x) * LV_AO_BLOCK + threadIdx.x) : nullptr,
-            gridDim.x * LV_AO_BLOCK);
+    st.init(s_stack, S.stackOverflow);
     LvCounters cnt = {0, 0, 0, 0};
     unsigned long long phIt[3] = {0, 0, 0}, phLn[3] = {0, 0, 0};
     unsigned long long mayAxis = 0, mayBoth = 0, primHits = 0;
@@ -637,7 +636,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             {
                 const lv_ao_key key = keyW[owner];
                 best = lv_ao_key_t(key); // shrinks the slab interval of the following node steps
-                if (ANY_HIT && key != keyInit) { cur = LV_INVALID; st.sp = 0; }
+                if (ANY_HIT && key != keyInit) { cur = LV_INVALID; st.clear(); }
             }
             continue;
         }
@@ -653,7 +652,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             }
             if (nNode <= LV_HANDOVER_MAX_BUSY) { // subtree hand-over, as in lv_trace_closest (exchange slots: the idle s_gen)
                 const bool idle = cur == LV_INVALID;
-                const bool donor = !idle && st.sp > 0;
+                const bool donor = !idle && st.has_entries();
                 const unsigned long long mFree = __ballot(idle), mDonor = __ballot(donor);
                 const unsigned nPairs = min(unsigned(__popcll(mFree)), unsigned(__popcll(mDonor)));
                 if (nPairs) {
@@ -672,7 +671,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                             inv = lv_traversal_inv(mk3(r1.y, r2.x, r2.y));
                             oi = mk3(r0.x * inv.x, r0.y * inv.y, r1.x * inv.z);
                             best = lv_ao_key_t(keyW[owner]);
-                            st.sp = 0;
+                            st.clear();
                         }
                     }
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -753,7 +752,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                     r = genBase + gs;
                     owner = lane;
                     cur = 0;
-                    st.sp = 0;
+                    st.clear();
                     enq = false;
                     hasRay = true;
                     if (STATS) cnt.rays++;
@@ -3484,11 +3483,22 @@ static LvAoGeometry lv_ao_geometry(const lv_ctx* ctx, const LvUniforms& U, const
 }
 
 // ---------------------------------------------------------------- the global part of the traversal stacks
-// Bytes of the slab for one launch, one column of entries per thread (0: the LDS-staged part holds the whole stack, the tree is not
-// higher than that): a step of the 4-wide tree pushes at most 3 references per level
-static size_t lv_overflow_bytes(const lv_ctx* ctx, uint64_t gridBlocks, uint32_t ldsEntries, bool triangles) {
-    const uint64_t maxEntries = 3ull * uint64_t(triangles ? ctx->triWideDepth : ctx->wideDepth) + 2;
-    return maxEntries > ldsEntries ? size_t(gridBlocks) * LV_BLOCK * (maxEntries - ldsEntries) * 4 : 0;
+// Entries of one thread's slab column (0: the LDS window holds the whole stack).  A step of the 4-wide tree pushes at most 3
+// references per level: the logical stack never holds more than M = 3 * levels + 2 entries, and a step at level d (root: 0) finds at
+// most 3 d <= M - 5 of them.  The window is W = ldsSlots - 1 entries (slot 0: the sentinel) and a thread spills only at sp + 3 > ldsSlots,
+// i.e. with >= W - 2 entries in the window:
+//   M <= W: a step finds at most W - 5 entries, so nothing ever spills -- no slab, LvStackT never touches its pointer;
+//   else:   before a spill, spilled + (W - 2) <= entries <= M, so afterwards spilled <= M - (W - 2) + K; spills and refills move whole
+//           blocks of K = LV_STACK_SPILL_BLOCK, hence the column is that bound rounded up to a multiple of K.
+static uint64_t lv_overflow_entries(uint64_t wideLevels, uint32_t ldsSlots) {
+    const uint64_t M = 3ull * wideLevels + 2, W = ldsSlots - 1u, K = LV_STACK_SPILL_BLOCK;
+    return M > W ? (M - (W - 2) + K + K - 1) / K * K : 0;
+}
+// Bytes of the slab for one launch, one column per thread.  LvStackT addresses its column by 32-bit byte offsets from the slab's base:
+// a launch whose slab would not fit them is refused (lv_prepare_overflow, the asynchronous bake)
+static constexpr size_t LV_OVERFLOW_MAX_BYTES = 0xFFFFFFFFull;
+static size_t lv_overflow_bytes(const lv_ctx* ctx, uint64_t gridBlocks, uint32_t ldsSlots, bool triangles) {
+    return size_t(gridBlocks) * LV_BLOCK * lv_overflow_entries(triangles ? ctx->triWideDepth : ctx->wideDepth, ldsSlots) * 4;
 }
 // ... for every launch of a frame: lv_frame_render reserves ctx->stackOverflow once, BEFORE it builds a scene view, because a later,
 // larger request would free the slab under the views built before it.  Same geometries as the launches: lv_ao_geometry.
@@ -3516,6 +3526,9 @@ static int lv_prepare_overflow(lv_ctx* ctx, LvSceneDev& S, const char* launch, u
     S.stackOverflow = nullptr;
     const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, triangles);
     if (bytes == 0) return LV_OK;
+    if (bytes > LV_OVERFLOW_MAX_BYTES)
+        return lv_fail(ctx, LV_E_CAPACITY, "%s: the traversal stacks would need %llu bytes; a launch addresses at most 4 GiB of them", launch,
+                       (unsigned long long)bytes);
     if (!ctx->stackOverflow.ptr || ctx->stackOverflow.bytes < bytes)
         return lv_fail(ctx, LV_E_CAPACITY, "%s: the traversal stacks need %llu bytes, the frame reserved %llu", launch,
                        (unsigned long long)bytes, (unsigned long long)ctx->stackOverflow.bytes);
@@ -4943,6 +4956,95 @@ int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, f
     return LV_OK;
 }
 
+// ---------------------------------------------------------------- lv_selftest_stack: the traversal stack on scripts
+// One workgroup, every thread runs its own script on the stack type of the kernels (same members, same window and stride).
+template <int NLDS>
+__global__ __launch_bounds__(LV_BLOCK) void k_selftest_stack(unsigned* slab, const uint32_t* __restrict__ ops, uint32_t opsPerThread,
+                                                             uint32_t* __restrict__ outWords, uint32_t* __restrict__ outCounts) {
+    __shared__ unsigned s_stack[NLDS * LV_BLOCK];
+    LvStackT<NLDS, LV_BLOCK, true> st;
+    st.init(s_stack, slab);
+    const uint32_t* my = ops + size_t(threadIdx.x) * opsPerThread * 4;
+    uint32_t* out = outWords + size_t(threadIdx.x) * opsPerThread;
+    uint32_t pops = 0;
+    for (uint32_t i = 0; i < opsPerThread; i++) {
+        const uint32_t op = my[4 * i];
+        if ((op & 0xFFu) == LV_STACK_OP_PUSH3) st.push3(my[4 * i + 1], (op & 0x100u) != 0, my[4 * i + 2], (op & 0x200u) != 0, my[4 * i + 3], (op & 0x400u) != 0);
+        else if ((op & 0xFFu) == LV_STACK_OP_POP) out[pops++] = lv_pop_or_done(st);
+        else if ((op & 0xFFu) == LV_STACK_OP_CLEAR) st.clear();
+    }
+    outCounts[3 * threadIdx.x] = pops;
+    outCounts[3 * threadIdx.x + 1] = st.spills;
+    outCounts[3 * threadIdx.x + 2] = st.refills;
+}
+
+int lv_selftest_stack(lv_ctx* ctx, uint32_t instantiation, uint32_t wide_levels, const uint32_t* ops, uint32_t ops_per_thread,
+                      uint32_t* out_words, uint32_t* out_counts, uint64_t* out_info) {
+    if (!ctx) return LV_E_INVALID;
+    if (instantiation > LV_STACK_INST_TILE) return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: unknown instantiation %u", instantiation);
+    (void)hipSetDevice(ctx->device);
+    const uint32_t slots = instantiation == LV_STACK_INST_AO ? LV_AO_STACK_LDS : LV_STACK_LDS;
+    const uint64_t maxEntries = 3ull * wide_levels + 2, column = lv_overflow_entries(wide_levels, slots);
+    if (out_info) {
+        out_info[0] = slots - 1u;
+        out_info[1] = LV_STACK_SPILL_BLOCK;
+        out_info[2] = column;
+        out_info[3] = ctx->stackOverflow.bytes;   // what the context's launches have reserved so far
+        out_info[4] = ctx->wideDepth;
+        out_info[5] = ctx->triWideDepth;
+    }
+    if (ops_per_thread == 0) return LV_OK;
+    if (!ops || !out_words || !out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: null array");
+    if (wide_levels > 4096u || ops_per_thread > 65536u) return lv_fail(ctx, LV_E_CAPACITY, "lv_selftest_stack: script or depth too large");
+    // A script is run only if it stays inside what the slab bound covers: never more than 3 * wide_levels + 2 entries, no spill without
+    // a slab, no reference that reads as a marker or as "finished", nothing but clear after the pop that found the stack empty.
+    for (uint32_t t = 0; t < LV_BLOCK; t++) {
+        uint64_t depth = 0;
+        bool finished = false;
+        for (uint32_t i = 0; i < ops_per_thread; i++) {
+            const uint32_t* op = ops + (size_t(t) * ops_per_thread + i) * 4;
+            const uint32_t code = op[0] & 0xFFu;
+            if (code == LV_STACK_OP_END) continue;
+            if (code == LV_STACK_OP_CLEAR) { depth = 0; finished = false; continue; }
+            if (finished) return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: thread %u op %u follows a pop of the empty stack without clear", t, i);
+            if (code == LV_STACK_OP_POP) {
+                if (depth == 0) finished = true; else depth--;
+            } else if (code == LV_STACK_OP_PUSH3) {
+                if (column == 0 && depth + 3 > slots - 1u)
+                    return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: thread %u op %u would spill, but %u levels need no slab", t, i, wide_levels);
+                for (int k = 0; k < 3; k++)
+                    if (op[1 + k] == LV_INVALID || int32_t(op[1 + k]) >= int32_t(0x7C000000))
+                        return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: thread %u op %u pushes a word that is no reference", t, i);
+                depth += ((op[0] >> 8) & 1u) + ((op[0] >> 9) & 1u) + ((op[0] >> 10) & 1u);
+                if (depth > maxEntries)
+                    return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: thread %u op %u exceeds %llu entries", t, i, (unsigned long long)maxEntries);
+            } else {
+                return lv_fail(ctx, LV_E_INVALID, "lv_selftest_stack: thread %u op %u: unknown operation %u", t, i, code);
+            }
+        }
+    }
+    int rc;
+    hipStream_t st = ctx->stream;
+    const size_t opBytes = size_t(LV_BLOCK) * ops_per_thread * 16, wordBytes = size_t(LV_BLOCK) * ops_per_thread * 4, countBytes = size_t(LV_BLOCK) * 12;
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, opBytes + wordBytes + countBytes))) return rc;
+    const size_t slabBytes = size_t(LV_BLOCK) * column * 4;   // one workgroup: lv_overflow_bytes with gridBlocks = 1
+    if (slabBytes && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, slabBytes))) return rc;
+    char* base = (char*)ctx->scratchRays.ptr;
+    uint32_t* dOps = (uint32_t*)base;
+    uint32_t* dWords = (uint32_t*)(base + opBytes);
+    uint32_t* dCounts = (uint32_t*)(base + opBytes + wordBytes);
+    unsigned* slab = slabBytes ? (unsigned*)ctx->stackOverflow.ptr : nullptr;
+    LV_HIP(ctx, hipMemcpyAsync(dOps, ops, opBytes, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(dWords, 0, wordBytes + countBytes, st));
+    if (instantiation == LV_STACK_INST_AO) k_selftest_stack<LV_AO_STACK_LDS><<<1, LV_BLOCK, 0, st>>>(slab, dOps, ops_per_thread, dWords, dCounts);
+    else k_selftest_stack<LV_STACK_LDS><<<1, LV_BLOCK, 0, st>>>(slab, dOps, ops_per_thread, dWords, dCounts);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(out_words, dWords, wordBytes, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipMemcpyAsync(out_counts, dCounts, countBytes, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    return LV_OK;
+}
+
 // VulkanAmbientOcclusionBaker::bakeAoTexture (VulkanAmbientOcclusionBaker.cpp:193-262): maxNumIterations passes of the
 // baking shader, each averaging numAmbientOcclusionSamplesPerFrame rays per (parametrisation vertex, tube subdivision),
 // accumulated as a running mean.  Rays hit the triangle tubes (the reference binds the triangle TLAS, cpp:480) and run
@@ -5009,6 +5111,9 @@ int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async, bool inFrame) {
         // stack overflow slab of its own (the frames' slab is in use on the other stream)
         SA.stackOverflow = nullptr;
         const size_t bytes = lv_overflow_bytes(ctx, gridRays, LV_AO_STACK_LDS, true);
+        if (bytes > LV_OVERFLOW_MAX_BYTES)
+            return lv_fail(ctx, LV_E_CAPACITY, "RTAO prebaker: the traversal stacks would need %llu bytes; a launch addresses at most 4 GiB of them",
+                           (unsigned long long)bytes);
         if (bytes) {
             if ((rc = lv_buf_reserve(ctx, ctx->bakeOverflow, bytes))) return rc;
             SA.stackOverflow = (unsigned*)ctx->bakeOverflow.ptr;

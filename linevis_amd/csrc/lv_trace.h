@@ -213,53 +213,112 @@ __device__ __forceinline__ bool lv_ray_triangle(f3 o, f3 d, f3 inv, f3 v0, f3 v1
     return true;
 }
 
-// ---------------------------------------------------------------- traversal stack: LDS-staged, HBM overflow
-// Entry i of a thread lives at lds[i * LV_BLOCK] (conflict-free ds_read/write_b32 across the wave).  An LBVH over
-// N segments is usually ~log2(N)+10 deep, so LV_STACK_LDS = 32 entries cover the common case entirely in LDS; deeper
-// trees (up to 63 key bits + 32 duplicate-index bits) continue in a per-thread column of a global overflow slab that is
-// only allocated when the built tree is that deep.  All members are scalars so the struct lives in registers.
-// Pointers carry their address space so that pushes/pops compile to ds_write_b32 / ds_read_b32 and
-// global_store / global_load; with generic pointers the two pop paths were merged into one flat_load (which waits on
-// both the LDS and the vector-memory counter).
+// ---------------------------------------------------------------- traversal stack: a window in LDS, spilled to HBM in blocks
+// Slot i of a thread lives at lds[i * STRIDE] (conflict-free ds_read/write_b32 across the wave).  An LBVH over N segments is
+// usually ~log2(N)+10 deep, so the NLDS slots cover the common case entirely in LDS.  They are a WINDOW onto the top of the logical
+// stack: slot 0 holds a sentinel, slots 1 .. NLDS - 1 the topmost entries, and every push and pop touches LDS only.
+//   spill   a node step that finds no room for three references (sp + 3 > NLDS) first moves the bottom LV_STACK_SPILL_BLOCK entries
+//           of the window to the thread's column of the global slab ([entry][global thread], as before), shifts the rest down and
+//           pushes as usual.
+//   refill  a pop that meets the sentinel while entries are spilled reloads the last block and continues: LIFO order is kept
+//           exactly, so traversal order, counters and results do not depend on where an entry spent its time.
+// The number of spilled entries costs no register: it lives in the sentinel.  Slot 0 is LV_INVALID while nothing is spilled -- a pop
+// of it IS "finished", no sp == 0 select -- and LV_STACK_MARK | count otherwise.  A marker has bit 31 clear and bits 26-30 set:
+// node references and leaf indices stay below 2^26 (lv_set_segments / lv_set_triangles refuse more), leaf references and LV_INVALID
+// are negative as integers, so one signed compare tells a marker from every reference.  The marker never leaves pop().
+// Both slow paths sit behind branches that a wave skips when none of its lanes takes them, and recompute the thread's slab column
+// from the (wave-uniform) slab pointer and the launch geometry: nothing but sp and the LDS address is live across a descend loop.
+// Popping the sentinel leaves sp = 0: whoever starts a new traversal on the stack (next ray, hand-over taker) calls clear().
+// Slab size: lv_overflow_bytes (lv_render.hip) -- the host allocates it exactly when a spill can happen.
 typedef __attribute__((address_space(3))) unsigned lv_lds_u32;
 typedef __attribute__((address_space(1))) unsigned lv_glb_u32;
+#define LV_STACK_MARK 0x7C000000u
+#define LV_STACK_COUNT_MASK 0x03FFFFFFu
 
-template <int NLDS, int STRIDE = LV_BLOCK>
+template <int NLDS, int STRIDE = LV_BLOCK, bool COUNT = false>
 struct LvStackT {
     static constexpr int kLds = NLDS;
     static constexpr int kStride = STRIDE;
+    static constexpr int kBlock = LV_STACK_SPILL_BLOCK;
+    // a spill happens at sp >= NLDS - 2, i.e. with >= NLDS - 3 entries in the window, and must leave room for three pushes
+    static_assert(kBlock >= 3 && kBlock <= NLDS - 3, "LV_STACK_SPILL_BLOCK does not fit the LDS window");
     lv_lds_u32* lds;     // &s_stack[threadIdx.x]
-    lv_glb_u32* ovf;     // &overflow[global thread], entries strided by ovfStride; may be null if height <= NLDS
-    unsigned ovfStride;
-    int sp;
-    __device__ __forceinline__ void init(unsigned* ldsBase, unsigned* ovfBase, unsigned stride) {
-        lds = (lv_lds_u32*)ldsBase; ovf = (lv_glb_u32*)ovfBase; ovfStride = stride; sp = 0;
+    lv_lds_u32* base;    // s_stack: an address the compiler knows, so the slow paths recover the thread index from lds without keeping it
+    lv_glb_u32* slab;    // S.stackOverflow (wave-uniform); null when the tree is not higher than the window
+    int sp;              // next free slot
+    unsigned spills, refills;   // COUNT only (lv_selftest_stack)
+    __device__ __forceinline__ void init(unsigned* ldsArray, unsigned* slabBase) {
+        base = (lv_lds_u32*)ldsArray; lds = base + threadIdx.x; slab = (lv_glb_u32*)slabBase; spills = refills = 0;
+        clear();
     }
-    __device__ __forceinline__ void push(unsigned v) {
-        if (sp < NLDS) lds[sp * STRIDE] = v;
-        else ovf[size_t(sp - NLDS) * ovfStride] = v;
-        sp++;
+    // drops every entry, spilled ones included
+    __device__ __forceinline__ void clear() { lds[0] = LV_INVALID; sp = 1; }
+    __device__ __forceinline__ bool has_entries() const { return sp > 1 || (sp == 1 && int(lds[0]) >= int(LV_STACK_MARK)); }
+    // Slow paths.  They address the slab by 32-bit byte offsets from its (wave-uniform) base -- the host refuses a slab of 4 GiB or
+    // more (lv_overflow_bytes) -- and walk a column by adding the stride: with a 64-bit address per entry they needed registers that
+    // the kernels compiled to a register limit paid for in scratch, although the paths hardly ever run.
+    __device__ __forceinline__ unsigned column_offset() const { return (blockIdx.x * STRIDE + unsigned(lds - base)) * 4u; }
+    __device__ __forceinline__ void spill() {
+        const unsigned s0 = lds[0];
+        const unsigned count = int(s0) >= int(LV_STACK_MARK) ? (s0 & LV_STACK_COUNT_MASK) : 0u;
+        const unsigned stride = gridDim.x * STRIDE * 4u;
+        unsigned off = column_offset() + count * stride;
+        const char __attribute__((address_space(1)))* sb = (const char __attribute__((address_space(1)))*)slab;
+        _Pragma("unroll 1") for (int i = 0; i < kBlock; i++, off += stride) *(lv_glb_u32*)(sb + off) = lds[(1 + i) * STRIDE];
+        _Pragma("unroll 1") for (int j = 1 + kBlock; j < sp; j++) lds[(j - kBlock) * STRIDE] = lds[j * STRIDE];
+        sp -= kBlock;
+        lds[0] = LV_STACK_MARK | (count + kBlock);
+        if (COUNT) spills++;
     }
+    __device__ __forceinline__ unsigned refill(unsigned marker) {
+        const unsigned count = (marker & LV_STACK_COUNT_MASK) - kBlock;
+        const unsigned stride = gridDim.x * STRIDE * 4u;
+        unsigned off = column_offset() + count * stride;
+        const char __attribute__((address_space(1)))* sb = (const char __attribute__((address_space(1)))*)slab;
+        unsigned v = 0;
+        _Pragma("unroll 1") for (int i = 0; i < kBlock; i++, off += stride) {
+            v = *(const lv_glb_u32*)(sb + off);
+            lds[(1 + i) * STRIDE] = v;
+        }
+        lds[0] = count ? (LV_STACK_MARK | count) : LV_INVALID;
+        sp = kBlock;
+        if (COUNT) refills++;
+        return v;
+    }
+    // The three pushes of a node step, in two halves.  reserve3 makes room for three references (the only place that spills); write3
+    // stores them unconditionally and advances the stack pointer only for the references to keep.  lv_node_step calls reserve3 either
+    // before it fetches the node or right before write3, per walk (see there): where the spill's registers come on top of the
+    // kernel's busiest point decides whether a kernel compiled to a register limit gains scratch.
+    __device__ __forceinline__ void reserve3() {
+        if (__builtin_expect(sp + 3 > NLDS, 0)) spill();
+    }
+    __device__ __forceinline__ void write3(unsigned c3, bool keep3, unsigned c2, bool keep2, unsigned c1, bool keep1) {
+        lds[sp * STRIDE] = c3; sp += keep3 ? 1 : 0;
+        lds[sp * STRIDE] = c2; sp += keep2 ? 1 : 0;
+        lds[sp * STRIDE] = c1; sp += keep1 ? 1 : 0;
+    }
+    __device__ __forceinline__ void push3(unsigned c3, bool keep3, unsigned c2, bool keep2, unsigned c1, bool keep1) {
+        reserve3();
+        write3(c3, keep3, c2, keep2, c1, keep1);
+    }
+    // LV_INVALID: the stack is empty (the sentinel)
     __device__ __forceinline__ unsigned pop() {
         sp--;
-        unsigned v;
-        if (sp < NLDS) v = lds[sp * STRIDE];
-        else v = ovf[size_t(sp - NLDS) * ovfStride];
+        unsigned v = lds[sp * STRIDE];
+        if (__builtin_expect(int(v) >= int(LV_STACK_MARK), 0)) v = refill(v);
         return v;
     }
 };
 typedef LvStackT<LV_STACK_LDS> LvStack;
 // stack memory handed to the traversal routines by a kernel
 struct LvStackMem {
-    unsigned* lds;
-    unsigned* ovf;
-    unsigned ovfStride;
+    unsigned* lds;    // the kernel's s_stack array
+    unsigned* slab;
 };
 __device__ __forceinline__ LvStackMem lv_stack_mem(unsigned* sStack, unsigned* ovfSlab) {
     LvStackMem m;
-    m.lds = sStack + threadIdx.x;
-    m.ovfStride = gridDim.x * LV_BLOCK;
-    m.ovf = ovfSlab ? ovfSlab + (size_t(blockIdx.x) * LV_BLOCK + threadIdx.x) : nullptr;
+    m.lds = sStack;
+    m.slab = ovfSlab;
     return m;
 }
 
@@ -271,8 +330,11 @@ struct LvHit {
 };
 
 // Child references: index | LV_LEAF_BIT for leaves, LV_INVALID (which has the leaf bit set) = finished.
+// Precondition: the stack has not yet handed out its sentinel since the last init() / clear().  The pop that finds the stack empty
+// returns LV_INVALID ONCE and leaves sp = 0; a further pop would read below the thread's slots.  Every caller pops only while its
+// current reference is valid (a lane whose reference is LV_INVALID neither steps nor pops) and calls clear() before it starts anew.
 template <class STACK>
-__device__ __forceinline__ unsigned lv_pop_or_done(STACK& st) { return st.sp == 0 ? LV_INVALID : st.pop(); }
+__device__ __forceinline__ unsigned lv_pop_or_done(STACK& st) { return st.pop(); }
 
 // One node step on the compressed 4-wide LBVH: fetch the 64-byte node (4 x dwordx4), decode + slab-test the four child
 // boxes, continue with the nearest hit child and push the others.  Children may be leaves; the caller looks at the
@@ -343,6 +405,11 @@ __device__ __forceinline__ f3 lv_traversal_inv(f3 d) {
 template <bool STATS, int ORDERED = 1, class STACK>
 __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned node, f3 oi, f3 inv, float tMin, float tMax,
                                                  STACK& st, LvCounters& cnt) {
+    // Room for the three pushes is made before the node is fetched in k_ao_rays and in the all-hits / ordered walks, and after the
+    // slab test in the closest-hit walk of the tile kernels: measured per kernel on the register report (k_ao_rays and
+    // k_render_rt_mlat keep their scratch and waves per SIMD with the early check, k_render_rt with the late one; tools/isa_report.py)
+    constexpr bool RESERVE_EARLY = STACK::kLds != LV_STACK_LDS || ORDERED != 1;
+    if (RESERVE_EARLY) st.reserve3();
     const float4* p = S.nodes + 4 * size_t(node);
     const float4 q0 = p[0], q1 = p[1], q2 = p[2], cf = p[3];
     if (STATS) cnt.nodes++;
@@ -378,17 +445,8 @@ __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned n
         lv_cswap(k2, c2, k3, c3);
         lv_cswap(k0, c0, k2, c2);
     }
-    // Pushes: write unconditionally and advance the stack pointer only for real references (no branches) as long as
-    // the three slots are inside the LDS part; the rare deep case takes the checked path.
-    if (st.sp + 3 <= STACK::kLds) {
-        st.lds[st.sp * STACK::kStride] = c3; st.sp += (k3 < INF) ? 1 : 0;
-        st.lds[st.sp * STACK::kStride] = c2; st.sp += (k2 < INF) ? 1 : 0;
-        st.lds[st.sp * STACK::kStride] = c1; st.sp += (k1 < INF) ? 1 : 0;
-    } else {
-        if (k3 < INF) st.push(c3);
-        if (k2 < INF) st.push(c2);
-        if (k1 < INF) st.push(c1);
-    }
+    if (!RESERVE_EARLY) st.reserve3();
+    st.write3(c3, k3 < INF, c2, k2 < INF, c1, k1 < INF);
     if (k0 < INF) return c0;
     return lv_pop_or_done(st);
 }
@@ -692,7 +750,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
     f3 inv = FAST_INV ? lv_traversal_inv(d) : mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     f3 oi = mk3(o.x * inv.x, o.y * inv.y, o.z * inv.z);
     LvStack st;
-    st.init(sm.lds, sm.ovf, sm.ovfStride);
+    st.init(sm.lds, sm.slab);
     cm.ray[2 * lane] = make_float4(o.x, o.y, o.z, tMin);
     cm.ray[2 * lane + 1] = make_float4(d.x, d.y, d.z, tMax);
     cm.key[lane] = keyInit;
@@ -737,7 +795,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             const unsigned long long key = cm.key[owner];
             best = __uint_as_float(unsigned(key >> 32)); // shrinks the slab interval of the following node steps
-            if (ANY_HIT && key != keyInit) { cur = LV_INVALID; st.sp = 0; }
+            if (ANY_HIT && key != keyInit) { cur = LV_INVALID; st.clear(); }
             continue;
         }
         if (nNode == 0) break;
@@ -749,7 +807,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
         // who visits which subtree.
         if (nNode <= LV_HANDOVER_MAX_BUSY) {
             const bool idle = cur == LV_INVALID;
-            const bool donor = !idle && st.sp > 0;
+            const bool donor = !idle && st.has_entries();
             const unsigned long long mIdle = __ballot(idle), mDonor = __ballot(donor);
             const unsigned nPairs = min(unsigned(__popcll(mIdle)), unsigned(__popcll(mDonor)));
             if (nPairs) {
@@ -764,6 +822,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
                         const uint2 x = cm.xchg[r];
                         cur = x.x;
                         owner = x.y;
+                        st.clear();
                         const float4 ro = cm.ray[2 * owner], rd = cm.ray[2 * owner + 1];
                         inv = FAST_INV ? lv_traversal_inv(mk3(rd.x, rd.y, rd.z)) : mk3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
                         oi = mk3(ro.x * inv.x, ro.y * inv.y, ro.z * inv.z);
@@ -832,7 +891,7 @@ __device__ __forceinline__ void lv_trace_all(const LvSceneDev& S, float radius, 
     f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     f3 oi = mk3(o.x * inv.x, o.y * inv.y, o.z * inv.z);
     LvStack st;
-    st.init(sm.lds, sm.ovf, sm.ovfStride);
+    st.init(sm.lds, sm.slab);
     // every lane has its OWN interval [tMin, tMax) (depth slices): it travels with the ray, the payload words go in the
     // key slot (unused by the all-hits routine)
     cm.ray[2 * lane] = make_float4(o.x, o.y, o.z, tMin);
@@ -980,7 +1039,7 @@ __device__ __forceinline__ void lv_trace_all(const LvSceneDev& S, float radius, 
         if (nNode == 0) break;
         if (nNode <= HO_BUSY) { // subtree hand-over, as in lv_trace_closest
             const bool idle = cur == LV_INVALID;
-            const bool donor = !idle && st.sp > 0;
+            const bool donor = !idle && st.has_entries();
             const unsigned long long mIdle = __ballot(idle), mDonor = __ballot(donor);
             const unsigned nPairs = min(unsigned(__popcll(mIdle)), unsigned(__popcll(mDonor)));
             if (nPairs) {
@@ -995,6 +1054,7 @@ __device__ __forceinline__ void lv_trace_all(const LvSceneDev& S, float radius, 
                         const uint2 x = cm.xchg[r];
                         cur = x.x;
                         owner = x.y;
+                        st.clear();
                         const float4 ro = cm.ray[2 * owner], rd = cm.ray[2 * owner + 1];
                         inv = mk3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
                         oi = mk3(ro.x * inv.x, ro.y * inv.y, ro.z * inv.z);

@@ -25,6 +25,12 @@ PRESETS = {
     "inv_ieee": "-DLV_TRAVERSAL_INV_IEEE=1",                       # node-step reciprocals by IEEE division
     "key64": "-DLV_AO_KEY64=1",                                    # 64-bit (t, primitive) hit keys in k_ao_rays
     "inv_ieee_key64": "-DLV_TRAVERSAL_INV_IEEE=1,-DLV_AO_KEY64=1",
+    # traversal stack: entries per spilled block (default 4: spill4 is the regular build), LDS slots of k_ao_rays (default 16 = sentinel + 15 entries)
+    "spill4": "-DLV_STACK_SPILL_BLOCK=4",
+    "spill8": "-DLV_STACK_SPILL_BLOCK=8",
+    "spill12": "-DLV_STACK_SPILL_BLOCK=12",
+    "ao_lds15": "-DLV_AO_STACK_LDS=15",
+    "ao_lds16": "-DLV_AO_STACK_LDS=16",
 }
 
 
