@@ -42,6 +42,9 @@ extern "C" {
 /* Moment-based order-independent transparency (src/Renderers/OIT/MBOITRenderer.cpp) with power moments stored as float32, over the
  * fragments of mode 2's rasterised prism; see mboit_num_moments and lv_mboit_resolve_buffers below */
 #define LV_RENDERING_MODE_MBOIT 6
+/* Weighted Blended OIT (src/Renderers/OIT/WBOITRenderer.cpp): the weighted average of all fragments of mode 2's rasterised prism per
+ * pixel, in 5 * 8 bytes per pixel; see wboit_depth_weight, lv_wboit_get_buffers and lv_wboit_resolve_buffers below */
+#define LV_RENDERING_MODE_WBOIT 8
 /* Atomic Loop 64 (src/Renderers/OIT/AtomicLoop64Renderer.cpp): the K nearest fragments of mode 2's rasterised prism per pixel,
  * exactly, in K * 8 bytes per pixel; see atomic_loop_num_layers, lv_atomic_loop_get_buffers and lv_atomic_loop_resolve_buffers below */
 #define LV_RENDERING_MODE_ATOMIC_LOOP_64 10
@@ -308,6 +311,31 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   the resolve.  Limit: the sums are exact for up to 131071 kept fragments on a pixel; a pixel with more sets the flag of
  *   mboit_fragment_storage = streamed below, with the same contract (LV_E_CAPACITY from lv_render; the flag stays with the frame
  *   for the asynchronous entry points; a later successful frame clears it).
+ *   wboit_depth_weight: "reference" (default) | "opengl": the depth weight of rendering mode 8 (WBOITGather.glsl:21-24); anything
+ *   else is LV_E_INVALID and the old value stays; modes other than 8 ignore it.  Mode 8 adds, per pixel, ALL fragments the fragment
+ *   stage of mode 2 produces (the `kept` rules only: WBOITGather.glsl has no alpha < 0.001 discard, as mode 6; RTAO, depth cues,
+ *   band data and rotating helicity bands as in mode 2) into five sums and keeps no fragment.  Per fragment with the straight colour
+ *   (r, g, b, alpha) and the window depth z of mode 3, float32, one operation at a time, left to right: A = min(1, alpha) * 8 +
+ *   0.01; B = ((2 * z - 1) * 0.95) - 1 under "reference" (the line the shader runs, with Vulkan's z in [0, 1]) or ((-z) * 0.95) + 1
+ *   under "opengl" (the line the shader keeps as a comment); raw = (((((A * A) * A) * 1e8) * B) * B) * B; w = min(max(raw, 0.01),
+ *   300), a NaN gives 0.01.  Under "reference" B lies in [-1.95, -0.05], raw is negative and w = 0.01 for every fragment a valid
+ *   camera can produce: the reference's frame is the alpha-weighted average of the colours.  Terms, in the
+ *   2^-36 fixed point of mode 6 (`fixed`: saturation at +-1024): SR += fixed((r * alpha) * w), SG += fixed((g * alpha) * w), SB +=
+ *   fixed((b * alpha) * w), SA += fixed(alpha * w).  Rule this build owns: the reference multiplies 1 - alpha into the revealage in
+ *   the blend unit in the order of the racing invocations, and a float product depends on that order; here SL += the term of t = 1 -
+ *   alpha: fixed(1024) for t <= 0, 0 for t >= 1 or a NaN, fixed(-log(t)) otherwise (the log of mode 6), and the revealage is R =
+ *   exp(-unfixed(SL)).  All sums are 64-bit integers: any order and any split of the fragments gives the same bits.  Resolve
+ *   (WBOITResolve.glsl:38-48, then BACK_TO_FRONT_STRAIGHT_ALPHA over the clear colour): a pixel without fragments or with R > 0.9999
+ *   is the clear colour; otherwise c = unfixed(S) / max(unfixed(SA), 1e-5) per channel, a = 1 - R, out.rgb = c * a + clear.rgb * (1
+ *   - a), out.a = a + clear.a * (1 - a), stored as RGBA8 like every frame.  (The shader's isinf branch cannot be reached: the terms
+ *   saturate.)  Memory: 5 * 8 bytes per pixel of the viewport padded to ppll_tile_width x ppll_tile_height plus the two 4-byte
+ *   per-pixel words of mode 2; nothing grows with the number of fragments.  One rasteriser launch per frame, no host
+ *   synchronisation.  The pool options (ppll_expected_avg_depth_complexity, ppll_max_num_frags, sorting_mode) have no effect;
+ *   ppll_prism_rasteriser = lbvh, ppll_fragment_source = capsule_entry and band data with rotating helicity bands return
+ *   LV_E_INVALID at render time (the context stays usable).  Statistics: fragments = the kept fragments, ppll_pool_nodes = 0,
+ *   max_depth_complexity.  Timers: LV_KERNEL_PPLL_RASTER times the pass (with the tile marking and segment culling of a sharded
+ *   frame), LV_KERNEL_PPLL_RESOLVE the resolve.  Limit: the sums are exact for up to 131071 kept fragments on a pixel; a pixel with
+ *   more sets the flag of mboit_fragment_storage = streamed below, with mode 10's contract.
  *   mboit_num_moments: 4 | 6 | 8 power moments of rendering mode 6 (default 4)   (MBOITRenderer.cpp:41-45).  Mode 6 sweeps, per
  *   pixel, ALL fragments the fragment stage of mode 2 produces (the alpha < 0.001 discard of modes 2 and 3 is not MBOIT's; its own
  *   rules are transmittance > 0.9999999 per fragment in the moment pass and b_0 < 0.00100050033 per pixel) twice: power moments of
@@ -721,6 +749,18 @@ int lv_atomic_loop_get_buffers(lv_ctx* ctx, uint64_t* out_slots, uint64_t* out_t
  * atomic_loop_num_layers.  out_slots (w * h * K) and out_tail (w * h * 5) may be NULL. */
 int lv_atomic_loop_resolve_buffers(lv_ctx* ctx, const uint64_t* keys, uint64_t num_keys, const uint64_t* offsets, uint32_t w,
                                    uint32_t h, uint8_t* out_rgba8, uint64_t* out_slots, uint64_t* out_tail);
+/* The sums and counts of the last frame when that was a mode-8 frame over the whole viewport, row-major: out_sums = width * height *
+ * 5 sums {SR, SG, SB, SA, SL} (the 2^-36 fixed point), out_counts = width * height kept-fragment counts.  LV_E_STATE when the last
+ * frame was anything else (another mode, a tile list that does not cover the viewport, a multi-device handle); LV_E_INVALID for a
+ * null pointer or capacity_pixels below width * height; LV_E_CAPACITY when a pixel of that frame holds more than 131071 kept
+ * fragments.  Synchronises the context's stream. */
+int lv_wboit_get_buffers(lv_ctx* ctx, int64_t* out_sums, uint32_t* out_counts, uint64_t capacity_pixels);
+/* Test entry point of mode 8's accumulation and resolve: pixel p = y * w + x of the w x h rectangle owns entries [offsets[p],
+ * offsets[p + 1]) (offsets: w * h + 1 values from 0 to num_entries); an entry is 5 float words {r, g, b, alpha, window depth}.  The
+ * fragments are added on the device, one lane per fragment with all lanes racing, under wboit_depth_weight, then resolved over the
+ * background.  At most 131071 entries per pixel: more returns LV_E_CAPACITY (the resolve's flag).  out_sums (w * h * 5) may be NULL. */
+int lv_wboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w, uint32_t h,
+                             uint8_t* out_rgba8, int64_t* out_sums);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

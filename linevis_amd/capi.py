@@ -17,6 +17,7 @@ LV_OK = 0
 MODE_PPLL = 2          # RENDERING_MODE_PER_PIXEL_LINKED_LIST, src/Renderers/RenderingModes.hpp:32-53
 MODE_MLAB = 3          # RENDERING_MODE_MLAB (Multi-Layer Alpha Blending over mode 2's fragments)
 MODE_MBOIT = 6         # RENDERING_MODE_MBOIT (moment-based OIT, power moments as float32, over mode 2's fragments)
+MODE_WBOIT = 8         # RENDERING_MODE_WBOIT (weighted blended OIT: five 64-bit sums per pixel over mode 2's fragments)
 MODE_ATOMIC_LOOP_64 = 10   # RENDERING_MODE_ATOMIC_LOOP_64 (the K nearest fragments of mode 2 in 64-bit atomicMin slots)
 MODE_RAY_TRACER = 11   # RENDERING_MODE_VULKAN_RAY_TRACER
 
@@ -105,7 +106,7 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_wboit_get_buffers", "lv_wboit_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -188,6 +189,8 @@ def load():
         ("lv_atomic_loop_get_num_layers", [vp, C.POINTER(u32)]),
         ("lv_atomic_loop_get_buffers", [vp, vp, vp, u64]),
         ("lv_atomic_loop_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp, vp]),
+        ("lv_wboit_get_buffers", [vp, vp, vp, u64]),
+        ("lv_wboit_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -656,6 +659,27 @@ class Context:
         tail = np.zeros((h, w, 5), dtype=np.uint64)
         self._ck(self.L.lv_atomic_loop_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(slots), _p(tail)))
         return out, slots, tail
+
+    def wboit_buffers(self):
+        """The sums and counts of the last mode-8 frame over the whole viewport (lv_wboit_get_buffers): ((height, width, 5) int64
+        {SR, SG, SB, SA, SL} in the 2^-36 fixed point, (height, width) uint32 kept-fragment counts)."""
+        sums = np.zeros((self.height, self.width, 5), dtype=np.int64)
+        counts = np.zeros((self.height, self.width), dtype=np.uint32)
+        self._ck(self.L.lv_wboit_get_buffers(self.h, _p(sums), _p(counts), self.width * self.height))
+        return sums, counts
+
+    def wboit_resolve(self, entries, offsets, w, h):
+        """Mode 8's accumulation and resolve of caller-supplied fragments (lv_wboit_resolve_buffers) under wboit_depth_weight:
+        entries = (n, 5) float32 {r, g, b, alpha, window depth}, pixel p = y * w + x owns entries[offsets[p]:offsets[p + 1]].
+        Returns ((h, w, 4) uint8, (h, w, 5) int64 sums)."""
+        e = np.ascontiguousarray(entries, dtype=np.float32).reshape(-1, 5)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if o.shape[0] != w * h + 1:
+            raise ValueError("offsets must hold w * h + 1 values")
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        sums = np.zeros((h, w, 5), dtype=np.int64)
+        self._ck(self.L.lv_wboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(sums)))
+        return out, sums
 
     def svgf_denoise(self, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history):
         """One SVGF denoise() on caller-supplied images (lv_svgf_denoise_buffers): noisy (h, w), normal_depth (h, w, 4), flow_fwidth

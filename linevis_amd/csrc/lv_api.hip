@@ -114,7 +114,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
-            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
+            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
@@ -661,6 +661,11 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // numLayers of the Atomic Loop 64 renderer (rendering mode 10): default 8 (AtomicLoop64Renderer.hpp:112), 1 ... 64 as mode 3
         if (!parseUint(value, u) || u == 0 || u > 64) return bad();
         o.al64NumLayers = u;
+    } else if (k == "wboit_depth_weight") {
+        // the depth weight of the WBOIT renderer (rendering mode 8): the line WBOITGather.glsl:23 runs, or the one it keeps as a comment
+        if (strcmp(value, "reference") == 0) o.wboitOpenglWeight = false;
+        else if (strcmp(value, "opengl") == 0) o.wboitOpenglWeight = true;
+        else return bad();
     } else if (k == "mboit_num_moments") {
         // numMoments of the MBOIT renderer (rendering mode 6): the combo box offers 4, 6 and 8 (MBOITRenderer.cpp:41,560-566)
         if (!parseUint(value, u) || (u != 4 && u != 6 && u != 8)) return bad();
@@ -949,10 +954,10 @@ int lv_render(lv_ctx* ctx, int mode, uint32_t x0, uint32_t y0, uint32_t w, uint3
     if ((rc = lv_render_device(ctx, mode, x0, y0, w, h, ctx->outDev.ptr))) return rc;
     LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, size_t(w) * h * 4, hipMemcpyDeviceToHost, ctx->stream));
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // mboit_fragment_storage = streamed and mode 10: the resolve's overflow flag (the frame is synchronised anyway)
+    // mboit_fragment_storage = streamed, mode 8 and mode 10: the resolve's overflow flag (the frame is synchronised anyway)
     for (int r = 0; r < lv_multi_num_ranks(ctx); r++) {
         lv_ctx* c = lv_multi_rank(ctx, r);
-        if (!c->mboitStreamLast && !c->al64Last) continue;
+        if (!c->mboitStreamLast && !c->al64Last && !c->wboitLast) continue;
         (void)hipSetDevice(c->device);
         rc = lv_mboit_stream_overflow(c);
         (void)hipSetDevice(ctx->device);
@@ -1015,6 +1020,8 @@ static int lv_get_stats_impl(lv_ctx* ctx, lv_stats* out, bool aggregate) {
         s.mboit_degenerate_pixels = hc.mboitDegenerate;
         if (ctx->mboitStreamLast && hc.mboitOverflow)
             return lv_fail(ctx, LV_E_CAPACITY, "MBOIT (streamed): a pixel of the last frame is covered by more than 131071 kept fragments");
+        if (ctx->wboitLast && hc.mboitOverflow)
+            return lv_fail(ctx, LV_E_CAPACITY, "WBOIT: a pixel of the last frame is covered by more than 131071 kept fragments");
         if (ctx->al64Last && hc.mboitOverflow)
             return lv_fail(ctx, LV_E_CAPACITY, "Atomic Loop 64: a pixel of the last frame is covered by more than 131071 kept fragments");
         for (int k = 0; k < 3; k++) { s.ao_phase_iterations[k] = hc.aoPhaseIters[k]; s.ao_phase_lanes[k] = hc.aoPhaseLanes[k]; }
@@ -1527,6 +1534,22 @@ int lv_atomic_loop_resolve_buffers(lv_ctx* ctx, const uint64_t* keys, uint64_t n
     if ((num_keys && !keys) || !offsets || !out_rgba8 || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
     (void)hipSetDevice(ctx->device);
     return lv_frame_al64_resolve_only(ctx, keys, num_keys, offsets, w, h, out_rgba8, out_slots, out_tail);
+}
+
+int lv_wboit_get_buffers(lv_ctx* ctx, int64_t* out_sums, uint32_t* out_counts, uint64_t capacity_pixels) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out_sums || !out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_wboit_get_buffers: null output");
+    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_wboit_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_wboit_buffers(ctx, out_sums, out_counts, capacity_pixels);
+}
+
+int lv_wboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w, uint32_t h,
+                             uint8_t* out_rgba8, int64_t* out_sums) {
+    if (!ctx) return LV_E_INVALID;
+    if ((num_entries && !entries) || !offsets || !out_rgba8 || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_wboit_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_sums);
 }
 
 int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_depth,

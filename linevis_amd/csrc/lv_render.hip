@@ -24,6 +24,7 @@
 #include "lv_tile.h"
 #include "lv_mboit.h"
 #include "lv_al64.h"
+#include "lv_wboit.h"
 
 namespace {
 
@@ -3114,6 +3115,245 @@ __global__ __launch_bounds__(LV_BLOCK) void k_al64_read(const unsigned long long
     for (uint32_t i = 0u; i < LV_AL64_TAIL; i++) outTail[p * LV_AL64_TAIL + i] = a[K + i];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Weighted Blended OIT (rendering mode 8, WBOITRenderer): every per-pixel quantity is a sum (lv_wboit.h).  5 x 8 B per padded pixel
+// (addressed like ppllCount), no fragment pool, no regrowth, no read-back; ppllCount is the 32-bit count of the kept fragments.
+//   k_wboit_stream_pass  the loop of k_al64_stream_pass (stages A and B through the lv_seg_walk_* / lv_seg_pair_coverage helpers, the
+//                        second LDS queue, stage C one lane per fragment) with lv_wboit_add as the fragment's store; ONE launch per
+//                        frame.  A third copy of the loop: the other two must compile as they do, and folding the three into one
+//                        skeleton is a refactoring of its own, gated on identical device assembly
+//   k_wboit_resolve      the cells and groups of k_al64_resolve over the frame's tile list: lv_wboit_resolve_pixel, the maximum
+//                        count and the overflow flag (a count above LV_WBOIT_MAX_COUNT)
+// The sums are zeroed per frame (a memset) and not by the resolve: a tile list may repeat or overlap pixels.
+template <int NT, int SHADE, int FAST>
+__global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_wboit_stream_pass(const LvUniforms U, const LvSceneDev S,
+                                                                   const uint32_t* __restrict__ startOffset,
+                                                                   uint32_t* __restrict__ fragCount, unsigned long long* sums,
+                                                                   LvDevCounters* dc, uint32_t allRequested,
+                                                                   const uint32_t* __restrict__ leafList, uint32_t weightMode,
+                                                                   uint32_t collectStats) {
+    __shared__ uint32_t s_qLeaf[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE], s_qPix[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE];
+    __shared__ uint32_t s_fFrag[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE], s_fPix[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE];
+    __shared__ float s_seg[LV_BLOCK / LV_WAVE][20][LV_WAVE];
+    __shared__ float s_prismRing[4 * LV_PRISM_MAX_SUBDIV];
+    // what stages A and B keep per lane, parked here while stage C runs (as k_mboit_stream_pass, for the registers of stage C)
+    __shared__ uint32_t s_park[19][LV_BLOCK];
+    if (threadIdx.x < LV_PRISM_MAX_SUBDIV) {
+        s_prismRing[threadIdx.x] = S.prism.c[threadIdx.x];
+        s_prismRing[LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.s[threadIdx.x];
+        s_prismRing[2 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.cp[threadIdx.x];
+        s_prismRing[3 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.sn[threadIdx.x];
+    }
+    __syncthreads();
+    const LvPrismDev& R = S.prism;
+    const uint32_t N = NT > 0 ? uint32_t(NT) : R.n;
+    const unsigned lane = lv_lane();
+    // (the wave's index as a scalar: the five LDS bases and the item counter below then hold no vector registers either)
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t* qLeaf = s_qLeaf[wave];
+    uint32_t* qPix = s_qPix[wave];
+    uint32_t* fFrag = s_fFrag[wave];
+    uint32_t* fPix = s_fPix[wave];
+    float (*segLds)[LV_WAVE] = s_seg[wave];
+    const f3 o = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
+    // the frame's set-up constants are the same in every lane: kept in scalar registers, so that the 15 of them do not hold vector
+    // registers across stage C
+    auto uniform = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
+    float mx[4], my[4], mw[4];
+    lv_clip_rows(U, mx, my, mw);
+#pragma unroll
+    for (int c = 0; c < 4; c++) { mx[c] = uniform(mx[c]); my[c] = uniform(my[c]); mw[c] = uniform(mw[c]); }
+    const float halfW = uniform(0.5f * float(U.width)), halfH = uniform(0.5f * float(U.height));
+    const float wEps = uniform(1e-3f * U.nearDist);
+    const float tLo = 0.0001f, tHi = __uint_as_float(__float_as_uint(1000.0f) + 1u);
+    const bool stats = collectStats != 0u;
+    unsigned qHead = 0u, qCount = 0u;   // (pixel, segment) pairs (wave-uniform)
+    unsigned fHead = 0u, fCount = 0u;   // covered triangles (wave-uniform)
+    // the frame's counters, per wave (ballots: wave-uniform values need no vector registers across the stages)
+    unsigned long long tests = 0, hits = 0;
+    uint32_t keptSum = 0u;
+    // stage A's walk over the lane's segment: candidate rectangle and oriented box, position in it
+    uint32_t leafA = 0u;
+    LvSegWalk w = {};
+    int px = 0, py = 0;
+    bool more = false;
+
+    // stage C on the m <= 64 oldest fragments of the queue: shaded as k_ppll_shade_prism<..., LV_ENTRY_MBOIT> shades them (only the
+    // `kept` rules discard: WBOITGather.glsl has no alpha test), the window depth of mode 3, the five terms added.
+    // (One call site, as in k_mboit_stream_pass.)
+    auto fragmentStage = [&](unsigned m) __attribute__((always_inline)) {
+        bool hit = false;
+        if (lane < m) {
+            const unsigned q = (fHead + lane) & (LV_MBOIT_STREAM_QUEUE - 1u);
+            const uint32_t w0 = fPix[q], w1 = fFrag[q];
+            const uint32_t px = w0 & 0xFFFFu, py = w0 >> 16;
+            const uint32_t leaf = w1 & 0x03FFFFFFu, tt = w1 >> 26;
+            const float aoTexel = (U.useAmbientOcclusion && !U.aoPrebaked) ? S.ao[size_t(py) * U.width + px] : 1.0f;
+            f3 oo, d;
+            lv_primary_ray(U, px, py, 0.5f, 0.5f, oo, d);
+            const LvRasterQuad rq = lv_make_raster_quad(U, px, py);
+            bool kept;
+            float depth;
+            const f4 color = lv_shade_prism<SHADE, FAST>(S, U, s_prismRing, aoTexel, o, d, tLo, tHi, leaf, tt, rq, U.ppllRasterColour != 0u, depth, kept);
+            hit = kept;
+            if (kept) {
+                const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+                const float z = lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
+                lv_wboit_add(sums + size_t(addr) * LV_WBOIT_SUMS, color, z, weightMode);
+                atomicAdd(&fragCount[addr], 1u);
+            }
+        }
+        const uint32_t keptNow = uint32_t(__popcll(__ballot(hit)));
+        keptSum += keptNow;
+        if (stats) hits += (unsigned long long)keptNow;
+        fHead = (fHead + m) & (LV_MBOIT_STREAM_QUEUE - 1u);
+        fCount -= m;
+    };
+
+    // stage B on the m <= 64 oldest pairs of the queue (k_mboit_stream_pass's: the covered triangles go to the second queue);
+    // flush: the wave's last batch -- stage C also takes what is left in its queue
+    auto coverageStage = [&](unsigned m, bool flush) __attribute__((always_inline)) {
+        unsigned mask = 0u;
+        uint32_t leaf = 0u, pix = 0u;
+        if (lane < m) {
+            mask = lv_seg_pair_coverage<NT>(R, segLds, qLeaf, qPix, (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u), o, leaf, pix);
+        }
+        if (stats) tests += m;
+        while (true) {
+            const bool hit = mask != 0u;
+            const unsigned long long hm = __ballot(hit);
+            if (hm == 0ull && !(flush && fCount > 0u)) break;
+            if (hit) {
+                const unsigned tt = unsigned(__ffs(int(mask))) - 1u;
+                mask &= mask - 1u;
+                const unsigned q = (fHead + fCount + unsigned(__popcll(hm & ((1ull << lane) - 1ull)))) & (LV_MBOIT_STREAM_QUEUE - 1u);
+                fPix[q] = pix;
+                fFrag[q] = leaf | (tt << 26);
+            }
+            fCount += unsigned(__popcll(hm));
+            if (fCount >= LV_WAVE || hm == 0ull) {
+                uint32_t* park = &s_park[0][threadIdx.x];
+                const float pf[8] = {w.ax, w.ay, w.cx0, w.cy0, w.aMid, w.aHalf, w.nMid, w.nHalf};
+                const uint32_t pu[11] = {mask, leaf, pix, leafA, uint32_t(w.x0), uint32_t(w.x1), uint32_t(w.y0), uint32_t(w.y1),
+                                         uint32_t(px), uint32_t(py), more ? 1u : 0u};
+#pragma unroll
+                for (int i = 0; i < 8; i++) park[i * LV_BLOCK] = __float_as_uint(pf[i]);
+#pragma unroll
+                for (int i = 0; i < 11; i++) park[(8 + i) * LV_BLOCK] = pu[i];
+                fragmentStage(fCount < LV_WAVE ? fCount : LV_WAVE);
+                w.ax = __uint_as_float(park[0]); w.ay = __uint_as_float(park[LV_BLOCK]); w.cx0 = __uint_as_float(park[2 * LV_BLOCK]);
+                w.cy0 = __uint_as_float(park[3 * LV_BLOCK]); w.aMid = __uint_as_float(park[4 * LV_BLOCK]); w.aHalf = __uint_as_float(park[5 * LV_BLOCK]);
+                w.nMid = __uint_as_float(park[6 * LV_BLOCK]); w.nHalf = __uint_as_float(park[7 * LV_BLOCK]);
+                mask = park[8 * LV_BLOCK]; leaf = park[9 * LV_BLOCK]; pix = park[10 * LV_BLOCK]; leafA = park[11 * LV_BLOCK];
+                w.x0 = int(park[12 * LV_BLOCK]); w.x1 = int(park[13 * LV_BLOCK]); w.y0 = int(park[14 * LV_BLOCK]); w.y1 = int(park[15 * LV_BLOCK]);
+                px = int(park[16 * LV_BLOCK]); py = int(park[17 * LV_BLOCK]); more = park[18 * LV_BLOCK] != 0u;
+            }
+        }
+        qHead = (qHead + m) & (LV_PRISM_RASTER_QUEUE - 1u);
+        qCount -= m;
+    };
+
+    const uint32_t waveId = blockIdx.x * (LV_BLOCK / LV_WAVE) + wave, numWaves = gridDim.x * (LV_BLOCK / LV_WAVE);
+    const uint32_t numItems = leafList ? dc->prismListCount : S.numSegs;
+    for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
+        const bool valid = itemBase + lane < numItems;
+        const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
+        leafA = leaf;
+        w = lv_seg_walk_setup(U, S, segLds, mx, my, mw, halfW, halfH, wEps, N, valid, leaf, lane);
+        px = w.x0; py = w.y0;
+        more = valid && w.x1 >= w.x0 && w.y1 >= w.y0;
+        const bool lastItem = itemBase + numWaves * LV_WAVE >= numItems;   // (overflow: numItems < 2^26)
+        while (true) {
+            const bool drain = !__any(more);   // every rectangle walked: the rest of the pairs, 64 at a time
+            const bool cand = more && lv_seg_walk_candidate(U, w, px, py, allRequested, startOffset);
+            const unsigned long long cm = __ballot(cand);
+            if (cand) {
+                const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
+                qLeaf[q] = leafA | (lane << 26);
+                qPix[q] = uint32_t(px) | (uint32_t(py) << 16);
+            }
+            qCount += unsigned(__popcll(cm));
+            if (qCount >= LV_WAVE || drain) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE, lastItem && drain && qCount <= LV_WAVE);
+            if (drain && qCount == 0u) break;   // (the next 64 segments replace the frames in LDS)
+            if (more) more = lv_seg_walk_advance(w, px, py);
+        }
+    }
+    if (lane == 0u && keptSum > 0u) atomicAdd(&dc->fragCounter, keptSum);   // every kept fragment
+    if (stats) {
+        if (lane == 0u && tests) atomicAdd(&dc->prims, tests);
+        if (lane == 0u && hits) atomicAdd(&dc->hits, hits);
+    }
+}
+
+// One lane per pixel, one wave per workgroup, the cells and groups of k_al64_resolve
+__global__ __launch_bounds__(LV_WAVE) void k_wboit_resolve(const LvUniforms U, const LvTiles T, const unsigned long long* __restrict__ sums,
+                                                           const uint32_t* __restrict__ fragCount, uint32_t* __restrict__ out,
+                                                           uint32_t numGroups, LvDevCounters* dc) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t maxCount = 0u;
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        const bool inTile = lx < T.tileW && ly < T.tileH;
+        if (!__any(inTile)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        const uint32_t outIndex = (tile * T.tileH + ly) * T.tileW + lx;
+        if (!inTile) continue;
+        uint32_t packed;
+        if (x < U.width && y < U.height) {
+            const uint32_t addr = lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+            const uint32_t count = fragCount[addr];
+            maxCount = max(maxCount, count);
+            packed = lv_wboit_resolve_pixel(U, sums + size_t(addr) * LV_WBOIT_SUMS, count);
+        } else {
+            f4 r;
+            r.x = U.background[0]; r.y = U.background[1]; r.z = U.background[2]; r.w = U.background[3];
+            packed = lv_pack_unorm4x8(r);
+        }
+        out[outIndex] = packed;
+    }
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) maxCount = max(maxCount, (uint32_t)__shfl_xor(maxCount, ofs, 64));
+    if (lane == 0 && maxCount > 0u) atomicMax(&dc->maxDepthComplexity, maxCount);
+    if (lane == 0 && maxCount > LV_WBOIT_MAX_COUNT) atomicOr(&dc->mboitOverflow, 1u);
+}
+
+// lv_wboit_resolve_buffers: one lane per given fragment {r, g, b, alpha, window depth}, all lanes racing; pixel = the run of `offsets`
+// that holds the fragment (binary search over the numPixels + 1 ascending offsets on the device)
+__global__ __launch_bounds__(LV_BLOCK) void k_wboit_add_given(const float* __restrict__ entries, uint64_t numEntries,
+                                                             const unsigned long long* __restrict__ offsets, uint32_t numPixels,
+                                                             unsigned long long* sums, uint32_t* __restrict__ fragCount,
+                                                             uint32_t weightMode) {
+    const uint64_t i = uint64_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (i >= numEntries) return;
+    uint32_t lo = 0u, hi = numPixels;   // the last p in [0, numPixels) with offsets[p] <= i  (offsets[0] = 0, offsets[numPixels] = numEntries > i)
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    const float* e = entries + size_t(i) * 5u;
+    f4 color;
+    color.x = e[0]; color.y = e[1]; color.z = e[2]; color.w = e[3];
+    lv_wboit_add(sums + size_t(lo) * LV_WBOIT_SUMS, color, e[4], weightMode);
+    atomicAdd(&fragCount[lo], 1u);
+}
+
+// lv_wboit_get_buffers: the five sums and the count of every pixel of the viewport, row-major
+__global__ __launch_bounds__(LV_BLOCK) void k_wboit_read(const unsigned long long* __restrict__ sums, const uint32_t* __restrict__ fragCount,
+                                                        uint32_t width, uint32_t height, uint32_t paddedW, uint32_t tileW, uint32_t tileH,
+                                                        unsigned long long* __restrict__ outSums, uint32_t* __restrict__ outCounts) {
+    const size_t p = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (p >= size_t(width) * height) return;
+    const uint32_t x = uint32_t(p % width), y = uint32_t(p / width);
+    const uint32_t addr = lv_ppll_addr(x, y, paddedW, tileW, tileH);
+    for (uint32_t i = 0u; i < LV_WBOIT_SUMS; i++) outSums[p * LV_WBOIT_SUMS + i] = sums[size_t(addr) * LV_WBOIT_SUMS + i];
+    if (outCounts) outCounts[p] = fragCount[addr];
+}
+
 // ================================================================ depth range
 __global__ __launch_bounds__(LV_BLOCK) void k_depth_minmax(const LvUniforms U, const lv_line_point* __restrict__ points,
                                                            uint32_t numPoints, LvDevCounters* dc) {
@@ -4083,14 +4323,14 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
     return LV_OK;
 }
 
-// the overflow flag of the last frame when that was a streamed mode-6 frame or a mode-10 frame (host-synchronous)
+// the overflow flag of the last frame when that was a streamed mode-6 frame, a mode-8 or a mode-10 frame (host-synchronous)
 int lv_mboit_stream_overflow(lv_ctx* ctx) {
-    if ((!ctx->mboitStreamLast && !ctx->al64Last) || !ctx->counters.ptr) return LV_OK;
+    if ((!ctx->mboitStreamLast && !ctx->al64Last && !ctx->wboitLast) || !ctx->counters.ptr) return LV_OK;
     uint32_t flag = 0u;
     LV_HIP(ctx, hipMemcpy(&flag, &((const LvDevCounters*)ctx->counters.ptr)->mboitOverflow, 4, hipMemcpyDeviceToHost));
     if (flag)
         return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than %u kept fragments (the 64-bit sums are "
-                                           "exact up to that count)", ctx->al64Last ? "Atomic Loop 64" : "MBOIT (streamed)",
+                                           "exact up to that count)", ctx->wboitLast ? "WBOIT" : ctx->al64Last ? "Atomic Loop 64" : "MBOIT (streamed)",
                        LV_MBOIT_STREAM_MAX_COUNT);
     return LV_OK;
 }
@@ -4222,20 +4462,113 @@ int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, ui
     return LV_OK;
 }
 
+// A mode-8 frame (Weighted Blended OIT): the sums zeroed, ONE launch of k_wboit_stream_pass, the resolve.  No pool, no scan, no
+// regrowth and no host synchronisation; the resolve's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
+static int lv_wboit_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
+                          LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    // (use_ribbons with rotating_helicity_bands never gets here: lv_frame_render refuses that pair for every mode)
+    if (!lv_ppll_prism_source(ctx))
+        return lv_fail(ctx, LV_E_INVALID, "mode 8 (WBOIT) works on the fragments of the rasterised prism, which this line data does not have");
+    if (ctx->opt.ppllPrismLbvhWalk)
+        return lv_fail(ctx, LV_E_INVALID, "mode 8 (WBOIT) runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported");
+    lv_fill_prism(ctx, U, S.prism);
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
+    const size_t sumBytes = padded4 * 4 * size_t(LV_WBOIT_SUMS) * 8;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->wboitBuf, sumBytes))) return rc;
+    ctx->ppllPoolNodes = 0;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    const bool allRequested = ctx->tilesCoverViewport;
+    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
+    LV_HIP(ctx, hipMemsetAsync(ctx->wboitBuf.ptr, 0, sumBytes, st));
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    // LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in modes 2, 3, 6 and 10)
+    uint32_t* leafList;
+    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
+    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
+    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);   // the instances and the selection of the streamed MBOIT pass
+    const uint32_t weightMode = ctx->opt.wboitOpenglWeight ? LV_WBOIT_WEIGHT_OPENGL : LV_WBOIT_WEIGHT_REFERENCE;
+#define LV_LAUNCH_WBOIT(NT, SH, FA)                                                                                             \
+    k_wboit_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr,                   \
+            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->wboitBuf.ptr, dc, allRequested ? 1u : 0u, leafList,        \
+            weightMode, stats ? 1u : 0u)
+#define LV_LAUNCH_WBOIT_2(NT)                                                        \
+    do {                                                                             \
+        if (fastShade) LV_LAUNCH_WBOIT(NT, LV_SHADE_PLAIN, 2);                       \
+        else if (S.prism.bands) LV_LAUNCH_WBOIT(NT, LV_SHADE_BANDS, 0);              \
+        else if (U.useHelicityBands) LV_LAUNCH_WBOIT(NT, LV_SHADE_HELICITY, 0);      \
+        else LV_LAUNCH_WBOIT(NT, LV_SHADE_PLAIN, 0);                                 \
+    } while (0)
+    if (S.numSegs != 0) {
+        if (S.prism.n == 6u) LV_LAUNCH_WBOIT_2(6); else LV_LAUNCH_WBOIT_2(0);
+    }
+    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
+        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
+        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
+    }
+#undef LV_LAUNCH_WBOIT_2
+#undef LV_LAUNCH_WBOIT
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_wboit_resolve<<<numGroups, LV_WAVE, 0, st>>>(
+            U, T, (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, dc)));
+    ctx->wboitLast = true;
+    ctx->wboitFull = allRequested;
+    ctx->wboitW = U.width;
+    ctx->wboitH = U.height;
+    ctx->wboitTile[0] = U.ppllTileW;
+    ctx->wboitTile[1] = U.ppllTileH;
+    return LV_OK;
+}
+
+// lv_wboit_get_buffers
+int lv_frame_wboit_buffers(lv_ctx* ctx, int64_t* outSums, uint32_t* outCounts, uint64_t capacityPixels) {
+    if (!ctx->wboitLast || !ctx->wboitFull || !ctx->wboitBuf.ptr || ctx->wboitW != ctx->width || ctx->wboitH != ctx->height)
+        return lv_fail(ctx, LV_E_STATE, "lv_wboit_get_buffers: the last frame was not a mode-8 frame over the whole viewport");
+    const uint64_t pixels = uint64_t(ctx->wboitW) * ctx->wboitH;
+    if (capacityPixels < pixels)
+        return lv_fail(ctx, LV_E_INVALID, "lv_wboit_get_buffers: the arrays hold %llu pixels, need %llu",
+                       (unsigned long long)capacityPixels, (unsigned long long)pixels);
+    int rc;
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
+    const size_t sumBytes = size_t(pixels) * LV_WBOIT_SUMS * 8, countBytes = size_t(pixels) * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, sumBytes + countBytes))) return rc;
+    unsigned long long* dSums = (unsigned long long*)ctx->scratchRays.ptr;
+    uint32_t* dCounts = (uint32_t*)(dSums + size_t(pixels) * LV_WBOIT_SUMS);
+    k_wboit_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
+            (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr, ctx->wboitW, ctx->wboitH, ctx->ppllPaddedW,
+            ctx->wboitTile[0], ctx->wboitTile[1], dSums, dCounts);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(outSums, dSums, sumBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipMemcpyAsync(outCounts, dCounts, countBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LV_OK;
+}
+
 int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
                     uint32_t tileH, void* outDevice) {
     if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
-        mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64)
-        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 6 = MBOIT, 10 = Atomic Loop 64)", mode);
+        mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64)
+        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 6 = MBOIT, 8 = WBOIT, "
+                                          "10 = Atomic Loop 64)", mode);
     // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
     const bool mboit = mode == LV_RENDERING_MODE_MBOIT;
     const bool mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
-    const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64;   // (the prism's fragments too, but no pool: lv_al64_frame)
+    const bool wboit = mode == LV_RENDERING_MODE_WBOIT;           // (the prism's fragments too, but no pool: lv_wboit_frame)
+    const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 || wboit;   // (the same, lv_al64_frame: `al64` = either pool-free mode)
     ctx->mboitStreamLast = false;   // (set again at the end of a streamed mode-6 frame)
     ctx->mboitStreamFull = false;
     ctx->al64Last = false;          // (set again at the end of a mode-10 frame)
     ctx->al64Full = false;
-    const char* const poolName = al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
+    ctx->wboitLast = false;         // (set again at the end of a mode-8 frame)
+    ctx->wboitFull = false;
+    const char* const poolName = wboit ? "WBOIT" : al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
     if ((mlab || al64) && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
                                           "capsule_entry is not supported", mode, poolName);
@@ -4455,6 +4788,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         }
     } else if (mboit && ctx->opt.mboitStreamed) {
         if ((rc = lv_mboit_stream_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
+    } else if (wboit) {
+        if ((rc = lv_wboit_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else if (al64) {
         if ((rc = lv_al64_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else {
@@ -4923,6 +5258,59 @@ int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKe
         if (outTail) LV_HIP(ctx, hipMemcpyAsync(outTail, dTail, tailBytes, hipMemcpyDeviceToHost, st));
     }
     return lv_resolve_read_back(ctx, out, size_t(numPixels));
+}
+
+// lv_wboit_resolve_buffers: the caller's fragments (pixel p of the w x h rectangle owns entries [offsets[p], offsets[p + 1])) added
+// by k_wboit_add_given, one lane per fragment with all lanes racing, then k_wboit_resolve with row-major addressing.  A pixel with
+// more than LV_WBOIT_MAX_COUNT fragments is found where a frame finds it: by the resolve's overflow flag.
+int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
+                                uint8_t* out, int64_t* outSums) {
+    const uint64_t numPixels = uint64_t(w) * h;
+    if (numEntries >= 0xFFFFFFF0ull / 5u || numPixels > 0x7FFFFFF0ull / LV_WBOIT_SUMS) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
+    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
+    for (uint64_t p = 0; p < numPixels; p++)
+        if (offsets[p + 1] < offsets[p]) return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend", (unsigned long long)p);
+    hipStream_t st = ctx->stream;
+    LvUniforms U;
+    lv_row_major_uniforms(ctx, U, w, h);
+    const size_t sumBytes = size_t(numPixels) * LV_WBOIT_SUMS * 8;
+    const size_t entryBytes = size_t(numEntries ? numEntries : 1) * 20, offBytes = size_t(numPixels + 1) * 8;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->wboitBuf, sumBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, entryBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
+    ctx->wboitLast = false;   // (the buffers no longer hold a frame)
+    ctx->al64Last = false;
+    ctx->mboitStreamLast = false;
+    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 20, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, size_t(numPixels) * 4, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->wboitBuf.ptr, 0, sumBytes, st));
+    if (numEntries)
+        k_wboit_add_given<<<uint32_t((numEntries + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
+                (const float*)ctx->ppllNodes.ptr, numEntries, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels),
+                (unsigned long long*)ctx->wboitBuf.ptr, (uint32_t*)ctx->ppllCount.ptr,
+                ctx->opt.wboitOpenglWeight ? LV_WBOIT_WEIGHT_OPENGL : LV_WBOIT_WEIGHT_REFERENCE);
+    static const uint32_t txy[2] = {0u, 0u};
+    LvTiles T;
+    uint32_t numGroups;
+    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
+    k_wboit_resolve<<<numGroups, LV_WAVE, 0, st>>>(U, T, (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr,
+                                                   (uint32_t*)ctx->outDev.ptr, numGroups, (LvDevCounters*)ctx->counters.ptr);
+    // (row-major addressing: the sums lie as the caller's array does)
+    if (outSums) LV_HIP(ctx, hipMemcpyAsync(outSums, ctx->wboitBuf.ptr, sumBytes, hipMemcpyDeviceToHost, st));
+    if ((rc = lv_resolve_read_back(ctx, out, size_t(numPixels)))) return rc;
+    uint32_t flag = 0u;
+    LV_HIP(ctx, hipMemcpy(&flag, &((const LvDevCounters*)ctx->counters.ptr)->mboitOverflow, 4, hipMemcpyDeviceToHost));
+    if (flag)
+        return lv_fail(ctx, LV_E_CAPACITY, "WBOIT: a pixel holds more than %u fragments (the 64-bit sums are exact up to that count)",
+                       LV_WBOIT_MAX_COUNT);
+    return LV_OK;
 }
 
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,

@@ -33,6 +33,8 @@ void HeadlessLineRenderer::createRenderer(RenderingMode mode) {
         lineRenderer.reset(new HipMLABRenderer(&sceneData, transferFunctionWindow));
     else if (mode == RENDERING_MODE_MBOIT)
         lineRenderer.reset(new HipMBOITRenderer(&sceneData, transferFunctionWindow));
+    else if (mode == RENDERING_MODE_WBOIT)
+        lineRenderer.reset(new HipWBOITRenderer(&sceneData, transferFunctionWindow));
     else if (mode == RENDERING_MODE_ATOMIC_LOOP_64)
         lineRenderer.reset(new HipAtomicLoop64Renderer(&sceneData, transferFunctionWindow));
     else

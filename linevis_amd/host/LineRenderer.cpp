@@ -821,4 +821,38 @@ void HipPerPixelLinkedListLineRenderer::computeStatistics(uint64_t& totalNumFrag
     maxComplexity = s.max_depth_complexity;
 }
 
+HipWBOITRenderer::HipWBOITRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Weighted Blended OIT Renderer", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipWBOITRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipWBOITRenderer::setNewState(const InternalState& newState) {
+    currentStateName = newState.name;   // (WBOITRenderer reads no renderer settings)
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipWBOITRenderer::render() {
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    setOption("wboit_depth_weight", depthWeight);
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_WBOIT); // clear -> rasterise, shade and accumulate -> resolve
+}
+
+bool HipWBOITRenderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    std::string weight;
+    if (settings.getValueOpt("wboit_depth_weight", weight) && setOption("wboit_depth_weight", weight))
+        depthWeight = weight;   // (a value the C ABI refuses leaves depthWeight as it is)
+    for (const char* key : {"ppll_tile_width", "ppll_tile_height", "ppll_fragment_source", "ppll_fragment_colour", "ppll_prism_rasteriser"}) {
+        std::string s;
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
 } // namespace lv

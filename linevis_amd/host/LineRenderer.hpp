@@ -27,6 +27,7 @@ enum RenderingMode : int32_t {
     RENDERING_MODE_PER_PIXEL_LINKED_LIST = 2,
     RENDERING_MODE_MLAB = 3,
     RENDERING_MODE_MBOIT = 6,
+    RENDERING_MODE_WBOIT = 8,
     RENDERING_MODE_ATOMIC_LOOP_64 = 10,
     RENDERING_MODE_VULKAN_RAY_TRACER = 11,
 };
@@ -408,6 +409,26 @@ public:
 private:
     std::string currentStateName;
     int numLayers = 8;                              // AtomicLoop64Renderer.hpp:112
+};
+
+/// "Weighted Blended OIT" plugin (src/Renderers/OIT/WBOITRenderer.hpp) re-hosted on HIP (rendering mode 8): the weighted average of
+/// all fragments of the PPLL plugin's rasterised prism per pixel.  WBOITRenderer has no renderer settings of its own; the build-owned
+/// key wboit_depth_weight picks the depth weight (linevis_hip.h).
+class HipWBOITRenderer : public LineRenderer {
+public:
+    HipWBOITRenderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_WBOIT; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    bool setNewSettings(const SettingsMap& settings) override;
+    bool getUseAnalyticEllipticTubes() const override { return true; }
+    const std::string& getDepthWeight() const { return depthWeight; }
+
+private:
+    std::string currentStateName;
+    std::string depthWeight = "reference";          // wboit_depth_weight
 };
 
 } // namespace lv

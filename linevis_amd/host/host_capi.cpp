@@ -504,6 +504,13 @@ int lvh_renderer_atomic_loop_state(void* r, int32_t* out1) {   // {numLayers} of
     out1[0] = m->getNumLayers();
     return 0;
 }
+int lvh_renderer_wboit_state(void* r, int32_t* out1) {   // {depth weight: 0 = reference, 1 = opengl} of a mode-8 plugin
+    HeadlessLineRenderer* h = static_cast<HeadlessLineRenderer*>(r);
+    const HipWBOITRenderer* m = dynamic_cast<const HipWBOITRenderer*>(h->getLineRenderer());
+    if (!m) return -1;
+    out1[0] = m->getDepthWeight() == "opengl" ? 1 : 0;
+    return 0;
+}
 void lvh_renderer_destroy(void* r) { delete static_cast<HeadlessLineRenderer*>(r); }
 void lvh_renderer_set_resolution(void* r, uint32_t w, uint32_t h) { static_cast<HeadlessLineRenderer*>(r)->setRenderingResolution(w, h); }
 void lvh_renderer_set_line_data(void* r, void* flow, int isNewData) {

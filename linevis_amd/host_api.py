@@ -87,6 +87,7 @@ def load():
         "lvh_test_mode_mboit": (u32, [u32, vp, u32]),
         "lvh_renderer_mboit_state": (i32, [vp, vp, vp]),
         "lvh_renderer_atomic_loop_state": (i32, [vp, vp]),
+        "lvh_renderer_wboit_state": (i32, [vp, vp]),
         "lvh_renderer_destroy": (None, [vp]),
         "lvh_renderer_set_resolution": (None, [vp, u32, u32]),
         "lvh_renderer_set_line_data": (None, [vp, vp, i32]),
@@ -630,6 +631,13 @@ class HeadlessLineRenderer:
         if self.L.lvh_renderer_atomic_loop_state(self.h, _p(v)) != 0:
             return None
         return {"numLayers": int(v[0])}
+
+    def wboit_state(self):
+        """{depthWeight} of the mode-8 plugin (None for the other plugins)"""
+        v = np.zeros(1, dtype=np.int32)
+        if self.L.lvh_renderer_wboit_state(self.h, _p(v)) != 0:
+            return None
+        return {"depthWeight": "opengl" if int(v[0]) else "reference"}
 
     def needs_re_render(self):
         return bool(self.L.lvh_renderer_needs_re_render(self.h))

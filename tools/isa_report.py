@@ -17,7 +17,7 @@ sys.path.insert(0, ROOT)
 from linevis_amd import build as lv_build  # noqa: E402
 
 HOT = ["k_ao_rays", "k_ao_primary", "k_render_rt", "k_ppll_gather", "k_ppll_resolve", "k_render_rt_mlat", "k_ao_reduce",
-       "k_ppll_raster_prism", "k_ppll_shade_prism", "k_ppll_cull_segments", "k_ppll_select_nearest", "k_mboit_stream_pass", "k_al64_stream_pass"]
+       "k_ppll_raster_prism", "k_ppll_shade_prism", "k_ppll_cull_segments", "k_ppll_select_nearest", "k_mboit_stream_pass", "k_al64_stream_pass", "k_wboit_stream_pass"]
 
 
 def demangle(names):
