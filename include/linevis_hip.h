@@ -39,12 +39,19 @@ extern "C" {
 /* Multi-Layer Alpha Blending (src/Renderers/OIT/MLABRenderer.cpp) over the fragments of mode 2's rasterised prism; see
  * mlab_num_layers and lv_mlab_resolve_buffers below */
 #define LV_RENDERING_MODE_MLAB 3
+/* Depth complexity (src/Renderers/OIT/DepthComplexityRenderer.cpp): the number of fragments of mode 2's rasterised prism per pixel as
+ * a colour, and its statistics; see depth_complexity_max_colour, lv_depth_complexity_get_buffers and lv_depth_complexity_get_stats */
+#define LV_RENDERING_MODE_DEPTH_COMPLEXITY 5
 /* Moment-based order-independent transparency (src/Renderers/OIT/MBOITRenderer.cpp) with power moments stored as float32, over the
  * fragments of mode 2's rasterised prism; see mboit_num_moments and lv_mboit_resolve_buffers below */
 #define LV_RENDERING_MODE_MBOIT 6
 /* Weighted Blended OIT (src/Renderers/OIT/WBOITRenderer.cpp): the weighted average of all fragments of mode 2's rasterised prism per
  * pixel, in 5 * 8 bytes per pixel; see wboit_depth_weight, lv_wboit_get_buffers and lv_wboit_resolve_buffers below */
 #define LV_RENDERING_MODE_WBOIT 8
+/* Depth peeling (src/Renderers/OIT/DepthPeelingRenderer.cpp): every fragment layer of mode 2's rasterised prism composited in depth
+ * order, exactly, with no fragment storage: memory is bounded by the viewport; see depth_peeling_max_layers,
+ * lv_depth_peeling_get_buffers and lv_depth_peeling_resolve_buffers below */
+#define LV_RENDERING_MODE_DEPTH_PEELING 9
 /* Atomic Loop 64 (src/Renderers/OIT/AtomicLoop64Renderer.cpp): the K nearest fragments of mode 2's rasterised prism per pixel,
  * exactly, in K * 8 bytes per pixel; see atomic_loop_num_layers, lv_atomic_loop_get_buffers and lv_atomic_loop_resolve_buffers below */
 #define LV_RENDERING_MODE_ATOMIC_LOOP_64 10
@@ -336,6 +343,38 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   max_depth_complexity.  Timers: LV_KERNEL_PPLL_RASTER times the pass (with the tile marking and segment culling of a sharded
  *   frame), LV_KERNEL_PPLL_RESOLVE the resolve.  Limit: the sums are exact for up to 131071 kept fragments on a pixel; a pixel with
  *   more sets the flag of mboit_fragment_storage = streamed below, with mode 10's contract.
+ *   depth_peeling_max_layers: 1 ... 2000 (default 2000, the reference's constant, DepthPeelingRenderer.cpp:288): the cap of rendering
+ *   mode 9's passes; anything else is LV_E_INVALID and the old value stays; modes other than 9 ignore it.  Mode 9 peels, per pixel,
+ *   the fragments mode 8 adds (the `kept` rules only, no alpha discard; RTAO, depth cues, band data and rotating helicity bands as in
+ *   mode 2) layer by layer in depth order.  Per fragment: the straight float32 colour c, the window depth z of mode 3 and the
+ *   primitive key k of mode 3 (segment << 6 | triangle: index-buffer order).  The frame first counts the fragments per pixel (as mode
+ *   5) and reads the maximum D back: the frame's one host synchronisation, the reference's syncWithCpu; with lv_create_multi it
+ *   serialises the ranks' front ends as mode 3's does.  Then min(D, depth_peeling_max_layers) passes.  Pass i takes, per pixel, what
+ *   DepthPeelingGather.glsl:42-49 and the depth test leave (cleared to 1.0, LESS, depth write on): the fragment with the smallest z
+ *   that is > the previous layer's z (any z in pass 0) and < 1.0; among fragments of equal z the smallest k.  A fragment with z >=
+ *   1.0 (or a z whose sign bit is set) is never peeled; fragments that share a depth with a peeled one are never peeled later.  The
+ *   layer's colour s = (c.rgb * c.a, c.a) goes into the accumulator A (cleared to 0) with FRONT_TO_BACK_PREMUL_ALPHA, float32,
+ *   unfused: t = 1 - A.a; A.x = A.x + s.x * t for x in r, g, b, a, all four with the old A.a.  After the last pass out = A + clear *
+ *   (1 - A.a) on all four channels (BACK_TO_FRONT_PREMUL_ALPHA), stored as RGBA8 like every frame.  The passes do not shade: the
+ *   discard depends on the depth only, so a pass is the rasteriser plus the position of every kept fragment and one 64-bit atomicMin
+ *   on (bits(z) << 32 | k); the winner of every pixel is shaded once, afterwards.  Memory: 32 bytes per pixel of the viewport padded
+ *   to ppll_tile_width x ppll_tile_height plus the two 4-byte per-pixel words of mode 2; nothing grows with the number of fragments.
+ *   The pool options have no effect; ppll_prism_rasteriser = lbvh, ppll_fragment_source = capsule_entry and band data with rotating
+ *   helicity bands return LV_E_INVALID at render time (the context stays usable).  Statistics: fragments = the kept fragments,
+ *   ppll_pool_nodes = 0, max_depth_complexity.  Timers: LV_KERNEL_PPLL_RASTER times the count pass (with the tile marking and
+ *   segment culling of a sharded frame) and then every peel pass, LV_KERNEL_PPLL_GATHER the reduction of the counts,
+ *   LV_KERNEL_PPLL_SHADE the layer launches, LV_KERNEL_PPLL_RESOLVE the blit.
+ *   depth_complexity_max_colour: 0 (default) ... 1000000: numFragmentsMaxColor of rendering mode 5; anything else is LV_E_INVALID and
+ *   the old value stays; modes other than 5 ignore it.  Mode 5 counts, per pixel, the fragments mode 8 adds (n) and shows percentage =
+ *   clamp(float(n) / float(min(numFragmentsMaxColor, 512)), 0, 1) (DepthComplexityResolve.glsl:48-57) as the colour (0, 1, 1,
+ *   percentage) blended over the clear colour: out.rgb = colour.rgb * percentage + clear.rgb * (1 - percentage), out.a = percentage +
+ *   clear.a * (1 - percentage) (BACK_TO_FRONT_STRAIGHT_ALPHA), float32, unfused.  0 = auto: numFragmentsMaxColor = uint32(float(max(
+ *   maxComplexity, 4)) / 1.5f) (DepthComplexityRenderer.cpp:332).  Rule this build owns: the reference takes maxComplexity from a
+ *   statistics read-back that lags by up to a second; here it is the maximum over THIS frame's requested pixels, computed on the
+ *   device and read by the resolve from device memory: a mode-5 frame has no host synchronisation.  A tile list or a shard of a
+ *   multi-device frame sees only its own pixels' maximum, so only an explicit value makes them reproduce the whole frame.  The
+ *   restrictions, memory (without the 32 bytes) and statistics of mode 9; timers: LV_KERNEL_PPLL_RASTER the count pass,
+ *   LV_KERNEL_PPLL_GATHER the reduction, LV_KERNEL_PPLL_RESOLVE the resolve.
  *   mboit_num_moments: 4 | 6 | 8 power moments of rendering mode 6 (default 4)   (MBOITRenderer.cpp:41-45).  Mode 6 sweeps, per
  *   pixel, ALL fragments the fragment stage of mode 2 produces (the alpha < 0.001 discard of modes 2 and 3 is not MBOIT's; its own
  *   rules are transmittance > 0.9999999 per fragment in the moment pass and b_0 < 0.00100050033 per pixel) twice: power moments of
@@ -761,6 +800,31 @@ int lv_wboit_get_buffers(lv_ctx* ctx, int64_t* out_sums, uint32_t* out_counts, u
  * background.  At most 131071 entries per pixel: more returns LV_E_CAPACITY (the resolve's flag).  out_sums (w * h * 5) may be NULL. */
 int lv_wboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w, uint32_t h,
                              uint8_t* out_rgba8, int64_t* out_sums);
+/* The kept-fragment counts of the last frame when that was a mode-5 frame over the whole viewport, row-major (width * height).
+ * LV_E_STATE when the last frame was anything else (another mode, a tile list that does not cover the viewport, a multi-device handle);
+ * LV_E_INVALID for a null pointer or capacity_pixels below width * height.  Synchronises the context's stream. */
+int lv_depth_complexity_get_buffers(lv_ctx* ctx, uint32_t* out_counts, uint64_t capacity_pixels);
+/* What the reference's performance measurer records per frame (pushDepthComplexityFrame): the sum of the counts, the pixels with at
+ * least one fragment, the largest and the smallest count, and width * height.  (The reference reports used_locations = 1 for a frame
+ * without fragments to avoid a division; here 0 stays 0.) */
+typedef struct lv_depth_complexity_stats {
+    uint64_t total;
+    uint64_t used_locations;
+    uint64_t max;
+    uint64_t min;
+    uint64_t buffer_size;
+} lv_depth_complexity_stats;
+/* The statistics of the last frame under the conditions of lv_depth_complexity_get_buffers, reduced on the device. */
+int lv_depth_complexity_get_stats(lv_ctx* ctx, lv_depth_complexity_stats* out);
+/* The accumulators {r, g, b, a} (float32, premultiplied, before the blit), the numbers of peeled layers and the kept-fragment counts of
+ * the last frame when that was a mode-9 frame over the whole viewport, row-major.  Errors as lv_depth_complexity_get_buffers. */
+int lv_depth_peeling_get_buffers(lv_ctx* ctx, float* out_accum_rgba, uint32_t* out_layers, uint32_t* out_counts, uint64_t capacity_pixels);
+/* Test entry point of mode 9's passes and blit: pixel p = y * w + x of the w x h rectangle owns entries [offsets[p], offsets[p + 1])
+ * (offsets: w * h + 1 values from 0 to num_entries); an entry is 6 words {r, g, b, alpha, window depth (float32), primitive key
+ * (uint32)}.  min(longest run, depth_peeling_max_layers) passes with one lane per entry, all lanes racing for the pixel's slot.
+ * Precondition: the keys of a pixel's entries are distinct.  out_accum_rgba (w * h * 4) and out_layers (w * h) may be NULL. */
+int lv_depth_peeling_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                                     uint32_t h, uint8_t* out_rgba8, float* out_accum_rgba, uint32_t* out_layers);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

@@ -1,4 +1,4 @@
-"""Headless command line renderer: `python -m linevis_amd <input> -o frame.png [--mode rt|ppll|mlab|al64|wboit|mboit] [key=value ...]`.
+"""Headless command line renderer: `python -m linevis_amd <input> -o frame.png [--mode rt|ppll|mlab|al64|wboit|mboit|"Depth Peeling"|"Depth Complexity Renderer"] [key=value ...]`.
 
 <input> is a .binlines / .obj trajectory file (LineDataFlow::loadFromFile) or the name of a synthetic scene
 (lattice, helix, tornado, rayleigh_benard, abc_flow).  key=value pairs are the reference's SettingsMap keys
@@ -29,7 +29,7 @@ def main(argv=None):
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input")
     ap.add_argument("-o", "--output", default="frame.png")
-    ap.add_argument("--mode", choices=["rt", "ppll", "mlab", "al64", "wboit", "mboit"], default="rt")
+    ap.add_argument("--mode", choices=["rt", "ppll", "mlab", "al64", "wboit", "Depth Peeling", "Depth Complexity Renderer", "mboit"], default="rt")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--camera", type=float, nargs=3, default=(0.0, 0.0, 0.8), metavar=("X", "Y", "Z"))
@@ -53,10 +53,11 @@ def main(argv=None):
     else:
         flow.load_file(args.input)
     mode = {"rt": capi.MODE_RAY_TRACER, "ppll": capi.MODE_PPLL, "mlab": capi.MODE_MLAB, "mboit": capi.MODE_MBOIT, "al64": capi.MODE_ATOMIC_LOOP_64,
-            "wboit": capi.MODE_WBOIT}[args.mode]
+            "wboit": capi.MODE_WBOIT, "Depth Peeling": capi.MODE_DEPTH_PEELING,
+            "Depth Complexity Renderer": capi.MODE_DEPTH_COMPLEXITY}[args.mode]
     r = host_api.HeadlessLineRenderer(mode, args.device)
     r.set_rendering_resolution(args.width, args.height)
-    tf_name = args.transfer_function or ("transparent" if args.mode in ("ppll", "mlab", "mboit", "al64", "wboit") else "standard")
+    tf_name = args.transfer_function or ("transparent" if args.mode in ("ppll", "mlab", "mboit", "al64", "wboit", "Depth Peeling", "Depth Complexity Renderer") else "standard")
     r.set_transfer_function(tfm.standard_transparent() if tf_name == "transparent" else tfm.standard())
     r.set_camera(args.camera)
     r.set_line_data(flow)

@@ -16,8 +16,10 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "linevis_hip.h")
 LV_OK = 0
 MODE_PPLL = 2          # RENDERING_MODE_PER_PIXEL_LINKED_LIST, src/Renderers/RenderingModes.hpp:32-53
 MODE_MLAB = 3          # RENDERING_MODE_MLAB (Multi-Layer Alpha Blending over mode 2's fragments)
+MODE_DEPTH_COMPLEXITY = 5   # RENDERING_MODE_DEPTH_COMPLEXITY (fragments per pixel of mode 2's rasterised prism as a colour, and their statistics)
 MODE_MBOIT = 6         # RENDERING_MODE_MBOIT (moment-based OIT, power moments as float32, over mode 2's fragments)
 MODE_WBOIT = 8         # RENDERING_MODE_WBOIT (weighted blended OIT: five 64-bit sums per pixel over mode 2's fragments)
+MODE_DEPTH_PEELING = 9  # RENDERING_MODE_DEPTH_PEELING (every layer of mode 2's fragments in depth order, exactly, no fragment storage)
 MODE_ATOMIC_LOOP_64 = 10   # RENDERING_MODE_ATOMIC_LOOP_64 (the K nearest fragments of mode 2 in 64-bit atomicMin slots)
 MODE_RAY_TRACER = 11   # RENDERING_MODE_VULKAN_RAY_TRACER
 
@@ -106,7 +108,8 @@ class LineVisError(RuntimeError):
 SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_stream", "lv_set_lines",
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
-           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_wboit_get_buffers", "lv_wboit_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
+           "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_wboit_get_buffers", "lv_wboit_resolve_buffers",
+           "lv_depth_complexity_get_buffers", "lv_depth_complexity_get_stats", "lv_depth_peeling_get_buffers", "lv_depth_peeling_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -191,6 +194,10 @@ def load():
         ("lv_atomic_loop_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp, vp]),
         ("lv_wboit_get_buffers", [vp, vp, vp, u64]),
         ("lv_wboit_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp]),
+        ("lv_depth_complexity_get_buffers", [vp, vp, u64]),
+        ("lv_depth_complexity_get_stats", [vp, vp]),
+        ("lv_depth_peeling_get_buffers", [vp, vp, vp, vp, u64]),
+        ("lv_depth_peeling_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp, vp]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -680,6 +687,48 @@ class Context:
         sums = np.zeros((h, w, 5), dtype=np.int64)
         self._ck(self.L.lv_wboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(sums)))
         return out, sums
+
+    def depth_complexity_buffers(self):
+        """The kept-fragment counts of the last mode-5 frame over the whole viewport (lv_depth_complexity_get_buffers): (height,
+        width) uint32."""
+        counts = np.zeros((self.height, self.width), dtype=np.uint32)
+        self._ck(self.L.lv_depth_complexity_get_buffers(self.h, _p(counts), self.width * self.height))
+        return counts
+
+    def depth_complexity_stats(self):
+        """The device-side reduction of the last mode-5 frame's counts (lv_depth_complexity_get_stats): a dict with total,
+        used_locations, max, min and buffer_size."""
+        v = np.zeros(5, dtype=np.uint64)
+        self._ck(self.L.lv_depth_complexity_get_stats(self.h, _p(v)))
+        return dict(zip(("total", "used_locations", "max", "min", "buffer_size"), (int(x) for x in v)))
+
+    def depth_peeling_buffers(self):
+        """The accumulators, layer counts and kept-fragment counts of the last mode-9 frame over the whole viewport
+        (lv_depth_peeling_get_buffers): ((height, width, 4) float32 premultiplied, (height, width) uint32, (height, width) uint32)."""
+        accum = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        layers = np.zeros((self.height, self.width), dtype=np.uint32)
+        counts = np.zeros((self.height, self.width), dtype=np.uint32)
+        self._ck(self.L.lv_depth_peeling_get_buffers(self.h, _p(accum), _p(layers), _p(counts), self.width * self.height))
+        return accum, layers, counts
+
+    def depth_peeling_resolve(self, rgba, z, keys, offsets, w, h):
+        """Mode 9's passes and blit on caller-supplied fragments (lv_depth_peeling_resolve_buffers) under depth_peeling_max_layers:
+        rgba = (n, 4) float32 straight colours, z = (n,) float32 window depths, keys = (n,) uint32 primitive keys (distinct within a
+        pixel), pixel p = y * w + x owns entries offsets[p]:offsets[p + 1].  Returns ((h, w, 4) uint8, (h, w, 4) float32 accumulators,
+        (h, w) uint32 layer counts)."""
+        c = np.ascontiguousarray(rgba, dtype=np.float32).reshape(-1, 4)
+        e = np.empty((c.shape[0], 6), dtype=np.uint32)
+        e[:, :4] = c.view(np.uint32)
+        e[:, 4] = np.ascontiguousarray(z, dtype=np.float32).reshape(-1).view(np.uint32)
+        e[:, 5] = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if o.shape[0] != w * h + 1:
+            raise ValueError("offsets must hold w * h + 1 values")
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        accum = np.zeros((h, w, 4), dtype=np.float32)
+        layers = np.zeros((h, w), dtype=np.uint32)
+        self._ck(self.L.lv_depth_peeling_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(accum), _p(layers)))
+        return out, accum, layers
 
     def svgf_denoise(self, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history):
         """One SVGF denoise() on caller-supplied images (lv_svgf_denoise_buffers): noisy (h, w), normal_depth (h, w, 4), flow_fwidth

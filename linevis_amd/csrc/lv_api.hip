@@ -114,7 +114,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
-            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
+            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
@@ -661,6 +661,14 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // numLayers of the Atomic Loop 64 renderer (rendering mode 10): default 8 (AtomicLoop64Renderer.hpp:112), 1 ... 64 as mode 3
         if (!parseUint(value, u) || u == 0 || u > 64) return bad();
         o.al64NumLayers = u;
+    } else if (k == "depth_peeling_max_layers") {
+        // the cap of the depth peeling renderer's passes (rendering mode 9): the reference's constant 2000 (DepthPeelingRenderer.cpp:288)
+        if (!parseUint(value, u) || u == 0 || u > 2000) return bad();
+        o.peelMaxLayers = u;
+    } else if (k == "depth_complexity_max_colour") {
+        // numFragmentsMaxColor of the depth complexity renderer (rendering mode 5): 0 = from the frame's maximum (DepthComplexityRenderer.cpp:332)
+        if (!parseUint(value, u) || u > 1000000) return bad();
+        o.dcMaxColour = u;
     } else if (k == "wboit_depth_weight") {
         // the depth weight of the WBOIT renderer (rendering mode 8): the line WBOITGather.glsl:23 runs, or the one it keeps as a comment
         if (strcmp(value, "reference") == 0) o.wboitOpenglWeight = false;
@@ -1542,6 +1550,42 @@ int lv_wboit_get_buffers(lv_ctx* ctx, int64_t* out_sums, uint32_t* out_counts, u
     if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_wboit_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
     (void)hipSetDevice(ctx->device);
     return lv_frame_wboit_buffers(ctx, out_sums, out_counts, capacity_pixels);
+}
+
+int lv_depth_complexity_get_buffers(lv_ctx* ctx, uint32_t* out_counts, uint64_t capacity_pixels) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_depth_complexity_get_buffers: null output");
+    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_peel_buffers(ctx, LV_RENDERING_MODE_DEPTH_COMPLEXITY, nullptr, nullptr, out_counts, capacity_pixels);
+}
+
+int lv_depth_complexity_get_stats(lv_ctx* ctx, lv_depth_complexity_stats* out) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out) return lv_fail(ctx, LV_E_INVALID, "lv_depth_complexity_get_stats: null output");
+    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_stats: a multi-device handle keeps no counts of the whole viewport");
+    (void)hipSetDevice(ctx->device);
+    uint64_t w[5];
+    int rc;
+    if ((rc = lv_frame_dc_stats(ctx, w))) return rc;
+    out->total = w[0]; out->used_locations = w[1]; out->max = w[2]; out->min = w[3]; out->buffer_size = w[4];
+    return LV_OK;
+}
+
+int lv_depth_peeling_get_buffers(lv_ctx* ctx, float* out_accum_rgba, uint32_t* out_layers, uint32_t* out_counts, uint64_t capacity_pixels) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out_accum_rgba || !out_layers || !out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_depth_peeling_get_buffers: null output");
+    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_depth_peeling_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_peel_buffers(ctx, LV_RENDERING_MODE_DEPTH_PEELING, out_accum_rgba, out_layers, out_counts, capacity_pixels);
+}
+
+int lv_depth_peeling_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                                     uint32_t h, uint8_t* out_rgba8, float* out_accum_rgba, uint32_t* out_layers) {
+    if (!ctx) return LV_E_INVALID;
+    if ((num_entries && !entries) || !offsets || !out_rgba8 || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_peel_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_accum_rgba, out_layers);
 }
 
 int lv_wboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w, uint32_t h,

@@ -88,6 +88,8 @@ struct LvOptions {
     float mboitMomentBias = 0.0f;             // mboit_moment_bias: 0 = auto (5e-7 / 5e-6 / 5e-5 for 4 / 6 / 8, MBOITRenderer.cpp:136-145), else (0, 0.1]
     uint32_t al64NumLayers = 8;               // atomic_loop_num_layers: numLayers of rendering mode 10, 1 ... 64 (AtomicLoop64Renderer.hpp:112)
     bool wboitOpenglWeight = false;           // wboit_depth_weight: false = "reference" (default, WBOITGather.glsl:23), true = "opengl" (the commented line)
+    uint32_t peelMaxLayers = 2000;            // depth_peeling_max_layers: the cap of rendering mode 9's passes, 1 ... 2000 (DepthPeelingRenderer.cpp:288)
+    uint32_t dcMaxColour = 0;                 // depth_complexity_max_colour: 0 = auto (numFragmentsMaxColor from the frame's maximum), else that value
     bool mboitStreamed = false;               // mboit_fragment_storage: false = "pool" (default), true = "streamed" (k_mboit_stream_pass: no fragment pool)
     // EAW denoiser of the RTAO pass (ambient_occlusion_denoiser; AO defaults of createDenoiserObject, Denoiser.cpp:54-62)
     bool eawEnabled = false;
@@ -256,6 +258,10 @@ struct lv_ctx {
     LvDeviceBuffer wboitBuf;                  // mode 8: 5 sums of 8 B per padded pixel (addressed like ppllCount)
     bool wboitLast = false, wboitFull = false;   // the last frame was a mode-8 frame / one over the whole viewport
     uint32_t wboitW = 0, wboitH = 0, wboitTile[2] = {0, 0};   // that frame's viewport and ppll tile
+    LvDeviceBuffer peelBuf, dcStatsDev;       // mode 9: 32 B per padded pixel (lv_peel_buffers); modes 5 and 9: the words of k_dc_reduce
+    int peelLast = 0;                         // 5 / 9: the last frame was a frame of that mode (ppllCount holds its counts); 0: neither
+    bool peelFull = false;                    // ... over the whole viewport
+    uint32_t peelW = 0, peelH = 0, peelTile[2] = {0, 0};   // that frame's viewport and ppll tile
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
     LvDeviceBuffer selftestIn, selftestOut;   // lv_selftest_eval: argument and result words
@@ -401,6 +407,10 @@ int lv_mboit_stream_overflow(lv_ctx* ctx);
 int lv_frame_wboit_buffers(lv_ctx* ctx, int64_t* outSums, uint32_t* outCounts, uint64_t capacityPixels);
 int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
                                 uint8_t* out, int64_t* outSums);
+int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outLayers, uint32_t* outCounts, uint64_t capacityPixels);
+int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]);
+int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
+                               uint8_t* out, float* outAccum, uint32_t* outLayers);
 int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out);
 int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, uint64_t capacityPixels);
 int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKeys, const uint64_t* offsets, uint32_t w, uint32_t h,

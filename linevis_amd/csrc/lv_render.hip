@@ -25,6 +25,7 @@
 #include "lv_mboit.h"
 #include "lv_al64.h"
 #include "lv_wboit.h"
+#include "lv_peel.h"
 
 namespace {
 
@@ -3354,6 +3355,293 @@ __global__ __launch_bounds__(LV_BLOCK) void k_wboit_read(const unsigned long lon
     if (outCounts) outCounts[p] = fragCount[addr];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Depth complexity (rendering mode 5, DepthComplexityRenderer) and depth peeling (rendering mode 9, DepthPeelingRenderer); the rules
+// are lv_peel.h's.  Both walk the kept fragments of the rasterised prism WITHOUT shading them: whether a fragment is kept
+// (lv_prism_accept) and its window depth need the interpolated position only.
+//   k_dc_count_pass   one launch: ppllCount[pixel] += 1 per kept fragment (modes 5 and 9; gatherInc of DepthComplexityGatherInc.glsl)
+//   k_dc_reduce       total, used pixels, maximum and minimum of the requested pixels' counts into device words
+//   k_dc_resolve      mode 5's frame (the cells and groups of k_wboit_resolve); reads the maximum from device memory
+//   k_peel_pass       one launch per layer: 64-bit atomicMin of (z bits << 32 | primitive key) into the pixel's slot
+//   k_peel_layer      (lv_peel.hip) one lane per VIEWPORT pixel (a tile list may repeat or overlap pixels; a pixel must be accumulated
+//                     once): shades the slot's winner as stage C of k_wboit_stream_pass shades, accumulates, resets the slot.  In a file
+//                     of its own: as a kernel of this one it changed the code of every kernel here that calls lv_shade_prism and
+//                     lv_prism_frag_pos (38 instances), which must compile as they do
+//   k_peel_blit       the accumulator over the clear colour, over the tile list's cells (a pure read)
+// Mode 9 shades every peeled layer once; its D passes are a rasteriser plus a position evaluation each.
+
+// The steps of lv_shade_prism up to lv_prism_accept, on the same operands (as lv_prism_frag_pos: the normals do not enter the
+// position): decides bit for bit what the shading stage decides, and returns the interpolated position.
+__device__ __forceinline__ bool lv_prism_frag_kept(const LvSceneDev& S, const LvUniforms& U, const float* ringTab, f3 o, f3 d, float tLo,
+                                                   float tHi, uint32_t leaf, uint32_t tt, f3& pos) {
+    const LvPrismDev& R = S.prism;
+    uint32_t pi[2];
+    LvPrismPoint pt[2];
+    lv_prism_frames(S, leaf, S.segs[2 * size_t(leaf)], S.segs[2 * size_t(leaf) + 1], pt, pi);
+    const LvPrismTri T = lv_prism_tri_setup(ringTab, R.n, pt, pi, R.radius, tt);
+    f3 nrm[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) nrm[i] = norm3q<false>(T.dir[i]);
+    const f3 cam = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
+    const LvPrismPlanes pl = lv_prism_planes(R, T, cam, d);
+    pos = lv_prism_interpolate(T, nrm, pl, d).pos;
+    return lv_prism_accept(R, pt, R.radius, o, d, pos, len3(pos - o), tLo, tHi);
+}
+
+// The loop of the two passes: stages A and B of k_ppll_raster_prism (one LDS queue of (pixel, segment) pairs), stage B's lane then
+// loops over the bits of its coverage mask and calls onKept(addr, leaf, tt, pos) for every kept fragment.  Without a 2 100-instruction
+// shading stage behind it there is no second queue and nothing to park: a covered pair has 1 - 2 triangles (front faces of a convex
+// prism), so the loop is short and the lanes of a batch stay together.  COUNTERS: the frame's fragCounter and statistics (the count
+// pass; the peel passes walk the same fragments again and must not add them again).
+template <int NT, bool COUNTERS, class OnKept>
+__device__ __forceinline__ void lv_kept_fragments_walk(const LvUniforms& U, const LvSceneDev& S, const uint32_t* __restrict__ startOffset,
+                                                       LvDevCounters* dc, uint32_t allRequested, const uint32_t* __restrict__ leafList,
+                                                       uint32_t collectStats, OnKept&& onKept) {
+    __shared__ uint32_t s_qLeaf[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE], s_qPix[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE];
+    __shared__ float s_seg[LV_BLOCK / LV_WAVE][20][LV_WAVE];
+    __shared__ float s_prismRing[4 * LV_PRISM_MAX_SUBDIV];
+    if (threadIdx.x < LV_PRISM_MAX_SUBDIV) {
+        s_prismRing[threadIdx.x] = S.prism.c[threadIdx.x];
+        s_prismRing[LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.s[threadIdx.x];
+        s_prismRing[2 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.cp[threadIdx.x];
+        s_prismRing[3 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.sn[threadIdx.x];
+    }
+    __syncthreads();
+    const LvPrismDev& R = S.prism;
+    const uint32_t N = NT > 0 ? uint32_t(NT) : R.n;
+    const unsigned lane = lv_lane();
+    uint32_t* qLeaf = s_qLeaf[threadIdx.x >> 6];
+    uint32_t* qPix = s_qPix[threadIdx.x >> 6];
+    float (*segLds)[LV_WAVE] = s_seg[threadIdx.x >> 6];
+    const f3 o = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
+    float mx[4], my[4], mw[4];
+    lv_clip_rows(U, mx, my, mw);
+    const float halfW = 0.5f * float(U.width), halfH = 0.5f * float(U.height);
+    const float wEps = 1e-3f * U.nearDist;
+    const float tLo = 0.0001f, tHi = __uint_as_float(__float_as_uint(1000.0f) + 1u);   // the interval of the streamed passes' stage C
+    const bool stats = COUNTERS && collectStats != 0u;
+    unsigned qHead = 0u, qCount = 0u;   // the queue (wave-uniform)
+    unsigned long long tests = 0;
+    uint32_t keptLane = 0u;
+
+    // stage B on the m <= 64 oldest pairs of the queue
+    auto coverageStage = [&](unsigned m) {
+        if (lane < m) {
+            uint32_t leaf, pix;
+            unsigned mask = lv_seg_pair_coverage<NT>(R, segLds, qLeaf, qPix, (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u), o, leaf, pix);
+            if (mask != 0u) {
+                const uint32_t px = pix & 0xFFFFu, py = pix >> 16;
+                const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+                f3 oo, d;
+                lv_primary_ray(U, px, py, 0.5f, 0.5f, oo, d);   // the viewing ray the shading stage shades on
+                while (mask != 0u) {
+                    const unsigned tt = unsigned(__ffs(int(mask))) - 1u;
+                    mask &= mask - 1u;
+                    f3 pos;
+                    if (lv_prism_frag_kept(S, U, s_prismRing, o, d, tLo, tHi, leaf, tt, pos)) {
+                        keptLane++;
+                        onKept(addr, leaf, tt, pos);
+                    }
+                }
+            }
+        }
+        if (stats) tests += m;
+        qHead = (qHead + m) & (LV_PRISM_RASTER_QUEUE - 1u);
+        qCount -= m;
+    };
+
+    const uint32_t waveId = blockIdx.x * (LV_BLOCK / LV_WAVE) + (threadIdx.x >> 6), numWaves = gridDim.x * (LV_BLOCK / LV_WAVE);
+    const uint32_t numItems = leafList ? dc->prismListCount : S.numSegs;
+    for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
+        const bool valid = itemBase + lane < numItems;
+        const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
+        const LvSegWalk w = lv_seg_walk_setup(U, S, segLds, mx, my, mw, halfW, halfH, wEps, N, valid, leaf, lane);
+        int px = w.x0, py = w.y0;
+        bool more = valid && w.x1 >= w.x0 && w.y1 >= w.y0;
+        while (__any(more)) {
+            const bool cand = more && lv_seg_walk_candidate(U, w, px, py, allRequested, startOffset);
+            const unsigned long long cm = __ballot(cand);
+            if (cand) {
+                const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
+                qLeaf[q] = leaf | (lane << 26);
+                qPix[q] = uint32_t(px) | (uint32_t(py) << 16);
+            }
+            qCount += unsigned(__popcll(cm));
+            if (qCount >= LV_WAVE) coverageStage(LV_WAVE);
+            if (more) more = lv_seg_walk_advance(w, px, py);
+        }
+        while (qCount > 0u) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE);   // (the next 64 segments replace the frames in LDS)
+    }
+    if (COUNTERS) {
+        const unsigned long long kept = lv_wave_sum_u64(keptLane);
+        if (lane == 0u && kept) atomicAdd(&dc->fragCounter, uint32_t(kept));   // every kept fragment
+        if (stats) {
+            if (lane == 0u && tests) atomicAdd(&dc->prims, tests);
+            if (lane == 0u && kept) atomicAdd(&dc->hits, kept);
+        }
+    }
+}
+
+template <int NT>
+__global__ __launch_bounds__(LV_BLOCK, LV_PRISM_RASTER_MIN_WAVES) void k_dc_count_pass(const LvUniforms U, const LvSceneDev S,
+                                                               const uint32_t* __restrict__ startOffset,
+                                                               uint32_t* __restrict__ fragCount, LvDevCounters* dc,
+                                                               uint32_t allRequested, const uint32_t* __restrict__ leafList,
+                                                               uint32_t collectStats) {
+    lv_kept_fragments_walk<NT, true>(U, S, startOffset, dc, allRequested, leafList, collectStats,
+                                     [&](uint32_t addr, uint32_t, uint32_t, const f3&) { atomicAdd(&fragCount[addr], 1u); });
+}
+
+// first: pass 0 (the gather's `i != 0`: any depth below 1.0)
+template <int NT>
+__global__ __launch_bounds__(LV_BLOCK, LV_PRISM_RASTER_MIN_WAVES) void k_peel_pass(const LvUniforms U, const LvSceneDev S,
+                                                           const uint32_t* __restrict__ startOffset, unsigned long long* slot,
+                                                           const uint32_t* __restrict__ prevZ, LvDevCounters* dc,
+                                                           uint32_t allRequested, const uint32_t* __restrict__ leafList,
+                                                           uint32_t first) {
+    lv_kept_fragments_walk<NT, false>(U, S, startOffset, dc, allRequested, leafList, 0u,
+                                      [&](uint32_t addr, uint32_t leaf, uint32_t tt, const f3& pos) {
+        const uint32_t zbits = __float_as_uint(lv_window_depth(U, pos));
+        if (lv_peel_candidate(zbits, prevZ[addr], first != 0u)) lv_peel_offer(slot + addr, lv_peel_key(zbits, (S.leafSeg[leaf] << 6) | tt));
+    });
+}
+
+// The requested pixels of the viewport, grid-stride, one lane per pixel: total, used pixels, maximum, minimum; wave reductions, then one
+// atomic per wave and word.  (One wave per 64 pixels -- 32 K waves on a 1920 x 1080 viewport, five atomics each on the same five
+// addresses -- took 0.62 ms on config 4; the grid is a few workgroups per CU instead.)
+__global__ __launch_bounds__(LV_BLOCK) void k_dc_reduce(const LvUniforms U, const uint32_t* __restrict__ startOffset,
+                                                       const uint32_t* __restrict__ fragCount, uint32_t allRequested, LvDcStats* st,
+                                                       LvDevCounters* dc) {
+    const size_t pixels = size_t(U.width) * U.height;
+    unsigned long long total = 0ull;
+    uint32_t used = 0u, hi = 0u, lo = 0xFFFFFFFFu;
+    for (size_t p = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x; p < pixels; p += size_t(gridDim.x) * LV_BLOCK) {
+        const uint32_t addr = lv_ppll_addr(uint32_t(p % U.width), uint32_t(p / U.width), U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+        if (allRequested == 0u && startOffset[addr] != 0u) continue;
+        const uint32_t n = fragCount[addr];
+        total += n;
+        used += n != 0u ? 1u : 0u;
+        hi = max(hi, n);
+        lo = min(lo, n);
+    }
+    total = lv_wave_sum_u64(total);
+    used = uint32_t(lv_wave_sum_u64(used));
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) {
+        hi = max(hi, (uint32_t)__shfl_xor(hi, ofs, 64));
+        lo = min(lo, (uint32_t)__shfl_xor(lo, ofs, 64));
+    }
+    if (lv_lane() == 0u) {
+        if (total) atomicAdd(&st->total, total);
+        if (used) atomicAdd(&st->used, used);
+        if (hi) { atomicMax(&st->maxCount, hi); atomicMax(&dc->maxDepthComplexity, hi); }
+        if (lo != 0xFFFFFFFFu) atomicMin(&st->minCount, lo);
+    }
+}
+
+// One lane per pixel, one wave per workgroup, the cells and groups of k_wboit_resolve
+__global__ __launch_bounds__(LV_WAVE) void k_dc_resolve(const LvUniforms U, const LvTiles T, const uint32_t* __restrict__ fragCount,
+                                                        const LvDcStats* __restrict__ st, uint32_t explicitMaxColour,
+                                                        uint32_t* __restrict__ out, uint32_t numGroups) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t maxColour = lv_dc_max_colour(st->maxCount, explicitMaxColour);
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        if (!(lx < T.tileW && ly < T.tileH)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        const uint32_t n = (x < U.width && y < U.height) ? fragCount[lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH)] : 0u;
+        out[(tile * T.tileH + ly) * T.tileW + lx] = lv_dc_resolve_pixel(U, n, maxColour);
+    }
+}
+
+// The cells and groups of k_wboit_resolve: a pure read of the accumulators
+__global__ __launch_bounds__(LV_WAVE) void k_peel_blit(const LvUniforms U, const LvTiles T, const float4* __restrict__ accum,
+                                                       uint32_t* __restrict__ out, uint32_t numGroups) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t groupsX = T.blocksX / 4u, groupsPerTile = groupsX * (T.blocksY / 4u);
+    for (uint32_t g = blockIdx.x; g < numGroups; g += gridDim.x) {
+        const uint32_t slot = g >> 6, cell = g & 63u;
+        const uint32_t grp = T.groupOrder ? T.groupOrder[slot] : slot;
+        const uint32_t tile = grp / groupsPerTile, gi = grp % groupsPerTile;
+        const uint32_t lx = (gi % groupsX) * 64u + (cell & 7u) * 8u + (lane & 7u);
+        const uint32_t ly = (gi / groupsX) * 64u + (cell >> 3) * 8u + (lane >> 3);
+        if (!(lx < T.tileW && ly < T.tileH)) continue;
+        const uint32_t x = T.tilesXY[2 * tile] + lx, y = T.tilesXY[2 * tile + 1] + ly;
+        float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (x < U.width && y < U.height) A = accum[lv_ppll_addr(x, y, U.ppllPaddedW, U.ppllTileW, U.ppllTileH)];
+        out[(tile * T.tileH + ly) * T.tileW + lx] = lv_peel_blit_pixel(U, A);
+    }
+}
+
+// every word of a mode-9 frame (n padded pixels) and the reduce's words
+__global__ __launch_bounds__(LV_BLOCK) void k_peel_clear(LvPeelBuffers B, size_t n, LvDcStats* st) {
+    const size_t i = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (i < n) {
+        if (B.slot) {
+            B.slot[i] = LV_PEEL_SLOT_EMPTY;
+            B.prevZ[i] = 0u;
+            B.accum[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            B.layers[i] = 0u;
+        }
+    }
+    if (i == 0) { st->total = 0ull; st->used = 0u; st->maxCount = 0u; st->minCount = 0xFFFFFFFFu; st->pad = 0u; }
+}
+
+// lv_depth_peeling_resolve_buffers: one lane per given entry {r, g, b, a, z, key}, all lanes racing for the pixel's slot; pixel = the
+// run of `offsets` that holds the entry (the binary search of k_wboit_add_given)
+__global__ __launch_bounds__(LV_BLOCK) void k_peel_given(const uint32_t* __restrict__ entries, uint64_t numEntries,
+                                                        const unsigned long long* __restrict__ offsets, uint32_t numPixels,
+                                                        LvPeelBuffers B, uint32_t first) {
+    const uint64_t i = uint64_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (i >= numEntries) return;
+    uint32_t lo = 0u, hi = numPixels;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    const uint32_t zbits = entries[size_t(i) * 6u + 4u];
+    if (lv_peel_candidate(zbits, B.prevZ[lo], first != 0u)) lv_peel_offer(B.slot + lo, lv_peel_key(zbits, entries[size_t(i) * 6u + 5u]));
+}
+// ... and its layer kernel: one lane per pixel; the winner is the entry of the pixel's run with the slot's key (unique within a run)
+__global__ __launch_bounds__(LV_BLOCK) void k_peel_layer_given(const uint32_t* __restrict__ entries,
+                                                              const unsigned long long* __restrict__ offsets, uint32_t numPixels,
+                                                              LvPeelBuffers B) {
+    const uint32_t p = blockIdx.x * LV_BLOCK + threadIdx.x;
+    if (p >= numPixels) return;
+    const unsigned long long won = B.slot[p];
+    if (won >= LV_PEEL_SLOT_EMPTY) return;
+    const uint32_t key = uint32_t(won), zbits = uint32_t(won >> 32);
+    for (unsigned long long i = offsets[p]; i < offsets[p + 1]; i++) {
+        const uint32_t* e = entries + size_t(i) * 6u;
+        if (e[5] != key || e[4] != zbits) continue;
+        f4 c;
+        c.x = __uint_as_float(e[0]); c.y = __uint_as_float(e[1]); c.z = __uint_as_float(e[2]); c.w = __uint_as_float(e[3]);
+        B.accum[p] = lv_peel_accumulate(B.accum[p], c);
+        break;
+    }
+    B.prevZ[p] = zbits;
+    B.layers[p] += 1u;
+    B.slot[p] = LV_PEEL_SLOT_EMPTY;
+}
+
+// lv_depth_peeling_get_buffers / lv_depth_complexity_get_buffers: the per-pixel words of the viewport, row-major (null = not wanted)
+__global__ __launch_bounds__(LV_BLOCK) void k_peel_read(LvPeelBuffers B, const uint32_t* __restrict__ fragCount, uint32_t width,
+                                                       uint32_t height, uint32_t paddedW, uint32_t tileW, uint32_t tileH,
+                                                       float4* __restrict__ outAccum, uint32_t* __restrict__ outLayers,
+                                                       uint32_t* __restrict__ outCounts) {
+    const size_t p = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x;
+    if (p >= size_t(width) * height) return;
+    const uint32_t addr = lv_ppll_addr(uint32_t(p % width), uint32_t(p / width), paddedW, tileW, tileH);
+    if (outAccum) outAccum[p] = B.accum[addr];
+    if (outLayers) outLayers[p] = B.layers[addr];
+    outCounts[p] = fragCount[addr];
+}
+
 // ================================================================ depth range
 __global__ __launch_bounds__(LV_BLOCK) void k_depth_minmax(const LvUniforms U, const lv_line_point* __restrict__ points,
                                                            uint32_t numPoints, LvDevCounters* dc) {
@@ -4551,24 +4839,197 @@ int lv_frame_wboit_buffers(lv_ctx* ctx, int64_t* outSums, uint32_t* outCounts, u
     return LV_OK;
 }
 
+// the per-pixel words of mode 9 behind ctx->peelBuf for n pixels: 16 B accumulator, 8 B slot, 4 B prevZ, 4 B layer count
+static LvPeelBuffers lv_peel_buffers(const lv_ctx* ctx, size_t n) {
+    LvPeelBuffers B;
+    char* base = (char*)ctx->peelBuf.ptr;
+    B.accum = (float4*)base;
+    B.slot = (unsigned long long*)(base + n * 16);
+    B.prevZ = (uint32_t*)(base + n * 24);
+    B.layers = (uint32_t*)(base + n * 28);
+    return B;
+}
+#define LV_PEEL_BYTES_PER_PIXEL 32u
+
+// What modes 5 and 9 share: the restrictions of the streamed modes, clear, the front of the segment rasteriser, ONE launch of
+// k_dc_count_pass and k_dc_reduce.  LV_KERNEL_PPLL_RASTER times the count pass (with the tile marking and segment culling of a sharded
+// frame), LV_KERNEL_PPLL_GATHER the reduce.  peel: the words of mode 9 are reserved and cleared too.
+static int lv_dc_count(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, LvDevCounters* dc,
+                       bool peel, const char* name, uint32_t*& leafList) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (!lv_ppll_prism_source(ctx))
+        return lv_fail(ctx, LV_E_INVALID, "%s works on the fragments of the rasterised prism, which this line data does not have", name);
+    if (ctx->opt.ppllPrismLbvhWalk)
+        return lv_fail(ctx, LV_E_INVALID, "%s runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported", name);
+    lv_fill_prism(ctx, U, S.prism);
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
+    const size_t n = padded4 * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->dcStatsDev, sizeof(LvDcStats)))) return rc;
+    if (peel && (rc = lv_buf_reserve(ctx, ctx->peelBuf, n * LV_PEEL_BYTES_PER_PIXEL))) return rc;
+    ctx->ppllPoolNodes = 0;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    const bool allRequested = ctx->tilesCoverViewport;
+    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
+    LvPeelBuffers B = {nullptr, nullptr, nullptr, nullptr};
+    if (peel) B = lv_peel_buffers(ctx, n);
+    k_peel_clear<<<uint32_t(peel ? (n + LV_BLOCK - 1) / LV_BLOCK : 1), LV_BLOCK, 0, st>>>(B, n, (LvDcStats*)ctx->dcStatsDev.ptr);
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
+    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU;
+    if (S.numSegs != 0) {
+        if (S.prism.n == 6u)
+            k_dc_count_pass<6><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc,
+                                                             allRequested ? 1u : 0u, leafList, stats ? 1u : 0u);
+        else
+            k_dc_count_pass<0><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc,
+                                                             allRequested ? 1u : 0u, leafList, stats ? 1u : 0u);
+    }
+    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
+        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
+        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
+    }
+    const uint32_t pixels = U.width * U.height;
+    const uint32_t reduceGrid = std::min<uint32_t>((pixels + LV_BLOCK - 1) / LV_BLOCK, uint32_t(ctx->numCUs) * 4u);
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_GATHER, (k_dc_reduce<<<reduceGrid, LV_BLOCK, 0, st>>>(
+            U, (const uint32_t*)ctx->ppllStart.ptr, (const uint32_t*)ctx->ppllCount.ptr, allRequested ? 1u : 0u,
+            (LvDcStats*)ctx->dcStatsDev.ptr, dc)));
+    ctx->peelW = U.width;
+    ctx->peelH = U.height;
+    ctx->peelTile[0] = U.ppllTileW;
+    ctx->peelTile[1] = U.ppllTileH;
+    return LV_OK;
+}
+
+// A mode-5 frame (depth complexity): count, reduce, resolve.  No host synchronisation: the resolve reads the maximum from device memory.
+static int lv_dc_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
+                       LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    uint32_t* leafList;
+    if ((rc = lv_dc_count(ctx, U, S, T, gridTiles, stats, dc, false, "mode 5 (depth complexity)", leafList))) return rc;
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_dc_resolve<<<numGroups, LV_WAVE, 0, st>>>(
+            U, T, (const uint32_t*)ctx->ppllCount.ptr, (const LvDcStats*)ctx->dcStatsDev.ptr, ctx->opt.dcMaxColour, out, numGroups)));
+    ctx->peelLast = LV_RENDERING_MODE_DEPTH_COMPLEXITY;
+    ctx->peelFull = ctx->tilesCoverViewport;
+    return LV_OK;
+}
+
+// A mode-9 frame (depth peeling): count and reduce as mode 5, the read-back of the maximum -- the frame's ONE host synchronisation, the
+// reference's syncWithCpu --, then min(maximum, depth_peeling_max_layers) times k_peel_pass + k_peel_layer, the blit.
+// LV_KERNEL_PPLL_RASTER: the count pass, then the peel passes; LV_KERNEL_PPLL_SHADE: the layer launches; LV_KERNEL_PPLL_RESOLVE: the blit.
+static int lv_peel_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
+                         LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    uint32_t* leafList;
+    if ((rc = lv_dc_count(ctx, U, S, T, gridTiles, stats, dc, true, "mode 9 (depth peeling)", leafList))) return rc;
+    LvDcStats hs;
+    LV_HIP(ctx, hipMemcpyAsync(&hs, ctx->dcStatsDev.ptr, sizeof(hs), hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    const uint32_t passes = std::min(hs.maxCount, ctx->opt.peelMaxLayers);
+    const bool allRequested = ctx->tilesCoverViewport;
+    const size_t n = ((size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4) * 4;
+    const LvPeelBuffers B = lv_peel_buffers(ctx, n);
+    uint32_t* const startOffset = (uint32_t*)ctx->ppllStart.ptr;
+    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU;
+    const uint32_t layerGrid = (((U.width + 7u) / 8u) * ((U.height + 7u) / 8u) + LV_BLOCK / LV_WAVE - 1u) / (LV_BLOCK / LV_WAVE);
+    // the instances and the selection of the pooled fragment stage
+    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);
+    const int layerShade = fastShade ? LV_SHADE_PLAIN : S.prism.bands ? LV_SHADE_BANDS : U.useHelicityBands ? LV_SHADE_HELICITY : LV_SHADE_PLAIN;
+    const int layerFast = fastShade ? 2 : 0;
+    for (uint32_t i = 0; i < passes && S.numSegs != 0; i++) {
+        // (LV_PEEL_MASK_DONE: the finished pixels have left the requested-pixel mask, stage A has to look)
+        const uint32_t allReq = (allRequested && (i == 0u || !LV_PEEL_MASK_DONE)) ? 1u : 0u;
+        if (S.prism.n == 6u)
+            LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RASTER, (k_peel_pass<6><<<passGrid, LV_BLOCK, 0, st>>>(U, S, startOffset, B.slot, B.prevZ, dc,
+                                                                                                    allReq, leafList, i == 0u ? 1u : 0u)));
+        else
+            LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RASTER, (k_peel_pass<0><<<passGrid, LV_BLOCK, 0, st>>>(U, S, startOffset, B.slot, B.prevZ, dc,
+                                                                                                    allReq, leafList, i == 0u ? 1u : 0u)));
+        LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, lv_peel_launch_layer(st, layerGrid, layerShade, layerFast, U, S, startOffset, B));
+    }
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_peel_blit<<<numGroups, LV_WAVE, 0, st>>>(U, T, B.accum, out, numGroups)));
+    ctx->peelLast = LV_RENDERING_MODE_DEPTH_PEELING;
+    ctx->peelFull = allRequested;
+    return LV_OK;
+}
+
+// lv_depth_complexity_get_buffers (accum = layers = null) and lv_depth_peeling_get_buffers
+int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outLayers, uint32_t* outCounts, uint64_t capacityPixels) {
+    const char* fn = mode == LV_RENDERING_MODE_DEPTH_PEELING ? "lv_depth_peeling_get_buffers" : "lv_depth_complexity_get_buffers";
+    if (ctx->peelLast != mode || !ctx->peelFull || !ctx->ppllCount.ptr || ctx->peelW != ctx->width || ctx->peelH != ctx->height)
+        return lv_fail(ctx, LV_E_STATE, "%s: the last frame was not a mode-%d frame over the whole viewport", fn, mode);
+    const uint64_t pixels = uint64_t(ctx->peelW) * ctx->peelH;
+    if (capacityPixels < pixels)
+        return lv_fail(ctx, LV_E_INVALID, "%s: the arrays hold %llu pixels, need %llu", fn, (unsigned long long)capacityPixels,
+                       (unsigned long long)pixels);
+    const bool peel = mode == LV_RENDERING_MODE_DEPTH_PEELING;
+    int rc;
+    const size_t accBytes = peel ? size_t(pixels) * 16 : 0, wordBytes = size_t(pixels) * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, accBytes + 2 * wordBytes))) return rc;
+    float4* dAccum = (float4*)ctx->scratchRays.ptr;
+    uint32_t* dLayers = (uint32_t*)((char*)ctx->scratchRays.ptr + accBytes);
+    uint32_t* dCounts = dLayers + size_t(pixels);
+    LvPeelBuffers B = {nullptr, nullptr, nullptr, nullptr};
+    if (peel) B = lv_peel_buffers(ctx, ((size_t(ctx->ppllPaddedW) * ctx->ppllPaddedH + 3) / 4) * 4);
+    k_peel_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
+            B, (const uint32_t*)ctx->ppllCount.ptr, ctx->peelW, ctx->peelH, ctx->ppllPaddedW, ctx->peelTile[0], ctx->peelTile[1],
+            peel ? dAccum : nullptr, peel ? dLayers : nullptr, dCounts);
+    LV_HIP(ctx, hipGetLastError());
+    if (peel) {
+        LV_HIP(ctx, hipMemcpyAsync(outAccum, dAccum, accBytes, hipMemcpyDeviceToHost, ctx->stream));
+        LV_HIP(ctx, hipMemcpyAsync(outLayers, dLayers, wordBytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    LV_HIP(ctx, hipMemcpyAsync(outCounts, dCounts, wordBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LV_OK;
+}
+
+// lv_depth_complexity_get_stats: the words of k_dc_reduce
+int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]) {
+    if (ctx->peelLast != LV_RENDERING_MODE_DEPTH_COMPLEXITY || !ctx->peelFull || !ctx->dcStatsDev.ptr || ctx->peelW != ctx->width ||
+        ctx->peelH != ctx->height)
+        return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_stats: the last frame was not a mode-5 frame over the whole viewport");
+    LvDcStats hs;
+    LV_HIP(ctx, hipMemcpyAsync(&hs, ctx->dcStatsDev.ptr, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = hs.total; out[1] = hs.used; out[2] = hs.maxCount; out[3] = hs.minCount == 0xFFFFFFFFu ? 0u : hs.minCount;
+    out[4] = uint64_t(ctx->peelW) * ctx->peelH;
+    return LV_OK;
+}
+
 int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
                     uint32_t tileH, void* outDevice) {
     if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
-        mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64)
-        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 6 = MBOIT, 8 = WBOIT, "
-                                          "10 = Atomic Loop 64)", mode);
+        mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64 &&
+        mode != LV_RENDERING_MODE_DEPTH_COMPLEXITY && mode != LV_RENDERING_MODE_DEPTH_PEELING)
+        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 5 = depth complexity, "
+                                          "6 = MBOIT, 8 = WBOIT, 9 = depth peeling, 10 = Atomic Loop 64)", mode);
     // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
     const bool mboit = mode == LV_RENDERING_MODE_MBOIT;
     const bool mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
     const bool wboit = mode == LV_RENDERING_MODE_WBOIT;           // (the prism's fragments too, but no pool: lv_wboit_frame)
-    const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 || wboit;   // (the same, lv_al64_frame: `al64` = either pool-free mode)
+    const bool dcMode = mode == LV_RENDERING_MODE_DEPTH_COMPLEXITY, peel = mode == LV_RENDERING_MODE_DEPTH_PEELING;   // (lv_dc_frame, lv_peel_frame)
+    const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 || wboit || dcMode || peel;   // (lv_al64_frame: `al64` = any pool-free mode)
     ctx->mboitStreamLast = false;   // (set again at the end of a streamed mode-6 frame)
     ctx->mboitStreamFull = false;
     ctx->al64Last = false;          // (set again at the end of a mode-10 frame)
     ctx->al64Full = false;
     ctx->wboitLast = false;         // (set again at the end of a mode-8 frame)
     ctx->wboitFull = false;
-    const char* const poolName = wboit ? "WBOIT" : al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
+    ctx->peelLast = 0;              // (set again at the end of a mode-5 or mode-9 frame)
+    ctx->peelFull = false;
+    const char* const poolName = dcMode ? "depth complexity" : peel ? "depth peeling" : wboit ? "WBOIT" : al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
     if ((mlab || al64) && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
                                           "capsule_entry is not supported", mode, poolName);
@@ -4790,6 +5251,10 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         if ((rc = lv_mboit_stream_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else if (wboit) {
         if ((rc = lv_wboit_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
+    } else if (dcMode) {
+        if ((rc = lv_dc_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
+    } else if (peel) {
+        if ((rc = lv_peel_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else if (al64) {
         if ((rc = lv_al64_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
     } else {
@@ -5087,6 +5552,7 @@ static int lv_upload_runs(lv_ctx* ctx, const uint32_t* entries, size_t entryByte
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), numPixels * 4, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), numPixels * 4, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    ctx->peelLast = 0;   // (ppllCount no longer holds a mode-5 or mode-9 frame)
     return lv_single_tile(ctx, txy, w, h, T, numGroups);
 }
 // row-major addressing of a w x h rectangle: one 1 x 1-pixel tiling, address = y * w + x
@@ -5231,6 +5697,7 @@ int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKe
     if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
     ctx->al64Last = false;   // (the buffer no longer holds a frame)
+    ctx->peelLast = 0;
     ctx->mboitStreamLast = false;
     if (numKeys) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, keys, size_t(numKeys) * 8, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
@@ -5284,6 +5751,7 @@ int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
     if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
     ctx->wboitLast = false;   // (the buffers no longer hold a frame)
+    ctx->peelLast = 0;
     ctx->al64Last = false;
     ctx->mboitStreamLast = false;
     if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 20, hipMemcpyHostToDevice, st));
@@ -5311,6 +5779,54 @@ int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
         return lv_fail(ctx, LV_E_CAPACITY, "WBOIT: a pixel holds more than %u fragments (the 64-bit sums are exact up to that count)",
                        LV_WBOIT_MAX_COUNT);
     return LV_OK;
+}
+
+// lv_depth_peeling_resolve_buffers: the caller's fragments (pixel p of the w x h rectangle owns entries [offsets[p], offsets[p + 1]))
+// peeled by min(longest run, depth_peeling_max_layers) times k_peel_given + k_peel_layer_given, then k_peel_blit, row-major addressing
+int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
+                               uint8_t* out, float* outAccum, uint32_t* outLayers) {
+    const uint64_t numPixels = uint64_t(w) * h;
+    if (numEntries >= 0xFFFFFFF0ull / 6u || numPixels > 0x7FFFFFF0ull / 8u) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
+    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
+    uint64_t longest = 0;
+    for (uint64_t p = 0; p < numPixels; p++) {
+        if (offsets[p + 1] < offsets[p]) return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend", (unsigned long long)p);
+        longest = std::max<uint64_t>(longest, offsets[p + 1] - offsets[p]);
+    }
+    hipStream_t st = ctx->stream;
+    LvUniforms U;
+    lv_row_major_uniforms(ctx, U, w, h);
+    const size_t n = size_t(numPixels);
+    const size_t entryBytes = size_t(numEntries ? numEntries : 1) * 24, offBytes = size_t(numPixels + 1) * 8;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->peelBuf, n * LV_PEEL_BYTES_PER_PIXEL))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->dcStatsDev, sizeof(LvDcStats)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, entryBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, n * 4))) return rc;
+    ctx->peelLast = 0;   // (the buffers no longer hold a frame)
+    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 24, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
+    const LvPeelBuffers B = lv_peel_buffers(ctx, n);
+    k_peel_clear<<<uint32_t((n + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(B, n, (LvDcStats*)ctx->dcStatsDev.ptr);
+    const uint32_t passes = uint32_t(std::min<uint64_t>(longest, ctx->opt.peelMaxLayers));
+    for (uint32_t i = 0; i < passes; i++) {
+        k_peel_given<<<uint32_t((numEntries + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
+                (const uint32_t*)ctx->ppllNodes.ptr, numEntries, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels), B,
+                i == 0u ? 1u : 0u);
+        k_peel_layer_given<<<uint32_t((n + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
+                (const uint32_t*)ctx->ppllNodes.ptr, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels), B);
+    }
+    static const uint32_t txy[2] = {0u, 0u};
+    LvTiles T;
+    uint32_t numGroups;
+    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
+    k_peel_blit<<<numGroups, LV_WAVE, 0, st>>>(U, T, B.accum, (uint32_t*)ctx->outDev.ptr, numGroups);
+    // (row-major addressing: the words lie as the caller's arrays do)
+    if (outAccum) LV_HIP(ctx, hipMemcpyAsync(outAccum, B.accum, n * 16, hipMemcpyDeviceToHost, st));
+    if (outLayers) LV_HIP(ctx, hipMemcpyAsync(outLayers, B.layers, n * 4, hipMemcpyDeviceToHost, st));
+    return lv_resolve_read_back(ctx, out, n);
 }
 
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,

@@ -35,6 +35,10 @@ void HeadlessLineRenderer::createRenderer(RenderingMode mode) {
         lineRenderer.reset(new HipMBOITRenderer(&sceneData, transferFunctionWindow));
     else if (mode == RENDERING_MODE_WBOIT)
         lineRenderer.reset(new HipWBOITRenderer(&sceneData, transferFunctionWindow));
+    else if (mode == RENDERING_MODE_DEPTH_PEELING)
+        lineRenderer.reset(new HipDepthPeelingRenderer(&sceneData, transferFunctionWindow));
+    else if (mode == RENDERING_MODE_DEPTH_COMPLEXITY)
+        lineRenderer.reset(new HipDepthComplexityRenderer(&sceneData, transferFunctionWindow));
     else if (mode == RENDERING_MODE_ATOMIC_LOOP_64)
         lineRenderer.reset(new HipAtomicLoop64Renderer(&sceneData, transferFunctionWindow));
     else

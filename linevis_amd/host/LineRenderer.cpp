@@ -855,4 +855,72 @@ bool HipWBOITRenderer::setNewSettings(const SettingsMap& settings) {
     return r;
 }
 
+HipDepthPeelingRenderer::HipDepthPeelingRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Depth Peeling", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipDepthPeelingRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipDepthPeelingRenderer::setNewState(const InternalState& newState) {
+    currentStateName = newState.name;   // (DepthPeelingRenderer reads no renderer settings)
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipDepthPeelingRenderer::render() {
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    setOption("depth_peeling_max_layers", std::to_string(maxLayers));
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_DEPTH_PEELING); // clear -> count -> (peel pass, shade the layer) x D -> blit
+}
+
+bool HipDepthPeelingRenderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    std::string layers;
+    if (settings.getValueOpt("depth_peeling_max_layers", layers) && setOption("depth_peeling_max_layers", layers))
+        maxLayers = std::atoi(layers.c_str());   // (a value the C ABI refuses leaves maxLayers as it is)
+    for (const char* key : {"ppll_tile_width", "ppll_tile_height", "ppll_fragment_source", "ppll_fragment_colour", "ppll_prism_rasteriser"}) {
+        std::string s;
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
+HipDepthComplexityRenderer::HipDepthComplexityRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Depth Complexity Renderer", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipDepthComplexityRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipDepthComplexityRenderer::setNewState(const InternalState& newState) {
+    currentStateName = newState.name;   // (DepthComplexityRenderer reads no renderer settings)
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipDepthComplexityRenderer::render() {
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    setOption("depth_complexity_max_colour", std::to_string(maxColour));
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_DEPTH_COMPLEXITY); // clear -> count -> reduce -> resolve
+}
+
+bool HipDepthComplexityRenderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    std::string colour;
+    if (settings.getValueOpt("depth_complexity_max_colour", colour) && setOption("depth_complexity_max_colour", colour))
+        maxColour = std::atoi(colour.c_str());   // (a value the C ABI refuses leaves maxColour as it is)
+    for (const char* key : {"ppll_tile_width", "ppll_tile_height", "ppll_fragment_source", "ppll_fragment_colour", "ppll_prism_rasteriser"}) {
+        std::string s;
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
 } // namespace lv

@@ -26,8 +26,10 @@ enum RenderingMode : int32_t {
     RENDERING_MODE_NONE = -1,
     RENDERING_MODE_PER_PIXEL_LINKED_LIST = 2,
     RENDERING_MODE_MLAB = 3,
+    RENDERING_MODE_DEPTH_COMPLEXITY = 5,
     RENDERING_MODE_MBOIT = 6,
     RENDERING_MODE_WBOIT = 8,
+    RENDERING_MODE_DEPTH_PEELING = 9,
     RENDERING_MODE_ATOMIC_LOOP_64 = 10,
     RENDERING_MODE_VULKAN_RAY_TRACER = 11,
 };
@@ -429,6 +431,46 @@ public:
 private:
     std::string currentStateName;
     std::string depthWeight = "reference";          // wboit_depth_weight
+};
+
+/// "Depth Peeling" plugin (src/Renderers/OIT/DepthPeelingRenderer.hpp) re-hosted on HIP (rendering mode 9): every layer of the PPLL
+/// plugin's rasterised prism composited in depth order.  DepthPeelingRenderer::setNewState does nothing; the build-owned key
+/// depth_peeling_max_layers caps the passes (linevis_hip.h).
+class HipDepthPeelingRenderer : public LineRenderer {
+public:
+    HipDepthPeelingRenderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_DEPTH_PEELING; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    bool setNewSettings(const SettingsMap& settings) override;
+    bool getUseAnalyticEllipticTubes() const override { return true; }
+    int getMaxLayers() const { return maxLayers; }
+
+private:
+    std::string currentStateName;
+    int maxLayers = 2000;                           // depth_peeling_max_layers (DepthPeelingRenderer.cpp:288)
+};
+
+/// "Depth Complexity Renderer" plugin (src/Renderers/OIT/DepthComplexityRenderer.hpp) re-hosted on HIP (rendering mode 5): the number
+/// of fragments of the PPLL plugin's rasterised prism per pixel.  DepthComplexityRenderer::setNewState does nothing; the build-owned
+/// key depth_complexity_max_colour fixes numFragmentsMaxColor (0 = from the frame's maximum).
+class HipDepthComplexityRenderer : public LineRenderer {
+public:
+    HipDepthComplexityRenderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_DEPTH_COMPLEXITY; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    bool setNewSettings(const SettingsMap& settings) override;
+    bool getUseAnalyticEllipticTubes() const override { return true; }
+    int getMaxColour() const { return maxColour; }
+
+private:
+    std::string currentStateName;
+    int maxColour = 0;                              // depth_complexity_max_colour
 };
 
 } // namespace lv

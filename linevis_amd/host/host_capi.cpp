@@ -511,6 +511,20 @@ int lvh_renderer_wboit_state(void* r, int32_t* out1) {   // {depth weight: 0 = r
     out1[0] = m->getDepthWeight() == "opengl" ? 1 : 0;
     return 0;
 }
+int lvh_renderer_depth_peeling_state(void* r, int32_t* out1) {   // {maxLayers} of a mode-9 plugin
+    HeadlessLineRenderer* h = static_cast<HeadlessLineRenderer*>(r);
+    const HipDepthPeelingRenderer* m = dynamic_cast<const HipDepthPeelingRenderer*>(h->getLineRenderer());
+    if (!m) return -1;
+    out1[0] = m->getMaxLayers();
+    return 0;
+}
+int lvh_renderer_depth_complexity_state(void* r, int32_t* out1) {   // {maxColour} of a mode-5 plugin
+    HeadlessLineRenderer* h = static_cast<HeadlessLineRenderer*>(r);
+    const HipDepthComplexityRenderer* m = dynamic_cast<const HipDepthComplexityRenderer*>(h->getLineRenderer());
+    if (!m) return -1;
+    out1[0] = m->getMaxColour();
+    return 0;
+}
 void lvh_renderer_destroy(void* r) { delete static_cast<HeadlessLineRenderer*>(r); }
 void lvh_renderer_set_resolution(void* r, uint32_t w, uint32_t h) { static_cast<HeadlessLineRenderer*>(r)->setRenderingResolution(w, h); }
 void lvh_renderer_set_line_data(void* r, void* flow, int isNewData) {

@@ -88,6 +88,8 @@ def load():
         "lvh_renderer_mboit_state": (i32, [vp, vp, vp]),
         "lvh_renderer_atomic_loop_state": (i32, [vp, vp]),
         "lvh_renderer_wboit_state": (i32, [vp, vp]),
+        "lvh_renderer_depth_peeling_state": (i32, [vp, vp]),
+        "lvh_renderer_depth_complexity_state": (i32, [vp, vp]),
         "lvh_renderer_destroy": (None, [vp]),
         "lvh_renderer_set_resolution": (None, [vp, u32, u32]),
         "lvh_renderer_set_line_data": (None, [vp, vp, i32]),
@@ -638,6 +640,20 @@ class HeadlessLineRenderer:
         if self.L.lvh_renderer_wboit_state(self.h, _p(v)) != 0:
             return None
         return {"depthWeight": "opengl" if int(v[0]) else "reference"}
+
+    def depth_peeling_state(self):
+        """{maxLayers} of the mode-9 plugin (None for the other plugins)"""
+        v = np.zeros(1, dtype=np.int32)
+        if self.L.lvh_renderer_depth_peeling_state(self.h, _p(v)) != 0:
+            return None
+        return {"maxLayers": int(v[0])}
+
+    def depth_complexity_state(self):
+        """{maxColour} of the mode-5 plugin (None for the other plugins)"""
+        v = np.zeros(1, dtype=np.int32)
+        if self.L.lvh_renderer_depth_complexity_state(self.h, _p(v)) != 0:
+            return None
+        return {"maxColour": int(v[0])}
 
     def needs_re_render(self):
         return bool(self.L.lvh_renderer_needs_re_render(self.h))

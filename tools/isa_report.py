@@ -17,7 +17,8 @@ sys.path.insert(0, ROOT)
 from linevis_amd import build as lv_build  # noqa: E402
 
 HOT = ["k_ao_rays", "k_ao_primary", "k_render_rt", "k_ppll_gather", "k_ppll_resolve", "k_render_rt_mlat", "k_ao_reduce",
-       "k_ppll_raster_prism", "k_ppll_shade_prism", "k_ppll_cull_segments", "k_ppll_select_nearest", "k_mboit_stream_pass", "k_al64_stream_pass", "k_wboit_stream_pass"]
+       "k_ppll_raster_prism", "k_ppll_shade_prism", "k_ppll_cull_segments", "k_ppll_select_nearest", "k_mboit_stream_pass", "k_al64_stream_pass", "k_wboit_stream_pass",
+       "k_dc_count_pass", "k_peel_pass", "k_peel_layer"]
 
 
 def demangle(names):
@@ -120,7 +121,7 @@ def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "isa_r06.txt")
     lines = ["# ISA report of the frame kernels (hipcc %s, gfx950); generated by tools/isa_report.py" % " ".join(lv_build.FLAGS), ""]
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("lv_render.hip", "lv_mlat.hip"):
+        for src in ("lv_render.hip", "lv_peel.hip", "lv_mlat.hip"):
             asm, rpass = compile_s(os.path.join(lv_build.CSRC, src), tmp)
             res = resources(rpass)
             fns = functions(asm)
