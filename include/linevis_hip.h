@@ -767,7 +767,13 @@ int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_e
  * floats, b_0 then the normalised b_1 ... b_N of each pixel, zeros where b_0 is under the threshold. */
 int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                              uint32_t h, float log_depth_min, float log_depth_max, float* out_moments, uint8_t* out_rgba8);
-/* The moments of the last frame when that was a mode-6 frame with mboit_fragment_storage = streamed over the whole viewport:
+/* The *_get_* calls below (lv_mboit_get_moments, lv_atomic_loop_get_num_layers / _get_buffers, lv_wboit_get_buffers,
+ * lv_depth_complexity_get_buffers / _get_stats, lv_depth_peeling_get_buffers) read what the last frame left on the device.  The
+ * context keeps ONE record of that frame: lv_render of any mode replaces it, and every *_resolve_buffers test entry point of modes
+ * 3, 6, 8, 9 and 10 clears it (they overwrite the per-pixel counts and the counters), whichever mode it belongs to.  After such a
+ * call every *_get_* call returns LV_E_STATE until the next frame of its mode.
+ *
+ * The moments of the last frame when that was a mode-6 frame with mboit_fragment_storage = streamed over the whole viewport:
  * width * height * (1 + N) floats, row-major, in the layout of out_moments above (b_0, then the normalised b_1 ... b_N, zeros
  * where b_0 is under the threshold).  LV_E_STATE when the last frame was anything else (pooled storage, another mode, a tile list
  * that does not cover the viewport, a multi-device handle); LV_E_INVALID for a null pointer or capacity_floats below that size;

@@ -965,7 +965,8 @@ int lv_render(lv_ctx* ctx, int mode, uint32_t x0, uint32_t y0, uint32_t w, uint3
     // mboit_fragment_storage = streamed, mode 8 and mode 10: the resolve's overflow flag (the frame is synchronised anyway)
     for (int r = 0; r < lv_multi_num_ranks(ctx); r++) {
         lv_ctx* c = lv_multi_rank(ctx, r);
-        if (!c->mboitStreamLast && !c->al64Last && !c->wboitLast) continue;
+        if (c->streamed.mode != LV_RENDERING_MODE_MBOIT && c->streamed.mode != LV_RENDERING_MODE_WBOIT &&
+            c->streamed.mode != LV_RENDERING_MODE_ATOMIC_LOOP_64) continue;
         (void)hipSetDevice(c->device);
         rc = lv_mboit_stream_overflow(c);
         (void)hipSetDevice(ctx->device);
@@ -1026,11 +1027,11 @@ static int lv_get_stats_impl(lv_ctx* ctx, lv_stats* out, bool aggregate) {
         s.ao_prim_may_axis = hc.aoPrimMayAxis;
         s.ao_prim_may_both = hc.aoPrimMayBoth;
         s.mboit_degenerate_pixels = hc.mboitDegenerate;
-        if (ctx->mboitStreamLast && hc.mboitOverflow)
+        if (ctx->streamed.mode == LV_RENDERING_MODE_MBOIT && hc.mboitOverflow)
             return lv_fail(ctx, LV_E_CAPACITY, "MBOIT (streamed): a pixel of the last frame is covered by more than 131071 kept fragments");
-        if (ctx->wboitLast && hc.mboitOverflow)
+        if (ctx->streamed.mode == LV_RENDERING_MODE_WBOIT && hc.mboitOverflow)
             return lv_fail(ctx, LV_E_CAPACITY, "WBOIT: a pixel of the last frame is covered by more than 131071 kept fragments");
-        if (ctx->al64Last && hc.mboitOverflow)
+        if (ctx->streamed.mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 && hc.mboitOverflow)
             return lv_fail(ctx, LV_E_CAPACITY, "Atomic Loop 64: a pixel of the last frame is covered by more than 131071 kept fragments");
         for (int k = 0; k < 3; k++) { s.ao_phase_iterations[k] = hc.aoPhaseIters[k]; s.ao_phase_lanes[k] = hc.aoPhaseLanes[k]; }
     }

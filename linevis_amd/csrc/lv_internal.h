@@ -250,18 +250,19 @@ struct lv_ctx {
     uint32_t mboitBoxOrd[6] = {0, 0, 0, 0, 0, 0};   // mode 6: k_mboit_points_box's result for the current line points (lv_bvh_build resets)
     bool mboitBoxValid = false;
     LvDeviceBuffer mboitAccum;                // mode 6, streamed storage: 1 + N moment sums and 4 colour sums of 8 B per padded pixel (addressed like ppllCount)
-    bool mboitStreamLast = false, mboitStreamFull = false;   // the last frame was a streamed mode-6 frame / one over the whole viewport
-    uint32_t mboitStreamW = 0, mboitStreamH = 0, mboitStreamN = 0, mboitStreamTile[2] = {0, 0};   // that frame's viewport, moment count and ppll tile
     LvDeviceBuffer al64Buf;                   // mode 10: K slots and 5 tail sums of 8 B per padded pixel (addressed like ppllCount)
-    bool al64Last = false, al64Full = false;  // the last frame was a mode-10 frame / one over the whole viewport
-    uint32_t al64W = 0, al64H = 0, al64K = 0, al64Tile[2] = {0, 0};   // that frame's viewport, layer count and ppll tile
     LvDeviceBuffer wboitBuf;                  // mode 8: 5 sums of 8 B per padded pixel (addressed like ppllCount)
-    bool wboitLast = false, wboitFull = false;   // the last frame was a mode-8 frame / one over the whole viewport
-    uint32_t wboitW = 0, wboitH = 0, wboitTile[2] = {0, 0};   // that frame's viewport and ppll tile
     LvDeviceBuffer peelBuf, dcStatsDev;       // mode 9: 32 B per padded pixel (lv_peel_buffers); modes 5 and 9: the words of k_dc_reduce
-    int peelLast = 0;                         // 5 / 9: the last frame was a frame of that mode (ppllCount holds its counts); 0: neither
-    bool peelFull = false;                    // ... over the whole viewport
-    uint32_t peelW = 0, peelH = 0, peelTile[2] = {0, 0};   // that frame's viewport and ppll tile
+    // The last frame, when it left per-pixel buffers behind that a *_get_* call reads: a streamed mode-6 frame (mboitAccum), a mode-8
+    // (wboitBuf), mode-10 (al64Buf), mode-5 or mode-9 frame (ppllCount, peelBuf, dcStatsDev).  Each of these frame functions sets it;
+    // lv_frame_render clears it at its top, and so does every resolve-only entry point (they overwrite ppllCount and the counters).
+    struct StreamedFrame {
+        int mode = 0;                         // 0: none; else LV_RENDERING_MODE_* (5, 6, 8, 9 or 10)
+        bool full = false;                    // the frame covered the whole viewport
+        uint32_t w = 0, h = 0;                // its viewport
+        uint32_t tile[2] = {0, 0};            // its ppll tile
+        uint32_t param = 0;                   // mode 6: the moment count N; mode 10: the layer count K
+    } streamed;
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
     LvDeviceBuffer selftestIn, selftestOut;   // lv_selftest_eval: argument and result words

@@ -2869,30 +2869,31 @@ __global__ __launch_bounds__(LV_BLOCK) void k_mboit_stream_moments(const unsigne
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Atomic Loop 64 (rendering mode 10, AtomicLoop64Renderer): the K nearest fragments of every pixel exactly, the rest as a weighted
-// average behind them (lv_al64.h).  (K + 5) x 8 B per padded pixel (addressed like ppllCount), no fragment pool, no regrowth, no
-// read-back; ppllCount is the 32-bit count of the fragments past the discard.
-//   k_al64_stream_pass   the loop of k_mboit_stream_pass (stages A and B through the lv_seg_walk_* / lv_seg_pair_coverage helpers,
-//                        the second LDS queue, stage C one lane per fragment) with lv_al64_insert as the fragment's store; ONE
-//                        launch per frame.  The loop is a copy because k_mboit_stream_pass sits at the edge of its register budget
-//                        and must compile as it does; once that allows it, the two kernels should share one skeleton with
-//                        stage C as a parameter
-//   k_al64_resolve       the cells and groups of k_mboit_stream_blend over the frame's tile list: lv_al64_resolve_pixel, the maximum
-//                        count and the overflow flag (a count above LV_AL64_MAX_COUNT)
-// The buffer is cleared per frame and not by the resolve (as the reference does): a tile list may repeat or overlap pixels.
-__global__ __launch_bounds__(LV_BLOCK) void k_al64_clear(unsigned long long* __restrict__ buf, size_t numWords, uint32_t K) {
-    const uint32_t stride = K + LV_AL64_TAIL;
-    for (size_t i = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x; i < numWords; i += size_t(gridDim.x) * LV_BLOCK)
-        buf[i] = uint32_t(i % stride) < K ? LV_AL64_EMPTY : 0ull;
-}
-
-template <int NT, int SHADE, int FAST>
-__global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_al64_stream_pass(const LvUniforms U, const LvSceneDev S,
+// The streamed fragment pass of modes 8 and 10: ONE launch per frame, no fragment pool.
+//   k_stream_pass   the skeleton: stage A walks the wave's 64 segments and queues (pixel, segment) pairs in LDS, stage B tests 64 pairs
+//                   at a time (lv_seg_walk_* / lv_seg_pair_coverage, as k_ppll_raster_prism) and queues the covered triangles in a
+//                   second LDS queue, stage C shades 64 of them, one lane per fragment, while the 19 words stages A and B keep per lane
+//                   are parked in LDS.  A mode supplies the meaning of `buf` and `arg` and two pieces of stage C: the fragment's
+//                   store, and the two lines that count kept and stored fragments.
+//                     MODE = LV_RENDERING_MODE_ATOMIC_LOOP_64   buf: (K + 5) words per pixel, arg: K, store: lv_al64_insert
+//                     MODE = LV_RENDERING_MODE_WBOIT            buf: 5 sums per pixel, arg: the weight mode, store: lv_wboit_add
+// It is a single __global__ template with the mode's text under `if constexpr`, not an inlined helper: with the body as a
+// __forceinline__ device function that takes stage C as a lambda, every instance gained 20 to 30 VGPRs (mode 10's
+// <0, 1, 0> instance reached 256 and spilled); as a __forceinline__ function template on the mode behind two thin kernels every instance
+// still changed by a few dozen instructions.  This shape compiles every instance to the instructions of the two kernels it
+// replaces (tools/isa_report.py --compare; EXPERIMENTS.md).
+// k_mboit_stream_pass is not an instance.  Joining it would take:
+//   - LvMboitParams out of the kernel's signature, and its two launches per frame (count / colour) expressed as modes;
+//   - its per-lane counters with wave reductions at the end replaced by the per-wave ballot counts below;
+//   - the scalarised wave index and uniform() constants, which change its code at the edge of its register budget.
+template <int MODE, int NT, int SHADE, int FAST>
+__global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_stream_pass(const LvUniforms U, const LvSceneDev S,
                                                                    const uint32_t* __restrict__ startOffset,
                                                                    uint32_t* __restrict__ fragCount, unsigned long long* buf,
                                                                    LvDevCounters* dc, uint32_t allRequested,
-                                                                   const uint32_t* __restrict__ leafList, uint32_t K,
+                                                                   const uint32_t* __restrict__ leafList, uint32_t arg,
                                                                    uint32_t collectStats) {
+    static_assert(MODE == LV_RENDERING_MODE_ATOMIC_LOOP_64 || MODE == LV_RENDERING_MODE_WBOIT, "k_stream_pass: no stage C for this mode");
     __shared__ uint32_t s_qLeaf[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE], s_qPix[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE];
     __shared__ uint32_t s_fFrag[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE], s_fPix[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE];
     __shared__ float s_seg[LV_BLOCK / LV_WAVE][20][LV_WAVE];
@@ -2927,7 +2928,7 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_al64_st
     const float halfW = uniform(0.5f * float(U.width)), halfH = uniform(0.5f * float(U.height));
     const float wEps = uniform(1e-3f * U.nearDist);
     const float tLo = 0.0001f, tHi = __uint_as_float(__float_as_uint(1000.0f) + 1u);
-    const size_t stride = size_t(K) + LV_AL64_TAIL;
+    [[maybe_unused]] const size_t stride = size_t(arg) + LV_AL64_TAIL;   // mode 10: words per pixel (here, not in stage C: there its instances compile differently)
     const bool stats = collectStats != 0u;
     unsigned qHead = 0u, qCount = 0u;   // (pixel, segment) pairs (wave-uniform)
     unsigned fHead = 0u, fCount = 0u;   // covered triangles (wave-uniform)
@@ -2940,11 +2941,14 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_al64_st
     int px = 0, py = 0;
     bool more = false;
 
-    // stage C on the m <= 64 oldest fragments of the queue: shaded as k_ppll_shade_prism<..., LV_ENTRY_MLAB> shades them (the `kept`
-    // rules, then the gather's discard, AtomicLoop64Gather.glsl:56), key = window depth bits << 32 | packUnorm4x8(colour), inserted.
+    // stage C on the m <= 64 oldest fragments of the queue, shaded as k_ppll_shade_prism shades them, with the window depth of mode 3.
+    //   mode 10: the `kept` rules, then the gather's discard (AtomicLoop64Gather.glsl:56); key = window depth bits << 32 |
+    //            packUnorm4x8(colour), inserted
+    //   mode 8:  only the `kept` rules discard (WBOITGather.glsl has no alpha test); the five terms added
     // (One call site, as in k_mboit_stream_pass.)
     auto fragmentStage = [&](unsigned m) __attribute__((always_inline)) {
-        bool hit = false, stored = false;
+        bool hit = false;
+        [[maybe_unused]] bool stored = false;
         if (lane < m) {
             const unsigned q = (fHead + lane) & (LV_MBOIT_STREAM_QUEUE - 1u);
             const uint32_t w0 = fPix[q], w1 = fFrag[q];
@@ -2958,18 +2962,33 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_al64_st
             float depth;
             const f4 color = lv_shade_prism<SHADE, FAST>(S, U, s_prismRing, aoTexel, o, d, tLo, tHi, leaf, tt, rq, U.ppllRasterColour != 0u, depth, kept);
             hit = kept;
-            if (kept && color.w >= 0.001f) {
-                const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
-                const float z = lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
-                const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | lv_pack_unorm4x8(color);
-                unsigned long long* slots = buf + size_t(addr) * stride;
-                lv_al64_insert(slots, K, key, slots + K);
-                atomicAdd(&fragCount[addr], 1u);
-                stored = true;
+            if constexpr (MODE == LV_RENDERING_MODE_ATOMIC_LOOP_64) {
+                if (kept && color.w >= 0.001f) {
+                    const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+                    const float z = lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | lv_pack_unorm4x8(color);
+                    unsigned long long* slots = buf + size_t(addr) * stride;
+                    lv_al64_insert(slots, arg, key, slots + arg);
+                    atomicAdd(&fragCount[addr], 1u);
+                    stored = true;
+                }
+            } else {
+                if (kept) {
+                    const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
+                    const float z = lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
+                    lv_wboit_add(buf + size_t(addr) * LV_WBOIT_SUMS, color, z, arg);
+                    atomicAdd(&fragCount[addr], 1u);
+                }
             }
         }
-        keptSum += uint32_t(__popcll(__ballot(stored)));
-        if (stats) hits += (unsigned long long)__popcll(__ballot(hit));
+        if constexpr (MODE == LV_RENDERING_MODE_ATOMIC_LOOP_64) {   // every fragment past the discard; hits: every kept one
+            keptSum += uint32_t(__popcll(__ballot(stored)));
+            if (stats) hits += (unsigned long long)__popcll(__ballot(hit));
+        } else {   // every kept fragment
+            const uint32_t keptNow = uint32_t(__popcll(__ballot(hit)));
+            keptSum += keptNow;
+            if (stats) hits += (unsigned long long)keptNow;
+        }
         fHead = (fHead + m) & (LV_MBOIT_STREAM_QUEUE - 1u);
         fCount -= m;
     };
@@ -3042,11 +3061,25 @@ __global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_al64_st
             if (more) more = lv_seg_walk_advance(w, px, py);
         }
     }
-    if (lane == 0u && keptSum > 0u) atomicAdd(&dc->fragCounter, keptSum);   // every fragment past the discard
+    if (lane == 0u && keptSum > 0u) atomicAdd(&dc->fragCounter, keptSum);
     if (stats) {
         if (lane == 0u && tests) atomicAdd(&dc->prims, tests);
         if (lane == 0u && hits) atomicAdd(&dc->hits, hits);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Atomic Loop 64 (rendering mode 10, AtomicLoop64Renderer): the K nearest fragments of every pixel exactly, the rest as a weighted
+// average behind them (lv_al64.h).  (K + 5) x 8 B per padded pixel (addressed like ppllCount), no fragment pool, no regrowth, no
+// read-back; ppllCount is the 32-bit count of the fragments past the discard.
+//   k_stream_pass<10>    (above) with lv_al64_insert as the fragment's store
+//   k_al64_resolve       the cells and groups of k_mboit_stream_blend over the frame's tile list: lv_al64_resolve_pixel, the maximum
+//                        count and the overflow flag (a count above LV_AL64_MAX_COUNT)
+// The buffer is cleared per frame and not by the resolve (as the reference does): a tile list may repeat or overlap pixels.
+__global__ __launch_bounds__(LV_BLOCK) void k_al64_clear(unsigned long long* __restrict__ buf, size_t numWords, uint32_t K) {
+    const uint32_t stride = K + LV_AL64_TAIL;
+    for (size_t i = size_t(blockIdx.x) * LV_BLOCK + threadIdx.x; i < numWords; i += size_t(gridDim.x) * LV_BLOCK)
+        buf[i] = uint32_t(i % stride) < K ? LV_AL64_EMPTY : 0ull;
 }
 
 // One lane per pixel, one wave per workgroup, the cells and groups of k_mboit_stream_blend
@@ -3119,172 +3152,10 @@ __global__ __launch_bounds__(LV_BLOCK) void k_al64_read(const unsigned long long
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Weighted Blended OIT (rendering mode 8, WBOITRenderer): every per-pixel quantity is a sum (lv_wboit.h).  5 x 8 B per padded pixel
 // (addressed like ppllCount), no fragment pool, no regrowth, no read-back; ppllCount is the 32-bit count of the kept fragments.
-//   k_wboit_stream_pass  the loop of k_al64_stream_pass (stages A and B through the lv_seg_walk_* / lv_seg_pair_coverage helpers, the
-//                        second LDS queue, stage C one lane per fragment) with lv_wboit_add as the fragment's store; ONE launch per
-//                        frame.  A third copy of the loop: the other two must compile as they do, and folding the three into one
-//                        skeleton is a refactoring of its own, gated on identical device assembly
+//   k_stream_pass<8>     (above) with lv_wboit_add as the fragment's store
 //   k_wboit_resolve      the cells and groups of k_al64_resolve over the frame's tile list: lv_wboit_resolve_pixel, the maximum
 //                        count and the overflow flag (a count above LV_WBOIT_MAX_COUNT)
 // The sums are zeroed per frame (a memset) and not by the resolve: a tile list may repeat or overlap pixels.
-template <int NT, int SHADE, int FAST>
-__global__ __launch_bounds__(LV_BLOCK, LV_MBOIT_STREAM_MIN_WAVES) void k_wboit_stream_pass(const LvUniforms U, const LvSceneDev S,
-                                                                   const uint32_t* __restrict__ startOffset,
-                                                                   uint32_t* __restrict__ fragCount, unsigned long long* sums,
-                                                                   LvDevCounters* dc, uint32_t allRequested,
-                                                                   const uint32_t* __restrict__ leafList, uint32_t weightMode,
-                                                                   uint32_t collectStats) {
-    __shared__ uint32_t s_qLeaf[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE], s_qPix[LV_BLOCK / LV_WAVE][LV_PRISM_RASTER_QUEUE];
-    __shared__ uint32_t s_fFrag[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE], s_fPix[LV_BLOCK / LV_WAVE][LV_MBOIT_STREAM_QUEUE];
-    __shared__ float s_seg[LV_BLOCK / LV_WAVE][20][LV_WAVE];
-    __shared__ float s_prismRing[4 * LV_PRISM_MAX_SUBDIV];
-    // what stages A and B keep per lane, parked here while stage C runs (as k_mboit_stream_pass, for the registers of stage C)
-    __shared__ uint32_t s_park[19][LV_BLOCK];
-    if (threadIdx.x < LV_PRISM_MAX_SUBDIV) {
-        s_prismRing[threadIdx.x] = S.prism.c[threadIdx.x];
-        s_prismRing[LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.s[threadIdx.x];
-        s_prismRing[2 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.cp[threadIdx.x];
-        s_prismRing[3 * LV_PRISM_MAX_SUBDIV + threadIdx.x] = S.prism.sn[threadIdx.x];
-    }
-    __syncthreads();
-    const LvPrismDev& R = S.prism;
-    const uint32_t N = NT > 0 ? uint32_t(NT) : R.n;
-    const unsigned lane = lv_lane();
-    // (the wave's index as a scalar: the five LDS bases and the item counter below then hold no vector registers either)
-    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t* qLeaf = s_qLeaf[wave];
-    uint32_t* qPix = s_qPix[wave];
-    uint32_t* fFrag = s_fFrag[wave];
-    uint32_t* fPix = s_fPix[wave];
-    float (*segLds)[LV_WAVE] = s_seg[wave];
-    const f3 o = mk3(U.camPos[0], U.camPos[1], U.camPos[2]);
-    // the frame's set-up constants are the same in every lane: kept in scalar registers, so that the 15 of them do not hold vector
-    // registers across stage C
-    auto uniform = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
-    float mx[4], my[4], mw[4];
-    lv_clip_rows(U, mx, my, mw);
-#pragma unroll
-    for (int c = 0; c < 4; c++) { mx[c] = uniform(mx[c]); my[c] = uniform(my[c]); mw[c] = uniform(mw[c]); }
-    const float halfW = uniform(0.5f * float(U.width)), halfH = uniform(0.5f * float(U.height));
-    const float wEps = uniform(1e-3f * U.nearDist);
-    const float tLo = 0.0001f, tHi = __uint_as_float(__float_as_uint(1000.0f) + 1u);
-    const bool stats = collectStats != 0u;
-    unsigned qHead = 0u, qCount = 0u;   // (pixel, segment) pairs (wave-uniform)
-    unsigned fHead = 0u, fCount = 0u;   // covered triangles (wave-uniform)
-    // the frame's counters, per wave (ballots: wave-uniform values need no vector registers across the stages)
-    unsigned long long tests = 0, hits = 0;
-    uint32_t keptSum = 0u;
-    // stage A's walk over the lane's segment: candidate rectangle and oriented box, position in it
-    uint32_t leafA = 0u;
-    LvSegWalk w = {};
-    int px = 0, py = 0;
-    bool more = false;
-
-    // stage C on the m <= 64 oldest fragments of the queue: shaded as k_ppll_shade_prism<..., LV_ENTRY_MBOIT> shades them (only the
-    // `kept` rules discard: WBOITGather.glsl has no alpha test), the window depth of mode 3, the five terms added.
-    // (One call site, as in k_mboit_stream_pass.)
-    auto fragmentStage = [&](unsigned m) __attribute__((always_inline)) {
-        bool hit = false;
-        if (lane < m) {
-            const unsigned q = (fHead + lane) & (LV_MBOIT_STREAM_QUEUE - 1u);
-            const uint32_t w0 = fPix[q], w1 = fFrag[q];
-            const uint32_t px = w0 & 0xFFFFu, py = w0 >> 16;
-            const uint32_t leaf = w1 & 0x03FFFFFFu, tt = w1 >> 26;
-            const float aoTexel = (U.useAmbientOcclusion && !U.aoPrebaked) ? S.ao[size_t(py) * U.width + px] : 1.0f;
-            f3 oo, d;
-            lv_primary_ray(U, px, py, 0.5f, 0.5f, oo, d);
-            const LvRasterQuad rq = lv_make_raster_quad(U, px, py);
-            bool kept;
-            float depth;
-            const f4 color = lv_shade_prism<SHADE, FAST>(S, U, s_prismRing, aoTexel, o, d, tLo, tHi, leaf, tt, rq, U.ppllRasterColour != 0u, depth, kept);
-            hit = kept;
-            if (kept) {
-                const uint32_t addr = lv_ppll_addr(px, py, U.ppllPaddedW, U.ppllTileW, U.ppllTileH);
-                const float z = lv_window_depth(U, lv_prism_frag_pos(S, U, s_prismRing, d, leaf, tt));
-                lv_wboit_add(sums + size_t(addr) * LV_WBOIT_SUMS, color, z, weightMode);
-                atomicAdd(&fragCount[addr], 1u);
-            }
-        }
-        const uint32_t keptNow = uint32_t(__popcll(__ballot(hit)));
-        keptSum += keptNow;
-        if (stats) hits += (unsigned long long)keptNow;
-        fHead = (fHead + m) & (LV_MBOIT_STREAM_QUEUE - 1u);
-        fCount -= m;
-    };
-
-    // stage B on the m <= 64 oldest pairs of the queue (k_mboit_stream_pass's: the covered triangles go to the second queue);
-    // flush: the wave's last batch -- stage C also takes what is left in its queue
-    auto coverageStage = [&](unsigned m, bool flush) __attribute__((always_inline)) {
-        unsigned mask = 0u;
-        uint32_t leaf = 0u, pix = 0u;
-        if (lane < m) {
-            mask = lv_seg_pair_coverage<NT>(R, segLds, qLeaf, qPix, (qHead + lane) & (LV_PRISM_RASTER_QUEUE - 1u), o, leaf, pix);
-        }
-        if (stats) tests += m;
-        while (true) {
-            const bool hit = mask != 0u;
-            const unsigned long long hm = __ballot(hit);
-            if (hm == 0ull && !(flush && fCount > 0u)) break;
-            if (hit) {
-                const unsigned tt = unsigned(__ffs(int(mask))) - 1u;
-                mask &= mask - 1u;
-                const unsigned q = (fHead + fCount + unsigned(__popcll(hm & ((1ull << lane) - 1ull)))) & (LV_MBOIT_STREAM_QUEUE - 1u);
-                fPix[q] = pix;
-                fFrag[q] = leaf | (tt << 26);
-            }
-            fCount += unsigned(__popcll(hm));
-            if (fCount >= LV_WAVE || hm == 0ull) {
-                uint32_t* park = &s_park[0][threadIdx.x];
-                const float pf[8] = {w.ax, w.ay, w.cx0, w.cy0, w.aMid, w.aHalf, w.nMid, w.nHalf};
-                const uint32_t pu[11] = {mask, leaf, pix, leafA, uint32_t(w.x0), uint32_t(w.x1), uint32_t(w.y0), uint32_t(w.y1),
-                                         uint32_t(px), uint32_t(py), more ? 1u : 0u};
-#pragma unroll
-                for (int i = 0; i < 8; i++) park[i * LV_BLOCK] = __float_as_uint(pf[i]);
-#pragma unroll
-                for (int i = 0; i < 11; i++) park[(8 + i) * LV_BLOCK] = pu[i];
-                fragmentStage(fCount < LV_WAVE ? fCount : LV_WAVE);
-                w.ax = __uint_as_float(park[0]); w.ay = __uint_as_float(park[LV_BLOCK]); w.cx0 = __uint_as_float(park[2 * LV_BLOCK]);
-                w.cy0 = __uint_as_float(park[3 * LV_BLOCK]); w.aMid = __uint_as_float(park[4 * LV_BLOCK]); w.aHalf = __uint_as_float(park[5 * LV_BLOCK]);
-                w.nMid = __uint_as_float(park[6 * LV_BLOCK]); w.nHalf = __uint_as_float(park[7 * LV_BLOCK]);
-                mask = park[8 * LV_BLOCK]; leaf = park[9 * LV_BLOCK]; pix = park[10 * LV_BLOCK]; leafA = park[11 * LV_BLOCK];
-                w.x0 = int(park[12 * LV_BLOCK]); w.x1 = int(park[13 * LV_BLOCK]); w.y0 = int(park[14 * LV_BLOCK]); w.y1 = int(park[15 * LV_BLOCK]);
-                px = int(park[16 * LV_BLOCK]); py = int(park[17 * LV_BLOCK]); more = park[18 * LV_BLOCK] != 0u;
-            }
-        }
-        qHead = (qHead + m) & (LV_PRISM_RASTER_QUEUE - 1u);
-        qCount -= m;
-    };
-
-    const uint32_t waveId = blockIdx.x * (LV_BLOCK / LV_WAVE) + wave, numWaves = gridDim.x * (LV_BLOCK / LV_WAVE);
-    const uint32_t numItems = leafList ? dc->prismListCount : S.numSegs;
-    for (uint32_t itemBase = waveId * LV_WAVE; itemBase < numItems; itemBase += numWaves * LV_WAVE) {
-        const bool valid = itemBase + lane < numItems;
-        const uint32_t leaf = !valid ? 0u : (leafList ? leafList[itemBase + lane] : itemBase + lane);
-        leafA = leaf;
-        w = lv_seg_walk_setup(U, S, segLds, mx, my, mw, halfW, halfH, wEps, N, valid, leaf, lane);
-        px = w.x0; py = w.y0;
-        more = valid && w.x1 >= w.x0 && w.y1 >= w.y0;
-        const bool lastItem = itemBase + numWaves * LV_WAVE >= numItems;   // (overflow: numItems < 2^26)
-        while (true) {
-            const bool drain = !__any(more);   // every rectangle walked: the rest of the pairs, 64 at a time
-            const bool cand = more && lv_seg_walk_candidate(U, w, px, py, allRequested, startOffset);
-            const unsigned long long cm = __ballot(cand);
-            if (cand) {
-                const unsigned q = (qHead + qCount + unsigned(__popcll(cm & ((1ull << lane) - 1ull)))) & (LV_PRISM_RASTER_QUEUE - 1u);
-                qLeaf[q] = leafA | (lane << 26);
-                qPix[q] = uint32_t(px) | (uint32_t(py) << 16);
-            }
-            qCount += unsigned(__popcll(cm));
-            if (qCount >= LV_WAVE || drain) coverageStage(qCount < LV_WAVE ? qCount : LV_WAVE, lastItem && drain && qCount <= LV_WAVE);
-            if (drain && qCount == 0u) break;   // (the next 64 segments replace the frames in LDS)
-            if (more) more = lv_seg_walk_advance(w, px, py);
-        }
-    }
-    if (lane == 0u && keptSum > 0u) atomicAdd(&dc->fragCounter, keptSum);   // every kept fragment
-    if (stats) {
-        if (lane == 0u && tests) atomicAdd(&dc->prims, tests);
-        if (lane == 0u && hits) atomicAdd(&dc->hits, hits);
-    }
-}
 
 // One lane per pixel, one wave per workgroup, the cells and groups of k_al64_resolve
 __global__ __launch_bounds__(LV_WAVE) void k_wboit_resolve(const LvUniforms U, const LvTiles T, const unsigned long long* __restrict__ sums,
@@ -3364,7 +3235,7 @@ __global__ __launch_bounds__(LV_BLOCK) void k_wboit_read(const unsigned long lon
 //   k_dc_resolve      mode 5's frame (the cells and groups of k_wboit_resolve); reads the maximum from device memory
 //   k_peel_pass       one launch per layer: 64-bit atomicMin of (z bits << 32 | primitive key) into the pixel's slot
 //   k_peel_layer      (lv_peel.hip) one lane per VIEWPORT pixel (a tile list may repeat or overlap pixels; a pixel must be accumulated
-//                     once): shades the slot's winner as stage C of k_wboit_stream_pass shades, accumulates, resets the slot.  In a file
+//                     once): shades the slot's winner as stage C of k_stream_pass<8> shades, accumulates, resets the slot.  In a file
 //                     of its own: as a kernel of this one it changed the code of every kernel here that calls lv_shade_prism and
 //                     lv_prism_frag_pos (38 instances), which must compile as they do
 //   k_peel_blit       the accumulator over the clear colour, over the tile list's cells (a pure read)
@@ -4533,6 +4404,73 @@ static int lv_segment_raster_front(lv_ctx* ctx, const LvUniforms& U, const LvSce
     return LV_OK;
 }
 
+// ---- The host side that the frames without a fragment pool share: streamed mode 6, modes 8 and 10, modes 5 and 9 ----
+struct LvStreamedOpen {
+    size_t pixels;       // padded pixels (whole uint4s, k_ppll_clear): what ppllStart, ppllCount and the mode's buffer hold
+    bool allRequested;   // the tile list covers the viewport: every pixel is requested
+};
+// The opening: the restrictions of these modes (`name` in the messages), the prism's constants, ppllStart, ppllCount and the mode's
+// own buffer (modeBytes per padded pixel; nullptr: none) reserved, clear().
+// (use_ribbons with rotating_helicity_bands never gets here: lv_frame_render refuses that pair for every mode)
+static int lv_streamed_open(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, bool stats, LvDevCounters* dc, const char* name,
+                            LvDeviceBuffer* modeBuf, size_t modeBytes, LvStreamedOpen& F) {
+    int rc;
+    if (!lv_ppll_prism_source(ctx))
+        return lv_fail(ctx, LV_E_INVALID, "%s works on the fragments of the rasterised prism, which this line data does not have", name);
+    if (ctx->opt.ppllPrismLbvhWalk)
+        return lv_fail(ctx, LV_E_INVALID, "%s runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported", name);
+    lv_fill_prism(ctx, U, S.prism);
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
+    F.pixels = padded4 * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    if (modeBuf && (rc = lv_buf_reserve(ctx, *modeBuf, F.pixels * modeBytes))) return rc;
+    ctx->ppllPoolNodes = 0;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    F.allRequested = ctx->tilesCoverViewport;
+    lv_ppll_clear(ctx, U, padded4, F.allRequested, stats, dc);
+    return LV_OK;
+}
+// The closing event of LV_KERNEL_PPLL_RASTER (lv_segment_raster_front recorded the opening one) and its launch count
+static int lv_segment_raster_end(lv_ctx* ctx) {
+    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
+        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), ctx->stream));
+        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
+    }
+    return LV_OK;
+}
+// The close in front of the frame's resolve: the phase mark and the resolve's grid, one wave per 8 x 8-pixel cell
+static int lv_streamed_close(lv_ctx* ctx, const LvTiles& T, uint32_t& numGroups) {
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], ctx->stream));
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    numGroups = uint32_t(lv_tiles_cells(T));
+    return LV_OK;
+}
+// ctx->streamed: set at the end of the frame function of `mode` (param: N of mode 6, K of mode 10); what every *_get_* call asks of
+// it -- the last frame was a `mode` frame over the whole viewport, and the viewport is still that one
+static void lv_streamed_done(lv_ctx* ctx, const LvUniforms& U, int mode, uint32_t param = 0u) {
+    ctx->streamed = {mode, ctx->tilesCoverViewport, U.width, U.height, {U.ppllTileW, U.ppllTileH}, param};
+}
+static bool lv_streamed_is(const lv_ctx* ctx, int mode) {
+    const lv_ctx::StreamedFrame& r = ctx->streamed;
+    return r.mode == mode && r.full && r.w == ctx->width && r.h == ctx->height;
+}
+// The instance of a streamed pass for the frame: LAUNCH(NT, SHADE, FAST) with NT = 6 for the six-sided prism (0: any n), then the
+// variants lv_frame_render selects for the pooled fragment stage -- fast (lv_prism_fast_shade), bands, helicity bands, plain
+#define LV_SELECT_STREAM_PASS_NT(LAUNCH, NT)                                         \
+    do {                                                                             \
+        if (fastShade) LAUNCH(NT, LV_SHADE_PLAIN, 2);                                \
+        else if (S.prism.bands) LAUNCH(NT, LV_SHADE_BANDS, 0);                       \
+        else if (U.useHelicityBands) LAUNCH(NT, LV_SHADE_HELICITY, 0);               \
+        else LAUNCH(NT, LV_SHADE_PLAIN, 0);                                          \
+    } while (0)
+#define LV_SELECT_STREAM_PASS(LAUNCH)                                                \
+    do {                                                                             \
+        const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);                \
+        if (S.prism.n == 6u) LV_SELECT_STREAM_PASS_NT(LAUNCH, 6); else LV_SELECT_STREAM_PASS_NT(LAUNCH, 0); \
+    } while (0)
+
 // A mode-6 frame with mboit_fragment_storage = streamed: clear, the two launches of k_mboit_stream_pass, the blend.  No record pool,
 // no fragment pool, no scan, no regrowth; the only host synchronisation is the read-back of the line points' box, once per
 // acceleration-structure build.  The blend's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
@@ -4545,91 +4483,59 @@ static int lv_mboit_stream_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, cons
     int rc;
     if (!lv_ppll_prism_source(ctx) || (ctx->opt.useRibbons && ctx->opt.helicityBands))
         return lv_fail(ctx, LV_E_INVALID, "mboit_fragment_storage = streamed: band data with rotating helicity bands has no prism fragment stage");
-    if (ctx->opt.ppllPrismLbvhWalk)
-        return lv_fail(ctx, LV_E_INVALID, "mboit_fragment_storage = streamed runs the segment rasteriser: ppll_prism_rasteriser = lbvh "
-                                          "is not supported");
-    lv_fill_prism(ctx, U, S.prism);
-    const uint32_t N = ctx->opt.mboitNumMoments;
-    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
-    const size_t accBytes = padded4 * 4 * size_t(1u + N + 4u) * 8;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->mboitAccum, accBytes))) return rc;
-    ctx->ppllPoolNodes = 0;
-    ctx->ppllPaddedW = U.ppllPaddedW;
-    ctx->ppllPaddedH = U.ppllPaddedH;
-    if (!ctx->mboitBoxValid) {
+    if (!ctx->mboitBoxValid) {   // (in front of the opening: the box kernel runs before clear())
         if ((rc = lv_mboit_box_queue(ctx, S, dc))) return rc;
         LV_HIP(ctx, hipStreamSynchronize(st));
         lv_mboit_box_adopt(ctx);
     }
+    const uint32_t N = ctx->opt.mboitNumMoments;
+    LvStreamedOpen F;
+    if ((rc = lv_streamed_open(ctx, U, S, stats, dc, "mboit_fragment_storage = streamed", &ctx->mboitAccum, size_t(1u + N + 4u) * 8, F))) return rc;
     const LvMboitParams M = lv_mboit_params(ctx, U, ctx->mboitBoxOrd, stats);
-    const bool allRequested = ctx->tilesCoverViewport;
-    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
-    LV_HIP(ctx, hipMemsetAsync(ctx->mboitAccum.ptr, 0, accBytes, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->mboitAccum.ptr, 0, F.pixels * size_t(1u + N + 4u) * 8, st));
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
     // LV_KERNEL_PPLL_RASTER: one launch per pass, the first with what a sharded frame runs in front of it (as in pooled storage)
     const bool rasterTimed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) != 0u;
     uint32_t* leafList;
-    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
+    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, F.allRequested, dc, leafList))) return rc;
     const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
-    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);   // the variants lv_frame_render selects for the pooled fragment stage
 #define LV_LAUNCH_STREAM(NT, SH, FA)                                                                                            \
     k_mboit_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, M, (const uint32_t*)ctx->ppllStart.ptr,               \
-            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->mboitAccum.ptr, dc, allRequested ? 1u : 0u, leafList, N, pass)
-#define LV_LAUNCH_STREAM2(NT)                                                        \
-    do {                                                                             \
-        if (fastShade) LV_LAUNCH_STREAM(NT, LV_SHADE_PLAIN, 2);                      \
-        else if (S.prism.bands) LV_LAUNCH_STREAM(NT, LV_SHADE_BANDS, 0);             \
-        else if (U.useHelicityBands) LV_LAUNCH_STREAM(NT, LV_SHADE_HELICITY, 0);     \
-        else LV_LAUNCH_STREAM(NT, LV_SHADE_PLAIN, 0);                                \
-    } while (0)
+            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->mboitAccum.ptr, dc, F.allRequested ? 1u : 0u, leafList, N, pass)
     for (uint32_t pass = 0u; pass < 2u; pass++) {
         if (rasterTimed && pass) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
-        if (S.numSegs != 0) {
-            if (S.prism.n == 6u) LV_LAUNCH_STREAM2(6); else LV_LAUNCH_STREAM2(0);
-        }
-        if (rasterTimed) {
-            LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
-            ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
-        }
+        if (S.numSegs != 0) LV_SELECT_STREAM_PASS(LV_LAUNCH_STREAM);
+        if ((rc = lv_segment_raster_end(ctx))) return rc;
     }
-#undef LV_LAUNCH_STREAM2
 #undef LV_LAUNCH_STREAM
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    uint32_t numGroups;
+    if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_mboit_stream_blend<<<numGroups, LV_WAVE, 0, st>>>(
             U, T, M, (const unsigned long long*)ctx->mboitAccum.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, N, dc)));
-    ctx->mboitStreamLast = true;
-    ctx->mboitStreamFull = allRequested;
-    ctx->mboitStreamW = U.width;
-    ctx->mboitStreamH = U.height;
-    ctx->mboitStreamN = N;
-    ctx->mboitStreamTile[0] = U.ppllTileW;
-    ctx->mboitStreamTile[1] = U.ppllTileH;
+    lv_streamed_done(ctx, U, LV_RENDERING_MODE_MBOIT, N);
     return LV_OK;
 }
 
 // the overflow flag of the last frame when that was a streamed mode-6 frame, a mode-8 or a mode-10 frame (host-synchronous)
 int lv_mboit_stream_overflow(lv_ctx* ctx) {
-    if ((!ctx->mboitStreamLast && !ctx->al64Last && !ctx->wboitLast) || !ctx->counters.ptr) return LV_OK;
+    const int mode = ctx->streamed.mode;
+    if ((mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64) || !ctx->counters.ptr)
+        return LV_OK;
     uint32_t flag = 0u;
     LV_HIP(ctx, hipMemcpy(&flag, &((const LvDevCounters*)ctx->counters.ptr)->mboitOverflow, 4, hipMemcpyDeviceToHost));
     if (flag)
         return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than %u kept fragments (the 64-bit sums are "
-                                           "exact up to that count)", ctx->wboitLast ? "WBOIT" : ctx->al64Last ? "Atomic Loop 64" : "MBOIT (streamed)",
+                                           "exact up to that count)", mode == LV_RENDERING_MODE_WBOIT ? "WBOIT" : mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 ? "Atomic Loop 64" : "MBOIT (streamed)",
                        LV_MBOIT_STREAM_MAX_COUNT);
     return LV_OK;
 }
 
 // lv_mboit_get_moments
 int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloats) {
-    if (!ctx->mboitStreamLast || !ctx->mboitStreamFull || !ctx->mboitAccum.ptr || ctx->mboitStreamW != ctx->width ||
-        ctx->mboitStreamH != ctx->height)
+    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_MBOIT) || !ctx->mboitAccum.ptr)
         return lv_fail(ctx, LV_E_STATE, "lv_mboit_get_moments: the last frame was not a mode-6 frame with mboit_fragment_storage = "
                                         "streamed over the whole viewport");
-    const uint64_t need = uint64_t(ctx->mboitStreamW) * ctx->mboitStreamH * (1u + ctx->mboitStreamN);
+    const uint64_t need = uint64_t(ctx->streamed.w) * ctx->streamed.h * (1u + ctx->streamed.param);
     if (capacityFloats < need)
         return lv_fail(ctx, LV_E_INVALID, "lv_mboit_get_moments: out holds %llu floats, need %llu", (unsigned long long)capacityFloats,
                        (unsigned long long)need);
@@ -4637,17 +4543,37 @@ int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloa
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, size_t(need) * 4))) return rc;
-    const uint64_t pixels = uint64_t(ctx->mboitStreamW) * ctx->mboitStreamH;
+    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
     k_mboit_stream_moments<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
-            (const unsigned long long*)ctx->mboitAccum.ptr, ctx->mboitStreamW, ctx->mboitStreamH, ctx->ppllPaddedW, ctx->mboitStreamTile[0],
-            ctx->mboitStreamTile[1], ctx->mboitStreamN, (float*)ctx->scratchRays.ptr);
+            (const unsigned long long*)ctx->mboitAccum.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW, ctx->streamed.tile[0],
+            ctx->streamed.tile[1], ctx->streamed.param, (float*)ctx->scratchRays.ptr);
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(out, ctx->scratchRays.ptr, size_t(need) * 4, hipMemcpyDeviceToHost, ctx->stream));
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LV_OK;
 }
 
-// A mode-10 frame (Atomic Loop 64): clear, ONE launch of k_al64_stream_pass, the resolve.  No pool, no scan, no regrowth and no host
+// The middle of a mode-8 or mode-10 frame, between the clear of the mode's buffer and the close: the phase mark and ONE launch of
+// k_stream_pass<MODE> on `buf` and `arg`.  LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in
+// modes 2, 3 and 6)
+template <int MODE>
+static int lv_stream_pass(lv_ctx* ctx, const LvUniforms& U, const LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats,
+                          const LvStreamedOpen& F, LvDevCounters* dc, unsigned long long* buf, uint32_t arg) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    uint32_t* leafList;
+    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, F.allRequested, dc, leafList))) return rc;
+    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
+#define LV_LAUNCH_STREAM(NT, SH, FA)                                                                                            \
+    k_stream_pass<MODE, NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr,                   \
+            (uint32_t*)ctx->ppllCount.ptr, buf, dc, F.allRequested ? 1u : 0u, leafList, arg, stats ? 1u : 0u)
+    if (S.numSegs != 0) LV_SELECT_STREAM_PASS(LV_LAUNCH_STREAM);
+#undef LV_LAUNCH_STREAM
+    return lv_segment_raster_end(ctx);
+}
+
+// A mode-10 frame (Atomic Loop 64): clear, ONE launch of k_stream_pass, the resolve.  No pool, no scan, no regrowth and no host
 // synchronisation; the resolve's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
 static void lv_al64_clear(lv_ctx* ctx, size_t numWords, uint32_t K) {
     const size_t blocks = (numWords + LV_BLOCK - 1) / LV_BLOCK, maxBlocks = size_t(ctx->numCUs) * 32u;
@@ -4656,92 +4582,46 @@ static void lv_al64_clear(lv_ctx* ctx, size_t numWords, uint32_t K) {
 }
 static int lv_al64_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
                          LvDevCounters* dc) {
-    hipStream_t st = ctx->stream;
     int rc;
-    // (use_ribbons with rotating_helicity_bands never gets here: lv_frame_render refuses that pair for every mode)
-    if (!lv_ppll_prism_source(ctx))
-        return lv_fail(ctx, LV_E_INVALID, "mode 10 (Atomic Loop 64) works on the fragments of the rasterised prism, which this line data does not have");
-    if (ctx->opt.ppllPrismLbvhWalk)
-        return lv_fail(ctx, LV_E_INVALID, "mode 10 (Atomic Loop 64) runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported");
-    lv_fill_prism(ctx, U, S.prism);
     const uint32_t K = ctx->opt.al64NumLayers;
-    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
-    const size_t numWords = padded4 * 4 * size_t(K + LV_AL64_TAIL);
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->al64Buf, numWords * 8))) return rc;
-    ctx->ppllPoolNodes = 0;
-    ctx->ppllPaddedW = U.ppllPaddedW;
-    ctx->ppllPaddedH = U.ppllPaddedH;
-    const bool allRequested = ctx->tilesCoverViewport;
-    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
-    lv_al64_clear(ctx, numWords, K);
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
-    // LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in modes 2, 3 and 6)
-    uint32_t* leafList;
-    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
-    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
-    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);   // the instances and the selection of the streamed MBOIT pass
-#define LV_LAUNCH_AL64(NT, SH, FA)                                                                                              \
-    k_al64_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr,                    \
-            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->al64Buf.ptr, dc, allRequested ? 1u : 0u, leafList, K,      \
-            stats ? 1u : 0u)
-#define LV_LAUNCH_AL64_2(NT)                                                         \
-    do {                                                                             \
-        if (fastShade) LV_LAUNCH_AL64(NT, LV_SHADE_PLAIN, 2);                        \
-        else if (S.prism.bands) LV_LAUNCH_AL64(NT, LV_SHADE_BANDS, 0);               \
-        else if (U.useHelicityBands) LV_LAUNCH_AL64(NT, LV_SHADE_HELICITY, 0);       \
-        else LV_LAUNCH_AL64(NT, LV_SHADE_PLAIN, 0);                                  \
-    } while (0)
-    if (S.numSegs != 0) {
-        if (S.prism.n == 6u) LV_LAUNCH_AL64_2(6); else LV_LAUNCH_AL64_2(0);
-    }
-    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
-        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
-        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
-    }
-#undef LV_LAUNCH_AL64_2
-#undef LV_LAUNCH_AL64
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_al64_resolve<<<numGroups, LV_WAVE, 0, st>>>(
+    LvStreamedOpen F;
+    if ((rc = lv_streamed_open(ctx, U, S, stats, dc, "mode 10 (Atomic Loop 64)", &ctx->al64Buf, size_t(K + LV_AL64_TAIL) * 8, F))) return rc;
+    lv_al64_clear(ctx, F.pixels * size_t(K + LV_AL64_TAIL), K);
+    if ((rc = lv_stream_pass<LV_RENDERING_MODE_ATOMIC_LOOP_64>(ctx, U, S, T, gridTiles, stats, F, dc, (unsigned long long*)ctx->al64Buf.ptr, K)))
+        return rc;
+    uint32_t numGroups;
+    if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_al64_resolve<<<numGroups, LV_WAVE, 0, ctx->stream>>>(
             U, T, (const unsigned long long*)ctx->al64Buf.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, K, dc)));
-    ctx->al64Last = true;
-    ctx->al64Full = allRequested;
-    ctx->al64W = U.width;
-    ctx->al64H = U.height;
-    ctx->al64K = K;
-    ctx->al64Tile[0] = U.ppllTileW;
-    ctx->al64Tile[1] = U.ppllTileH;
+    lv_streamed_done(ctx, U, LV_RENDERING_MODE_ATOMIC_LOOP_64, K);
     return LV_OK;
 }
 
 // lv_atomic_loop_get_num_layers: K of the last frame when that was a mode-10 frame (what lv_atomic_loop_get_buffers returns per pixel)
 int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out) {
-    if (!ctx->al64Last) return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_num_layers: the last frame was not a mode-10 frame");
-    *out = ctx->al64K;
+    if (ctx->streamed.mode != LV_RENDERING_MODE_ATOMIC_LOOP_64) return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_num_layers: the last frame was not a mode-10 frame");
+    *out = ctx->streamed.param;
     return LV_OK;
 }
 
 // lv_atomic_loop_get_buffers
 int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, uint64_t capacityPixels) {
-    if (!ctx->al64Last || !ctx->al64Full || !ctx->al64Buf.ptr || ctx->al64W != ctx->width || ctx->al64H != ctx->height)
+    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_ATOMIC_LOOP_64) || !ctx->al64Buf.ptr)
         return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_buffers: the last frame was not a mode-10 frame over the whole viewport");
-    const uint64_t pixels = uint64_t(ctx->al64W) * ctx->al64H;
+    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
     if (capacityPixels < pixels)
         return lv_fail(ctx, LV_E_INVALID, "lv_atomic_loop_get_buffers: the arrays hold %llu pixels, need %llu",
                        (unsigned long long)capacityPixels, (unsigned long long)pixels);
     int rc;
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
-    const uint32_t K = ctx->al64K;
+    const uint32_t K = ctx->streamed.param;
     const size_t slotBytes = size_t(pixels) * K * 8, tailBytes = size_t(pixels) * LV_AL64_TAIL * 8;
     if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, slotBytes + tailBytes))) return rc;
     unsigned long long* dSlots = (unsigned long long*)ctx->scratchRays.ptr;
     unsigned long long* dTail = dSlots + size_t(pixels) * K;
     k_al64_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
-            (const unsigned long long*)ctx->al64Buf.ptr, ctx->al64W, ctx->al64H, ctx->ppllPaddedW, ctx->al64Tile[0], ctx->al64Tile[1], K,
+            (const unsigned long long*)ctx->al64Buf.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW, ctx->streamed.tile[0], ctx->streamed.tile[1], K,
             dSlots, dTail);
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(outSlots, dSlots, slotBytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -4750,75 +4630,30 @@ int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, ui
     return LV_OK;
 }
 
-// A mode-8 frame (Weighted Blended OIT): the sums zeroed, ONE launch of k_wboit_stream_pass, the resolve.  No pool, no scan, no
+// A mode-8 frame (Weighted Blended OIT): the sums zeroed, ONE launch of k_stream_pass, the resolve.  No pool, no scan, no
 // regrowth and no host synchronisation; the resolve's overflow flag stays in the frame's counters (lv_mboit_stream_overflow reads it).
 static int lv_wboit_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
                           LvDevCounters* dc) {
-    hipStream_t st = ctx->stream;
     int rc;
-    // (use_ribbons with rotating_helicity_bands never gets here: lv_frame_render refuses that pair for every mode)
-    if (!lv_ppll_prism_source(ctx))
-        return lv_fail(ctx, LV_E_INVALID, "mode 8 (WBOIT) works on the fragments of the rasterised prism, which this line data does not have");
-    if (ctx->opt.ppllPrismLbvhWalk)
-        return lv_fail(ctx, LV_E_INVALID, "mode 8 (WBOIT) runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported");
-    lv_fill_prism(ctx, U, S.prism);
-    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
-    const size_t sumBytes = padded4 * 4 * size_t(LV_WBOIT_SUMS) * 8;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->wboitBuf, sumBytes))) return rc;
-    ctx->ppllPoolNodes = 0;
-    ctx->ppllPaddedW = U.ppllPaddedW;
-    ctx->ppllPaddedH = U.ppllPaddedH;
-    const bool allRequested = ctx->tilesCoverViewport;
-    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
-    LV_HIP(ctx, hipMemsetAsync(ctx->wboitBuf.ptr, 0, sumBytes, st));
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
-    // LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in modes 2, 3, 6 and 10)
-    uint32_t* leafList;
-    if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
-    const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_MBOIT_STREAM_BLOCKS_PER_CU;
-    const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);   // the instances and the selection of the streamed MBOIT pass
+    LvStreamedOpen F;
+    if ((rc = lv_streamed_open(ctx, U, S, stats, dc, "mode 8 (WBOIT)", &ctx->wboitBuf, size_t(LV_WBOIT_SUMS) * 8, F))) return rc;
+    LV_HIP(ctx, hipMemsetAsync(ctx->wboitBuf.ptr, 0, F.pixels * size_t(LV_WBOIT_SUMS) * 8, ctx->stream));
     const uint32_t weightMode = ctx->opt.wboitOpenglWeight ? LV_WBOIT_WEIGHT_OPENGL : LV_WBOIT_WEIGHT_REFERENCE;
-#define LV_LAUNCH_WBOIT(NT, SH, FA)                                                                                             \
-    k_wboit_stream_pass<NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr,                   \
-            (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)ctx->wboitBuf.ptr, dc, allRequested ? 1u : 0u, leafList,        \
-            weightMode, stats ? 1u : 0u)
-#define LV_LAUNCH_WBOIT_2(NT)                                                        \
-    do {                                                                             \
-        if (fastShade) LV_LAUNCH_WBOIT(NT, LV_SHADE_PLAIN, 2);                       \
-        else if (S.prism.bands) LV_LAUNCH_WBOIT(NT, LV_SHADE_BANDS, 0);              \
-        else if (U.useHelicityBands) LV_LAUNCH_WBOIT(NT, LV_SHADE_HELICITY, 0);      \
-        else LV_LAUNCH_WBOIT(NT, LV_SHADE_PLAIN, 0);                                 \
-    } while (0)
-    if (S.numSegs != 0) {
-        if (S.prism.n == 6u) LV_LAUNCH_WBOIT_2(6); else LV_LAUNCH_WBOIT_2(0);
-    }
-    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
-        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
-        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
-    }
-#undef LV_LAUNCH_WBOIT_2
-#undef LV_LAUNCH_WBOIT
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
-    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_wboit_resolve<<<numGroups, LV_WAVE, 0, st>>>(
+    if ((rc = lv_stream_pass<LV_RENDERING_MODE_WBOIT>(ctx, U, S, T, gridTiles, stats, F, dc, (unsigned long long*)ctx->wboitBuf.ptr, weightMode)))
+        return rc;
+    uint32_t numGroups;
+    if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_wboit_resolve<<<numGroups, LV_WAVE, 0, ctx->stream>>>(
             U, T, (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr, out, numGroups, dc)));
-    ctx->wboitLast = true;
-    ctx->wboitFull = allRequested;
-    ctx->wboitW = U.width;
-    ctx->wboitH = U.height;
-    ctx->wboitTile[0] = U.ppllTileW;
-    ctx->wboitTile[1] = U.ppllTileH;
+    lv_streamed_done(ctx, U, LV_RENDERING_MODE_WBOIT);
     return LV_OK;
 }
 
 // lv_wboit_get_buffers
 int lv_frame_wboit_buffers(lv_ctx* ctx, int64_t* outSums, uint32_t* outCounts, uint64_t capacityPixels) {
-    if (!ctx->wboitLast || !ctx->wboitFull || !ctx->wboitBuf.ptr || ctx->wboitW != ctx->width || ctx->wboitH != ctx->height)
+    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_WBOIT) || !ctx->wboitBuf.ptr)
         return lv_fail(ctx, LV_E_STATE, "lv_wboit_get_buffers: the last frame was not a mode-8 frame over the whole viewport");
-    const uint64_t pixels = uint64_t(ctx->wboitW) * ctx->wboitH;
+    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
     if (capacityPixels < pixels)
         return lv_fail(ctx, LV_E_INVALID, "lv_wboit_get_buffers: the arrays hold %llu pixels, need %llu",
                        (unsigned long long)capacityPixels, (unsigned long long)pixels);
@@ -4830,8 +4665,8 @@ int lv_frame_wboit_buffers(lv_ctx* ctx, int64_t* outSums, uint32_t* outCounts, u
     unsigned long long* dSums = (unsigned long long*)ctx->scratchRays.ptr;
     uint32_t* dCounts = (uint32_t*)(dSums + size_t(pixels) * LV_WBOIT_SUMS);
     k_wboit_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
-            (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr, ctx->wboitW, ctx->wboitH, ctx->ppllPaddedW,
-            ctx->wboitTile[0], ctx->wboitTile[1], dSums, dCounts);
+            (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW,
+            ctx->streamed.tile[0], ctx->streamed.tile[1], dSums, dCounts);
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(outSums, dSums, sumBytes, hipMemcpyDeviceToHost, ctx->stream));
     LV_HIP(ctx, hipMemcpyAsync(outCounts, dCounts, countBytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -4858,22 +4693,11 @@ static int lv_dc_count(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles&
                        bool peel, const char* name, uint32_t*& leafList) {
     hipStream_t st = ctx->stream;
     int rc;
-    if (!lv_ppll_prism_source(ctx))
-        return lv_fail(ctx, LV_E_INVALID, "%s works on the fragments of the rasterised prism, which this line data does not have", name);
-    if (ctx->opt.ppllPrismLbvhWalk)
-        return lv_fail(ctx, LV_E_INVALID, "%s runs the segment rasteriser: ppll_prism_rasteriser = lbvh is not supported", name);
-    lv_fill_prism(ctx, U, S.prism);
-    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
-    const size_t n = padded4 * 4;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    LvStreamedOpen F;
+    if ((rc = lv_streamed_open(ctx, U, S, stats, dc, name, peel ? &ctx->peelBuf : nullptr, LV_PEEL_BYTES_PER_PIXEL, F))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->dcStatsDev, sizeof(LvDcStats)))) return rc;
-    if (peel && (rc = lv_buf_reserve(ctx, ctx->peelBuf, n * LV_PEEL_BYTES_PER_PIXEL))) return rc;
-    ctx->ppllPoolNodes = 0;
-    ctx->ppllPaddedW = U.ppllPaddedW;
-    ctx->ppllPaddedH = U.ppllPaddedH;
-    const bool allRequested = ctx->tilesCoverViewport;
-    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
+    const size_t n = F.pixels;
+    const bool allRequested = F.allRequested;
     LvPeelBuffers B = {nullptr, nullptr, nullptr, nullptr};
     if (peel) B = lv_peel_buffers(ctx, n);
     k_peel_clear<<<uint32_t(peel ? (n + LV_BLOCK - 1) / LV_BLOCK : 1), LV_BLOCK, 0, st>>>(B, n, (LvDcStats*)ctx->dcStatsDev.ptr);
@@ -4888,19 +4712,12 @@ static int lv_dc_count(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles&
             k_dc_count_pass<0><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc,
                                                              allRequested ? 1u : 0u, leafList, stats ? 1u : 0u);
     }
-    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
-        LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
-        ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
-    }
+    if ((rc = lv_segment_raster_end(ctx))) return rc;
     const uint32_t pixels = U.width * U.height;
     const uint32_t reduceGrid = std::min<uint32_t>((pixels + LV_BLOCK - 1) / LV_BLOCK, uint32_t(ctx->numCUs) * 4u);
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_GATHER, (k_dc_reduce<<<reduceGrid, LV_BLOCK, 0, st>>>(
             U, (const uint32_t*)ctx->ppllStart.ptr, (const uint32_t*)ctx->ppllCount.ptr, allRequested ? 1u : 0u,
             (LvDcStats*)ctx->dcStatsDev.ptr, dc)));
-    ctx->peelW = U.width;
-    ctx->peelH = U.height;
-    ctx->peelTile[0] = U.ppllTileW;
-    ctx->peelTile[1] = U.ppllTileH;
     return LV_OK;
 }
 
@@ -4911,13 +4728,11 @@ static int lv_dc_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles&
     int rc;
     uint32_t* leafList;
     if ((rc = lv_dc_count(ctx, U, S, T, gridTiles, stats, dc, false, "mode 5 (depth complexity)", leafList))) return rc;
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    uint32_t numGroups;
+    if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_dc_resolve<<<numGroups, LV_WAVE, 0, st>>>(
             U, T, (const uint32_t*)ctx->ppllCount.ptr, (const LvDcStats*)ctx->dcStatsDev.ptr, ctx->opt.dcMaxColour, out, numGroups)));
-    ctx->peelLast = LV_RENDERING_MODE_DEPTH_COMPLEXITY;
-    ctx->peelFull = ctx->tilesCoverViewport;
+    lv_streamed_done(ctx, U, LV_RENDERING_MODE_DEPTH_COMPLEXITY);
     return LV_OK;
 }
 
@@ -4955,21 +4770,19 @@ static int lv_peel_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTile
                                                                                                     allReq, leafList, i == 0u ? 1u : 0u)));
         LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, lv_peel_launch_layer(st, layerGrid, layerShade, layerFast, U, S, startOffset, B));
     }
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    uint32_t numGroups;
+    if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_peel_blit<<<numGroups, LV_WAVE, 0, st>>>(U, T, B.accum, out, numGroups)));
-    ctx->peelLast = LV_RENDERING_MODE_DEPTH_PEELING;
-    ctx->peelFull = allRequested;
+    lv_streamed_done(ctx, U, LV_RENDERING_MODE_DEPTH_PEELING);
     return LV_OK;
 }
 
 // lv_depth_complexity_get_buffers (accum = layers = null) and lv_depth_peeling_get_buffers
 int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outLayers, uint32_t* outCounts, uint64_t capacityPixels) {
     const char* fn = mode == LV_RENDERING_MODE_DEPTH_PEELING ? "lv_depth_peeling_get_buffers" : "lv_depth_complexity_get_buffers";
-    if (ctx->peelLast != mode || !ctx->peelFull || !ctx->ppllCount.ptr || ctx->peelW != ctx->width || ctx->peelH != ctx->height)
+    if (!lv_streamed_is(ctx, mode) || !ctx->ppllCount.ptr)
         return lv_fail(ctx, LV_E_STATE, "%s: the last frame was not a mode-%d frame over the whole viewport", fn, mode);
-    const uint64_t pixels = uint64_t(ctx->peelW) * ctx->peelH;
+    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
     if (capacityPixels < pixels)
         return lv_fail(ctx, LV_E_INVALID, "%s: the arrays hold %llu pixels, need %llu", fn, (unsigned long long)capacityPixels,
                        (unsigned long long)pixels);
@@ -4983,7 +4796,7 @@ int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outL
     LvPeelBuffers B = {nullptr, nullptr, nullptr, nullptr};
     if (peel) B = lv_peel_buffers(ctx, ((size_t(ctx->ppllPaddedW) * ctx->ppllPaddedH + 3) / 4) * 4);
     k_peel_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
-            B, (const uint32_t*)ctx->ppllCount.ptr, ctx->peelW, ctx->peelH, ctx->ppllPaddedW, ctx->peelTile[0], ctx->peelTile[1],
+            B, (const uint32_t*)ctx->ppllCount.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW, ctx->streamed.tile[0], ctx->streamed.tile[1],
             peel ? dAccum : nullptr, peel ? dLayers : nullptr, dCounts);
     LV_HIP(ctx, hipGetLastError());
     if (peel) {
@@ -4997,14 +4810,13 @@ int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outL
 
 // lv_depth_complexity_get_stats: the words of k_dc_reduce
 int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]) {
-    if (ctx->peelLast != LV_RENDERING_MODE_DEPTH_COMPLEXITY || !ctx->peelFull || !ctx->dcStatsDev.ptr || ctx->peelW != ctx->width ||
-        ctx->peelH != ctx->height)
+    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_DEPTH_COMPLEXITY) || !ctx->dcStatsDev.ptr)
         return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_stats: the last frame was not a mode-5 frame over the whole viewport");
     LvDcStats hs;
     LV_HIP(ctx, hipMemcpyAsync(&hs, ctx->dcStatsDev.ptr, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     out[0] = hs.total; out[1] = hs.used; out[2] = hs.maxCount; out[3] = hs.minCount == 0xFFFFFFFFu ? 0u : hs.minCount;
-    out[4] = uint64_t(ctx->peelW) * ctx->peelH;
+    out[4] = uint64_t(ctx->streamed.w) * ctx->streamed.h;
     return LV_OK;
 }
 
@@ -5021,14 +4833,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     const bool wboit = mode == LV_RENDERING_MODE_WBOIT;           // (the prism's fragments too, but no pool: lv_wboit_frame)
     const bool dcMode = mode == LV_RENDERING_MODE_DEPTH_COMPLEXITY, peel = mode == LV_RENDERING_MODE_DEPTH_PEELING;   // (lv_dc_frame, lv_peel_frame)
     const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 || wboit || dcMode || peel;   // (lv_al64_frame: `al64` = any pool-free mode)
-    ctx->mboitStreamLast = false;   // (set again at the end of a streamed mode-6 frame)
-    ctx->mboitStreamFull = false;
-    ctx->al64Last = false;          // (set again at the end of a mode-10 frame)
-    ctx->al64Full = false;
-    ctx->wboitLast = false;         // (set again at the end of a mode-8 frame)
-    ctx->wboitFull = false;
-    ctx->peelLast = 0;              // (set again at the end of a mode-5 or mode-9 frame)
-    ctx->peelFull = false;
+    ctx->streamed = {};   // (set again at the end of a streamed mode-6, a mode-5, 8, 9 or 10 frame: lv_streamed_done)
     const char* const poolName = dcMode ? "depth complexity" : peel ? "depth peeling" : wboit ? "WBOIT" : al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
     if ((mlab || al64) && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
@@ -5552,7 +5357,7 @@ static int lv_upload_runs(lv_ctx* ctx, const uint32_t* entries, size_t entryByte
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), numPixels * 4, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), numPixels * 4, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
-    ctx->peelLast = 0;   // (ppllCount no longer holds a mode-5 or mode-9 frame)
+    ctx->streamed = {};   // (ppllCount and the padded size no longer belong to a frame)
     return lv_single_tile(ctx, txy, w, h, T, numGroups);
 }
 // row-major addressing of a w x h rectangle: one 1 x 1-pixel tiling, address = y * w + x
@@ -5696,9 +5501,7 @@ int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKe
     if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
-    ctx->al64Last = false;   // (the buffer no longer holds a frame)
-    ctx->peelLast = 0;
-    ctx->mboitStreamLast = false;
+    ctx->streamed = {};   // (the buffers no longer hold a frame)
     if (numKeys) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, keys, size_t(numKeys) * 8, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, size_t(numPixels) * 4, st));
@@ -5750,10 +5553,7 @@ int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
     if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
-    ctx->wboitLast = false;   // (the buffers no longer hold a frame)
-    ctx->peelLast = 0;
-    ctx->al64Last = false;
-    ctx->mboitStreamLast = false;
+    ctx->streamed = {};   // (the buffers no longer hold a frame)
     if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 20, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, size_t(numPixels) * 4, st));
@@ -5805,7 +5605,7 @@ int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
     if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->outDev, n * 4))) return rc;
-    ctx->peelLast = 0;   // (the buffers no longer hold a frame)
+    ctx->streamed = {};   // (the buffers no longer hold a frame)
     if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 24, hipMemcpyHostToDevice, st));
     LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
     const LvPeelBuffers B = lv_peel_buffers(ctx, n);

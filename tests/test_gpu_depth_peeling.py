@@ -285,6 +285,59 @@ def test_buffers_shared_with_the_other_modes(hip_lib):
         assert np.array_equal(ctx.render(mode), fresh[mode]), mode
 
 
+def _equal(a, b):
+    if isinstance(a, dict):
+        return a == b
+    if isinstance(a, tuple):
+        return len(a) == len(b) and all(_equal(x, y) for x, y in zip(a, b))
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def test_one_record_of_the_last_frame_for_every_getter(hip_lib):
+    """The context keeps ONE record of the last frame behind the *_get_* calls of modes 5, 6 (streamed), 8, 9 and 10.  A frame sets it;
+    a *_resolve_buffers call of ANY other mode overwrites the per-pixel counts and the counters and clears it, so the getter answers
+    LV_E_STATE (-3) until the next frame of its mode, whose buffers are those of a fresh context."""
+    c = small_case(width=64, height=48, n_lines=4, pts_per_line=9, transparent=True)   # 32 segments
+    streamed = {"mboit_fragment_storage": "streamed"}
+    getters = {5: lambda x: (x.depth_complexity_buffers(), x.depth_complexity_stats()), 6: lambda x: x.mboit_moments(),
+               8: lambda x: x.wboit_buffers(), 9: lambda x: x.depth_peeling_buffers(), 10: lambda x: x.atomic_loop_buffers()}
+    # two pixels, three entries
+    off = np.array([0, 2, 3], np.uint64)
+    rgba = np.array([[0.9, 0.2, 0.1, 0.5], [0.1, 0.8, 0.3, 0.25], [0.2, 0.3, 0.7, 0.75]], F)
+    z = np.array([0.25, 0.5, 0.75], F)
+    packed = np.array([0x80112233, 0x40445566, 0xC0778899], np.uint32)
+    resolves = {
+        3: lambda x: x.mlab_resolve(np.stack([packed, z.view(np.uint32), np.arange(3, dtype=np.uint32)], axis=1), off, 2, 1),
+        6: lambda x: x.mboit_resolve(np.concatenate([rgba, 1.0 + z[:, None]], axis=1), off, 2, 1, -1.0, 3.0),
+        8: lambda x: x.wboit_resolve(np.concatenate([rgba, z[:, None]], axis=1), off, 2, 1),
+        9: lambda x: x.depth_peeling_resolve(rgba, z, np.arange(3, dtype=np.uint32), off, 2, 1),
+        10: lambda x: x.atomic_loop_resolve((z.view(np.uint32).astype(np.uint64) << np.uint64(32)) | packed.astype(np.uint64), off, 2, 1),
+    }
+    fresh = {}
+    for mode, get in getters.items():
+        f = c.hip_context()
+        f.set_options(streamed)
+        fresh[mode] = (f.render(mode), get(f))
+    ctx = c.hip_context()
+    ctx.set_options(streamed)
+    for mode, get in getters.items():
+        for other, resolve in resolves.items():
+            if other == mode:
+                continue
+            assert np.array_equal(ctx.render(mode), fresh[mode][0]), (mode, other)
+            assert _equal(get(ctx), fresh[mode][1]), (mode, other)   # the getter succeeds, with a fresh context's buffers
+            resolve(ctx)
+            assert _code(lambda: get(ctx)) == -3, (mode, other)
+        assert np.array_equal(ctx.render(mode), fresh[mode][0]), mode
+        assert _equal(get(ctx), fresh[mode][1]), mode
+    # the pair that used to answer LV_OK with the counts of the given lists: mode 8, mode 10's lists, mode 8's getter
+    ctx.render(8)
+    ctx.wboit_buffers()
+    resolves[10](ctx)
+    assert _code(ctx.wboit_buffers) == -3
+    assert _code(ctx.atomic_loop_buffers) == -3   # (and the lists' own mode has no frame either)
+
+
 # ---------------------------------------------------------------- 6. host plugin
 def test_host_plugin(hip_lib):
     import ctypes

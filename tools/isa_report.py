@@ -4,8 +4,10 @@
 that holds the node step (the innermost loop with the four global_load_dwordx4 of lv_node_step).
 
 Usage: python tools/isa_report.py [out.txt]   (cross-compiles with the library's flags; no GPU needed)
+       python tools/isa_report.py --compare OTHER_CSRC [a.hip ...] [OLD=NEW ...]   (two builds, function by function: see compare())
 """
 import collections
+import concurrent.futures
 import os
 import re
 import subprocess
@@ -17,13 +19,14 @@ sys.path.insert(0, ROOT)
 from linevis_amd import build as lv_build  # noqa: E402
 
 HOT = ["k_ao_rays", "k_ao_primary", "k_render_rt", "k_ppll_gather", "k_ppll_resolve", "k_render_rt_mlat", "k_ao_reduce",
-       "k_ppll_raster_prism", "k_ppll_shade_prism", "k_ppll_cull_segments", "k_ppll_select_nearest", "k_mboit_stream_pass", "k_al64_stream_pass", "k_wboit_stream_pass",
+       "k_ppll_raster_prism", "k_ppll_shade_prism", "k_ppll_cull_segments", "k_ppll_select_nearest", "k_mboit_stream_pass", "k_stream_pass",
        "k_dc_count_pass", "k_peel_pass", "k_peel_layer"]
 
 
-def demangle(names):
+def demangle(names, signature=False):
     out = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
-    return [o.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0] for o in out[:len(names)]]
+    out = [o.replace("(anonymous namespace)::", "").replace("void ", "") for o in out[:len(names)]]
+    return out if signature else [o.split("(")[0] for o in out]
 
 
 def compile_s(src, tmp):
@@ -117,7 +120,64 @@ def node_step_loop(body):
     return best
 
 
+def normalised(body):
+    """The instruction stream with block labels renumbered in order of first appearance (definition or branch target): two
+    functions with the same code compare equal wherever they stand in their files."""
+    ids = {}
+
+    def sub(m):
+        return ".LBB_%d" % ids.setdefault(m.group(0), len(ids))
+    return [re.sub(r"\.LBB\d+_\d+", sub, lab if lab else t) for lab, t in body]
+
+
+def compare(other_csrc, args):
+    """python tools/isa_report.py --compare OTHER_CSRC [a.hip ...] [OLD=NEW ...]: compiles the named sources (default lv_render.hip
+    and lv_peel.hip) of OTHER_CSRC (the csrc directory of another checkout) and of this tree, and lists every device function of the
+    other build as identical to its counterpart here or as differing.  OLD=NEW renames a prefix of the other build's demangled names
+    first, e.g. 'k_al64_stream_pass<=k_stream_pass<10, '."""
+    renames = [a.split("=", 1) for a in args if "=" in a]
+    sources = [a for a in args if "=" not in a] or ["lv_render.hip", "lv_peel.hip"]
+    keys = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
+    total = same = 0
+    def compile_one(path):
+        with tempfile.TemporaryDirectory() as tmp:
+            return compile_s(path, tmp)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=4) as pool:   # (the threads only wait for hipcc)
+        compiled = list(pool.map(compile_one, [os.path.join(c, s) for s in sources for c in (other_csrc, lv_build.CSRC)]))
+    for i, src in enumerate(sources):
+        built = []
+        for asm, rpass in compiled[2 * i:2 * i + 2]:
+            fns, res = functions(asm), resources(rpass)
+            built.append((dict(zip(demangle(list(fns), True), fns.values())), dict(zip(demangle(list(res), True), res.values()))))
+            assert len(built[-1][0]) == len(fns), "two functions of %s share a demangled name" % src
+        (old_fns, old_res), (new_fns, new_res) = built
+        print("## %s: %d device functions there, %d here" % (src, len(old_fns), len(new_fns)))
+        for name in sorted(old_fns):
+            here = name
+            for old, new in renames:
+                if here.startswith(old):
+                    here = new + here[len(old):]
+            total += 1
+            title = name if here == name else "%s -> %s" % (name, here)
+            if here not in new_fns:
+                print("%s: MISSING here" % title)
+                continue
+            a, b = normalised(old_fns[name]), normalised(new_fns[here])
+            ra, rb = old_res.get(name, {}), new_res.get(here, {})
+            if a == b and ra == rb:
+                same += 1
+                print("%s: identical (%d instructions)" % (title, sum(1 for x in a if not x.startswith(".LBB_"))))
+            else:
+                print("%s: differs (%d -> %d instructions; %s)" % (
+                    title, sum(1 for x in a if not x.startswith(".LBB_")), sum(1 for x in b if not x.startswith(".LBB_")),
+                    ", ".join("%s %s -> %s" % (k.split(" [")[0], ra.get(k), rb.get(k)) for k in keys)))
+    print("summary: %d of %d device functions of %s have an instruction-identical counterpart with equal resources" % (same, total, other_csrc))
+    return 0 if same == total else 1
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "--compare":
+        raise SystemExit(compare(sys.argv[2], sys.argv[3:]))
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "isa_r06.txt")
     lines = ["# ISA report of the frame kernels (hipcc %s, gfx950); generated by tools/isa_report.py" % " ".join(lv_build.FLAGS), ""]
     with tempfile.TemporaryDirectory() as tmp:

@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from linevis_amd import build  # noqa: E402
 
-KERNELS = ["k_al64_stream_pass", "k_mboit_stream_pass", "k_ppll_raster_prism", "k_ppll_shade_prism"]
+KERNELS = ["k_stream_pass",   # (mode 10: the probe renders no mode-8 frame)
+           "k_mboit_stream_pass", "k_ppll_raster_prism", "k_ppll_shade_prism"]
 
 
 def main():
@@ -37,10 +38,10 @@ def main():
         d[r["Counter_Name"]] = float(r["Counter_Value"])
         d["us"] = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
     groups = collections.OrderedDict()
-    al64 = [d for d in disp.values() if d["kernel"] == "k_al64_stream_pass"]
+    al64 = [d for d in disp.values() if d["kernel"] == "k_stream_pass"]
     per_k = len(al64) // 3
     for i, d in enumerate(al64):
-        groups.setdefault("k_al64_stream_pass K=%d" % (4, 8, 16)[min(i // max(per_k, 1), 2)], []).append(d)
+        groups.setdefault("k_stream_pass<10> K=%d" % (4, 8, 16)[min(i // max(per_k, 1), 2)], []).append(d)
     mboit = [d for d in disp.values() if d["kernel"] == "k_mboit_stream_pass"]
     for i, d in enumerate(mboit):
         groups.setdefault("k_mboit_stream_pass N=4 %s" % ("moments", "colours")[i % 2], []).append(d)
