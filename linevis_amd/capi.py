@@ -230,6 +230,15 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _given_lists(offsets, w, h):
+    """What the *_resolve methods share: the offsets of a w x h rectangle as contiguous uint64 (w * h + 1 of them) and the
+    (h, w, 4) uint8 image the call fills."""
+    o = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if o.shape[0] != w * h + 1:
+        raise ValueError("offsets must hold w * h + 1 values")
+    return o, np.empty((h, w, 4), dtype=np.uint8)
+
+
 def tile_deal(costs, num_tiles, num_ranks):
     """lv_tile_deal: tile -> rank, longest processing time first (costs None: round robin).  Pure host code."""
     out = np.zeros(max(int(num_tiles), 1), dtype=np.uint32)
@@ -609,10 +618,7 @@ class Context:
         """Mode 3's fold of caller-supplied runs (lv_mlab_resolve_buffers): entries = (n, 3) uint32 {colour, depth bits, key},
         pixel p = y * w + x owns entries[offsets[p]:offsets[p + 1]] in any order.  Returns (h, w, 4) uint8."""
         e = np.ascontiguousarray(entries, dtype=np.uint32).reshape(-1, 3)
-        o = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if o.shape[0] != w * h + 1:
-            raise ValueError("offsets must hold w * h + 1 values")
-        out = np.empty((h, w, 4), dtype=np.uint8)
+        o, out = _given_lists(offsets, w, h)
         self._ck(self.L.lv_mlab_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out)))
         return out
 
@@ -622,10 +628,7 @@ class Context:
         Returns ((h, w, 4) uint8, (h, w, 1 + num_moments) float32: b_0 and the normalised moments)."""
         self.set_option("mboit_num_moments", int(num_moments))
         e = np.ascontiguousarray(entries, dtype=np.float32).reshape(-1, 5)
-        o = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if o.shape[0] != w * h + 1:
-            raise ValueError("offsets must hold w * h + 1 values")
-        out = np.empty((h, w, 4), dtype=np.uint8)
+        o, out = _given_lists(offsets, w, h)
         mom = np.zeros((h, w, 1 + int(num_moments)), dtype=np.float32)
         self._ck(self.L.lv_mboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, float(log_depth_min), float(log_depth_max),
                                                  _p(mom), _p(out)))
@@ -658,10 +661,7 @@ class Context:
         4) uint8, (h, w, K) uint64 slots, (h, w, 5) uint64 tail sums)."""
         k = getattr(self, "_atomic_loop_num_layers", 8)
         e = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
-        o = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if o.shape[0] != w * h + 1:
-            raise ValueError("offsets must hold w * h + 1 values")
-        out = np.empty((h, w, 4), dtype=np.uint8)
+        o, out = _given_lists(offsets, w, h)
         slots = np.zeros((h, w, k), dtype=np.uint64)
         tail = np.zeros((h, w, 5), dtype=np.uint64)
         self._ck(self.L.lv_atomic_loop_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(slots), _p(tail)))
@@ -680,10 +680,7 @@ class Context:
         entries = (n, 5) float32 {r, g, b, alpha, window depth}, pixel p = y * w + x owns entries[offsets[p]:offsets[p + 1]].
         Returns ((h, w, 4) uint8, (h, w, 5) int64 sums)."""
         e = np.ascontiguousarray(entries, dtype=np.float32).reshape(-1, 5)
-        o = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if o.shape[0] != w * h + 1:
-            raise ValueError("offsets must hold w * h + 1 values")
-        out = np.empty((h, w, 4), dtype=np.uint8)
+        o, out = _given_lists(offsets, w, h)
         sums = np.zeros((h, w, 5), dtype=np.int64)
         self._ck(self.L.lv_wboit_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(sums)))
         return out, sums
@@ -721,10 +718,7 @@ class Context:
         e[:, :4] = c.view(np.uint32)
         e[:, 4] = np.ascontiguousarray(z, dtype=np.float32).reshape(-1).view(np.uint32)
         e[:, 5] = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
-        o = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if o.shape[0] != w * h + 1:
-            raise ValueError("offsets must hold w * h + 1 values")
-        out = np.empty((h, w, 4), dtype=np.uint8)
+        o, out = _given_lists(offsets, w, h)
         accum = np.zeros((h, w, 4), dtype=np.float32)
         layers = np.zeros((h, w), dtype=np.uint32)
         self._ck(self.L.lv_depth_peeling_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(accum), _p(layers)))

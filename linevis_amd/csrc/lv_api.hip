@@ -1498,103 +1498,91 @@ int lv_ppll_resolve_buffers(lv_ctx* ctx, const uint32_t* nodes, uint64_t num_nod
     return lv_frame_ppll_resolve_only(ctx, nodes, num_nodes, start_offset, num_pixels, x0, y0, w, h, out);
 }
 
-int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
-                            uint32_t h, uint8_t* out) {
+// What the *_resolve_buffers calls of modes 3, 6, 8, 9 and 10 refuse before they look at the lists; the device is set when they pass
+static int lv_given_lists_args(lv_ctx* ctx, const void* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w, uint32_t h,
+                               const void* out) {
     if (!ctx) return LV_E_INVALID;
     if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
     (void)hipSetDevice(ctx->device);
-    return lv_frame_mlab_resolve_only(ctx, entries, num_entries, offsets, w, h, out);
+    return LV_OK;
+}
+// ... and the *_get_* calls (`fn`) of the pool-free modes before they look at the last frame (outputs: all of them were given; what: what
+// a multi-device handle does not keep)
+static int lv_getter_args(lv_ctx* ctx, bool outputs, const char* fn, const char* what) {
+    if (!ctx) return LV_E_INVALID;
+    if (!outputs) return lv_fail(ctx, LV_E_INVALID, "%s: null output", fn);
+    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "%s: a multi-device handle keeps no %s of the whole viewport", fn, what);
+    (void)hipSetDevice(ctx->device);
+    return LV_OK;
+}
+
+int lv_mlab_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
+                            uint32_t h, uint8_t* out) {
+    const int rc = lv_given_lists_args(ctx, entries, num_entries, offsets, w, h, out);
+    return rc ? rc : lv_frame_mlab_resolve_only(ctx, entries, num_entries, offsets, w, h, out);
 }
 
 int lv_mboit_get_moments(lv_ctx* ctx, float* out, uint64_t capacity_floats) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out) return lv_fail(ctx, LV_E_INVALID, "lv_mboit_get_moments: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_mboit_get_moments: a multi-device handle keeps no moments of the whole viewport");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_mboit_stream_moments(ctx, out, capacity_floats);
+    const int rc = lv_getter_args(ctx, out, "lv_mboit_get_moments", "moments");
+    return rc ? rc : lv_frame_mboit_stream_moments(ctx, out, capacity_floats);
 }
 
 int lv_mboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                              uint32_t h, float log_depth_min, float log_depth_max, float* out_moments, uint8_t* out) {
-    if (!ctx) return LV_E_INVALID;
-    if ((num_entries && !entries) || !offsets || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_mboit_resolve_only(ctx, entries, num_entries, offsets, w, h, log_depth_min, log_depth_max, out_moments, out);
+    const int rc = lv_given_lists_args(ctx, entries, num_entries, offsets, w, h, out);
+    return rc ? rc : lv_frame_mboit_resolve_only(ctx, entries, num_entries, offsets, w, h, log_depth_min, log_depth_max, out_moments, out);
 }
 
 int lv_atomic_loop_get_num_layers(lv_ctx* ctx, uint32_t* out_num_layers) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out_num_layers) return lv_fail(ctx, LV_E_INVALID, "lv_atomic_loop_get_num_layers: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_num_layers: a multi-device handle keeps no buffers of the whole viewport");
-    return lv_frame_al64_num_layers(ctx, out_num_layers);
+    const int rc = lv_getter_args(ctx, out_num_layers, "lv_atomic_loop_get_num_layers", "buffers");
+    return rc ? rc : lv_frame_al64_num_layers(ctx, out_num_layers);
 }
 
 int lv_atomic_loop_get_buffers(lv_ctx* ctx, uint64_t* out_slots, uint64_t* out_tail, uint64_t capacity_pixels) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out_slots || !out_tail) return lv_fail(ctx, LV_E_INVALID, "lv_atomic_loop_get_buffers: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_al64_buffers(ctx, out_slots, out_tail, capacity_pixels);
+    const int rc = lv_getter_args(ctx, out_slots && out_tail, "lv_atomic_loop_get_buffers", "buffers");
+    return rc ? rc : lv_frame_al64_buffers(ctx, out_slots, out_tail, capacity_pixels);
 }
 
 int lv_atomic_loop_resolve_buffers(lv_ctx* ctx, const uint64_t* keys, uint64_t num_keys, const uint64_t* offsets, uint32_t w, uint32_t h,
                                    uint8_t* out_rgba8, uint64_t* out_slots, uint64_t* out_tail) {
-    if (!ctx) return LV_E_INVALID;
-    if ((num_keys && !keys) || !offsets || !out_rgba8 || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_al64_resolve_only(ctx, keys, num_keys, offsets, w, h, out_rgba8, out_slots, out_tail);
+    const int rc = lv_given_lists_args(ctx, keys, num_keys, offsets, w, h, out_rgba8);
+    return rc ? rc : lv_frame_al64_resolve_only(ctx, keys, num_keys, offsets, w, h, out_rgba8, out_slots, out_tail);
 }
 
 int lv_wboit_get_buffers(lv_ctx* ctx, int64_t* out_sums, uint32_t* out_counts, uint64_t capacity_pixels) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out_sums || !out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_wboit_get_buffers: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_wboit_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_wboit_buffers(ctx, out_sums, out_counts, capacity_pixels);
+    const int rc = lv_getter_args(ctx, out_sums && out_counts, "lv_wboit_get_buffers", "buffers");
+    return rc ? rc : lv_frame_wboit_buffers(ctx, out_sums, out_counts, capacity_pixels);
 }
 
 int lv_depth_complexity_get_buffers(lv_ctx* ctx, uint32_t* out_counts, uint64_t capacity_pixels) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_depth_complexity_get_buffers: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_peel_buffers(ctx, LV_RENDERING_MODE_DEPTH_COMPLEXITY, nullptr, nullptr, out_counts, capacity_pixels);
+    const int rc = lv_getter_args(ctx, out_counts, "lv_depth_complexity_get_buffers", "buffers");
+    return rc ? rc : lv_frame_peel_buffers(ctx, LV_RENDERING_MODE_DEPTH_COMPLEXITY, nullptr, nullptr, out_counts, capacity_pixels);
 }
 
 int lv_depth_complexity_get_stats(lv_ctx* ctx, lv_depth_complexity_stats* out) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out) return lv_fail(ctx, LV_E_INVALID, "lv_depth_complexity_get_stats: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_stats: a multi-device handle keeps no counts of the whole viewport");
-    (void)hipSetDevice(ctx->device);
-    uint64_t w[5];
     int rc;
+    if ((rc = lv_getter_args(ctx, out, "lv_depth_complexity_get_stats", "counts"))) return rc;
+    uint64_t w[5];
     if ((rc = lv_frame_dc_stats(ctx, w))) return rc;
     out->total = w[0]; out->used_locations = w[1]; out->max = w[2]; out->min = w[3]; out->buffer_size = w[4];
     return LV_OK;
 }
 
 int lv_depth_peeling_get_buffers(lv_ctx* ctx, float* out_accum_rgba, uint32_t* out_layers, uint32_t* out_counts, uint64_t capacity_pixels) {
-    if (!ctx) return LV_E_INVALID;
-    if (!out_accum_rgba || !out_layers || !out_counts) return lv_fail(ctx, LV_E_INVALID, "lv_depth_peeling_get_buffers: null output");
-    if (ctx->multi) return lv_fail(ctx, LV_E_STATE, "lv_depth_peeling_get_buffers: a multi-device handle keeps no buffers of the whole viewport");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_peel_buffers(ctx, LV_RENDERING_MODE_DEPTH_PEELING, out_accum_rgba, out_layers, out_counts, capacity_pixels);
+    const int rc = lv_getter_args(ctx, out_accum_rgba && out_layers && out_counts, "lv_depth_peeling_get_buffers", "buffers");
+    return rc ? rc : lv_frame_peel_buffers(ctx, LV_RENDERING_MODE_DEPTH_PEELING, out_accum_rgba, out_layers, out_counts, capacity_pixels);
 }
 
 int lv_depth_peeling_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                                      uint32_t h, uint8_t* out_rgba8, float* out_accum_rgba, uint32_t* out_layers) {
-    if (!ctx) return LV_E_INVALID;
-    if ((num_entries && !entries) || !offsets || !out_rgba8 || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_peel_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_accum_rgba, out_layers);
+    const int rc = lv_given_lists_args(ctx, entries, num_entries, offsets, w, h, out_rgba8);
+    return rc ? rc : lv_frame_peel_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_accum_rgba, out_layers);
 }
 
 int lv_wboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w, uint32_t h,
                              uint8_t* out_rgba8, int64_t* out_sums) {
-    if (!ctx) return LV_E_INVALID;
-    if ((num_entries && !entries) || !offsets || !out_rgba8 || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
-    (void)hipSetDevice(ctx->device);
-    return lv_frame_wboit_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_sums);
+    const int rc = lv_given_lists_args(ctx, entries, num_entries, offsets, w, h, out_rgba8);
+    return rc ? rc : lv_frame_wboit_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_sums);
 }
 
 int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_depth,

@@ -4530,27 +4530,50 @@ int lv_mboit_stream_overflow(lv_ctx* ctx) {
     return LV_OK;
 }
 
-// lv_mboit_get_moments
-int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloats) {
-    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_MBOIT) || !ctx->mboitAccum.ptr)
-        return lv_fail(ctx, LV_E_STATE, "lv_mboit_get_moments: the last frame was not a mode-6 frame with mboit_fragment_storage = "
-                                        "streamed over the whole viewport");
-    const uint64_t need = uint64_t(ctx->streamed.w) * ctx->streamed.h * (1u + ctx->streamed.param);
-    if (capacityFloats < need)
-        return lv_fail(ctx, LV_E_INVALID, "lv_mboit_get_moments: out holds %llu floats, need %llu", (unsigned long long)capacityFloats,
-                       (unsigned long long)need);
+// What every *_get_* call (`fn`) of the pool-free modes asks first: lv_streamed_is(mode) and `buf` of that frame exists, else
+// LV_E_STATE (`frame`: how the message names the frame)
+static int lv_streamed_require(lv_ctx* ctx, int mode, const char* frame, const LvDeviceBuffer& buf, const char* fn) {
+    if (lv_streamed_is(ctx, mode) && buf.ptr) return LV_OK;
+    return lv_fail(ctx, LV_E_STATE, "%s: the last frame was not a %s over the whole viewport", fn, frame);
+}
+// The opening of the calls that read per-pixel words back: lv_streamed_require; the caller's arrays hold `capacity` `unit`, `perPixel`
+// per pixel, else LV_E_INVALID; the frame has finished and kept every fragment (lv_mboit_stream_overflow); ctx->scratchRays has room
+// for scratchPerPixel bytes per pixel, where the mode's read kernel lays the words out in row-major order
+static int lv_read_back_open(lv_ctx* ctx, int mode, const char* frame, const LvDeviceBuffer& buf, const char* fn, uint64_t capacity,
+                             uint32_t perPixel, const char* unit, size_t scratchPerPixel, uint64_t& pixels) {
     int rc;
+    if ((rc = lv_streamed_require(ctx, mode, frame, buf, fn))) return rc;
+    pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
+    if (capacity < pixels * perPixel)
+        return lv_fail(ctx, LV_E_INVALID, "%s: out holds %llu %s, need %llu", fn, (unsigned long long)capacity, unit,
+                       (unsigned long long)(pixels * perPixel));
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, size_t(need) * 4))) return rc;
-    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
+    return lv_buf_reserve(ctx, ctx->scratchRays, size_t(pixels) * scratchPerPixel);
+}
+// ... and what it, and every *_resolve_buffers call, ends with: the launches went through, the copies to the caller's arrays (dst
+// null: not asked for), the synchronisation (also: host arrays of the call were sources of asynchronous uploads)
+struct LvCopyBack { void* dst; const void* src; size_t bytes; };
+static int lv_read_back(lv_ctx* ctx, std::initializer_list<LvCopyBack> copies) {
+    LV_HIP(ctx, hipGetLastError());
+    for (const LvCopyBack& c : copies)
+        if (c.dst) LV_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LV_OK;
+}
+
+// lv_mboit_get_moments (capacity in floats)
+int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloats) {
+    const uint32_t perPixel = 1u + ctx->streamed.param;
+    uint64_t pixels;
+    int rc;
+    if ((rc = lv_read_back_open(ctx, LV_RENDERING_MODE_MBOIT, "mode-6 frame with mboit_fragment_storage = streamed", ctx->mboitAccum,
+                                "lv_mboit_get_moments", capacityFloats, perPixel, "floats", size_t(perPixel) * 4, pixels)))
+        return rc;
     k_mboit_stream_moments<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
             (const unsigned long long*)ctx->mboitAccum.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW, ctx->streamed.tile[0],
             ctx->streamed.tile[1], ctx->streamed.param, (float*)ctx->scratchRays.ptr);
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(out, ctx->scratchRays.ptr, size_t(need) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LV_OK;
+    return lv_read_back(ctx, {{out, ctx->scratchRays.ptr, size_t(pixels) * perPixel * 4}});
 }
 
 // The middle of a mode-8 or mode-10 frame, between the clear of the mode's buffer and the close: the phase mark and ONE launch of
@@ -4606,28 +4629,18 @@ int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out) {
 
 // lv_atomic_loop_get_buffers
 int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, uint64_t capacityPixels) {
-    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_ATOMIC_LOOP_64) || !ctx->al64Buf.ptr)
-        return lv_fail(ctx, LV_E_STATE, "lv_atomic_loop_get_buffers: the last frame was not a mode-10 frame over the whole viewport");
-    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
-    if (capacityPixels < pixels)
-        return lv_fail(ctx, LV_E_INVALID, "lv_atomic_loop_get_buffers: the arrays hold %llu pixels, need %llu",
-                       (unsigned long long)capacityPixels, (unsigned long long)pixels);
-    int rc;
-    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
     const uint32_t K = ctx->streamed.param;
-    const size_t slotBytes = size_t(pixels) * K * 8, tailBytes = size_t(pixels) * LV_AL64_TAIL * 8;
-    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, slotBytes + tailBytes))) return rc;
+    uint64_t pixels;
+    int rc;
+    if ((rc = lv_read_back_open(ctx, LV_RENDERING_MODE_ATOMIC_LOOP_64, "mode-10 frame", ctx->al64Buf, "lv_atomic_loop_get_buffers",
+                                capacityPixels, 1u, "pixels", size_t(K + LV_AL64_TAIL) * 8, pixels)))
+        return rc;
     unsigned long long* dSlots = (unsigned long long*)ctx->scratchRays.ptr;
     unsigned long long* dTail = dSlots + size_t(pixels) * K;
     k_al64_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
             (const unsigned long long*)ctx->al64Buf.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW, ctx->streamed.tile[0], ctx->streamed.tile[1], K,
             dSlots, dTail);
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(outSlots, dSlots, slotBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LV_HIP(ctx, hipMemcpyAsync(outTail, dTail, tailBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LV_OK;
+    return lv_read_back(ctx, {{outSlots, dSlots, size_t(pixels) * K * 8}, {outTail, dTail, size_t(pixels) * LV_AL64_TAIL * 8}});
 }
 
 // A mode-8 frame (Weighted Blended OIT): the sums zeroed, ONE launch of k_stream_pass, the resolve.  No pool, no scan, no
@@ -4651,27 +4664,17 @@ static int lv_wboit_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTil
 
 // lv_wboit_get_buffers
 int lv_frame_wboit_buffers(lv_ctx* ctx, int64_t* outSums, uint32_t* outCounts, uint64_t capacityPixels) {
-    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_WBOIT) || !ctx->wboitBuf.ptr)
-        return lv_fail(ctx, LV_E_STATE, "lv_wboit_get_buffers: the last frame was not a mode-8 frame over the whole viewport");
-    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
-    if (capacityPixels < pixels)
-        return lv_fail(ctx, LV_E_INVALID, "lv_wboit_get_buffers: the arrays hold %llu pixels, need %llu",
-                       (unsigned long long)capacityPixels, (unsigned long long)pixels);
+    uint64_t pixels;
     int rc;
-    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = lv_mboit_stream_overflow(ctx))) return rc;
-    const size_t sumBytes = size_t(pixels) * LV_WBOIT_SUMS * 8, countBytes = size_t(pixels) * 4;
-    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, sumBytes + countBytes))) return rc;
+    if ((rc = lv_read_back_open(ctx, LV_RENDERING_MODE_WBOIT, "mode-8 frame", ctx->wboitBuf, "lv_wboit_get_buffers", capacityPixels, 1u,
+                                "pixels", size_t(LV_WBOIT_SUMS) * 8 + 4, pixels)))
+        return rc;
     unsigned long long* dSums = (unsigned long long*)ctx->scratchRays.ptr;
     uint32_t* dCounts = (uint32_t*)(dSums + size_t(pixels) * LV_WBOIT_SUMS);
     k_wboit_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
             (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW,
             ctx->streamed.tile[0], ctx->streamed.tile[1], dSums, dCounts);
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(outSums, dSums, sumBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LV_HIP(ctx, hipMemcpyAsync(outCounts, dCounts, countBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LV_OK;
+    return lv_read_back(ctx, {{outSums, dSums, size_t(pixels) * LV_WBOIT_SUMS * 8}, {outCounts, dCounts, size_t(pixels) * 4}});
 }
 
 // the per-pixel words of mode 9 behind ctx->peelBuf for n pixels: 16 B accumulator, 8 B slot, 4 B prevZ, 4 B layer count
@@ -4779,17 +4782,14 @@ static int lv_peel_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTile
 
 // lv_depth_complexity_get_buffers (accum = layers = null) and lv_depth_peeling_get_buffers
 int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outLayers, uint32_t* outCounts, uint64_t capacityPixels) {
-    const char* fn = mode == LV_RENDERING_MODE_DEPTH_PEELING ? "lv_depth_peeling_get_buffers" : "lv_depth_complexity_get_buffers";
-    if (!lv_streamed_is(ctx, mode) || !ctx->ppllCount.ptr)
-        return lv_fail(ctx, LV_E_STATE, "%s: the last frame was not a mode-%d frame over the whole viewport", fn, mode);
-    const uint64_t pixels = uint64_t(ctx->streamed.w) * ctx->streamed.h;
-    if (capacityPixels < pixels)
-        return lv_fail(ctx, LV_E_INVALID, "%s: the arrays hold %llu pixels, need %llu", fn, (unsigned long long)capacityPixels,
-                       (unsigned long long)pixels);
     const bool peel = mode == LV_RENDERING_MODE_DEPTH_PEELING;
+    uint64_t pixels;
     int rc;
+    if ((rc = lv_read_back_open(ctx, mode, peel ? "mode-9 frame" : "mode-5 frame", ctx->ppllCount,
+                                peel ? "lv_depth_peeling_get_buffers" : "lv_depth_complexity_get_buffers", capacityPixels, 1u, "pixels",
+                                peel ? 24 : 8, pixels)))
+        return rc;
     const size_t accBytes = peel ? size_t(pixels) * 16 : 0, wordBytes = size_t(pixels) * 4;
-    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, accBytes + 2 * wordBytes))) return rc;
     float4* dAccum = (float4*)ctx->scratchRays.ptr;
     uint32_t* dLayers = (uint32_t*)((char*)ctx->scratchRays.ptr + accBytes);
     uint32_t* dCounts = dLayers + size_t(pixels);
@@ -4798,20 +4798,14 @@ int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outL
     k_peel_read<<<uint32_t((pixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, ctx->stream>>>(
             B, (const uint32_t*)ctx->ppllCount.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW, ctx->streamed.tile[0], ctx->streamed.tile[1],
             peel ? dAccum : nullptr, peel ? dLayers : nullptr, dCounts);
-    LV_HIP(ctx, hipGetLastError());
-    if (peel) {
-        LV_HIP(ctx, hipMemcpyAsync(outAccum, dAccum, accBytes, hipMemcpyDeviceToHost, ctx->stream));
-        LV_HIP(ctx, hipMemcpyAsync(outLayers, dLayers, wordBytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    LV_HIP(ctx, hipMemcpyAsync(outCounts, dCounts, wordBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LV_OK;
+    return lv_read_back(ctx, {{outAccum, dAccum, accBytes}, {outLayers, dLayers, wordBytes}, {outCounts, dCounts, wordBytes}});
 }
 
 // lv_depth_complexity_get_stats: the words of k_dc_reduce
 int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]) {
-    if (!lv_streamed_is(ctx, LV_RENDERING_MODE_DEPTH_COMPLEXITY) || !ctx->dcStatsDev.ptr)
-        return lv_fail(ctx, LV_E_STATE, "lv_depth_complexity_get_stats: the last frame was not a mode-5 frame over the whole viewport");
+    int rc;
+    if ((rc = lv_streamed_require(ctx, LV_RENDERING_MODE_DEPTH_COMPLEXITY, "mode-5 frame", ctx->dcStatsDev, "lv_depth_complexity_get_stats")))
+        return rc;
     LvDcStats hs;
     LV_HIP(ctx, hipMemcpyAsync(&hs, ctx->dcStatsDev.ptr, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -5318,53 +5312,84 @@ static int lv_single_tile(lv_ctx* ctx, const uint32_t* txy, uint32_t w, uint32_t
     numGroups = uint32_t(lv_tiles_cells(T));
     return LV_OK;
 }
-// ... and the resolved rectangle (ctx->outDev), with mode 6's moments (ctx->ppllScratch) when asked for, back to the caller
-static int lv_resolve_read_back(lv_ctx* ctx, uint8_t* out, size_t numPixels, float* outMoments = nullptr, size_t momBytes = 0) {
-    hipStream_t st = ctx->stream;
-    LV_HIP(ctx, hipGetLastError());
-    LV_HIP(ctx, hipMemcpyAsync(out, ctx->outDev.ptr, numPixels * 4, hipMemcpyDeviceToHost, st));
-    if (outMoments) LV_HIP(ctx, hipMemcpyAsync(outMoments, ctx->ppllScratch.ptr, momBytes, hipMemcpyDeviceToHost, st));
-    LV_HIP(ctx, hipStreamSynchronize(st));   // (also: the host arrays of the call were sources of asynchronous uploads)
-    return LV_OK;
-}
-// Pixel p owns entries [offsets[p], offsets[p + 1]): the runs' starts and lengths, at most maxCount entries per pixel
-static int lv_runs_from_offsets(lv_ctx* ctx, const uint64_t* offsets, uint64_t numPixels, uint64_t numEntries, uint32_t maxCount,
-                                std::vector<uint32_t>& start, std::vector<uint32_t>& count) {
-    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
-    start.resize(numPixels); count.resize(numPixels);
-    for (uint64_t p = 0; p < numPixels; p++) {
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > maxCount)
-            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most %u entries per pixel", (unsigned long long)p, maxCount);
-        start[p] = uint32_t(offsets[p]);
-        count[p] = uint32_t(offsets[p + 1] - offsets[p]);
-    }
-    return LV_OK;
-}
-// Modes 3 and 6: the buffers of a w x h rectangle behind the caller's own (ppllNodes, ppllScratch), the uploads of the entries
-// (entryBytes of them; 0: none) and the runs, zeroed counters, the tile at the origin and its grid
-static int lv_upload_runs(lv_ctx* ctx, const uint32_t* entries, size_t entryBytes, const std::vector<uint32_t>& start,
-                          const std::vector<uint32_t>& count, uint32_t w, uint32_t h, LvTiles& T, uint32_t& numGroups) {
-    static const uint32_t txy[2] = {0u, 0u};
-    hipStream_t st = ctx->stream;
-    const size_t numPixels = start.size();
-    int rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, numPixels * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, numPixels * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->outDev, numPixels * 4))) return rc;
-    if (entryBytes) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, entryBytes, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, start.data(), numPixels * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, count.data(), numPixels * 4, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
-    ctx->streamed = {};   // (ppllCount and the padded size no longer belong to a frame)
-    return lv_single_tile(ctx, txy, w, h, T, numGroups);
+// ... and the resolved rectangle (ctx->outDev) back to the caller, with the call's other arrays (`more`; dst null: not asked for)
+static int lv_resolve_read_back(lv_ctx* ctx, uint8_t* out, size_t numPixels, LvCopyBack more0 = {}, LvCopyBack more1 = {}) {
+    return lv_read_back(ctx, {{out, ctx->outDev.ptr, numPixels * 4}, more0, more1});
 }
 // row-major addressing of a w x h rectangle: one 1 x 1-pixel tiling, address = y * w + x
 static void lv_row_major_uniforms(lv_ctx* ctx, LvUniforms& U, uint32_t w, uint32_t h) {
     lv_fill_uniforms(ctx, U);
     U.width = w; U.height = h;
     U.ppllTileW = 1u; U.ppllTileH = 1u; U.ppllPaddedW = w; U.ppllPaddedH = h;
+}
+
+// Given lists (modes 3, 6, 8, 9 and 10): pixel p of the w x h rectangle owns entries [offsets[p], offsets[p + 1]), in any order.
+// What a mode admits: fewer than maxEntries `noun` and at most maxPixels pixels (the 32-bit indices of its kernels), at most maxCount
+// of them in a pixel (0xFFFFFFFF: no maximum of its own -- a run is shorter than maxEntries)
+struct LvRunLimits { const char* noun; uint64_t maxEntries, maxPixels; uint32_t maxCount; };
+// The check every such call starts with, in this order: the sizes, else LV_E_CAPACITY; the offsets, else LV_E_INVALID.  The mode's
+// checks of reserved values follow it, and nothing of the context is touched before all of them have passed.  longest: the longest run
+static int lv_runs_from_offsets(lv_ctx* ctx, const LvRunLimits& lim, const uint64_t* offsets, uint64_t numPixels, uint64_t numEntries,
+                                uint64_t* longest = nullptr) {
+    if (numEntries >= lim.maxEntries || numPixels > lim.maxPixels) return lv_fail(ctx, LV_E_CAPACITY, "too many %s or pixels", lim.noun);
+    if (offsets[0] != 0 || offsets[numPixels] != numEntries)
+        return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to the number of %s", lim.noun);
+    uint64_t most = 0;
+    for (uint64_t p = 0; p < numPixels; p++) {
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > lim.maxCount)
+            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most %u %s per pixel", (unsigned long long)p,
+                           lim.maxCount, lim.noun);
+        most = std::max(most, offsets[p + 1] - offsets[p]);
+    }
+    if (longest) *longest = most;
+    return LV_OK;
+}
+// What such a call does to the context around its own kernels: row-major uniforms; the buffers it takes over -- ppllNodes for the
+// entries (entrySize bytes each), counters, tilesDev, outDev, and those of the runs' shape (below) --, after which no *_get_* call
+// finds a frame; the entries uploaded, the counters zeroed, the tile at the origin and the grid of its resolve
+struct LvGivenLists {
+    LvUniforms U;
+    LvTiles T;
+    uint32_t numGroups;
+    std::vector<uint32_t> runs;   // lv_upload_start_count: the host arrays, sources of uploads until the call's last synchronisation
+};
+static int lv_upload_runs(lv_ctx* ctx, const void* entries, uint64_t numEntries, size_t entrySize, uint32_t w, uint32_t h, LvGivenLists& G) {
+    static const uint32_t txy[2] = {0u, 0u};
+    hipStream_t st = ctx->stream;
+    int rc;
+    lv_row_major_uniforms(ctx, G.U, w, h);
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(numEntries ? numEntries : 1) * entrySize))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(w) * h * 4))) return rc;
+    ctx->streamed = {};   // (ppllCount, the mode's buffer and the padded size no longer belong to a frame)
+    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * entrySize, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
+    return lv_single_tile(ctx, txy, w, h, G.T, G.numGroups);
+}
+// The runs as modes 3 and 6 take them, whose resolves are the frame's own: 32-bit starts and counts in ppllStart and ppllCount
+static int lv_upload_start_count(lv_ctx* ctx, const uint64_t* offsets, size_t numPixels, std::vector<uint32_t>& runs) {
+    runs.resize(2 * numPixels);
+    for (size_t p = 0; p < numPixels; p++) {
+        runs[p] = uint32_t(offsets[p]);
+        runs[numPixels + p] = uint32_t(offsets[p + 1] - offsets[p]);
+    }
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, numPixels * 4))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, numPixels * 4))) return rc;
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllStart.ptr, runs.data(), numPixels * 4, hipMemcpyHostToDevice, ctx->stream));
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllCount.ptr, runs.data() + numPixels, numPixels * 4, hipMemcpyHostToDevice, ctx->stream));
+    return LV_OK;
+}
+// The runs as modes 8, 9 and 10 take them, whose *_given kernels look a lane's pixel up: the 64-bit offsets in ppllScratch, and the
+// per-pixel counts those kernels add to (ppllCount) zeroed
+static int lv_upload_offsets(lv_ctx* ctx, const uint64_t* offsets, size_t numPixels) {
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, (numPixels + 1) * 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, numPixels * 4))) return rc;
+    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, (numPixels + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, numPixels * 4, ctx->stream));
+    return LV_OK;
 }
 
 int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numNodes, const uint32_t* start,
@@ -5411,10 +5436,9 @@ int lv_frame_ppll_resolve_only(lv_ctx* ctx, const uint32_t* nodes, uint64_t numN
 int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w,
                                uint32_t h, uint8_t* out) {
     const uint64_t numPixels = uint64_t(w) * h;
-    if (numEntries >= 0xFFFFFFF0ull || numPixels > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
+    const LvRunLimits lim = {"entries", 0xFFFFFFF0ull, 0x7FFFFFF0ull, 0xFFFFu};
     int rc;
-    std::vector<uint32_t> start, count;
-    if ((rc = lv_runs_from_offsets(ctx, offsets, numPixels, numEntries, 0xFFFFu, start, count))) return rc;
+    if ((rc = lv_runs_from_offsets(ctx, lim, offsets, numPixels, numEntries))) return rc;
     for (uint64_t i = 0; i < numEntries; i++)
         if (entries[3 * i + 2] == LV_MLAB_NO_KEY) return lv_fail(ctx, LV_E_INVALID, "entry %llu: key 0xFFFFFFFF is reserved", (unsigned long long)i);
     {   // keys unique within a pixel: the ordering ranks by key (a repeated key would leave a rank unwritten)
@@ -5427,14 +5451,11 @@ int lv_frame_mlab_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
                 return lv_fail(ctx, LV_E_INVALID, "pixel %llu: keys must be unique within a pixel", (unsigned long long)p);
         }
     }
-    LvUniforms U;
-    lv_row_major_uniforms(ctx, U, w, h);
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(numEntries ? numEntries : 1) * 12))) return rc;
+    LvGivenLists G;
+    if ((rc = lv_upload_runs(ctx, entries, numEntries, 12, w, h, G))) return rc;
+    if ((rc = lv_upload_start_count(ctx, offsets, size_t(numPixels), G.runs))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, size_t(numEntries ? numEntries : 1) * 8))) return rc;
-    LvTiles T;
-    uint32_t numGroups;
-    if ((rc = lv_upload_runs(ctx, entries, size_t(numEntries) * 12, start, count, w, h, T, numGroups))) return rc;
-    if ((rc = lv_mlab_fold(ctx, U, T, numGroups, nullptr, (uint32_t*)ctx->outDev.ptr, (uint2*)ctx->ppllScratch.ptr,
+    if ((rc = lv_mlab_fold(ctx, G.U, G.T, G.numGroups, nullptr, (uint32_t*)ctx->outDev.ptr, (uint2*)ctx->ppllScratch.ptr,
                            (LvDevCounters*)ctx->counters.ptr)))
         return rc;
     return lv_resolve_read_back(ctx, out, size_t(numPixels));
@@ -5446,10 +5467,9 @@ int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
                                 uint32_t h, float logDepthMin, float logDepthMax, float* outMoments, uint8_t* out) {
     const uint64_t numPixels = uint64_t(w) * h;
     const uint32_t N = ctx->opt.mboitNumMoments;
-    if (numEntries >= 0xFFFFFFF0ull / 5 || numPixels > 0x7FFFFFF0ull / (1 + N)) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
+    const LvRunLimits lim = {"entries", 0xFFFFFFF0ull / 5, 0x7FFFFFF0ull / (1 + N), 0xFFFEu};
     int rc;
-    std::vector<uint32_t> start, count;
-    if ((rc = lv_runs_from_offsets(ctx, offsets, numPixels, numEntries, 0xFFFEu, start, count))) return rc;
+    if ((rc = lv_runs_from_offsets(ctx, lim, offsets, numPixels, numEntries))) return rc;
     const size_t cap = size_t(numEntries ? numEntries : 1);
     std::vector<uint32_t> split(cap * 5);
     for (uint64_t i = 0; i < numEntries; i++) {
@@ -5457,22 +5477,19 @@ int lv_frame_mboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
         for (int k = 0; k < 4; k++) split[4 * i + k] = entries[5 * i + k];
         split[4 * cap + i] = entries[5 * i + 4];
     }
-    LvUniforms U;
-    lv_row_major_uniforms(ctx, U, w, h);
+    LvGivenLists G;
+    if ((rc = lv_upload_runs(ctx, split.data(), numEntries, 20, w, h, G))) return rc;
+    if ((rc = lv_upload_start_count(ctx, offsets, size_t(numPixels), G.runs))) return rc;
     const size_t momBytes = size_t(numPixels) * (1 + N) * 4;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, cap * 20))) return rc;
     if (outMoments && (rc = lv_buf_reserve(ctx, ctx->ppllScratch, momBytes))) return rc;
-    LvTiles T;
-    uint32_t numGroups;
-    if ((rc = lv_upload_runs(ctx, split.data(), cap * 20, start, count, w, h, T, numGroups))) return rc;
     const uint32_t noBox[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    LvMboitParams M = lv_mboit_params(ctx, U, noBox, ctx->opt.collectStats);
+    LvMboitParams M = lv_mboit_params(ctx, G.U, noBox, ctx->opt.collectStats);
     M.logDepthMin = logDepthMin;
     M.logDepthMax = logDepthMax;
-    if ((rc = lv_mboit_resolve(ctx, U, T, M, numGroups, uint32_t(cap), nullptr, (uint32_t*)ctx->outDev.ptr,
+    if ((rc = lv_mboit_resolve(ctx, G.U, G.T, M, G.numGroups, uint32_t(cap), nullptr, (uint32_t*)ctx->outDev.ptr,
                                outMoments ? (float*)ctx->ppllScratch.ptr : nullptr, (LvDevCounters*)ctx->counters.ptr)))
         return rc;
-    return lv_resolve_read_back(ctx, out, size_t(numPixels), outMoments, momBytes);
+    return lv_resolve_read_back(ctx, out, size_t(numPixels), {outMoments, ctx->ppllScratch.ptr, momBytes});
 }
 
 // lv_atomic_loop_resolve_buffers: the caller's keys (pixel p of the w x h rectangle owns keys [offsets[p], offsets[p + 1])) inserted
@@ -5481,53 +5498,34 @@ int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKe
                                uint8_t* out, uint64_t* outSlots, uint64_t* outTail) {
     const uint64_t numPixels = uint64_t(w) * h;
     const uint32_t K = ctx->opt.al64NumLayers;
-    if (numKeys >= 0xFFFFFFF0ull || numPixels > 0x7FFFFFF0ull / (K + LV_AL64_TAIL)) return lv_fail(ctx, LV_E_CAPACITY, "too many keys or pixels");
-    if (offsets[0] != 0 || offsets[numPixels] != numKeys) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_keys");
-    for (uint64_t p = 0; p < numPixels; p++)
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] > LV_AL64_MAX_COUNT)
-            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend, at most %u keys per pixel", (unsigned long long)p, LV_AL64_MAX_COUNT);
+    const LvRunLimits lim = {"keys", 0xFFFFFFF0ull, 0x7FFFFFF0ull / (K + LV_AL64_TAIL), LV_AL64_MAX_COUNT};
+    int rc;
+    if ((rc = lv_runs_from_offsets(ctx, lim, offsets, numPixels, numKeys))) return rc;
     for (uint64_t i = 0; i < numKeys; i++)
         if (keys[i] == LV_AL64_EMPTY) return lv_fail(ctx, LV_E_INVALID, "key %llu: 0xFFFFFFFFFFFFFFFF is the empty slot", (unsigned long long)i);
     hipStream_t st = ctx->stream;
-    LvUniforms U;
-    lv_row_major_uniforms(ctx, U, w, h);
+    LvGivenLists G;
+    if ((rc = lv_upload_runs(ctx, keys, numKeys, 8, w, h, G))) return rc;
+    if ((rc = lv_upload_offsets(ctx, offsets, size_t(numPixels)))) return rc;
     const size_t numWords = size_t(numPixels) * (K + LV_AL64_TAIL);
-    const size_t keyBytes = size_t(numKeys ? numKeys : 1) * 8, offBytes = size_t(numPixels + 1) * 8;
-    int rc;
     if ((rc = lv_buf_reserve(ctx, ctx->al64Buf, numWords * 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, keyBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
-    ctx->streamed = {};   // (the buffers no longer hold a frame)
-    if (numKeys) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, keys, size_t(numKeys) * 8, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, size_t(numPixels) * 4, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
     lv_al64_clear(ctx, numWords, K);
     if (numKeys)
         k_al64_insert_given<<<uint32_t((numKeys + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
                 (const unsigned long long*)ctx->ppllNodes.ptr, numKeys, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels),
                 (unsigned long long*)ctx->al64Buf.ptr, (uint32_t*)ctx->ppllCount.ptr, K);
-    static const uint32_t txy[2] = {0u, 0u};
-    LvTiles T;
-    uint32_t numGroups;
-    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
-    k_al64_resolve<<<numGroups, LV_WAVE, 0, st>>>(U, T, (const unsigned long long*)ctx->al64Buf.ptr, (const uint32_t*)ctx->ppllCount.ptr,
-                                                  (uint32_t*)ctx->outDev.ptr, numGroups, K, (LvDevCounters*)ctx->counters.ptr);
+    k_al64_resolve<<<G.numGroups, LV_WAVE, 0, st>>>(G.U, G.T, (const unsigned long long*)ctx->al64Buf.ptr, (const uint32_t*)ctx->ppllCount.ptr,
+                                                    (uint32_t*)ctx->outDev.ptr, G.numGroups, K, (LvDevCounters*)ctx->counters.ptr);
+    unsigned long long *dSlots = nullptr, *dTail = nullptr;
     if (outSlots || outTail) {
-        const size_t slotBytes = size_t(numPixels) * K * 8, tailBytes = size_t(numPixels) * LV_AL64_TAIL * 8;
-        if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, slotBytes + tailBytes))) return rc;
-        unsigned long long* dSlots = (unsigned long long*)ctx->scratchRays.ptr;
-        unsigned long long* dTail = dSlots + size_t(numPixels) * K;
+        if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, numWords * 8))) return rc;
+        dSlots = (unsigned long long*)ctx->scratchRays.ptr;
+        dTail = dSlots + size_t(numPixels) * K;
         k_al64_read<<<uint32_t((numPixels + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
                 (const unsigned long long*)ctx->al64Buf.ptr, w, h, w, 1u, 1u, K, dSlots, dTail);
-        if (outSlots) LV_HIP(ctx, hipMemcpyAsync(outSlots, dSlots, slotBytes, hipMemcpyDeviceToHost, st));
-        if (outTail) LV_HIP(ctx, hipMemcpyAsync(outTail, dTail, tailBytes, hipMemcpyDeviceToHost, st));
     }
-    return lv_resolve_read_back(ctx, out, size_t(numPixels));
+    return lv_resolve_read_back(ctx, out, size_t(numPixels), {outSlots, dSlots, size_t(numPixels) * K * 8},
+                                {outTail, dTail, size_t(numPixels) * LV_AL64_TAIL * 8});
 }
 
 // lv_wboit_resolve_buffers: the caller's fragments (pixel p of the w x h rectangle owns entries [offsets[p], offsets[p + 1])) added
@@ -5536,43 +5534,25 @@ int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKe
 int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
                                 uint8_t* out, int64_t* outSums) {
     const uint64_t numPixels = uint64_t(w) * h;
-    if (numEntries >= 0xFFFFFFF0ull / 5u || numPixels > 0x7FFFFFF0ull / LV_WBOIT_SUMS) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
-    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
-    for (uint64_t p = 0; p < numPixels; p++)
-        if (offsets[p + 1] < offsets[p]) return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend", (unsigned long long)p);
-    hipStream_t st = ctx->stream;
-    LvUniforms U;
-    lv_row_major_uniforms(ctx, U, w, h);
-    const size_t sumBytes = size_t(numPixels) * LV_WBOIT_SUMS * 8;
-    const size_t entryBytes = size_t(numEntries ? numEntries : 1) * 20, offBytes = size_t(numPixels + 1) * 8;
+    const LvRunLimits lim = {"entries", 0xFFFFFFF0ull / 5u, 0x7FFFFFF0ull / LV_WBOIT_SUMS, 0xFFFFFFFFu};
     int rc;
+    if ((rc = lv_runs_from_offsets(ctx, lim, offsets, numPixels, numEntries))) return rc;
+    hipStream_t st = ctx->stream;
+    LvGivenLists G;
+    if ((rc = lv_upload_runs(ctx, entries, numEntries, 20, w, h, G))) return rc;
+    if ((rc = lv_upload_offsets(ctx, offsets, size_t(numPixels)))) return rc;
+    const size_t sumBytes = size_t(numPixels) * LV_WBOIT_SUMS * 8;
     if ((rc = lv_buf_reserve(ctx, ctx->wboitBuf, sumBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, entryBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, size_t(numPixels) * 4))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->outDev, size_t(numPixels) * 4))) return rc;
-    ctx->streamed = {};   // (the buffers no longer hold a frame)
-    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 20, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->ppllCount.ptr, 0, size_t(numPixels) * 4, st));
-    LV_HIP(ctx, hipMemsetAsync(ctx->counters.ptr, 0, sizeof(LvDevCounters), st));
     LV_HIP(ctx, hipMemsetAsync(ctx->wboitBuf.ptr, 0, sumBytes, st));
     if (numEntries)
         k_wboit_add_given<<<uint32_t((numEntries + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
                 (const float*)ctx->ppllNodes.ptr, numEntries, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels),
                 (unsigned long long*)ctx->wboitBuf.ptr, (uint32_t*)ctx->ppllCount.ptr,
                 ctx->opt.wboitOpenglWeight ? LV_WBOIT_WEIGHT_OPENGL : LV_WBOIT_WEIGHT_REFERENCE);
-    static const uint32_t txy[2] = {0u, 0u};
-    LvTiles T;
-    uint32_t numGroups;
-    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
-    k_wboit_resolve<<<numGroups, LV_WAVE, 0, st>>>(U, T, (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr,
-                                                   (uint32_t*)ctx->outDev.ptr, numGroups, (LvDevCounters*)ctx->counters.ptr);
+    k_wboit_resolve<<<G.numGroups, LV_WAVE, 0, st>>>(G.U, G.T, (const unsigned long long*)ctx->wboitBuf.ptr, (const uint32_t*)ctx->ppllCount.ptr,
+                                                     (uint32_t*)ctx->outDev.ptr, G.numGroups, (LvDevCounters*)ctx->counters.ptr);
     // (row-major addressing: the sums lie as the caller's array does)
-    if (outSums) LV_HIP(ctx, hipMemcpyAsync(outSums, ctx->wboitBuf.ptr, sumBytes, hipMemcpyDeviceToHost, st));
-    if ((rc = lv_resolve_read_back(ctx, out, size_t(numPixels)))) return rc;
+    if ((rc = lv_resolve_read_back(ctx, out, size_t(numPixels), {outSums, ctx->wboitBuf.ptr, sumBytes}))) return rc;
     uint32_t flag = 0u;
     LV_HIP(ctx, hipMemcpy(&flag, &((const LvDevCounters*)ctx->counters.ptr)->mboitOverflow, 4, hipMemcpyDeviceToHost));
     if (flag)
@@ -5586,28 +5566,17 @@ int lv_frame_wboit_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t n
 int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
                                uint8_t* out, float* outAccum, uint32_t* outLayers) {
     const uint64_t numPixels = uint64_t(w) * h;
-    if (numEntries >= 0xFFFFFFF0ull / 6u || numPixels > 0x7FFFFFF0ull / 8u) return lv_fail(ctx, LV_E_CAPACITY, "too many entries or pixels");
-    if (offsets[0] != 0 || offsets[numPixels] != numEntries) return lv_fail(ctx, LV_E_INVALID, "offsets must run from 0 to num_entries");
+    const LvRunLimits lim = {"entries", 0xFFFFFFF0ull / 6u, 0x7FFFFFF0ull / 8u, 0xFFFFFFFFu};
     uint64_t longest = 0;
-    for (uint64_t p = 0; p < numPixels; p++) {
-        if (offsets[p + 1] < offsets[p]) return lv_fail(ctx, LV_E_INVALID, "pixel %llu: offsets must ascend", (unsigned long long)p);
-        longest = std::max<uint64_t>(longest, offsets[p + 1] - offsets[p]);
-    }
-    hipStream_t st = ctx->stream;
-    LvUniforms U;
-    lv_row_major_uniforms(ctx, U, w, h);
-    const size_t n = size_t(numPixels);
-    const size_t entryBytes = size_t(numEntries ? numEntries : 1) * 24, offBytes = size_t(numPixels + 1) * 8;
     int rc;
+    if ((rc = lv_runs_from_offsets(ctx, lim, offsets, numPixels, numEntries, &longest))) return rc;
+    hipStream_t st = ctx->stream;
+    LvGivenLists G;
+    if ((rc = lv_upload_runs(ctx, entries, numEntries, 24, w, h, G))) return rc;
+    if ((rc = lv_upload_offsets(ctx, offsets, size_t(numPixels)))) return rc;
+    const size_t n = size_t(numPixels);
     if ((rc = lv_buf_reserve(ctx, ctx->peelBuf, n * LV_PEEL_BYTES_PER_PIXEL))) return rc;
     if ((rc = lv_buf_reserve(ctx, ctx->dcStatsDev, sizeof(LvDcStats)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, entryBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, offBytes))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->outDev, n * 4))) return rc;
-    ctx->streamed = {};   // (the buffers no longer hold a frame)
-    if (numEntries) LV_HIP(ctx, hipMemcpyAsync(ctx->ppllNodes.ptr, entries, size_t(numEntries) * 24, hipMemcpyHostToDevice, st));
-    LV_HIP(ctx, hipMemcpyAsync(ctx->ppllScratch.ptr, offsets, offBytes, hipMemcpyHostToDevice, st));
     const LvPeelBuffers B = lv_peel_buffers(ctx, n);
     k_peel_clear<<<uint32_t((n + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(B, n, (LvDcStats*)ctx->dcStatsDev.ptr);
     const uint32_t passes = uint32_t(std::min<uint64_t>(longest, ctx->opt.peelMaxLayers));
@@ -5618,15 +5587,9 @@ int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
         k_peel_layer_given<<<uint32_t((n + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>(
                 (const uint32_t*)ctx->ppllNodes.ptr, (const unsigned long long*)ctx->ppllScratch.ptr, uint32_t(numPixels), B);
     }
-    static const uint32_t txy[2] = {0u, 0u};
-    LvTiles T;
-    uint32_t numGroups;
-    if ((rc = lv_single_tile(ctx, txy, w, h, T, numGroups))) return rc;
-    k_peel_blit<<<numGroups, LV_WAVE, 0, st>>>(U, T, B.accum, (uint32_t*)ctx->outDev.ptr, numGroups);
+    k_peel_blit<<<G.numGroups, LV_WAVE, 0, st>>>(G.U, G.T, B.accum, (uint32_t*)ctx->outDev.ptr, G.numGroups);
     // (row-major addressing: the words lie as the caller's arrays do)
-    if (outAccum) LV_HIP(ctx, hipMemcpyAsync(outAccum, B.accum, n * 16, hipMemcpyDeviceToHost, st));
-    if (outLayers) LV_HIP(ctx, hipMemcpyAsync(outLayers, B.layers, n * 4, hipMemcpyDeviceToHost, st));
-    return lv_resolve_read_back(ctx, out, n);
+    return lv_resolve_read_back(ctx, out, n, {outAccum, B.accum, n * 16}, {outLayers, B.layers, n * 4});
 }
 
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,

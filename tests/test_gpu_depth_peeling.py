@@ -293,26 +293,40 @@ def _equal(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+STREAMED = {"mboit_fragment_storage": "streamed"}
+GETTERS = {5: lambda x: (x.depth_complexity_buffers(), x.depth_complexity_stats()), 6: lambda x: x.mboit_moments(),
+           8: lambda x: x.wboit_buffers(), 9: lambda x: x.depth_peeling_buffers(), 10: lambda x: x.atomic_loop_buffers()}
+
+
+def _getter_case():
+    return small_case(width=64, height=48, n_lines=4, pts_per_line=9, transparent=True)   # 32 segments
+
+
+def _resolves(off, n=3):
+    """The given-lists call of every mode that has one, on a rectangle of 2 x 1 pixels with n entries under the offsets `off`: colours
+    and packed colours repeat three values, depths ascend inside (0, 1), keys are arange (unique: mode 3's rule)"""
+    off = np.asarray(off, np.uint64)
+    reps = (n + 2) // 3
+    rgba = np.tile(np.array([[0.9, 0.2, 0.1, 0.5], [0.1, 0.8, 0.3, 0.25], [0.2, 0.3, 0.7, 0.75]], F), (reps, 1))[:n]
+    packed = np.tile(np.array([0x80112233, 0x40445566, 0xC0778899], np.uint32), reps)[:n]
+    z = (np.arange(1, n + 1, dtype=np.float64) / (n + 1)).astype(F)   # (n = 3: 0.25, 0.5, 0.75)
+    keys = np.arange(n, dtype=np.uint32)
+    return {
+        3: lambda x: x.mlab_resolve(np.stack([packed, z.view(np.uint32), keys], axis=1), off, 2, 1),
+        6: lambda x: x.mboit_resolve(np.concatenate([rgba, 1.0 + z[:, None]], axis=1), off, 2, 1, -1.0, 3.0),
+        8: lambda x: x.wboit_resolve(np.concatenate([rgba, z[:, None]], axis=1), off, 2, 1),
+        9: lambda x: x.depth_peeling_resolve(rgba, z, keys, off, 2, 1),
+        10: lambda x: x.atomic_loop_resolve((z.view(np.uint32).astype(np.uint64) << np.uint64(32)) | packed.astype(np.uint64), off, 2, 1),
+    }
+
+
 def test_one_record_of_the_last_frame_for_every_getter(hip_lib):
     """The context keeps ONE record of the last frame behind the *_get_* calls of modes 5, 6 (streamed), 8, 9 and 10.  A frame sets it;
     a *_resolve_buffers call of ANY other mode overwrites the per-pixel counts and the counters and clears it, so the getter answers
     LV_E_STATE (-3) until the next frame of its mode, whose buffers are those of a fresh context."""
-    c = small_case(width=64, height=48, n_lines=4, pts_per_line=9, transparent=True)   # 32 segments
-    streamed = {"mboit_fragment_storage": "streamed"}
-    getters = {5: lambda x: (x.depth_complexity_buffers(), x.depth_complexity_stats()), 6: lambda x: x.mboit_moments(),
-               8: lambda x: x.wboit_buffers(), 9: lambda x: x.depth_peeling_buffers(), 10: lambda x: x.atomic_loop_buffers()}
-    # two pixels, three entries
-    off = np.array([0, 2, 3], np.uint64)
-    rgba = np.array([[0.9, 0.2, 0.1, 0.5], [0.1, 0.8, 0.3, 0.25], [0.2, 0.3, 0.7, 0.75]], F)
-    z = np.array([0.25, 0.5, 0.75], F)
-    packed = np.array([0x80112233, 0x40445566, 0xC0778899], np.uint32)
-    resolves = {
-        3: lambda x: x.mlab_resolve(np.stack([packed, z.view(np.uint32), np.arange(3, dtype=np.uint32)], axis=1), off, 2, 1),
-        6: lambda x: x.mboit_resolve(np.concatenate([rgba, 1.0 + z[:, None]], axis=1), off, 2, 1, -1.0, 3.0),
-        8: lambda x: x.wboit_resolve(np.concatenate([rgba, z[:, None]], axis=1), off, 2, 1),
-        9: lambda x: x.depth_peeling_resolve(rgba, z, np.arange(3, dtype=np.uint32), off, 2, 1),
-        10: lambda x: x.atomic_loop_resolve((z.view(np.uint32).astype(np.uint64) << np.uint64(32)) | packed.astype(np.uint64), off, 2, 1),
-    }
+    c = _getter_case()
+    streamed, getters = STREAMED, GETTERS
+    resolves = _resolves([0, 2, 3])   # two pixels, three entries
     fresh = {}
     for mode, get in getters.items():
         f = c.hip_context()
@@ -336,6 +350,52 @@ def test_one_record_of_the_last_frame_for_every_getter(hip_lib):
     resolves[10](ctx)
     assert _code(ctx.wboit_buffers) == -3
     assert _code(ctx.atomic_loop_buffers) == -3   # (and the lists' own mode has no frame either)
+
+
+def test_malformed_given_lists_and_short_getter_capacities(hip_lib):
+    """What the *_resolve_buffers calls of modes 3, 6, 8, 9 and 10 refuse (LV_E_INVALID, -1) before they touch the context -- offsets
+    that do not run from 0 to num_entries or descend, a pixel over the mode's maximum, mode 6's reserved depth word -- with the longest
+    accepted pixel of every mode next to the refused one; a refused call leaves the last frame's getter as it was, byte for byte; and
+    every getter refuses a capacity one short of the viewport.  Codes and acceptance only: the results of given lists have the
+    bit-for-bit tests of each mode."""
+    c = _getter_case()
+    ctx = c.hip_context()
+    ctx.set_options(STREAMED)
+    # offsets: first not 0, last under and over num_entries = 3, a descending pair between the right ends
+    bad_offsets = ([1, 2, 3], [0, 2, 2], [0, 2, 4], [0, 5, 3])
+    for off in bad_offsets:
+        for mode, resolve in _resolves(off).items():
+            assert _code(lambda: resolve(ctx)) == -1, (mode, off)
+    # the per-pixel maximum: all n entries in pixel 0 (mode 8 finds its own through the resolve: test_gpu_wboit.py)
+    for mode, most in ((3, 65535), (6, 65534), (10, 131071)):
+        assert _code(lambda: _resolves([0, most + 1, most + 1], most + 1)[mode](ctx)) == -1, mode
+        _resolves([0, most, most], most)[mode](ctx)
+    ctx.set_option("depth_peeling_max_layers", 2000)
+    _resolves([0, 3000, 3000], 3000)[9](ctx)   # mode 9 has no maximum: more entries than layers
+    # mode 6: the depth word 0xFFFFFFFF is reserved
+    entries = np.array([[0.9, 0.2, 0.1, 0.5, 1.25], [0.1, 0.8, 0.3, 0.25, 1.5], [0.2, 0.3, 0.7, 0.75, 1.75]], F)
+    ctx.mboit_resolve(entries, [0, 2, 3], 2, 1, -1.0, 3.0)
+    entries.view(np.uint32)[1, 4] = 0xFFFFFFFF
+    assert _code(lambda: ctx.mboit_resolve(entries, [0, 2, 3], 2, 1, -1.0, 3.0)) == -1
+    # a refused call changes nothing: the getter of the last frame answers as before it
+    for mode in (6, 8, 9, 10):
+        ctx.render(mode)
+        before = GETTERS[mode](ctx)
+        assert _code(lambda: _resolves(bad_offsets[0])[mode](ctx)) == -1, mode
+        assert _equal(GETTERS[mode](ctx), before), mode
+    # a capacity one short of the viewport, then the exact one
+    n = c.width * c.height
+    a = [np.zeros(n * 16, np.uint64) for _ in range(3)]   # (room for the largest array of any getter: K = 8 slots per pixel)
+    p = lambda i: a[i].ctypes.data
+    calls = {5: lambda cap: ctx.L.lv_depth_complexity_get_buffers(ctx.h, p(0), cap),
+             6: lambda cap: ctx.L.lv_mboit_get_moments(ctx.h, p(0), cap + 4 * n),   # (counted in floats: 1 + N = 5 per pixel)
+             8: lambda cap: ctx.L.lv_wboit_get_buffers(ctx.h, p(0), p(1), cap),
+             9: lambda cap: ctx.L.lv_depth_peeling_get_buffers(ctx.h, p(0), p(1), p(2), cap),
+             10: lambda cap: ctx.L.lv_atomic_loop_get_buffers(ctx.h, p(0), p(1), cap)}
+    for mode, call in calls.items():
+        ctx.render(mode)
+        assert call(n - 1) == -1, mode
+        assert call(n) == 0, mode
 
 
 # ---------------------------------------------------------------- 6. host plugin
