@@ -1,7 +1,9 @@
 """Rendering mode 10 (Atomic Loop 64) on the GPU, byte for byte against al64_fold (test_atomic_loop_restatement.py): given key lists
 with all lanes racing, whole frames against the fold of the oracle's prism fragments, band data and helicity bands, K, tile lists,
 deep tails, buffers shared with the other modes, errors and the host plugin.  Every sum is an integer and lv_exp_det / lv_log_det
-are bit-identical on host and device, so 0 LSB is derived; max_lsb_diff <= 2 stands in front of the equality to size a failure."""
+are bit-identical on host and device, so 0 LSB is derived; max_lsb_diff <= 2 stands in front of the equality to size a failure.
+"Band data and helicity bands" here are the (any, band data) and (6, helicity) instances of k_stream_pass only;
+test_gpu_oit_instances.py holds all eight, at odd viewports and PPLL tile sizes."""
 import functools
 
 import numpy as np

@@ -2,7 +2,9 @@
 fragment lists with all lanes racing for the slots, whole frames against the fold of the oracle's prism fragments, RTAO and depth
 cues, band data and helicity bands, general cameras, deep pixels and the cap, tile lists (repeated and overlapping tiles), a one-rank
 multi handle, buffers shared with the other modes, errors and the host plugin.  One fixed float32 order and no library exp on this
-path, so 0 LSB is derived; max_lsb_diff <= 2 stands in front of the equality to size a failure."""
+path, so 0 LSB is derived; max_lsb_diff <= 2 stands in front of the equality to size a failure.  "Band data and helicity bands"
+here are the (any, band data) and (6, helicity) instances of k_peel_pass / k_peel_layer only; test_gpu_oit_instances.py holds all of
+them, at odd viewports and PPLL tile sizes."""
 import functools
 
 import numpy as np

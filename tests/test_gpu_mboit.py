@@ -1,7 +1,8 @@
 """Rendering mode 6 (MBOIT) on the GPU: the device sweeps (k_mboit_resolve / k_mboit_resolve_long) bit for bit against mboit_fold
 (test_mboit_restatement.py) on given runs -- frame and moments -- and on the oracle's prism fragments of whole frames; invariance
 under rasteriser, tiling, repetition, fragment order and the host plugin's states; long runs, pool growth, options, errors, the
-degenerate-pixel counter and isolation from modes 2 and 3."""
+degenerate-pixel counter and isolation from modes 2 and 3.  The band-data and helicity frames here run the (any, band data) and
+(6, helicity) instances of the fragment stage only; test_gpu_oit_instances.py holds all eight, at odd viewports and PPLL tile sizes."""
 import ctypes
 
 import numpy as np

@@ -1,6 +1,8 @@
 """Rendering mode 3 (MLAB) on the GPU: the device fold (k_mlab_resolve / k_mlab_resolve_long) bit for bit against mlab_fold
 (test_mlab_restatement.py) on given runs and on the oracle's prism fragments of whole frames; invariance under rasteriser, tiling,
-repetition and the host plugin's states; long runs, pool growth, K, errors and isolation from mode 2."""
+repetition and the host plugin's states; long runs, pool growth, K, errors and isolation from mode 2.  The band-data and helicity
+frames here run the (any, band data) and (6, helicity) instances of the fragment stage only; test_gpu_oit_instances.py holds all
+eight, at odd viewports and PPLL tile sizes."""
 import numpy as np
 import pytest
 

@@ -2,7 +2,9 @@
 lists with all lanes racing, whole frames against the fold of the oracle's prism fragments under both depth weights, RTAO and depth
 cues, band data and helicity bands, general cameras, deep pixels, tile lists, a one-rank multi handle, buffers shared with the other
 modes, errors and the host plugin.  Every sum is an integer and lv_exp_det / lv_log_det are bit-identical on host and device, so
-0 LSB is derived; max_lsb_diff <= 2 stands in front of the equality to size a failure."""
+0 LSB is derived; max_lsb_diff <= 2 stands in front of the equality to size a failure.  "Band data and helicity bands" here are the
+(any, band data) and (6, helicity) instances of k_stream_pass only; test_gpu_oit_instances.py holds all eight, at odd viewports and
+PPLL tile sizes."""
 import functools
 
 import numpy as np
