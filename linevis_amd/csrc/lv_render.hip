@@ -4411,7 +4411,7 @@ struct LvStreamedOpen {
 };
 // The opening: the restrictions of these modes (`name` in the messages), the prism's constants, ppllStart, ppllCount and the mode's
 // own buffer (modeBytes per padded pixel; nullptr: none) reserved, clear().
-// (use_ribbons with rotating_helicity_bands never gets here: lv_frame_render refuses that pair for every mode)
+// (use_ribbons with rotating_helicity_bands never gets here: lv_frame_check refuses that pair for every mode)
 static int lv_streamed_open(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, bool stats, LvDevCounters* dc, const char* name,
                             LvDeviceBuffer* modeBuf, size_t modeBytes, LvStreamedOpen& F) {
     int rc;
@@ -4457,7 +4457,7 @@ static bool lv_streamed_is(const lv_ctx* ctx, int mode) {
     return r.mode == mode && r.full && r.w == ctx->width && r.h == ctx->height;
 }
 // The instance of a streamed pass for the frame: LAUNCH(NT, SHADE, FAST) with NT = 6 for the six-sided prism (0: any n), then the
-// variants lv_frame_render selects for the pooled fragment stage -- fast (lv_prism_fast_shade), bands, helicity bands, plain
+// variants lv_pool_frame selects for the pooled fragment stage -- fast (lv_prism_fast_shade), bands, helicity bands, plain
 #define LV_SELECT_STREAM_PASS_NT(LAUNCH, NT)                                         \
     do {                                                                             \
         if (fastShade) LAUNCH(NT, LV_SHADE_PLAIN, 2);                                \
@@ -4814,36 +4814,39 @@ int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]) {
     return LV_OK;
 }
 
-int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
-                    uint32_t tileH, void* outDevice) {
+// ---- lv_frame_render: its refusals, its tile list, the two oldest frame functions (mode 11; modes 2, 3 and pooled 6), the frame ----
+
+// How the messages of the modes that work on the prism's fragments alone name them (modes 3, 5, 6, 8, 9 and 10)
+static const char* lv_prism_mode_name(int mode) {
+    return mode == LV_RENDERING_MODE_DEPTH_COMPLEXITY ? "depth complexity" : mode == LV_RENDERING_MODE_DEPTH_PEELING ? "depth peeling"
+         : mode == LV_RENDERING_MODE_WBOIT ? "WBOIT" : mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 ? "Atomic Loop 64"
+         : mode == LV_RENDERING_MODE_MBOIT ? "MBOIT" : "MLAB";
+}
+
+// What a frame call is refused for before anything is built or enqueued: the mode, the options that exclude each other, the state
+// the caller has not set.  A call of a supported mode ends the record of the last frame (ctx->streamed: set again at the end of a
+// streamed mode-6, a mode-5, 8, 9 or 10 frame, lv_streamed_done), refused or not.
+static int lv_frame_check(lv_ctx* ctx, int mode) {
     if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
         mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64 &&
         mode != LV_RENDERING_MODE_DEPTH_COMPLEXITY && mode != LV_RENDERING_MODE_DEPTH_PEELING)
         return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 5 = depth complexity, "
                                           "6 = MBOIT, 8 = WBOIT, 9 = depth peeling, 10 = Atomic Loop 64)", mode);
-    // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
-    const bool mboit = mode == LV_RENDERING_MODE_MBOIT;
-    const bool mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
-    const bool wboit = mode == LV_RENDERING_MODE_WBOIT;           // (the prism's fragments too, but no pool: lv_wboit_frame)
-    const bool dcMode = mode == LV_RENDERING_MODE_DEPTH_COMPLEXITY, peel = mode == LV_RENDERING_MODE_DEPTH_PEELING;   // (lv_dc_frame, lv_peel_frame)
-    const bool al64 = mode == LV_RENDERING_MODE_ATOMIC_LOOP_64 || wboit || dcMode || peel;   // (lv_al64_frame: `al64` = any pool-free mode)
-    ctx->streamed = {};   // (set again at the end of a streamed mode-6, a mode-5, 8, 9 or 10 frame: lv_streamed_done)
-    const char* const poolName = dcMode ? "depth complexity" : peel ? "depth peeling" : wboit ? "WBOIT" : al64 ? "Atomic Loop 64" : mboit ? "MBOIT" : "MLAB";
-    if ((mlab || al64) && ctx->opt.ppllFragmentSource == 1)
+    ctx->streamed = {};
+    const bool fragments = mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER;   // the modes whose colour pass works on fragments
+    if (fragments && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
-                                          "capsule_entry is not supported", mode, poolName);
+                                          "capsule_entry is not supported", mode, lv_prism_mode_name(mode));
     if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_set_camera has not been called");
     if (!ctx->tf.ptr || ctx->tfN == 0) return lv_fail(ctx, LV_E_STATE, "lv_set_transfer_function has not been called");
     if (!ctx->points.ptr && ctx->numSegs) return lv_fail(ctx, LV_E_STATE, "lv_set_lines has not been called");
-    if (numTiles == 0 || tileW == 0 || tileH == 0) return lv_fail(ctx, LV_E_INVALID, "empty tile list");
-    int rc;
     if (ctx->opt.useRibbons) {
         // band data: the closest-hit paths of the ray tracer (analytic geometry modes, or "Triangle Mesh" on the elliptic triangle
         // tubes the host layer tessellates for the data set); RTAO over the analytic tubelets / capsules or over those triangle
         // tubes (rtao_geometry = triangle_tubes); MLAT over the same geometries; the PPLL gather over the analytic tubelets /
         // capsules.  The static prebaker bakes band data on the elliptic cross-section against the elliptic triangle tubes the caller
         // passed (VulkanAmbientOcclusionBaker.glsl:200-257) and is looked up with the band's own angle (phiLine of the tubelets).
-        if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab || al64) && (ctx->opt.rtTriangleMesh || ctx->opt.rtLss))
+        if (fragments && (ctx->opt.rtTriangleMesh || ctx->opt.rtLss))
             return lv_fail(ctx, LV_E_INVALID, "use_ribbons: the PPLL gather of band data runs over the analytic tubelets / capsules "
                                               "(geometry_mode \"AABBs\")");
         if (ctx->opt.rtTriangleMesh && ctx->opt.ellipticTubes)
@@ -4855,39 +4858,30 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         return lv_fail(ctx, LV_E_INVALID, "rotating_helicity_bands and use_ribbons exclude each other (LineDataFlow.cpp:470,601-604)");
     if (ctx->opt.rtLss && ctx->opt.useRibbons && ctx->opt.ellipticTubes)
         return lv_fail(ctx, LV_E_INVALID, "Elliptic Tubes belong to the AABB geometry mode (VulkanRayTracer.cpp:198), not to Linear Swept Spheres");
-    if ((rc = lv_ensure_line_points(ctx))) return rc;   // lv_set_trajectories' records follow the band / helicity switches
-    if (!ctx->accelValid || ctx->accelLineWidth != lv_accel_width(ctx))
-        if ((rc = lv_bvh_build(ctx))) return rc;
-    const bool needTriangles = (ctx->opt.useAmbientOcclusion && ctx->opt.aoPrebaked) ||
-                               (ctx->opt.useAmbientOcclusion && lv_ao_triangle_tubes(ctx)) ||
-                               (ctx->opt.rtTriangleMesh && mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER);
-    if (needTriangles) {
-        if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
-        if (!ctx->triMeshSet)
-            return lv_fail(ctx, LV_E_STATE, "rtao_geometry = triangle_tubes / geometry_mode = Triangle Mesh / the RTAO "
-                                            "prebaker need lv_set_tube_triangle_mesh");
-        if (!ctx->triAccelValid || ctx->triAccelLineWidth != ctx->opt.lineWidth)
-            if ((rc = lv_bvh_build_triangles(ctx))) return rc;
+    return LV_OK;
+}
+
+// Do the tiles cover every pixel of the viewport?  (sufficient test: grid-aligned tiles, every grid cell present)
+static bool lv_tiles_cover(uint32_t width, uint32_t height, uint32_t tileW, uint32_t tileH, const uint32_t* tiles, uint32_t numTiles) {
+    const uint32_t gx = (width + tileW - 1u) / tileW, gy = (height + tileH - 1u) / tileH;
+    if (uint64_t(gx) * gy > uint64_t(numTiles)) return false;
+    std::vector<uint8_t> cell(size_t(gx) * gy, 0);
+    size_t present = 0;
+    for (uint32_t t = 0; t < numTiles; t++) {
+        const uint32_t tx = tiles[2 * t], ty = tiles[2 * t + 1];
+        if (tx % tileW || ty % tileH || tx / tileW >= gx || ty / tileH >= gy) continue;
+        uint8_t& c = cell[size_t(ty / tileH) * gx + tx / tileW];
+        if (!c) { c = 1; present++; }
     }
+    return present == size_t(gx) * gy;
+}
 
+// The frame's tile list on the device (ctx->tilesDev, reserved by the caller) and ctx->tilesCoverViewport.  The tile list is usually
+// the same from frame to frame (a rank keeps its tiles): it is uploaded only when it changes, so that consecutive frames need no host
+// synchronisation and the CPU can enqueue frame k+1 while frame k runs.  The cover test runs again when the list, the viewport or the
+// tile size changed (ctx->tilesCoverKey).
+static int lv_frame_tiles(lv_ctx* ctx, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW, uint32_t tileH) {
     hipStream_t st = ctx->stream;
-    LvUniforms U;
-    lv_fill_uniforms(ctx, U);
-    // AO lookup of the colour pass: literal projection + bilinear sample for jittered primary rays (ray tracer only; the PPLL
-    // fragments sit at pixel centres), the pixel's own texel otherwise
-    U.aoProjectLookup = (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER && U.useJitteredRays && U.useAmbientOcclusion && !U.aoPrebaked) ? 1u : 0u;
-    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->depthMinMax, 16))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, size_t(numTiles) * 8))) return rc;
-    if ((rc = lv_buf_reserve(ctx, ctx->ao, size_t(ctx->width) * ctx->height * 4))) return rc;
-    if (ctx->aoW != ctx->width || ctx->aoH != ctx->height) ctx->aoResult = nullptr; // images of another viewport size
-    ctx->aoW = ctx->width;
-    ctx->aoH = ctx->height;
-    LvDevCounters* dc = (LvDevCounters*)ctx->counters.ptr;
-
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[2], st));
-    // The tile list is usually the same from frame to frame (a rank keeps its tiles): upload it only when it changes, so
-    // that consecutive frames need no host synchronisation and the CPU can enqueue frame k+1 while frame k runs.
     const bool sameTiles = ctx->tilesUploaded && ctx->tilesHost.size() == 2 * size_t(numTiles) &&
                            memcmp(ctx->tilesHost.data(), tilesXYHost, size_t(numTiles) * 8) == 0;
     if (!sameTiles) {
@@ -4901,96 +4895,20 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     }
     if (ctx->tilesCoverKey[0] != ctx->width || ctx->tilesCoverKey[1] != ctx->height || ctx->tilesCoverKey[2] != tileW ||
         ctx->tilesCoverKey[3] != tileH) {
-        // do the tiles cover every pixel of the viewport?  (sufficient test: grid-aligned tiles, every grid cell present)
-        const uint32_t gx = (ctx->width + tileW - 1u) / tileW, gy = (ctx->height + tileH - 1u) / tileH;
-        bool cover = false;
-        if (uint64_t(gx) * gy <= uint64_t(numTiles)) {
-            std::vector<uint8_t> cell(size_t(gx) * gy, 0);
-            size_t present = 0;
-            for (uint32_t t = 0; t < numTiles; t++) {
-                const uint32_t tx = tilesXYHost[2 * t], ty = tilesXYHost[2 * t + 1];
-                if (tx % tileW || ty % tileH || tx / tileW >= gx || ty / tileH >= gy) continue;
-                uint8_t& c = cell[size_t(ty / tileH) * gx + tx / tileW];
-                if (!c) { c = 1; present++; }
-            }
-            cover = present == size_t(gx) * gy;
-        }
-        ctx->tilesCoverViewport = cover;
+        ctx->tilesCoverViewport = lv_tiles_cover(ctx->width, ctx->height, tileW, tileH, tilesXYHost, numTiles);
         ctx->tilesCoverKey[0] = ctx->width; ctx->tilesCoverKey[1] = ctx->height; ctx->tilesCoverKey[2] = tileW; ctx->tilesCoverKey[3] = tileH;
     }
-    LV_HIP(ctx, hipMemsetAsync(dc, 0, sizeof(LvDevCounters), st));
+    return LV_OK;
+}
 
-    LvTiles T = lv_tiles((const uint32_t*)ctx->tilesDev.ptr, numTiles, tileW, tileH);
-    if (lv_tiles_blocks(T) > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-    ctx->groupOrderSorted = false;
-    ctx->groupOrder[1].active = false;
-    if ((rc = lv_group_order_prepare(ctx, T, 0))) return rc;
-    const uint32_t gridTiles = uint32_t(lv_tiles_grid(T));
-    const uint64_t maxPixels = lv_tiles_pixels(T);
-    const bool stats = ctx->opt.collectStats;
-    // overlap_primary_passes (default on): the colour pass' first-hit trace rides along with the RTAO primaries (k_primary_pair) and the
-    // colour kernel after the RTAO pass only shades.  Where it applies: the ray tracer on the analytic capsules, one sample per pixel
-    // (the first ray of a pixel is then its only first ray), the per-frame RTAO pass on the caller's tiles (SVGF covers the viewport).
-    // "auto": while the colour pass' tile kernel is at most four rounds of workgroups (16 per CU; half a 1920 x 1080 frame) -- a frame
-    // that fills the GPU several times over is throughput-bound in both passes and only pays the second shading (measured, EXPERIMENTS 13.2)
-    const bool pairWanted = ctx->opt.overlapPrimaryPasses == 1 || (ctx->opt.overlapPrimaryPasses == 2 && gridTiles <= 16u * uint32_t(ctx->numCUs));
-    const bool pairPrimaries = pairWanted && mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER && U.useAmbientOcclusion &&
-                               !U.aoPrebaked && !ctx->opt.useMlat && !ctx->opt.rtTriangleMesh && !U.useEllipticTubes &&
-                               !ctx->opt.svgfEnabled && (U.useJitteredRays ? U.numSamplesPerFrame : 1u) == 1u && ctx->numSegs > 0u &&
-                               (ctx->opt.numAccumulatedFrames <= 1u || ctx->opt.frameNumber < ctx->opt.aoIterations);
-    // one reservation for every launch of this frame: no view built below can move the slab
-    const size_t need = lv_frame_overflow_bytes(ctx, U, T, mode, pairPrimaries);
-    if (need && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, need))) return rc;
-    LvSceneDev S = sceneDev(ctx);
-    if ((rc = lv_prepare_overflow(ctx, S, "colour pass", gridTiles))) return rc;
-
-    // LineRenderer::renderBase: depth range, LineRenderer.cpp:248-256
-    if (U.useDepthCues) {
-        k_depth_init<<<1, 64, 0, st>>>(U, dc);
-        if (ctx->numPoints)
-            k_depth_minmax<<<nblocks(ctx->numPoints), LV_BLOCK, 0, st>>>(U, S.points, ctx->numPoints, dc);
-        k_depth_finalize<<<1, 64, 0, st>>>(dc, (float*)ctx->depthMinMax.ptr);
-    }
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[5], st));
-
-    // ambientOcclusionBaker->updateIterative(), LineRenderer.cpp:257-264
-    ctx->aoNumGroups = 0;
-    bool firstHitsTraced = false;
-    if (U.useAmbientOcclusion && !U.aoPrebaked) {
-        LvSceneDev SP = S;
-        if (pairPrimaries) {
-            if (U.lssGeometry) SP.literalIntersection = 0u; // as the colour pass below
-            if ((rc = lv_buf_reserve(ctx, ctx->firstHit, size_t(maxPixels) * 8 * LV_PRE_HITS))) return rc;
-        }
-        if ((rc = lv_run_ao(ctx, U, S, T, pairPrimaries ? &SP : nullptr, &firstHitsTraced))) return rc;
-    }
-    if (U.aoPrebaked && !ctx->bakeValid && ctx->bakeAsyncPending) {
-        // a bake is running on the second stream (lv_bake_ao_start): adopt its table if it has finished; otherwise this frame is
-        // rendered without ambient occlusion -- "display the AO once baking has finished" (AmbientOcclusionBaker.hpp:66-70)
-        if ((rc = lv_bake_poll(ctx, false))) return rc;
-        if (!ctx->bakeValid && ctx->bakeAsyncPending) { U.aoPrebaked = 0u; U.useAmbientOcclusion = 0u; }
-    }
-    if (U.aoPrebaked) {
-        // static prebaker: view independent, (re)baked only when geometry or baking settings changed
-        if (!ctx->bakeValid) {
-            if ((rc = lv_bake_ambient_occlusion(ctx, false, true))) return rc;
-        }
-        S.bakedAo = (const float*)ctx->bakedAo.ptr;
-        S.bakedBlendingWeights = (const float*)ctx->bakeBlendingWeights.ptr;
-    }
-    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[7], st));
-    // The colour pass of a raster_prism frame with the segment rasteriser has no tile kernel: only its resolve pass could use the
-    // dispatch order, and measured it does not (config 4: 0.134 ms as numbered, 0.145 ms heaviest first + 11 us for k_group_order)
-    if ((mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mlab || al64) && lv_ppll_prism_source(ctx) && !ctx->opt.ppllPrismLbvhWalk &&
-        !ctx->groupOrderSorted) {
-        T.groupOrder = nullptr;
-        T.groupCost = nullptr;
-        ctx->groupOrder[0].active = false;
-    }
-    if ((rc = lv_group_order_sort(ctx))) return rc; // (queued by the RTAO pass already when that ran)
-
-    uint32_t* out = (uint32_t*)outDevice;
-    if (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER && ctx->opt.numAccumulatedFrames > 1u) {
+// A mode-11 frame's colour pass: the accumulation image of progressive frames, then use_mlat's single pass (lv_mlat.hip) or ONE launch
+// of k_render_rt -- on the hits k_primary_pair traced in the RTAO pass (firstHitsTraced; maxPixels of them per slot of ctx->firstHit),
+// or tracing its own first rays.
+static int lv_rt_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
+                       LvDevCounters* dc, bool firstHitsTraced, uint64_t maxPixels) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (ctx->opt.numAccumulatedFrames > 1u) {
         // the running mean lives in a full-viewport rgba8 image: a resize restarts it (onResolutionChanged resets
         // accumulatedFramesCounter, VulkanRayTracer.cpp:119-129)
         if (U.frameNumber != 0u && (ctx->accumW != ctx->width || ctx->accumH != ctx->height))
@@ -5001,20 +4919,16 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         ctx->accumH = ctx->height;
         S.accum = (uint32_t*)ctx->accum.ptr;
     }
-    if (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER) {
-        // geometry_mode (VulkanRayTracer.cpp:226-250): analytic capsules, or the triangle tubes with their own LBVH
-        const bool tri = ctx->opt.rtTriangleMesh;
-        if (ctx->opt.useMlat) { // use_mlat: single-pass approximate transparency (lv_mlat.hip)
-            LvSceneDev SM = tri ? sceneDevTriangles(ctx) : S;
-            SM.accum = S.accum;
-            if (U.lssGeometry) SM.literalIntersection = 0u; // the hardware primitive has no intersection shader
-            if (tri && (rc = lv_prepare_overflow(ctx, SM, "MLAT pass", gridTiles, LV_STACK_LDS, true))) return rc;
-            if ((rc = lv_mlat_render(ctx, U, SM, T, gridTiles, out, dc, tri))) return rc;
-        } else {
-        LvSceneDev SC = tri ? sceneDevTriangles(ctx) : S;
-        SC.accum = S.accum;
-        if (U.lssGeometry) SC.literalIntersection = 0u; // the hardware primitive has no intersection shader
-        if (tri && (rc = lv_prepare_overflow(ctx, SC, "colour pass (triangle mesh)", gridTiles, LV_STACK_LDS, true))) return rc;
+    // geometry_mode (VulkanRayTracer.cpp:226-250): analytic capsules, or the triangle tubes with their own LBVH
+    const bool tri = ctx->opt.rtTriangleMesh;
+    LvSceneDev SC = tri ? sceneDevTriangles(ctx) : S;
+    SC.accum = S.accum;
+    if (U.lssGeometry) SC.literalIntersection = 0u; // the hardware primitive has no intersection shader
+    if (ctx->opt.useMlat) { // use_mlat: single-pass approximate transparency (lv_mlat.hip)
+        if (tri && (rc = lv_prepare_overflow(ctx, SC, "MLAT pass", gridTiles, LV_STACK_LDS, true))) return rc;
+        return lv_mlat_render(ctx, U, SC, T, gridTiles, out, dc, tri);
+    }
+    if (tri && (rc = lv_prepare_overflow(ctx, SC, "colour pass (triangle mesh)", gridTiles, LV_STACK_LDS, true))) return rc;
 #define LV_LAUNCH_RT(ST, PR, BA) \
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_RENDER_RT, (k_render_rt<ST, PR, BA><<<gridTiles, LV_BLOCK, 0, st>>>(U, SC, T, out, dc)))
 #define LV_LAUNCH_RT_PRE(ST, BA) \
@@ -5039,78 +4953,70 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         else if (U.useBands) LV_LAUNCH_RT(ST, LV_PRIM_CAPSULE, LV_SHADE_BANDS);  \
         else LV_LAUNCH_RT(ST, LV_PRIM_CAPSULE, LV_SHADE_PLAIN);                  \
     } while (0)
-        // shading_numerics = fast: the capsule colour pass of plain flow lines (lighting through the approximate operations, FAST = 1)
-        const bool fastPlain = ctx->opt.fastShading && !stats && !tri && !U.useHelicityBands && !U.useEllipticTubes && !U.useBands;
-        if (stats) LV_LAUNCH_RT2(true); else LV_LAUNCH_RT2(false);
+    // shading_numerics = fast: the capsule colour pass of plain flow lines (lighting through the approximate operations, FAST = 1)
+    const bool fastPlain = ctx->opt.fastShading && !stats && !tri && !U.useHelicityBands && !U.useEllipticTubes && !U.useBands;
+    if (stats) LV_LAUNCH_RT2(true); else LV_LAUNCH_RT2(false);
 #undef LV_LAUNCH_RT2
 #undef LV_LAUNCH_RT_PRE
 #undef LV_LAUNCH_RT
+    return LV_OK;
+}
+
+// The front end of a frame with a fragment pool (modes 2, 3 and pooled 6) on pools of poolSlots entries: the pools reserved, clear(),
+// then gather() -- the fragments of the rasterised programmable-pull prism (the reference's geometry, default) or capsule entry hits.
+// Modes 3 and 6 drop no fragment and never return a silently wrong frame: they read back what the rasteriser reserved and whether a
+// pixel's 16-bit record count saturated -- one host synchronisation per frame.  need: the slots the frame asked for (mode 2 drops
+// what does not fit: 0).
+static int lv_pool_front(lv_ctx* ctx, const LvUniforms& U, const LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats,
+                         LvDevCounters* dc, int mode, uint32_t poolSlots, uint32_t& need) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    const bool mboit = mode == LV_RENDERING_MODE_MBOIT, mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
+    const char* const poolName = lv_prism_mode_name(mode);
+    const bool prismSource = lv_ppll_prism_source(ctx);
+    const uint32_t numSlices = prismSource ? 1u : LV_PPLL_SLICES; // (the prism's coverage kernel has no depth: one slice)
+    // ppll_prism_rasteriser: "segments" (default) = one lane per segment over its screen rectangle, "lbvh" = the all-hits walk of
+    // the viewing rays (k_ppll_gather<LV_PRIM_PRISM>); same coverage test, same fragments
+    const bool segmentRaster = prismSource && !ctx->opt.ppllPrismLbvhWalk;
+    const uint32_t rasterGrid = uint32_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU;
+    need = 0u;
+    // (mode 6: 16-B colours + 4-B view depths per entry)
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(poolSlots) * (mboit ? 20 : 12))))
+        return mlab ? lv_fail(ctx, LV_E_CAPACITY, "%s: cannot allocate a fragment pool of %u entries", poolName, poolSlots) : rc;
+    // raster_prism: the coverage kernel writes 12-B records {pixel, leaf | triangle, rank} into a pool of their own; ppllNodes then
+    // holds the fragment array (8-B {colour, depth} entries, one contiguous run per pixel -- 12-B {colour, window depth, key} in
+    // mode 3), ppllStart the runs' offsets
+    if (prismSource && (rc = lv_buf_reserve(ctx, ctx->prismRecords, size_t(poolSlots) * 12)))
+        return mlab ? lv_fail(ctx, LV_E_CAPACITY, "%s: cannot allocate a record pool of %u entries", poolName, poolSlots) : rc;
+    ctx->ppllArrays = prismSource;
+    uint32_t* gatherPool = prismSource ? (uint32_t*)ctx->prismRecords.ptr : (uint32_t*)ctx->ppllNodes.ptr;
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+    ctx->ppllPoolNodes = poolSlots;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    const bool allRequested = segmentRaster && ctx->tilesCoverViewport;
+    lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    if (segmentRaster) {
+        // the segment rasteriser (k_ppll_raster_prism): requested pixels marked, then one lane per segment
+#define LV_LAUNCH_RASTER(ST, NT)                                                                                              \
+    k_ppll_raster_prism<ST, NT><<<rasterGrid, LV_BLOCK, 0, st>>>(                                                             \
+            U, S, gatherPool, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots,                \
+            allRequested ? 1u : 0u, leafList)
+        uint32_t* leafList;
+        if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
+        if (S.numSegs != 0) {
+            if (S.prism.n == 6u) { if (stats) LV_LAUNCH_RASTER(true, 6); else LV_LAUNCH_RASTER(false, 6); }
+            else { if (stats) LV_LAUNCH_RASTER(true, 0); else LV_LAUNCH_RASTER(false, 0); }
         }
-    } else if (mboit && ctx->opt.mboitStreamed) {
-        if ((rc = lv_mboit_stream_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
-    } else if (wboit) {
-        if ((rc = lv_wboit_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
-    } else if (dcMode) {
-        if ((rc = lv_dc_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
-    } else if (peel) {
-        if ((rc = lv_peel_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
-    } else if (al64) {
-        if ((rc = lv_al64_frame(ctx, U, S, T, gridTiles, stats, out, dc))) return rc;
+        if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) {
+            LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
+            ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
+        }
+#undef LV_LAUNCH_RASTER
     } else {
-        // reallocateFragmentBuffer, PerPixelLinkedListLineRenderer.cpp:251-357
-        // gather(): fragments of the rasterised programmable-pull prism (the reference's geometry, default) or capsule entry hits
-        const bool prismSource = lv_ppll_prism_source(ctx);
-        if (prismSource && ctx->opt.useRibbons && ctx->opt.helicityBands)
-            return lv_fail(ctx, LV_E_INVALID, "ppll_fragment_source = raster_prism: band data with rotating helicity bands has no prism "
-                                              "fragment stage (use auto or capsule_entry)");
-        if (prismSource && ctx->opt.useRibbons && ctx->opt.ppllPrismLbvhWalk)
-            return lv_fail(ctx, LV_E_INVALID, "ppll_prism_rasteriser = lbvh: the segment boxes do not enclose the band prism "
-                                              "(band_width / 2); band data uses the segment rasteriser");
-        if (prismSource) lv_fill_prism(ctx, U, S.prism);
-        const uint32_t numSlices = prismSource ? 1u : LV_PPLL_SLICES; // (the prism's coverage kernel has no depth: one slice)
-        // ppll_prism_rasteriser: "segments" (default) = one lane per segment over its screen rectangle, "lbvh" = the all-hits walk of
-        // the viewing rays (k_ppll_gather<LV_PRIM_PRISM>); same coverage test, same fragments
-        const bool segmentRaster = prismSource && !ctx->opt.ppllPrismLbvhWalk;
-        const uint32_t rasterGrid = uint32_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU;
-        if (uint64_t(gridTiles) * numSlices > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-        // physical pool = the reference's linkedListSize + the tail every wave of the gather may leave unused in its last
-        // chunk of node slots (k_ppll_gather / k_ppll_raster_prism), so that the effective capacity is never below the reference's
-        const uint64_t chunkSlack = segmentRaster ? uint64_t(rasterGrid) * (LV_BLOCK / LV_WAVE) * LV_PRISM_RASTER_CHUNK
-                                                  : uint64_t(gridTiles) * numSlices * (LV_BLOCK / LV_WAVE) * LV_PPLL_CHUNK;
-        uint64_t poolSlots64 = uint64_t(U.ppllLinkedListSize) + chunkSlack;
-        // MLAB drops no fragment (the reference's MLAB has no pool): it starts from the linkedListSize of the options (no chunk slack:
-        // a frame that needs more slots grows the pool below) or from what the largest mode-3 frame so far needed
-        if (mlab) poolSlots64 = std::max<uint64_t>(U.ppllLinkedListSize, ctx->mlabPoolSlots);
-        if (poolSlots64 > 0xFFFFFFF0ull) poolSlots64 = 0xFFFFFFF0ull; // node indices are 32 bit
-        uint32_t poolSlots = uint32_t(poolSlots64);
-        bool mlabGrown = false;
-        // a regrown mode-3 frame runs its front end twice: the statistics it adds (rays, nodes, prims, hits; k_ppll_clear resets the
-        // fragment counters) are restored from this copy before the second run.  (The per-kernel timers keep both runs' launches.)
-        const bool mlabStatsSnap = mlab && stats;
-        if (mlabStatsSnap) {
-            if ((rc = lv_buf_reserve(ctx, ctx->mlabStatsSnap, 4 * sizeof(unsigned long long)))) return rc;
-            LV_HIP(ctx, hipMemcpyAsync(ctx->mlabStatsSnap.ptr, &dc->rays, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-        }
-    mlab_regrow:   // (mode 3: the rasteriser needed more record slots than the pool held -- grown, and the front end runs again)
-        // (mode 6: 16-B colours + 4-B view depths per entry)
-        if ((rc = lv_buf_reserve(ctx, ctx->ppllNodes, size_t(poolSlots) * (mboit ? 20 : 12))))
-            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "%s: cannot allocate a fragment pool of %u entries", poolName, poolSlots) : rc;
-        // raster_prism: the coverage kernel writes 12-B records {pixel, leaf | triangle, rank} into a pool of their own; ppllNodes then
-        // holds the fragment array (8-B {colour, depth} entries, one contiguous run per pixel -- 12-B {colour, window depth, key} in
-        // mode 3), ppllStart the runs' offsets
-        if (prismSource && (rc = lv_buf_reserve(ctx, ctx->prismRecords, size_t(poolSlots) * 12)))
-            return mlab ? lv_fail(ctx, LV_E_CAPACITY, "%s: cannot allocate a record pool of %u entries", poolName, poolSlots) : rc;
-        ctx->ppllArrays = prismSource;
-        uint32_t* gatherPool = prismSource ? (uint32_t*)ctx->prismRecords.ptr : (uint32_t*)ctx->ppllNodes.ptr;
-        const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4; // cleared as whole uint4s (k_ppll_clear)
-        if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
-        if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
-        ctx->ppllPoolNodes = poolSlots;
-        ctx->ppllPaddedW = U.ppllPaddedW;
-        ctx->ppllPaddedH = U.ppllPaddedH;
-        const bool allRequested = segmentRaster && ctx->tilesCoverViewport;
-        lv_ppll_clear(ctx, U, padded4, allRequested, stats, dc);
-        if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
 #define LV_LAUNCH_GATHER(ST, PR, BA)                                                                             \
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_GATHER, (k_ppll_gather<ST, PR, BA><<<gridTiles * numSlices, LV_BLOCK, 0, st>>>( \
             U, S, T, gatherPool, (uint32_t*)ctx->ppllStart.ptr,                                                  \
@@ -5123,74 +5029,94 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         else if (U.useBands) LV_LAUNCH_GATHER(ST, LV_PRIM_CAPSULE, LV_SHADE_BANDS);    \
         else LV_LAUNCH_GATHER(ST, LV_PRIM_CAPSULE, LV_SHADE_PLAIN);                    \
     } while (0)
-        if (segmentRaster) {
-            // the segment rasteriser (k_ppll_raster_prism): requested pixels marked, then one lane per segment
-#define LV_LAUNCH_RASTER(ST, NT)                                                                                              \
-    k_ppll_raster_prism<ST, NT><<<rasterGrid, LV_BLOCK, 0, st>>>(                                                             \
-            U, S, gatherPool, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc, poolSlots,                \
-            allRequested ? 1u : 0u, leafList)
-            const bool rasterTimed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) != 0u;
-            uint32_t* leafList;
-            if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
-            if (S.numSegs != 0) {
-                if (S.prism.n == 6u) { if (stats) LV_LAUNCH_RASTER(true, 6); else LV_LAUNCH_RASTER(false, 6); }
-                else { if (stats) LV_LAUNCH_RASTER(true, 0); else LV_LAUNCH_RASTER(false, 0); }
-            }
-            if (rasterTimed) {
-                LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 1), st));
-                ctx->kernelLaunches[LV_KERNEL_PPLL_RASTER]++;
-            }
-#undef LV_LAUNCH_RASTER
-        } else {
         if (stats) LV_LAUNCH_GATHER2(true); else LV_LAUNCH_GATHER2(false);
-        }
 #undef LV_LAUNCH_GATHER2
 #undef LV_LAUNCH_GATHER
-        if (mlab) {
-            // mode 3 drops no fragment and never returns a silently wrong frame: read back what the rasteriser reserved and whether a
-            // pixel's 16-bit record count saturated -- one host synchronisation per mode-3 frame -- and grow the pool and run the
-            // front end again when it held too few slots
-            k_mlab_check_counts<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>((const uint4*)ctx->ppllCount.ptr, padded4, dc);
-            if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
-            volatile uint32_t* pin = ctx->pinned + 14;   // (words 14, 15 of the pinned block)
-            LV_HIP(ctx, hipMemcpyAsync((void*)pin, &dc->fragAlloc, 4, hipMemcpyDeviceToHost, st));
-            LV_HIP(ctx, hipMemcpyAsync((void*)(pin + 1), &dc->mlabSaturated, 4, hipMemcpyDeviceToHost, st));
-            const bool readBox = mboit && !ctx->mboitBoxValid;
-            if (readBox && (rc = lv_mboit_box_queue(ctx, S, dc))) return rc;   // read back with the same synchronisation
-            LV_HIP(ctx, hipStreamSynchronize(st));
-            if (readBox) lv_mboit_box_adopt(ctx);
-            const uint32_t need = pin[0], saturated = pin[1];
-            if (saturated)
-                return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than 65534 fragments (16-bit per-pixel count)", poolName);
-            if (need > poolSlots) {
-                const uint64_t grown = uint64_t(need) + chunkSlack;
-                if (mlabGrown || grown > 0xFFFFFFF0ull)
-                    return lv_fail(ctx, LV_E_CAPACITY, "%s: the frame needs %llu fragment slots (pool: %u)", poolName,
-                                   (unsigned long long)grown, poolSlots);
-                poolSlots = uint32_t(grown);
-                ctx->mlabPoolSlots = poolSlots;
-                mlabGrown = true;
-                if (mlabStatsSnap)
-                    LV_HIP(ctx, hipMemcpyAsync(&dc->rays, ctx->mlabStatsSnap.ptr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-                goto mlab_regrow;
-            }
-        }
-        uint32_t* blockBase = nullptr;
-        if (prismSource) {
-            // per-pixel counts -> offsets of the pixels' runs + the list of the pixels with more records than the sort arrays hold
-            const uint32_t numAddr = uint32_t(padded4 * 4);
-            const uint32_t scanBlocks = (numAddr + LV_SCAN_ITEMS - 1u) / LV_SCAN_ITEMS;
-            if ((rc = lv_buf_reserve(ctx, ctx->ppllOverflow, padded4 * 16))) return rc;
-            if ((rc = lv_buf_reserve(ctx, ctx->scanTemp, (2 * size_t(scanBlocks) + 1) * 4))) return rc;
-            uint32_t* blockTotals = (uint32_t*)ctx->scanTemp.ptr;
-            blockBase = blockTotals + scanBlocks;
-            // (mode 3 keeps every fragment: no pixel goes on the list)
-            k_ppll_scan<<<scanBlocks, LV_BLOCK, 0, st>>>((const uint32_t*)ctx->ppllCount.ptr, (uint32_t*)ctx->ppllStart.ptr, numAddr,
-                                                        blockTotals, mlab ? 0xFFFFFFFFu : U.ppllMaxNumFrags,
-                                                        (uint32_t*)ctx->ppllOverflow.ptr, dc);
-            k_ppll_scan_bases<<<1, LV_BLOCK, 0, st>>>(blockTotals, blockBase, scanBlocks);
-            ctx->ppllScanBlocks = scanBlocks;
-            const uint32_t shadeGrid = uint32_t(ctx->numCUs) * LV_PRISM_SHADE_BLOCKS_PER_CU;
+    }
+    if (!mlab) return LV_OK;
+    k_mlab_check_counts<<<uint32_t((padded4 + LV_BLOCK - 1) / LV_BLOCK), LV_BLOCK, 0, st>>>((const uint4*)ctx->ppllCount.ptr, padded4, dc);
+    if (!ctx->pinned) LV_HIP(ctx, hipHostMalloc((void**)&ctx->pinned, 64, hipHostMallocDefault));
+    volatile uint32_t* pin = ctx->pinned + 14;   // (words 14, 15 of the pinned block)
+    LV_HIP(ctx, hipMemcpyAsync((void*)pin, &dc->fragAlloc, 4, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipMemcpyAsync((void*)(pin + 1), &dc->mlabSaturated, 4, hipMemcpyDeviceToHost, st));
+    const bool readBox = mboit && !ctx->mboitBoxValid;
+    if (readBox && (rc = lv_mboit_box_queue(ctx, S, dc))) return rc;   // read back with the same synchronisation
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    if (readBox) lv_mboit_box_adopt(ctx);
+    need = pin[0];
+    if (pin[1])
+        return lv_fail(ctx, LV_E_CAPACITY, "%s: a pixel is covered by more than 65534 fragments (16-bit per-pixel count)", poolName);
+    return LV_OK;
+}
+
+// A mode-2, mode-3 or pooled mode-6 frame (reallocateFragmentBuffer, PerPixelLinkedListLineRenderer.cpp:251-357): the front end --
+// again, ONCE, on a grown pool when a mode-3 or mode-6 frame needed more slots than the pool held --, then for the prism's records the
+// scan of the per-pixel counts, the fragment stage and mode 2's selection of the nearest fragments, then resolve().
+static int lv_pool_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool stats, uint32_t* out,
+                         LvDevCounters* dc, int mode) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    // modes 3 and 6 share the front end and the pool that drops nothing (`mlab`); `mboit` picks the entry format and the resolve
+    const bool mboit = mode == LV_RENDERING_MODE_MBOIT, mlab = mode == LV_RENDERING_MODE_MLAB || mboit;
+    const bool prismSource = lv_ppll_prism_source(ctx);
+    if (prismSource && ctx->opt.useRibbons && ctx->opt.helicityBands)
+        return lv_fail(ctx, LV_E_INVALID, "ppll_fragment_source = raster_prism: band data with rotating helicity bands has no prism "
+                                          "fragment stage (use auto or capsule_entry)");
+    if (prismSource && ctx->opt.useRibbons && ctx->opt.ppllPrismLbvhWalk)
+        return lv_fail(ctx, LV_E_INVALID, "ppll_prism_rasteriser = lbvh: the segment boxes do not enclose the band prism "
+                                          "(band_width / 2); band data uses the segment rasteriser");
+    if (prismSource) lv_fill_prism(ctx, U, S.prism);
+    const uint32_t numSlices = prismSource ? 1u : LV_PPLL_SLICES;   // (as lv_pool_front launches the gather)
+    if (uint64_t(gridTiles) * numSlices > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    // physical pool = the reference's linkedListSize + the tail every wave of the gather may leave unused in its last
+    // chunk of node slots (k_ppll_gather / k_ppll_raster_prism), so that the effective capacity is never below the reference's
+    const bool segmentRaster = prismSource && !ctx->opt.ppllPrismLbvhWalk;
+    const uint64_t chunkSlack = segmentRaster ? uint64_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU * (LV_BLOCK / LV_WAVE) * LV_PRISM_RASTER_CHUNK
+                                              : uint64_t(gridTiles) * numSlices * (LV_BLOCK / LV_WAVE) * LV_PPLL_CHUNK;
+    uint64_t poolSlots64 = uint64_t(U.ppllLinkedListSize) + chunkSlack;
+    // MLAB drops no fragment (the reference's MLAB has no pool): it starts from the linkedListSize of the options (no chunk slack:
+    // a frame that needs more slots grows the pool below) or from what the largest mode-3 frame so far needed
+    if (mlab) poolSlots64 = std::max<uint64_t>(U.ppllLinkedListSize, ctx->mlabPoolSlots);
+    if (poolSlots64 > 0xFFFFFFF0ull) poolSlots64 = 0xFFFFFFF0ull; // node indices are 32 bit
+    uint32_t poolSlots = uint32_t(poolSlots64);
+    // a regrown mode-3 frame runs its front end twice: the statistics it adds (rays, nodes, prims, hits; k_ppll_clear resets the
+    // fragment counters) are restored from this copy before the second run.  (The per-kernel timers keep both runs' launches.)
+    const bool mlabStatsSnap = mlab && stats;
+    if (mlabStatsSnap) {
+        if ((rc = lv_buf_reserve(ctx, ctx->mlabStatsSnap, 4 * sizeof(unsigned long long)))) return rc;
+        LV_HIP(ctx, hipMemcpyAsync(ctx->mlabStatsSnap.ptr, &dc->rays, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    }
+    for (int round = 0;; round++) {
+        uint32_t need;
+        if ((rc = lv_pool_front(ctx, U, S, T, gridTiles, stats, dc, mode, poolSlots, need))) return rc;
+        if (need <= poolSlots) break;
+        // (modes 3 and 6: the rasteriser needed more record slots than the pool held -- grown, and the front end runs again)
+        const uint64_t grown = uint64_t(need) + chunkSlack;
+        if (round || grown > 0xFFFFFFF0ull)
+            return lv_fail(ctx, LV_E_CAPACITY, "%s: the frame needs %llu fragment slots (pool: %u)", lv_prism_mode_name(mode),
+                           (unsigned long long)grown, poolSlots);
+        poolSlots = uint32_t(grown);
+        ctx->mlabPoolSlots = poolSlots;
+        if (mlabStatsSnap)
+            LV_HIP(ctx, hipMemcpyAsync(&dc->rays, ctx->mlabStatsSnap.ptr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    }
+    uint32_t* blockBase = nullptr;
+    if (prismSource) {
+        // per-pixel counts -> offsets of the pixels' runs + the list of the pixels with more records than the sort arrays hold
+        const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4;   // (whole uint4s, as lv_pool_front reserved them)
+        const uint32_t numAddr = uint32_t(padded4 * 4);
+        const uint32_t scanBlocks = (numAddr + LV_SCAN_ITEMS - 1u) / LV_SCAN_ITEMS;
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllOverflow, padded4 * 16))) return rc;
+        if ((rc = lv_buf_reserve(ctx, ctx->scanTemp, (2 * size_t(scanBlocks) + 1) * 4))) return rc;
+        uint32_t* blockTotals = (uint32_t*)ctx->scanTemp.ptr;
+        blockBase = blockTotals + scanBlocks;
+        // (mode 3 keeps every fragment: no pixel goes on the list)
+        k_ppll_scan<<<scanBlocks, LV_BLOCK, 0, st>>>((const uint32_t*)ctx->ppllCount.ptr, (uint32_t*)ctx->ppllStart.ptr, numAddr,
+                                                    blockTotals, mlab ? 0xFFFFFFFFu : U.ppllMaxNumFrags,
+                                                    (uint32_t*)ctx->ppllOverflow.ptr, dc);
+        k_ppll_scan_bases<<<1, LV_BLOCK, 0, st>>>(blockTotals, blockBase, scanBlocks);
+        ctx->ppllScanBlocks = scanBlocks;
+        const uint32_t shadeGrid = uint32_t(ctx->numCUs) * LV_PRISM_SHADE_BLOCKS_PER_CU;
 #define LV_LAUNCH_SHADE(ST, BA, FA, ML)                                                                                         \
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_SHADE, (k_ppll_shade_prism<ST, BA, FA, ML><<<shadeGrid, LV_BLOCK, 0, st>>>(             \
             U, S, (const uint32_t*)ctx->prismRecords.ptr, (uint2*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,      \
@@ -5203,37 +5129,38 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         else LV_LAUNCH_SHADE(ST, LV_SHADE_PLAIN, 0, ML);                             \
     } while (0)
 #define LV_LAUNCH_SHADE3(ML) do { if (stats) LV_LAUNCH_SHADE2(true, ML); else LV_LAUNCH_SHADE2(false, ML); } while (0)
-            const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);
-            if (mboit) LV_LAUNCH_SHADE3(LV_ENTRY_MBOIT);
-            else if (mlab) LV_LAUNCH_SHADE3(LV_ENTRY_MLAB);
-            else LV_LAUNCH_SHADE3(LV_ENTRY_PPLL);
+        const bool fastShade = lv_prism_fast_shade(ctx, U, S, stats);
+        if (mboit) LV_LAUNCH_SHADE3(LV_ENTRY_MBOIT);
+        else if (mlab) LV_LAUNCH_SHADE3(LV_ENTRY_MLAB);
+        else LV_LAUNCH_SHADE3(LV_ENTRY_PPLL);
 #undef LV_LAUNCH_SHADE3
 #undef LV_LAUNCH_SHADE2
 #undef LV_LAUNCH_SHADE
-            // the listed pixels: their nearest ppllMaxNumFrags fragments to the front of the run
-            if (!mlab) k_ppll_select_nearest<<<uint32_t(ctx->numCUs) * 16u, LV_WAVE, 0, st>>>(
-                    U, (uint2*)ctx->ppllNodes.ptr, (uint2*)ctx->prismRecords.ptr, (const uint32_t*)ctx->ppllStart.ptr, blockBase,
-                    (const uint32_t*)ctx->ppllCount.ptr, (const uint32_t*)ctx->ppllOverflow.ptr, dc);
+        // the listed pixels: their nearest ppllMaxNumFrags fragments to the front of the run
+        if (!mlab) k_ppll_select_nearest<<<uint32_t(ctx->numCUs) * 16u, LV_WAVE, 0, st>>>(
+                U, (uint2*)ctx->ppllNodes.ptr, (uint2*)ctx->prismRecords.ptr, (const uint32_t*)ctx->ppllStart.ptr, blockBase,
+                (const uint32_t*)ctx->ppllCount.ptr, (const uint32_t*)ctx->ppllOverflow.ptr, dc);
+    }
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
+    // resolve()
+    if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
+    if (mlab) {
+        // the fold: k_mlab_resolve, then the pixels with long runs (k_mlab_resolve_long); both in the LV_KERNEL_PPLL_RESOLVE slot
+        const bool timed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RESOLVE) & 1u) != 0u;
+        if (timed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 0), st));
+        if (mboit) {
+            const LvMboitParams M = lv_mboit_params(ctx, U, ctx->mboitBoxOrd, stats);
+            if ((rc = lv_mboit_resolve(ctx, U, T, M, numGroups, poolSlots, blockBase, out, nullptr, dc))) return rc;
+        } else if ((rc = lv_mlab_fold(ctx, U, T, numGroups, blockBase, out, (uint2*)ctx->prismRecords.ptr, dc))) return rc;
+        if (timed) {
+            LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 1), st));
+            ctx->kernelLaunches[LV_KERNEL_PPLL_RESOLVE]++;
         }
-        if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[13], st));
-        // resolve()
-        const uint32_t* prismCount = prismSource ? (const uint32_t*)ctx->ppllCount.ptr : nullptr; // (kept fragments per pixel -> max depth complexity)
-        if (lv_tiles_cells(T) > 0xFFFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-        const uint32_t numGroups = uint32_t(lv_tiles_cells(T));
-        if (mlab) {
-            // the fold: k_mlab_resolve, then the pixels with long runs (k_mlab_resolve_long); both in the LV_KERNEL_PPLL_RESOLVE slot
-            const bool timed = ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RESOLVE) & 1u) != 0u;
-            if (timed) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 0), st));
-            if (mboit) {
-                const LvMboitParams M = lv_mboit_params(ctx, U, ctx->mboitBoxOrd, stats);
-                if ((rc = lv_mboit_resolve(ctx, U, T, M, numGroups, poolSlots, blockBase, out, nullptr, dc))) return rc;
-            } else if ((rc = lv_mlab_fold(ctx, U, T, numGroups, blockBase, out, (uint2*)ctx->prismRecords.ptr, dc))) return rc;
-            if (timed) {
-                LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RESOLVE, 1), st));
-                ctx->kernelLaunches[LV_KERNEL_PPLL_RESOLVE]++;
-            }
-        } else {
-        const size_t ldsBytes = size_t(U.ppllMaxNumFrags) * LV_WAVE * 8;
+        return LV_OK;
+    }
+    const uint32_t* prismCount = prismSource ? (const uint32_t*)ctx->ppllCount.ptr : nullptr; // (kept fragments per pixel -> max depth complexity)
+    const size_t ldsBytes = size_t(U.ppllMaxNumFrags) * LV_WAVE * 8;
 #define LV_LAUNCH_RESOLVE(LDS, PQ, GRID, BYTES, SCRATCH)                                                                        \
     do {                                                                                                                       \
         if (prismSource)                                                                                                       \
@@ -5245,18 +5172,142 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
                     U, T, (const uint32_t*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr, out, SCRATCH, numGroups,   \
                     nullptr, dc, nullptr)));                                                                                   \
     } while (0)
-        if (ldsBytes <= LV_RESOLVE_LDS_MAX) {
-            if (U.ppllSortingMode == 0u) LV_LAUNCH_RESOLVE(true, true, numGroups, ldsBytes, nullptr);
-            else LV_LAUNCH_RESOLVE(true, false, numGroups, ldsBytes, nullptr);
-        } else {
-            const uint32_t grid = numGroups < LV_RESOLVE_SLAB_GRID ? numGroups : LV_RESOLVE_SLAB_GRID;
-            if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, size_t(grid) * ldsBytes))) return rc;
-            if (U.ppllSortingMode == 0u) LV_LAUNCH_RESOLVE(false, true, grid, 0, (uint32_t*)ctx->ppllScratch.ptr);
-            else LV_LAUNCH_RESOLVE(false, false, grid, 0, (uint32_t*)ctx->ppllScratch.ptr);
-        }
-#undef LV_LAUNCH_RESOLVE
-        }
+    if (ldsBytes <= LV_RESOLVE_LDS_MAX) {
+        if (U.ppllSortingMode == 0u) LV_LAUNCH_RESOLVE(true, true, numGroups, ldsBytes, nullptr);
+        else LV_LAUNCH_RESOLVE(true, false, numGroups, ldsBytes, nullptr);
+    } else {
+        const uint32_t grid = numGroups < LV_RESOLVE_SLAB_GRID ? numGroups : LV_RESOLVE_SLAB_GRID;
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllScratch, size_t(grid) * ldsBytes))) return rc;
+        if (U.ppllSortingMode == 0u) LV_LAUNCH_RESOLVE(false, true, grid, 0, (uint32_t*)ctx->ppllScratch.ptr);
+        else LV_LAUNCH_RESOLVE(false, false, grid, 0, (uint32_t*)ctx->ppllScratch.ptr);
     }
+#undef LV_LAUNCH_RESOLVE
+    return LV_OK;
+}
+
+// A frame: the checks, what the frame reads brought up to date (line points, acceleration structures, uniforms, tiles), the depth
+// range, the RTAO pass or the prebaked table, then the mode's frame function between the phase marks.
+int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW,
+                    uint32_t tileH, void* outDevice) {
+    int rc;
+    if ((rc = lv_frame_check(ctx, mode))) return rc;
+    if (numTiles == 0 || tileW == 0 || tileH == 0) return lv_fail(ctx, LV_E_INVALID, "empty tile list");
+    const bool rayTracer = mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER;
+    if ((rc = lv_ensure_line_points(ctx))) return rc;   // lv_set_trajectories' records follow the band / helicity switches
+    if (!ctx->accelValid || ctx->accelLineWidth != lv_accel_width(ctx))
+        if ((rc = lv_bvh_build(ctx))) return rc;
+    const bool needTriangles = (ctx->opt.useAmbientOcclusion && ctx->opt.aoPrebaked) ||
+                               (ctx->opt.useAmbientOcclusion && lv_ao_triangle_tubes(ctx)) || (ctx->opt.rtTriangleMesh && rayTracer);
+    if (needTriangles) {
+        if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
+        if (!ctx->triMeshSet)
+            return lv_fail(ctx, LV_E_STATE, "rtao_geometry = triangle_tubes / geometry_mode = Triangle Mesh / the RTAO "
+                                            "prebaker need lv_set_tube_triangle_mesh");
+        if (!ctx->triAccelValid || ctx->triAccelLineWidth != ctx->opt.lineWidth)
+            if ((rc = lv_bvh_build_triangles(ctx))) return rc;
+    }
+
+    hipStream_t st = ctx->stream;
+    LvUniforms U;
+    lv_fill_uniforms(ctx, U);
+    // AO lookup of the colour pass: literal projection + bilinear sample for jittered primary rays (ray tracer only; the PPLL
+    // fragments sit at pixel centres), the pixel's own texel otherwise
+    U.aoProjectLookup = (rayTracer && U.useJitteredRays && U.useAmbientOcclusion && !U.aoPrebaked) ? 1u : 0u;
+    if ((rc = lv_buf_reserve(ctx, ctx->counters, sizeof(LvDevCounters)))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->depthMinMax, 16))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, size_t(numTiles) * 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->ao, size_t(ctx->width) * ctx->height * 4))) return rc;
+    if (ctx->aoW != ctx->width || ctx->aoH != ctx->height) ctx->aoResult = nullptr; // images of another viewport size
+    ctx->aoW = ctx->width;
+    ctx->aoH = ctx->height;
+    LvDevCounters* dc = (LvDevCounters*)ctx->counters.ptr;
+
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[2], st));
+    if ((rc = lv_frame_tiles(ctx, tilesXYHost, numTiles, tileW, tileH))) return rc;
+    LV_HIP(ctx, hipMemsetAsync(dc, 0, sizeof(LvDevCounters), st));
+
+    LvTiles T = lv_tiles((const uint32_t*)ctx->tilesDev.ptr, numTiles, tileW, tileH);
+    if (lv_tiles_blocks(T) > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
+    ctx->groupOrderSorted = false;
+    ctx->groupOrder[1].active = false;
+    if ((rc = lv_group_order_prepare(ctx, T, 0))) return rc;
+    const uint32_t gridTiles = uint32_t(lv_tiles_grid(T));
+    const uint64_t maxPixels = lv_tiles_pixels(T);
+    const bool stats = ctx->opt.collectStats;
+    // overlap_primary_passes (default on): the colour pass' first-hit trace rides along with the RTAO primaries (k_primary_pair) and the
+    // colour kernel after the RTAO pass only shades.  Where it applies: the ray tracer on the analytic capsules, one sample per pixel
+    // (the first ray of a pixel is then its only first ray), the per-frame RTAO pass on the caller's tiles (SVGF covers the viewport).
+    // "auto": while the colour pass' tile kernel is at most four rounds of workgroups (16 per CU; half a 1920 x 1080 frame) -- a frame
+    // that fills the GPU several times over is throughput-bound in both passes and only pays the second shading (measured, EXPERIMENTS 13.2)
+    const bool pairWanted = ctx->opt.overlapPrimaryPasses == 1 || (ctx->opt.overlapPrimaryPasses == 2 && gridTiles <= 16u * uint32_t(ctx->numCUs));
+    const bool pairPrimaries = pairWanted && rayTracer && U.useAmbientOcclusion &&
+                               !U.aoPrebaked && !ctx->opt.useMlat && !ctx->opt.rtTriangleMesh && !U.useEllipticTubes &&
+                               !ctx->opt.svgfEnabled && (U.useJitteredRays ? U.numSamplesPerFrame : 1u) == 1u && ctx->numSegs > 0u &&
+                               (ctx->opt.numAccumulatedFrames <= 1u || ctx->opt.frameNumber < ctx->opt.aoIterations);
+    // one reservation for every launch of this frame: no view built below can move the slab
+    const size_t need = lv_frame_overflow_bytes(ctx, U, T, mode, pairPrimaries);
+    if (need && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, need))) return rc;
+    LvSceneDev S = sceneDev(ctx);
+    if ((rc = lv_prepare_overflow(ctx, S, "colour pass", gridTiles))) return rc;
+
+    // LineRenderer::renderBase: depth range, LineRenderer.cpp:248-256
+    if (U.useDepthCues) {
+        k_depth_init<<<1, 64, 0, st>>>(U, dc);
+        if (ctx->numPoints)
+            k_depth_minmax<<<nblocks(ctx->numPoints), LV_BLOCK, 0, st>>>(U, S.points, ctx->numPoints, dc);
+        k_depth_finalize<<<1, 64, 0, st>>>(dc, (float*)ctx->depthMinMax.ptr);
+    }
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[5], st));
+
+    // ambientOcclusionBaker->updateIterative(), LineRenderer.cpp:257-264
+    ctx->aoNumGroups = 0;
+    bool firstHitsTraced = false;
+    if (U.useAmbientOcclusion && !U.aoPrebaked) {
+        LvSceneDev SP = S;
+        if (pairPrimaries) {
+            if (U.lssGeometry) SP.literalIntersection = 0u; // as the colour pass (lv_rt_frame)
+            if ((rc = lv_buf_reserve(ctx, ctx->firstHit, size_t(maxPixels) * 8 * LV_PRE_HITS))) return rc;
+        }
+        if ((rc = lv_run_ao(ctx, U, S, T, pairPrimaries ? &SP : nullptr, &firstHitsTraced))) return rc;
+    }
+    if (U.aoPrebaked && !ctx->bakeValid && ctx->bakeAsyncPending) {
+        // a bake is running on the second stream (lv_bake_ao_start): adopt its table if it has finished; otherwise this frame is
+        // rendered without ambient occlusion -- "display the AO once baking has finished" (AmbientOcclusionBaker.hpp:66-70)
+        if ((rc = lv_bake_poll(ctx, false))) return rc;
+        if (!ctx->bakeValid && ctx->bakeAsyncPending) { U.aoPrebaked = 0u; U.useAmbientOcclusion = 0u; }
+    }
+    if (U.aoPrebaked) {
+        // static prebaker: view independent, (re)baked only when geometry or baking settings changed
+        if (!ctx->bakeValid) {
+            if ((rc = lv_bake_ambient_occlusion(ctx, false, true))) return rc;
+        }
+        S.bakedAo = (const float*)ctx->bakedAo.ptr;
+        S.bakedBlendingWeights = (const float*)ctx->bakeBlendingWeights.ptr;
+    }
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[7], st));
+    // The colour pass of a raster_prism frame with the segment rasteriser has no tile kernel: only its resolve pass could use the
+    // dispatch order, and measured it does not (config 4: 0.134 ms as numbered, 0.145 ms heaviest first + 11 us for k_group_order)
+    if (!rayTracer && lv_ppll_prism_source(ctx) && !ctx->opt.ppllPrismLbvhWalk && !ctx->groupOrderSorted) {
+        T.groupOrder = nullptr;
+        T.groupCost = nullptr;
+        ctx->groupOrder[0].active = false;
+    }
+    if ((rc = lv_group_order_sort(ctx))) return rc; // (queued by the RTAO pass already when that ran)
+
+    uint32_t* out = (uint32_t*)outDevice;
+    switch (mode) {
+    case LV_RENDERING_MODE_VULKAN_RAY_TRACER: rc = lv_rt_frame(ctx, U, S, T, gridTiles, stats, out, dc, firstHitsTraced, maxPixels); break;
+    case LV_RENDERING_MODE_MBOIT:
+        rc = ctx->opt.mboitStreamed ? lv_mboit_stream_frame(ctx, U, S, T, gridTiles, stats, out, dc)
+                                    : lv_pool_frame(ctx, U, S, T, gridTiles, stats, out, dc, mode);
+        break;
+    case LV_RENDERING_MODE_WBOIT: rc = lv_wboit_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
+    case LV_RENDERING_MODE_DEPTH_COMPLEXITY: rc = lv_dc_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
+    case LV_RENDERING_MODE_DEPTH_PEELING: rc = lv_peel_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
+    case LV_RENDERING_MODE_ATOMIC_LOOP_64: rc = lv_al64_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
+    default: rc = lv_pool_frame(ctx, U, S, T, gridTiles, stats, out, dc, mode); break;   // modes 2 and 3
+    }
+    if (rc) return rc;
     LV_HIP(ctx, hipGetLastError());
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[3], st));
     ctx->evFrameValid = true;
