@@ -35,6 +35,10 @@ extern "C" {
 #define LV_E_CAPACITY (-4)  /* BVH deeper than the traversal stack, buffer too small */
 
 /* RenderingMode ids, src/Renderers/RenderingModes.hpp:32-53 */
+/* Deferred shading on a visibility buffer (src/Renderers/Deferred/DeferredRenderer.cpp, "Draw Indexed" with "Precomputed Triangles"):
+ * the tube triangle mesh rasterised into one word of primitive index and depth per pixel, every pixel shaded once, opaque; see
+ * deferred_rendering_mode, lv_deferred_get_buffers and lv_deferred_shade_buffers below */
+#define LV_RENDERING_MODE_DEFERRED_SHADING 1
 #define LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST 2
 /* Multi-Layer Alpha Blending (src/Renderers/OIT/MLABRenderer.cpp) over the fragments of mode 2's rasterised prism; see
  * mlab_num_layers and lv_mlab_resolve_buffers below */
@@ -364,6 +368,34 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   ppll_pool_nodes = 0, max_depth_complexity.  Timers: LV_KERNEL_PPLL_RASTER times the count pass (with the tile marking and
  *   segment culling of a sharded frame) and then every peel pass, LV_KERNEL_PPLL_GATHER the reduction of the counts,
  *   LV_KERNEL_PPLL_SHADE the layer launches, LV_KERNEL_PPLL_RESOLVE the blit.
+ *   deferred_rendering_mode: "Draw Indexed" (the reference's default, DeferredRenderer.hpp:297) only; draw_indexed_geometry_mode:
+ *   "Precomputed Triangles" (:300) only; supersampling: 1 only.  The other values the reference knows ("Draw Indirect", "Task/Mesh
+ *   Shader", "BVH Draw Indirect", "BVH Mesh Shader"; "Programmable Pulling"; 2, 4, 8 ...) are LV_E_INVALID with a message that says the
+ *   value is not built, and the old value stays; modes other than 1 ignore the three.  Mode 1 works on the context's tube triangle
+ *   mesh (lv_set_tube_triangle_mesh, or the device tessellation of lv_set_trajectories[_with_bands], tessellated first if stale);
+ *   without one lv_render returns LV_E_STATE.  Pass 1, the visibility buffer: one 64-bit word per pixel, (bits(z) << 32) | primitive
+ *   index, empty = (bits(1.0) << 32) | 0xFFFFFFFF (depth clear 1.0, primitive clear 0xFFFFFFFF, DeferredShading.glsl:73); every
+ *   covered, kept fragment is one atomicMin: depth test LESS, the first primitive in index-buffer order among equal depths.  The
+ *   rules the reference leaves to the driver are the build's: coverage is decided on the pixel-centre viewing ray (the coverage
+ *   direction D of mode 2's prism, its basis P = cross(right, D), Q = cross(D, P); a vertex is (A . P, A . Q) with A = position -
+ *   camera, unfused; edge function E(U, V) = yU * xV - xU * yV, unfused, so E(V, U) = -E(U, V) bit for bit; covered iff E(V1, V2),
+ *   E(V2, V0), E(V0, V1) and their sum are > 0, an edge with E == 0 belonging to the triangle that runs through it with ascending
+ *   vertex index); FRONT is det = A0 . cross(A1 - A0, A2 - A0) < 0, the sense of the tessellator's outward triangles, det == 0 covers
+ *   nothing, back faces are culled iff use_capped_tubes (VisibilityBufferDrawIndexedPass.cpp:77-81) and otherwise covered with the
+ *   signs reversed; a triangle that crosses the near plane is not clipped; z = clip.z / clip.w (rows of projection * view as mode 3's
+ *   window depth) of the perspective-correct position sum(b_i V_i), b_i = E_i * (1 / sum E); kept iff 0 <= z < 1 (a z whose sign bit
+ *   is set is refused).  Pass 2 shades every pixel once (DeferredShading.glsl:90-134): an empty word is the background colour; else
+ *   the position from the pixel centre and z through the inverse matrices, (u, v, 1 - u - v) from cross-product areas,
+ *   LineAttributesBarycentric.glsl (isCap, interpolateAngle, the helicity cap continuation), computeFragmentColor with
+ *   fragmentColor.a = 1, the AO texel the pixel's own; the screen-space RTAO, depth cues, band data (use_ribbons) and rotating
+ *   helicity bands as in mode 11's "Triangle Mesh".  The prebaked AO table is not built for this pass: lv_render returns
+ *   LV_E_INVALID with it (the context stays usable).  A triangle with a vertex at clip w <= 0 is tested against every pixel of the
+ *   viewport (64 pixels per wave step).  No host synchronisation, no pool; memory: 8 bytes per pixel of the viewport padded to ppll_tile_width x
+ *   ppll_tile_height plus mode 2's 4-byte mask word.  A rank of a sharded frame walks all triangles.  Statistics: fragments = the
+ *   requested pixels with a winner.  Timers: LV_KERNEL_PPLL_RASTER times the visibility pass (with its clear and the tile marking of a
+ *   sharded frame), LV_KERNEL_PPLL_RESOLVE the shading pass.  Not built: "Programmable Pulling" geometry, the Draw Indirect, BVH and
+ *   mesh-shader modes, HZB culling, meshlets, supersampling and upscalers, motion vectors, the hull pass, stress-line data, per-rank
+ *   triangle culling for sharded frames.
  *   depth_complexity_max_colour: 0 (default) ... 1000000: numFragmentsMaxColor of rendering mode 5; anything else is LV_E_INVALID and
  *   the old value stays; modes other than 5 ignore it.  Mode 5 counts, per pixel, the fragments mode 8 adds (n) and shows percentage =
  *   clamp(float(n) / float(min(numFragmentsMaxColor, 512)), 0, 1) (DepthComplexityResolve.glsl:48-57) as the colour (0, 1, 1,
@@ -831,6 +863,19 @@ int lv_depth_peeling_get_buffers(lv_ctx* ctx, float* out_accum_rgba, uint32_t* o
  * Precondition: the keys of a pixel's entries are distinct.  out_accum_rgba (w * h * 4) and out_layers (w * h) may be NULL. */
 int lv_depth_peeling_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_entries, const uint64_t* offsets, uint32_t w,
                                      uint32_t h, uint8_t* out_rgba8, float* out_accum_rgba, uint32_t* out_layers);
+/* The visibility buffer of the last frame when that was a mode-1 frame over the whole viewport, row-major: the primitive index
+ * (0xFFFFFFFF: none) and the depth (1.0: none) of every pixel -- which triangle, hence which line, lies under a pixel, and the scene
+ * depth.  Either array may be NULL.  LV_E_STATE if the last frame was not such a frame or the viewport changed since, LV_E_INVALID
+ * if max_pixels < width * height. */
+int lv_deferred_get_buffers(lv_ctx* ctx, uint32_t* primitive_index, float* depth, uint64_t max_pixels);
+/* Test entry point of mode 1's shading pass: the caller's visibility buffer of w x h pixels, row-major (pixel p = y * w + x), shaded
+ * into out (w * h RGBA8 words) with w x h as the viewport size, under the context's camera, options, transfer function and tube
+ * triangle mesh.  LV_E_INVALID for a null array, an empty rectangle or a primitive index that is neither 0xFFFFFFFF nor below the
+ * mesh's triangle count, and -- with the screen-space RTAO on -- a w x h other than the last RTAO image's; LV_E_STATE without camera,
+ * transfer function or mesh, and with depth cues before the first frame.  The mesh is brought up to date first (the index check needs
+ * its triangle count); nothing else of the context is touched before the checks pass, and a refused call leaves the last frame's
+ * lv_deferred_get_buffers as it was. */
+int lv_deferred_shade_buffers(lv_ctx* ctx, const uint32_t* primitive_index, const float* depth, uint32_t w, uint32_t h, uint32_t* out);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

@@ -1,4 +1,4 @@
-"""Headless command line renderer: `python -m linevis_amd <input> -o frame.png [--mode rt|ppll|mlab|al64|wboit|mboit|"Depth Peeling"|"Depth Complexity Renderer"] [key=value ...]`.
+"""Headless command line renderer: `python -m linevis_amd <input> -o frame.png [--mode rt|deferred|ppll|mlab|al64|wboit|mboit|"Depth Peeling"|"Depth Complexity Renderer"] [key=value ...]`.
 
 <input> is a .binlines / .obj trajectory file (LineDataFlow::loadFromFile) or the name of a synthetic scene
 (lattice, helix, tornado, rayleigh_benard, abc_flow).  key=value pairs are the reference's SettingsMap keys
@@ -29,7 +29,7 @@ def main(argv=None):
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input")
     ap.add_argument("-o", "--output", default="frame.png")
-    ap.add_argument("--mode", choices=["rt", "ppll", "mlab", "al64", "wboit", "Depth Peeling", "Depth Complexity Renderer", "mboit"], default="rt")
+    ap.add_argument("--mode", choices=["rt", "deferred", "ppll", "mlab", "al64", "wboit", "Depth Peeling", "Depth Complexity Renderer", "mboit"], default="rt")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--camera", type=float, nargs=3, default=(0.0, 0.0, 0.8), metavar=("X", "Y", "Z"))
@@ -52,7 +52,7 @@ def main(argv=None):
         flow.set_trajectories(host_api.normalize_positions(pos), att[1], off, rib)
     else:
         flow.load_file(args.input)
-    mode = {"rt": capi.MODE_RAY_TRACER, "ppll": capi.MODE_PPLL, "mlab": capi.MODE_MLAB, "mboit": capi.MODE_MBOIT, "al64": capi.MODE_ATOMIC_LOOP_64,
+    mode = {"rt": capi.MODE_RAY_TRACER, "deferred": capi.MODE_DEFERRED, "ppll": capi.MODE_PPLL, "mlab": capi.MODE_MLAB, "mboit": capi.MODE_MBOIT, "al64": capi.MODE_ATOMIC_LOOP_64,
             "wboit": capi.MODE_WBOIT, "Depth Peeling": capi.MODE_DEPTH_PEELING,
             "Depth Complexity Renderer": capi.MODE_DEPTH_COMPLEXITY}[args.mode]
     r = host_api.HeadlessLineRenderer(mode, args.device)

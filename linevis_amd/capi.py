@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("LV_LIB_PATH") or os.path.join(_HERE, "_lib", "libline
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "linevis_hip.h")
 
 LV_OK = 0
+MODE_DEFERRED = 1      # RENDERING_MODE_DEFERRED_SHADING (the tube triangle mesh into a visibility buffer, every pixel shaded once, opaque)
 MODE_PPLL = 2          # RENDERING_MODE_PER_PIXEL_LINKED_LIST, src/Renderers/RenderingModes.hpp:32-53
 MODE_MLAB = 3          # RENDERING_MODE_MLAB (Multi-Layer Alpha Blending over mode 2's fragments)
 MODE_DEPTH_COMPLEXITY = 5   # RENDERING_MODE_DEPTH_COMPLEXITY (fragments per pixel of mode 2's rasterised prism as a colour, and their statistics)
@@ -109,7 +110,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_set_transfer_function", "lv_set_twist_line_texture", "lv_set_camera", "lv_set_background", "lv_set_option", "lv_build_accel",
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
            "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_wboit_get_buffers", "lv_wboit_resolve_buffers",
-           "lv_depth_complexity_get_buffers", "lv_depth_complexity_get_stats", "lv_depth_peeling_get_buffers", "lv_depth_peeling_resolve_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
+           "lv_depth_complexity_get_buffers", "lv_depth_complexity_get_stats", "lv_depth_peeling_get_buffers", "lv_depth_peeling_resolve_buffers", "lv_deferred_get_buffers", "lv_deferred_shade_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -198,6 +199,8 @@ def load():
         ("lv_depth_complexity_get_stats", [vp, vp]),
         ("lv_depth_peeling_get_buffers", [vp, vp, vp, vp, u64]),
         ("lv_depth_peeling_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp, vp]),
+        ("lv_deferred_get_buffers", [vp, vp, vp, u64]),
+        ("lv_deferred_shade_buffers", [vp, vp, vp, u32, u32, vp]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -723,6 +726,26 @@ class Context:
         layers = np.zeros((h, w), dtype=np.uint32)
         self._ck(self.L.lv_depth_peeling_resolve_buffers(self.h, _p(e), e.shape[0], _p(o), w, h, _p(out), _p(accum), _p(layers)))
         return out, accum, layers
+
+    def deferred_buffers(self):
+        """The visibility buffer of the last mode-1 frame over the whole viewport (lv_deferred_get_buffers): ((height, width) uint32
+        primitive indices, 0xFFFFFFFF = none; (height, width) float32 depths, 1.0 = none)."""
+        prim = np.zeros((self.height, self.width), dtype=np.uint32)
+        depth = np.zeros((self.height, self.width), dtype=np.float32)
+        self._ck(self.L.lv_deferred_get_buffers(self.h, _p(prim), _p(depth), self.width * self.height))
+        return prim, depth
+
+    def deferred_shade(self, primitive_index, depth):
+        """Mode 1's shading pass on a caller-supplied visibility buffer (lv_deferred_shade_buffers): primitive_index (h, w) uint32,
+        depth (h, w) float32; (w, h) is the viewport size of the shading.  Returns (h, w, 4) uint8."""
+        prim = np.ascontiguousarray(primitive_index, dtype=np.uint32)
+        z = np.ascontiguousarray(depth, dtype=np.float32)
+        if prim.ndim != 2 or z.shape != prim.shape:
+            raise ValueError("primitive_index and depth must be (h, w)")
+        h, w = prim.shape
+        out = np.zeros((h, w, 4), dtype=np.uint8)
+        self._ck(self.L.lv_deferred_shade_buffers(self.h, _p(prim), _p(z), w, h, _p(out)))
+        return out
 
     def svgf_denoise(self, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history):
         """One SVGF denoise() on caller-supplied images (lv_svgf_denoise_buffers): noisy (h, w), normal_depth (h, w, 4), flow_fwidth

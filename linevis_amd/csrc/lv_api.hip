@@ -114,7 +114,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
-            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
+            &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->visBuf, &ctx->deferredTf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
@@ -669,6 +669,18 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // numFragmentsMaxColor of the depth complexity renderer (rendering mode 5): 0 = from the frame's maximum (DepthComplexityRenderer.cpp:332)
         if (!parseUint(value, u) || u > 1000000) return bad();
         o.dcMaxColour = u;
+    } else if (k == "deferred_rendering_mode") {
+        // deferredRenderingModeNames (DeferredModes.hpp:32-38): the deferred renderer (rendering mode 1) is built in its default form only
+        if (strcmp(value, "Draw Indexed") != 0)
+            return lv_fail(ctx, LV_E_INVALID, "deferred_rendering_mode = '%s' is not built (Draw Indexed only)", value);
+    } else if (k == "draw_indexed_geometry_mode") {
+        // drawIndexedGeometryModeNames (DeferredModes.hpp:47-50)
+        if (strcmp(value, "Precomputed Triangles") != 0)
+            return lv_fail(ctx, LV_E_INVALID, "draw_indexed_geometry_mode = '%s' is not built (Precomputed Triangles only)", value);
+    } else if (k == "supersampling") {
+        // DeferredRenderer.cpp:3003-3017: supersampling and the upscalers are not built
+        if (!parseUint(value, u) || u != 1u)
+            return lv_fail(ctx, LV_E_INVALID, "supersampling = '%s' is not built (1 only)", value);
     } else if (k == "wboit_depth_weight") {
         // the depth weight of the WBOIT renderer (rendering mode 8): the line WBOITGather.glsl:23 runs, or the one it keeps as a comment
         if (strcmp(value, "reference") == 0) o.wboitOpenglWeight = false;
@@ -1583,6 +1595,18 @@ int lv_wboit_resolve_buffers(lv_ctx* ctx, const uint32_t* entries, uint64_t num_
                              uint8_t* out_rgba8, int64_t* out_sums) {
     const int rc = lv_given_lists_args(ctx, entries, num_entries, offsets, w, h, out_rgba8);
     return rc ? rc : lv_frame_wboit_resolve_only(ctx, entries, num_entries, offsets, w, h, out_rgba8, out_sums);
+}
+
+int lv_deferred_get_buffers(lv_ctx* ctx, uint32_t* primitive_index, float* depth, uint64_t max_pixels) {
+    const int rc = lv_getter_args(ctx, true, "lv_deferred_get_buffers", "visibility buffer");
+    return rc ? rc : lv_frame_deferred_buffers(ctx, primitive_index, depth, max_pixels);
+}
+
+int lv_deferred_shade_buffers(lv_ctx* ctx, const uint32_t* primitive_index, const float* depth, uint32_t w, uint32_t h, uint32_t* out) {
+    if (!ctx) return LV_E_INVALID;
+    if (!primitive_index || !depth || !out || w == 0 || h == 0) return lv_fail(ctx, LV_E_INVALID, "null array");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_deferred_shade_only(ctx, primitive_index, depth, w, h, out);
 }
 
 int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_depth,

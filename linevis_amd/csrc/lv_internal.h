@@ -253,11 +253,12 @@ struct lv_ctx {
     LvDeviceBuffer al64Buf;                   // mode 10: K slots and 5 tail sums of 8 B per padded pixel (addressed like ppllCount)
     LvDeviceBuffer wboitBuf;                  // mode 8: 5 sums of 8 B per padded pixel (addressed like ppllCount)
     LvDeviceBuffer peelBuf, dcStatsDev;       // mode 9: 32 B per padded pixel (lv_peel_buffers); modes 5 and 9: the words of k_dc_reduce
+    LvDeviceBuffer visBuf, deferredTf;        // mode 1: the visibility buffer, 8 B per padded pixel (addressed like ppllCount); the transfer function with alpha 1
     // The last frame, when it left per-pixel buffers behind that a *_get_* call reads: a streamed mode-6 frame (mboitAccum), a mode-8
-    // (wboitBuf), mode-10 (al64Buf), mode-5 or mode-9 frame (ppllCount, peelBuf, dcStatsDev).  Each of these frame functions sets it;
+    // (wboitBuf), mode-10 (al64Buf), mode-5 or mode-9 frame (ppllCount, peelBuf, dcStatsDev), a mode-1 frame (visBuf).  Each of these frame functions sets it;
     // lv_frame_render clears it at its top, and so does every resolve-only entry point (they overwrite ppllCount and the counters).
     struct StreamedFrame {
-        int mode = 0;                         // 0: none; else LV_RENDERING_MODE_* (5, 6, 8, 9 or 10)
+        int mode = 0;                         // 0: none; else LV_RENDERING_MODE_* (1, 5, 6, 8, 9 or 10)
         bool full = false;                    // the frame covered the whole viewport
         uint32_t w = 0, h = 0;                // its viewport
         uint32_t tile[2] = {0, 0};            // its ppll tile
@@ -412,6 +413,8 @@ int lv_frame_peel_buffers(lv_ctx* ctx, int mode, float* outAccum, uint32_t* outL
 int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]);
 int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t numEntries, const uint64_t* offsets, uint32_t w, uint32_t h,
                                uint8_t* out, float* outAccum, uint32_t* outLayers);
+int lv_frame_deferred_buffers(lv_ctx* ctx, uint32_t* outPrimitive, float* outDepth, uint64_t capacityPixels);
+int lv_frame_deferred_shade_only(lv_ctx* ctx, const uint32_t* primitive, const float* depth, uint32_t w, uint32_t h, uint32_t* out);
 int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out);
 int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, uint64_t capacityPixels);
 int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKeys, const uint64_t* offsets, uint32_t w, uint32_t h,

@@ -26,6 +26,7 @@
 #include "lv_al64.h"
 #include "lv_wboit.h"
 #include "lv_peel.h"
+#include "lv_deferred.h"
 
 namespace {
 
@@ -4814,6 +4815,82 @@ int lv_frame_dc_stats(lv_ctx* ctx, uint64_t out[5]) {
     return LV_OK;
 }
 
+// The scene view and the uniforms of mode 1's shading pass: the triangle view with the transfer function's alpha forced to 1
+// (fragmentColor.a = 1.0, RayHitCommon.glsl:130-132: ctx->deferredTf, rewritten per call), the pixel's own AO texel
+static int lv_deferred_scene(lv_ctx* ctx, LvSceneDev& SD) {
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->deferredTf, size_t(ctx->tfN) * 16))) return rc;
+    lv_deferred_launch_tf(ctx->stream, (const float4*)ctx->tf.ptr, ctx->tfN, (float4*)ctx->deferredTf.ptr);
+    SD = sceneDevTriangles(ctx);
+    SD.tf = (const float4*)ctx->deferredTf.ptr;
+    return LV_OK;
+}
+// The variant of the shading pass, as lv_rt_frame selects the triangle closest-hit shading's
+static int lv_deferred_bands(const LvUniforms& U) {
+    return U.useHelicityBands ? LV_SHADE_HELICITY : U.useBands ? LV_SHADE_BANDS : LV_SHADE_PLAIN;
+}
+// What the shading pass of mode 1 is not built for: its AO texel is the pixel's own
+static int lv_deferred_check(lv_ctx* ctx, const char* what) {
+    if (ctx->opt.useAmbientOcclusion && ctx->opt.aoPrebaked)
+        return lv_fail(ctx, LV_E_INVALID, "%s: the prebaked AO table is not built for deferred shading (RTAO (Screen Space) is)", what);
+    return LV_OK;
+}
+
+// A mode-1 frame (deferred shading on a visibility buffer, lv_deferred.h): clear, k_vis_raster over the tube triangle mesh, the count of
+// the winners, k_deferred_shade.  No pool and no host synchronisation; 8 B per padded pixel.  LV_KERNEL_PPLL_RASTER: the visibility
+// pass with its clear and the tile marking of a sharded frame; LV_KERNEL_PPLL_RESOLVE: the shading pass.
+static int lv_deferred_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T, uint32_t gridTiles, bool /*stats*/, uint32_t* out,
+                             LvDevCounters* dc) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    lv_fill_prism(ctx, U, S.prism);   // the coverage direction's constants
+    const size_t padded4 = (size_t(U.ppllPaddedW) * U.ppllPaddedH + 3) / 4, pixels = padded4 * 4;
+    if ((rc = lv_buf_reserve(ctx, ctx->visBuf, pixels * 8))) return rc;
+    ctx->ppllPoolNodes = 0;
+    ctx->ppllPaddedW = U.ppllPaddedW;
+    ctx->ppllPaddedH = U.ppllPaddedH;
+    const bool allRequested = ctx->tilesCoverViewport;
+    LvSceneDev SD;
+    if ((rc = lv_deferred_scene(ctx, SD))) return rc;
+    SD.prism = S.prism;
+    unsigned long long* words = (unsigned long long*)ctx->visBuf.ptr;
+    if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
+    if ((ctx->opt.timerMask >> LV_KERNEL_PPLL_RASTER) & 1u) LV_HIP(ctx, hipEventRecord(lv_kernel_ev(ctx, LV_KERNEL_PPLL_RASTER, 0), st));
+    if (!allRequested) {   // the requested-pixel mask of the other modes (ppllStart: 0 = requested; k_ppll_clear clears ppllCount with it)
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllStart, padded4 * 16))) return rc;
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllCount, padded4 * 16))) return rc;
+        if ((rc = lv_buf_reserve(ctx, ctx->ppllCoarse, size_t((U.width + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE) *
+                                                       ((U.height + LV_PRISM_COARSE - 1u) / LV_PRISM_COARSE) * 4))) return rc;
+        lv_ppll_clear(ctx, U, padded4, false, false, dc);
+        k_ppll_mark_tiles<false><<<gridTiles, LV_BLOCK, 0, st>>>(U, T, (uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCoarse.ptr, dc);
+    }
+    const uint32_t* requested = allRequested ? nullptr : (const uint32_t*)ctx->ppllStart.ptr;
+    lv_vis_launch_clear(st, words, pixels);
+    lv_vis_launch_raster(st, U, SD, ctx->numTris, ctx->opt.useCappedTubes, requested, words);
+    if ((rc = lv_segment_raster_end(ctx))) return rc;
+    const uint32_t countGrid = std::min<uint32_t>(nblocks(uint64_t(U.width) * U.height), uint32_t(ctx->numCUs) * 4u);
+    lv_vis_launch_count(st, countGrid, U, requested, words, dc);
+    uint32_t numGroups;
+    if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, lv_deferred_launch_shade(st, numGroups, lv_deferred_bands(U), U, SD, T, words, out));
+    lv_streamed_done(ctx, U, LV_RENDERING_MODE_DEFERRED_SHADING);
+    return LV_OK;
+}
+
+// lv_deferred_get_buffers
+int lv_frame_deferred_buffers(lv_ctx* ctx, uint32_t* outPrimitive, float* outDepth, uint64_t capacityPixels) {
+    uint64_t pixels;
+    int rc;
+    if ((rc = lv_read_back_open(ctx, LV_RENDERING_MODE_DEFERRED_SHADING, "mode-1 frame", ctx->visBuf, "lv_deferred_get_buffers", capacityPixels,
+                                1u, "pixels", 8, pixels)))
+        return rc;
+    uint32_t* dPrimitive = (uint32_t*)ctx->scratchRays.ptr;
+    float* dDepth = (float*)(dPrimitive + size_t(pixels));
+    lv_vis_launch_read(ctx->stream, (const unsigned long long*)ctx->visBuf.ptr, ctx->streamed.w, ctx->streamed.h, ctx->ppllPaddedW,
+                       ctx->streamed.tile[0], ctx->streamed.tile[1], dPrimitive, dDepth);
+    return lv_read_back(ctx, {{outPrimitive, dPrimitive, size_t(pixels) * 4}, {outDepth, dDepth, size_t(pixels) * 4}});
+}
+
 // ---- lv_frame_render: its refusals, its tile list, the two oldest frame functions (mode 11; modes 2, 3 and pooled 6), the frame ----
 
 // How the messages of the modes that work on the prism's fragments alone name them (modes 3, 5, 6, 8, 9 and 10)
@@ -4829,14 +4906,17 @@ static const char* lv_prism_mode_name(int mode) {
 static int lv_frame_check(lv_ctx* ctx, int mode) {
     if (mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && mode != LV_RENDERING_MODE_MLAB &&
         mode != LV_RENDERING_MODE_MBOIT && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64 &&
-        mode != LV_RENDERING_MODE_DEPTH_COMPLEXITY && mode != LV_RENDERING_MODE_DEPTH_PEELING)
-        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 2 = PPLL, 3 = MLAB, 5 = depth complexity, "
-                                          "6 = MBOIT, 8 = WBOIT, 9 = depth peeling, 10 = Atomic Loop 64)", mode);
+        mode != LV_RENDERING_MODE_DEPTH_COMPLEXITY && mode != LV_RENDERING_MODE_DEPTH_PEELING && mode != LV_RENDERING_MODE_DEFERRED_SHADING)
+        return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 1 = deferred shading, 2 = PPLL, 3 = MLAB, "
+                                          "5 = depth complexity, 6 = MBOIT, 8 = WBOIT, 9 = depth peeling, 10 = Atomic Loop 64)", mode);
     ctx->streamed = {};
-    const bool fragments = mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER;   // the modes whose colour pass works on fragments
+    int rc;
+    // the modes whose colour pass works on fragments (mode 1 works on the tube triangle mesh)
+    const bool fragments = mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_DEFERRED_SHADING;
     if (fragments && mode != LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST && ctx->opt.ppllFragmentSource == 1)
         return lv_fail(ctx, LV_E_INVALID, "mode %d (%s) works on the fragments of the rasterised prism: ppll_fragment_source = "
                                           "capsule_entry is not supported", mode, lv_prism_mode_name(mode));
+    if (mode == LV_RENDERING_MODE_DEFERRED_SHADING && (rc = lv_deferred_check(ctx, "mode 1"))) return rc;
     if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_set_camera has not been called");
     if (!ctx->tf.ptr || ctx->tfN == 0) return lv_fail(ctx, LV_E_STATE, "lv_set_transfer_function has not been called");
     if (!ctx->points.ptr && ctx->numSegs) return lv_fail(ctx, LV_E_STATE, "lv_set_lines has not been called");
@@ -5206,6 +5286,12 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         if (!ctx->triAccelValid || ctx->triAccelLineWidth != ctx->opt.lineWidth)
             if ((rc = lv_bvh_build_triangles(ctx))) return rc;
     }
+    if (mode == LV_RENDERING_MODE_DEFERRED_SHADING) {   // the mesh itself, no LBVH over it
+        if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
+        if (!ctx->triMeshSet || ctx->numTris == 0u)
+            return lv_fail(ctx, LV_E_STATE, "mode 1 (deferred shading) rasterises the tube triangle mesh: lv_set_tube_triangle_mesh or "
+                                            "lv_set_trajectories has not been called");
+    }
 
     hipStream_t st = ctx->stream;
     LvUniforms U;
@@ -5305,6 +5391,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     case LV_RENDERING_MODE_DEPTH_COMPLEXITY: rc = lv_dc_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
     case LV_RENDERING_MODE_DEPTH_PEELING: rc = lv_peel_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
     case LV_RENDERING_MODE_ATOMIC_LOOP_64: rc = lv_al64_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
+    case LV_RENDERING_MODE_DEFERRED_SHADING: rc = lv_deferred_frame(ctx, U, S, T, gridTiles, stats, out, dc); break;
     default: rc = lv_pool_frame(ctx, U, S, T, gridTiles, stats, out, dc, mode); break;   // modes 2 and 3
     }
     if (rc) return rc;
@@ -5641,6 +5728,52 @@ int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
     k_peel_blit<<<G.numGroups, LV_WAVE, 0, st>>>(G.U, G.T, B.accum, (uint32_t*)ctx->outDev.ptr, G.numGroups);
     // (row-major addressing: the words lie as the caller's arrays do)
     return lv_resolve_read_back(ctx, out, n, {outAccum, B.accum, n * 16}, {outLayers, B.layers, n * 4});
+}
+
+// lv_deferred_shade_buffers: the caller's visibility buffer (row-major, w x h = the viewport size of the shading) packed into words by
+// k_vis_pack, then k_deferred_shade with row-major addressing over the one tile at the origin.  The checks come first -- state, sizes,
+// index range, the images the shading would read --, behind lv_ensure_tube_mesh only (the index check needs the mesh's triangle count; a
+// tessellation touches no buffer of a frame); after them the call takes over visBuf, scratchRays, tilesDev and outDev, and no *_get_*
+// call finds a frame.
+int lv_frame_deferred_shade_only(lv_ctx* ctx, const uint32_t* primitive, const float* depth, uint32_t w, uint32_t h, uint32_t* out) {
+    static const uint32_t txy[2] = {0u, 0u};
+    const uint64_t numPixels = uint64_t(w) * h;
+    int rc;
+    if (numPixels > 0x7FFFFFF0ull / 8u) return lv_fail(ctx, LV_E_CAPACITY, "too many pixels");
+    if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_set_camera has not been called");
+    if (!ctx->tf.ptr || ctx->tfN == 0) return lv_fail(ctx, LV_E_STATE, "lv_set_transfer_function has not been called");
+    if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
+    if (!ctx->triMeshSet || ctx->numTris == 0u)
+        return lv_fail(ctx, LV_E_STATE, "lv_deferred_shade_buffers shades the tube triangle mesh: lv_set_tube_triangle_mesh or "
+                                        "lv_set_trajectories has not been called");
+    for (uint64_t p = 0; p < numPixels; p++)
+        if (primitive[p] != LV_VIS_NO_PRIMITIVE && primitive[p] >= ctx->numTris)
+            return lv_fail(ctx, LV_E_INVALID, "pixel %llu: primitive index %u, the mesh has %u triangles", (unsigned long long)p, primitive[p],
+                           ctx->numTris);
+    if ((rc = lv_deferred_check(ctx, "lv_deferred_shade_buffers"))) return rc;
+    LvGivenLists G;
+    lv_row_major_uniforms(ctx, G.U, w, h);
+    if (G.U.useAmbientOcclusion && (!ctx->ao.ptr || ctx->aoW != w || ctx->aoH != h))
+        return lv_fail(ctx, LV_E_INVALID, "the screen-space RTAO image is %u x %u, the visibility buffer %u x %u", ctx->aoW, ctx->aoH, w, h);
+    if (G.U.useDepthCues && !ctx->depthMinMax.ptr) return lv_fail(ctx, LV_E_STATE, "depth cues need the depth range of a frame: render one first");
+    hipStream_t st = ctx->stream;
+    const size_t n = size_t(numPixels);
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, n * 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->visBuf, n * 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->tilesDev, 8))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->outDev, n * 4))) return rc;
+    ctx->streamed = {};   // (visBuf no longer belongs to a frame)
+    uint32_t* dPrimitive = (uint32_t*)ctx->scratchRays.ptr;
+    float* dDepth = (float*)(dPrimitive + n);
+    LV_HIP(ctx, hipMemcpyAsync(dPrimitive, primitive, n * 4, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(dDepth, depth, n * 4, hipMemcpyHostToDevice, st));
+    lv_vis_launch_pack(st, dPrimitive, dDepth, n, (unsigned long long*)ctx->visBuf.ptr);
+    LvSceneDev SD;
+    if ((rc = lv_deferred_scene(ctx, SD))) return rc;
+    if ((rc = lv_single_tile(ctx, txy, w, h, G.T, G.numGroups))) return rc;
+    lv_deferred_launch_shade(st, G.numGroups, lv_deferred_bands(G.U), G.U, SD, G.T, (const unsigned long long*)ctx->visBuf.ptr,
+                             (uint32_t*)ctx->outDev.ptr);
+    return lv_resolve_read_back(ctx, (uint8_t*)out, n);
 }
 
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,

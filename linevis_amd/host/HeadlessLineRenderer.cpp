@@ -27,7 +27,9 @@ HeadlessLineRenderer::HeadlessLineRenderer(RenderingMode mode, const std::vector
 // renderer factory of MainApp::setRenderer (src/MainApp.cpp:732-862), reduced to the two hot-path plugins
 void HeadlessLineRenderer::createRenderer(RenderingMode mode) {
     lineRenderer.reset(); // one context at a time: the old plugin releases its device memory first
-    if (mode == RENDERING_MODE_PER_PIXEL_LINKED_LIST)
+    if (mode == RENDERING_MODE_DEFERRED_SHADING)
+        lineRenderer.reset(new HipDeferredRenderer(&sceneData, transferFunctionWindow));
+    else if (mode == RENDERING_MODE_PER_PIXEL_LINKED_LIST)
         lineRenderer.reset(new HipPerPixelLinkedListLineRenderer(&sceneData, transferFunctionWindow));
     else if (mode == RENDERING_MODE_MLAB)
         lineRenderer.reset(new HipMLABRenderer(&sceneData, transferFunctionWindow));

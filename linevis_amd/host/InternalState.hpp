@@ -101,6 +101,15 @@ inline void getTestModesMboit(std::vector<InternalState>& states, InternalState 
     }
 }
 
+/// getTestModesDeferred, src/Utils/InternalState.cpp:472-509: the one state of the deferred renderer (rendering mode 1) this build can
+/// run, "Deferred Draw Indexed" (the Draw Indirect, mesh-shader and BVH states are not built).  Not part of getTestModes().
+inline void getTestModesDeferred(std::vector<InternalState>& states, InternalState state) {
+    state.renderingMode = 1;
+    state.name = "Deferred Draw Indexed";
+    state.rendererSettings = SettingsMap(std::map<std::string, std::string>{{"numSamples", "1"}, {"deferredRenderingMode", "Draw Indexed"}});
+    states.push_back(state);
+}
+
 /// The hot-path subset of getTestModes() (InternalState.cpp:641-644 -> getTestModesOIT, :149-214): 1920 x 1080, PPLL + the ray tracer
 /// states, every state twice for the error measure.
 inline std::vector<InternalState> getTestModes(bool runStatesTwoTimesForErrorMeasure = true) {

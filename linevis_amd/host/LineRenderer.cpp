@@ -889,6 +889,55 @@ bool HipDepthPeelingRenderer::setNewSettings(const SettingsMap& settings) {
     return r;
 }
 
+HipDeferredRenderer::HipDeferredRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
+        : LineRenderer("Deferred Renderer", sceneData, tfw) {
+    isRasterizer = true;
+}
+
+void HipDeferredRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
+    updateNewLineData(newLineData, isNewData);
+}
+
+void HipDeferredRenderer::setNewState(const InternalState& newState) {
+    const SettingsMap& m = newState.rendererSettings;
+    std::string mode = "Draw Indexed", geometry = "Precomputed Triangles";
+    int ss = 1, samples = numSamples;
+    refusedKey.clear();
+    if (m.getValueOpt("deferredRenderingMode", mode) && mode != "Draw Indexed") { refusedKey = "deferred_rendering_mode"; refusedValue = mode; }
+    else if (m.getValueOpt("drawIndexedGeometryMode", geometry) && geometry != "Precomputed Triangles") {
+        refusedKey = "draw_indexed_geometry_mode"; refusedValue = geometry;
+    } else if (m.getValueOpt("supersampling", ss) && ss != 1) { refusedKey = "supersampling"; refusedValue = std::to_string(ss); }
+    if (!refusedKey.empty()) return;   // the previous state stays; render() reports the error
+    if (refusalReported) { lastError.clear(); refusalReported = false; }   // (an accepted state ends the refusal's error)
+    currentStateName = newState.name;
+    if (m.getValueOpt("numSamples", samples)) numSamples = samples;   // (MSAA of the visibility pass: stored, one sample is built)
+    if (ctx) lv_reset_timers(ctx);
+}
+
+void HipDeferredRenderer::render() {
+    if (!refusedKey.empty()) {
+        setOption(refusedKey.c_str(), refusedValue);   // LV_E_INVALID: lastError names the value that is not built
+        refusalReported = true;
+        return;
+    }
+    setOption("ppll_tile_width", std::to_string(tileWidth));
+    setOption("ppll_tile_height", std::to_string(tileHeight));
+    LineRenderer::renderBase();
+    renderMode(LV_RENDERING_MODE_DEFERRED_SHADING); // clear -> visibility buffer -> shade every pixel once
+}
+
+bool HipDeferredRenderer::setNewSettings(const SettingsMap& settings) {
+    bool r = LineRenderer::setNewSettings(settings);
+    std::string s;
+    if (settings.getValueOpt("deferred_rendering_mode", s) && setOption("deferred_rendering_mode", s)) deferredRenderingMode = s;
+    if (settings.getValueOpt("draw_indexed_geometry_mode", s) && setOption("draw_indexed_geometry_mode", s)) drawIndexedGeometryMode = s;
+    if (settings.getValueOpt("supersampling", s) && setOption("supersampling", s)) supersampling = std::atoi(s.c_str());
+    for (const char* key : {"ppll_tile_width", "ppll_tile_height"}) {
+        if (settings.getValueOpt(key, s)) setOption(key, s);
+    }
+    return r;
+}
+
 HipDepthComplexityRenderer::HipDepthComplexityRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
         : LineRenderer("Depth Complexity Renderer", sceneData, tfw) {
     isRasterizer = true;

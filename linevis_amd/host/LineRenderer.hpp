@@ -24,6 +24,7 @@ namespace lv {
 
 enum RenderingMode : int32_t {
     RENDERING_MODE_NONE = -1,
+    RENDERING_MODE_DEFERRED_SHADING = 1,
     RENDERING_MODE_PER_PIXEL_LINKED_LIST = 2,
     RENDERING_MODE_MLAB = 3,
     RENDERING_MODE_DEPTH_COMPLEXITY = 5,
@@ -471,6 +472,41 @@ public:
 private:
     std::string currentStateName;
     int maxColour = 0;                              // depth_complexity_max_colour
+};
+
+/// "Deferred Renderer" plugin (src/Renderers/Deferred/DeferredRenderer.hpp) re-hosted on HIP (rendering mode 1) in its default form:
+/// deferredRenderingMode = "Draw Indexed" with drawIndexedGeometryMode = "Precomputed Triangles", no supersampling.  The tube triangle
+/// mesh goes into a visibility buffer, every pixel is shaded once (linevis_hip.h, deferred_rendering_mode).  A refused state is
+/// reported as HipMBOITRenderer reports one: by the next render(), and an accepted state ends it.  Not built: "Programmable
+/// Pulling", the Draw Indirect, BVH and mesh-shader modes, HZB culling, meshlets, supersampling and upscalers, motion vectors, the hull
+/// pass, stress-line data.
+class HipDeferredRenderer : public LineRenderer {
+public:
+    HipDeferredRenderer(SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);
+    RenderingMode getRenderingMode() const override { return RENDERING_MODE_DEFERRED_SHADING; }
+    bool getIsTriangleRepresentationUsed() const override { return true; }
+    void setLineData(LineDataPtr& lineData, bool isNewData) override;
+    void render() override;
+    /// DeferredRenderer::setNewState: deferredRenderingMode, drawIndexedGeometryMode, supersampling, numSamples.  A state that asks for
+    /// a value this build does not have is refused: the previous state stays and the next render() reports the error of the C ABI.
+    void setNewState(const InternalState& newState) override;
+    const std::string& getCurrentStateName() const { return currentStateName; }
+    /// DeferredRenderer::setNewSettings (DeferredRenderer.cpp:2988-3033): deferred_rendering_mode, supersampling,
+    /// draw_indexed_geometry_mode; a value the C ABI refuses goes to getLastError and the old one stays.
+    bool setNewSettings(const SettingsMap& settings) override;
+    const std::string& getDeferredRenderingMode() const { return deferredRenderingMode; }
+    const std::string& getDrawIndexedGeometryMode() const { return drawIndexedGeometryMode; }
+    int getSupersampling() const { return supersampling; }
+    int getNumSamples() const { return numSamples; }
+
+private:
+    std::string currentStateName;
+    std::string deferredRenderingMode = "Draw Indexed";               // DeferredRenderer.hpp:297
+    std::string drawIndexedGeometryMode = "Precomputed Triangles";    // :300
+    int supersampling = 1;
+    int numSamples = 1;
+    std::string refusedKey, refusedValue;           // the option a refused state asked for (reported by render())
+    bool refusalReported = false;                   // lastError holds that report
 };
 
 } // namespace lv

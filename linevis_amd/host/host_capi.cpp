@@ -525,6 +525,35 @@ int lvh_renderer_depth_complexity_state(void* r, int32_t* out1) {   // {maxColou
     out1[0] = m->getMaxColour();
     return 0;
 }
+uint32_t lvh_test_modes_deferred_count() {
+    std::vector<InternalState> states;
+    getTestModesDeferred(states, InternalState());
+    return uint32_t(states.size());
+}
+uint32_t lvh_test_mode_deferred(uint32_t index, char* buf, uint32_t capacity) {
+    std::vector<InternalState> states;
+    InternalState state;
+    state.windowResolution[0] = 1920;
+    state.windowResolution[1] = 1080;
+    getTestModesDeferred(states, state);
+    if (index >= states.size()) return 0;
+    const InternalState& s = states[index];
+    std::string out = s.name + "\n" + std::to_string(s.renderingMode) + "\n" + std::to_string(s.windowResolution[0]) + "\n" +
+                      std::to_string(s.windowResolution[1]) + "\n";
+    for (const auto& kv : s.rendererSettings.getMap()) out += kv.first + "=" + kv.second + "\n";
+    if (buf && capacity > out.size()) memcpy(buf, out.c_str(), out.size() + 1);
+    return uint32_t(out.size());
+}
+// {deferredRenderingMode: 0 = Draw Indexed, drawIndexedGeometryMode: 0 = Precomputed Triangles, supersampling, numSamples} of a mode-1 plugin
+int lvh_renderer_deferred_state(void* r, int32_t* out4) {
+    HeadlessLineRenderer* h = static_cast<HeadlessLineRenderer*>(r);
+    const HipDeferredRenderer* m = dynamic_cast<const HipDeferredRenderer*>(h->getLineRenderer());
+    if (!m) return -1;
+    out4[0] = m->getDeferredRenderingMode() == "Draw Indexed" ? 0 : -1;
+    out4[1] = m->getDrawIndexedGeometryMode() == "Precomputed Triangles" ? 0 : -1;
+    out4[2] = m->getSupersampling(); out4[3] = m->getNumSamples();
+    return 0;
+}
 void lvh_renderer_destroy(void* r) { delete static_cast<HeadlessLineRenderer*>(r); }
 void lvh_renderer_set_resolution(void* r, uint32_t w, uint32_t h) { static_cast<HeadlessLineRenderer*>(r)->setRenderingResolution(w, h); }
 void lvh_renderer_set_line_data(void* r, void* flow, int isNewData) {

@@ -83,6 +83,9 @@ def load():
         "lvh_test_modes_mlab_count": (u32, []),
         "lvh_test_mode_mlab": (u32, [u32, vp, u32]),
         "lvh_renderer_mlab_state": (i32, [vp, vp]),
+        "lvh_test_modes_deferred_count": (u32, []),
+        "lvh_test_mode_deferred": (u32, [u32, vp, u32]),
+        "lvh_renderer_deferred_state": (i32, [vp, vp]),
         "lvh_test_modes_mboit_count": (u32, []),
         "lvh_test_mode_mboit": (u32, [u32, vp, u32]),
         "lvh_renderer_mboit_state": (i32, [vp, vp, vp]),
@@ -518,6 +521,19 @@ def get_test_modes_mboit():
     return out
 
 
+def get_test_modes_deferred():
+    """The state of the deferred renderer this build can run (lv::getTestModesDeferred = InternalState.cpp:472-509, "Deferred Draw
+    Indexed"), same tuple form as get_test_modes; not part of get_test_modes."""
+    L = load()
+    out = []
+    for i in range(L.lvh_test_modes_deferred_count()):
+        n = L.lvh_test_mode_deferred(i, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        L.lvh_test_mode_deferred(i, buf, n + 1)
+        out.append(_parse_test_mode(buf.value.decode()))
+    return out
+
+
 class HeadlessLineRenderer:
     """lv::HeadlessLineRenderer: fixed-camera harness around one renderer plugin (mode 11, 2, 3 or 6)."""
 
@@ -640,6 +656,15 @@ class HeadlessLineRenderer:
         if self.L.lvh_renderer_wboit_state(self.h, _p(v)) != 0:
             return None
         return {"depthWeight": "opengl" if int(v[0]) else "reference"}
+
+    def deferred_state(self):
+        """{deferredRenderingMode, drawIndexedGeometryMode, supersampling, numSamples} of the mode-1 plugin (None for the other plugins)"""
+        v = np.zeros(4, dtype=np.int32)
+        if self.L.lvh_renderer_deferred_state(self.h, _p(v)) != 0:
+            return None
+        return {"deferredRenderingMode": "Draw Indexed" if int(v[0]) == 0 else None,
+                "drawIndexedGeometryMode": "Precomputed Triangles" if int(v[1]) == 0 else None,
+                "supersampling": int(v[2]), "numSamples": int(v[3])}
 
     def depth_peeling_state(self):
         """{maxLayers} of the mode-9 plugin (None for the other plugins)"""

@@ -18,7 +18,7 @@ sys.path.insert(0, R)
 from linevis_amd import build as B  # noqa: E402
 
 OUT = os.path.join(B.OUT_DIR, "variants")
-RECOMPILE = ["lv_render.hip", "lv_peel.hip", "lv_mlat.hip"]   # the translation units that instantiate lv_trace.h
+RECOMPILE = ["lv_render.hip", "lv_peel.hip", "lv_deferred.hip", "lv_mlat.hip"]   # the translation units that instantiate lv_trace.h
 # named rows: the build-time switches of k_ao_rays' per-ray overhead (the third part, per-pixel generation, is the run-time option
 # ao_ray_generation: run --set ao_ray_generation=per_ray base)
 PRESETS = {
