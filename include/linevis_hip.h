@@ -79,6 +79,15 @@ typedef struct lv_tube_vertex {
     float phi;
 } lv_tube_vertex;
 
+/* struct HullTriangleVertexData, src/LineData/LineRenderData.hpp:186-191 -- byte-identical (32 B): what lv_set_hull_mesh stores on the
+ * device (the paddings are 0). */
+typedef struct lv_hull_vertex {
+    float vertexPosition[3];
+    float padding0;
+    float vertexNormal[3];
+    float padding1;
+} lv_hull_vertex;
+
 /* Counters and timers.  Replaces the per-phase GPU timers of PerPixelLinkedListLineRenderer.cpp:411-420 and the
  * buffer-size reporting of VulkanRayTracer.cpp:671-675.  Ray/node/primitive counters are only filled when the
  * option "collect_stats" is "true" (instrumented kernels; not for timing runs). */
@@ -144,6 +153,9 @@ typedef struct lv_stats {
 #define LV_KERNEL_DEPTH_RANGE 5
 #define LV_KERNEL_PPLL_SHADE 6   /* fragment stage of ppll_fragment_source = raster_prism (k_ppll_shade_prism) */
 #define LV_KERNEL_PPLL_RASTER 7  /* segment rasteriser of raster_prism (k_ppll_raster_prism; ppll_prism_rasteriser = segments) */
+/* the simulation-mesh hull pass of modes 5, 8 and 10 (k_hull_pass).  lv_stats' two per-kernel arrays keep their eight entries: this
+ * id is read with lv_get_kernel_times and selected with kernel_timers like the others */
+#define LV_KERNEL_HULL 8
 
 typedef struct lv_ctx lv_ctx;
 
@@ -368,6 +380,22 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   ppll_pool_nodes = 0, max_depth_complexity.  Timers: LV_KERNEL_PPLL_RASTER times the count pass (with the tile marking and
  *   segment culling of a sharded frame) and then every peel pass, LV_KERNEL_PPLL_GATHER the reduction of the counts,
  *   LV_KERNEL_PPLL_SHADE the layer launches, LV_KERNEL_PPLL_RESOLVE the blit.
+ *   hull_opacity: 0 ... 1 (LineData.cpp:142-145): the opacity of the simulation-mesh hull (lv_set_hull_mesh).  The hull is drawn iff a
+ *   mesh is set AND this key has been set to a value > 0 -- the reference's shallRenderSimulationMeshBoundary, false until the
+ *   setting arrives; the value in force before any set is 0.3 (LineData.hpp:474) and draws nothing.
+ *   hull_color: three floats "r g b" (blanks or commas between them), linear RGB, each 0 ... 1.  Default: the linear value of sRGB 0.5
+ *   by the standard piecewise formula, ((0.5 + 0.055) / 1.055)^2.4 evaluated in double = 0.21404114048223255, as float32
+ *   0.214041144 (bits 0x3E5B2D9A), three times (LineData.hpp:472-473).
+ *   hull_use_shading: "true" | "1" | "false" | "0", default true (LineData.hpp:475): blinnPhongShading(hullColor, normal) of
+ *   Lighting.glsl:45-92 under MESH_HULL, else the plain hull_color.
+ *   What draws the hull: rendering modes 5, 8 and 10, between the mode's line pass and its resolve -- every hull fragment is one
+ *   more fragment of the pixel (coverage and depth by mode 1's rules with culling off, alpha = hull_opacity * (1 - |normal . v|) with
+ *   the interpolated normal NOT normalised, MeshHull.glsl:77-90; mode 10 discards alpha < 0.001, modes 8 and 5 discard nothing), so
+ *   mode 5's counts, maximum and statistics, mode 8's sums and counts and mode 10's slots, tail and counts include it; memory added
+ *   to a frame: none beyond the mesh; timer: LV_KERNEL_HULL.  Modes 6 and 9 draw no hull in the reference (MBOITRenderer.cpp:84 and
+ *   DepthPeelingRenderer.cpp:86 reset the pass) and none here: they render the same frame with or without a mesh.  Modes 1, 2, 3
+ *   and 11 are not built for the hull yet: while a hull would be drawn lv_render returns LV_E_INVALID for them (the message names
+ *   modes 5, 8 and 10; the context stays usable); with hull_opacity 0 or no mesh they render as without these keys, byte for byte.
  *   deferred_rendering_mode: "Draw Indexed" (the reference's default, DeferredRenderer.hpp:297) only; draw_indexed_geometry_mode:
  *   "Precomputed Triangles" (:300) only; supersampling: 1 only.  The other values the reference knows ("Draw Indirect", "Task/Mesh
  *   Shader", "BVH Draw Indirect", "BVH Mesh Shader"; "Programmable Pulling"; 2, 4, 8 ...) are LV_E_INVALID with a message that says the
@@ -876,6 +904,25 @@ int lv_deferred_get_buffers(lv_ctx* ctx, uint32_t* primitive_index, float* depth
  * its triangle count); nothing else of the context is touched before the checks pass, and a refused call leaves the last frame's
  * lv_deferred_get_buffers as it was. */
 int lv_deferred_shade_buffers(lv_ctx* ctx, const uint32_t* primitive_index, const float* depth, uint32_t w, uint32_t h, uint32_t* out);
+/* The simulation-mesh hull (LineData::simulationMeshOutline*, BinLinesLoader.cpp:107-121; LineRenderer::renderHull): an indexed
+ * triangle mesh with three floats per vertex for the positions and for the normals, both required; the normals are used as given
+ * (not renormalised).  Copied to HBM as 32-byte lv_hull_vertex records (8 * num_vertices + 3 * num_triangles words); every rank of
+ * an lv_create_multi handle gets a replica.  num_triangles == 0 removes the mesh.  LV_E_INVALID, with the previous mesh left in
+ * force, for a null array, an index >= num_vertices or a non-finite position or normal.  The mesh does not belong to the lines: it
+ * stays until it is replaced or removed.  What draws it: hull_opacity above. */
+int lv_set_hull_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uint32_t num_triangles, const float* positions, const float* normals,
+                     uint32_t num_vertices);
+/* The current hull mesh read back.  Any output pointer may be NULL (query the counts); LV_E_CAPACITY if a given array is too small. */
+int lv_get_hull_mesh(lv_ctx* ctx, uint32_t* out_triangle_indices, uint32_t max_triangles, float* out_positions, float* out_normals,
+                     uint32_t max_vertices, uint32_t* out_num_triangles, uint32_t* out_num_vertices);
+/* Every kept hull fragment of the whole viewport under the current camera and options, unordered -- the hull's picking query and the
+ * inspection entry point of its fragment stage: pixel = y * width + x, the triangle's index, the window depth, the straight float32
+ * colour (4 floats per fragment).  No alpha discard: that belongs to a mode.  It does not ask whether a hull would be drawn
+ * (hull_opacity is used as it stands).  *out_count is always the number of fragments; a smaller capacity returns LV_E_CAPACITY and
+ * writes nothing else.  Any output array may be NULL.  LV_E_STATE without a hull mesh, camera or lines.  Touches nothing a *_get_*
+ * call of the last frame reads. */
+int lv_hull_get_fragments(lv_ctx* ctx, uint32_t* pixel, uint32_t* triangle, float* depth, float* rgba, uint64_t capacity,
+                          uint64_t* out_count);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

@@ -3,7 +3,9 @@
 <input> is a .binlines / .obj trajectory file (LineDataFlow::loadFromFile) or the name of a synthetic scene
 (lattice, helix, tornado, rayleigh_benard, abc_flow).  key=value pairs are the reference's SettingsMap keys
 (src/Renderers/LineRenderer.cpp:433-498, VulkanRayTracer.cpp:226-278, ...), forwarded through
-LineRenderer::setNewSettings of the plugin classes in linevis_amd/host/.  Needs an MI355X: there is no CPU fallback.
+LineRenderer::setNewSettings of the plugin classes in linevis_amd/host/ and LineData::setNewSettings of the data set -- among them
+hull_opacity, hull_color ("r g b") and hull_use_shading of the simulation-mesh hull, which the modes al64, wboit and "Depth Complexity
+Renderer" draw when the data has an outline mesh (a version-2 .binlines file, or --hull-box).  Needs an MI355X: there is no CPU fallback.
 """
 import argparse
 import sys
@@ -35,6 +37,8 @@ def main(argv=None):
     ap.add_argument("--camera", type=float, nargs=3, default=(0.0, 0.0, 0.8), metavar=("X", "Y", "Z"))
     ap.add_argument("--transfer-function", choices=["standard", "transparent"], default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--hull-box", type=int, default=0, metavar="N",
+                    help="give the data a hull: a closed box of 12 N^2 triangles around its bounding box (scenes.box_hull, margin 0.05)")
     ap.add_argument("settings", nargs="*", help="SettingsMap entries: key=value")
     args = ap.parse_intermixed_args(argv)
 
@@ -52,6 +56,9 @@ def main(argv=None):
         flow.set_trajectories(host_api.normalize_positions(pos), att[1], off, rib)
     else:
         flow.load_file(args.input)
+    if args.hull_box > 0:
+        hull = scenes.box_hull(flow.bounding_box(), args.hull_box, 0.05)
+        flow.set_hull_mesh(hull.triangle_indices, hull.positions, hull.normals)
     mode = {"rt": capi.MODE_RAY_TRACER, "deferred": capi.MODE_DEFERRED, "ppll": capi.MODE_PPLL, "mlab": capi.MODE_MLAB, "mboit": capi.MODE_MBOIT, "al64": capi.MODE_ATOMIC_LOOP_64,
             "wboit": capi.MODE_WBOIT, "Depth Peeling": capi.MODE_DEPTH_PEELING,
             "Depth Complexity Renderer": capi.MODE_DEPTH_COMPLEXITY}[args.mode]

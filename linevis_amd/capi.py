@@ -90,6 +90,7 @@ def streamline_settings(method="Runge-Kutta 4th Order", direction="Forward & Bac
 
 
 KERNEL_AO_PRIMARY, KERNEL_AO_RAYS, KERNEL_RENDER_RT, KERNEL_PPLL_GATHER, KERNEL_PPLL_RESOLVE, KERNEL_DEPTH_RANGE = range(6)
+KERNEL_HULL = 8        # LV_KERNEL_HULL: the simulation-mesh hull pass (kernel_times(); lv_stats' arrays keep the eight KERNEL_NAMES)
 KERNEL_NAMES = ["k_ao_primary", "k_ao_rays", "k_render_rt", "k_ppll_gather", "k_ppll_resolve", "k_depth_minmax", "k_ppll_shade_prism",
                 "k_ppll_raster_prism"]
 
@@ -114,6 +115,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
+           "lv_set_hull_mesh", "lv_get_hull_mesh", "lv_hull_get_fragments",
            "lv_create_multi", "lv_multi_ranks", "lv_multi_rank_stats", "lv_multi_rebalance", "lv_multi_deal", "lv_tile_deal", "lv_make_tiles"]
 
 # function -> (LV_FN_* id, argument words, result words) of lv_selftest_eval
@@ -201,6 +203,9 @@ def load():
         ("lv_depth_peeling_resolve_buffers", [vp, vp, u64, vp, u32, u32, vp, vp, vp]),
         ("lv_deferred_get_buffers", [vp, vp, vp, u64]),
         ("lv_deferred_shade_buffers", [vp, vp, vp, u32, u32, vp]),
+        ("lv_set_hull_mesh", [vp, vp, u32, vp, vp, u32]),
+        ("lv_get_hull_mesh", [vp, vp, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
+        ("lv_hull_get_fragments", [vp, vp, vp, vp, vp, u64, C.POINTER(u64)]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -375,6 +380,45 @@ class Context:
         pts = np.zeros(npnt.value, dtype=LINE_POINT_DTYPE)
         self._ck(self.L.lv_get_tube_triangle_mesh(self.h, _p(idx), nt.value, _p(v), nv.value, _p(pts), npnt.value, None, None, None))
         return idx, v, pts
+
+    def set_hull_mesh(self, triangle_indices, positions, normals):
+        """lv_set_hull_mesh: the simulation-mesh hull, triangle indices [n, 3], positions and normals [m, 3] (normals are used as given).
+        No triangles (None or empty) removes the mesh.  Drawn by modes 5, 8 and 10 once hull_opacity has been set to a value > 0."""
+        idx = np.ascontiguousarray(triangle_indices if triangle_indices is not None else [], dtype=np.uint32).reshape(-1, 3)
+        if len(idx) == 0:
+            self._ck(self.L.lv_set_hull_mesh(self.h, None, 0, None, None, 0))
+            return
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if len(nrm) != len(pos):
+            raise ValueError("one normal per position")
+        self._ck(self.L.lv_set_hull_mesh(self.h, _p(idx), len(idx), _p(pos), _p(nrm), len(pos)))
+
+    def get_hull_mesh(self):
+        """(triangle indices [n, 3], positions [m, 3], normals [m, 3]) of the current hull mesh (lv_get_hull_mesh)"""
+        nt, nv = C.c_uint32(), C.c_uint32()
+        self._ck(self.L.lv_get_hull_mesh(self.h, None, 0, None, None, 0, C.byref(nt), C.byref(nv)))
+        idx = np.zeros((nt.value, 3), dtype=np.uint32)
+        pos = np.zeros((nv.value, 3), dtype=np.float32)
+        nrm = np.zeros((nv.value, 3), dtype=np.float32)
+        self._ck(self.L.lv_get_hull_mesh(self.h, _p(idx), nt.value, _p(pos), _p(nrm), nv.value, None, None))
+        return idx, pos, nrm
+
+    def hull_fragments(self, capacity=None):
+        """lv_hull_get_fragments: every kept hull fragment of the viewport under the current camera and options, unordered:
+        (pixel = y * width + x, triangle, window depth, straight rgba [n, 4]).  capacity None: as many as there are."""
+        n = C.c_uint64(0)
+        if capacity is None:
+            rc = self.L.lv_hull_get_fragments(self.h, None, None, None, None, 0, C.byref(n))
+            if rc not in (LV_OK, -4):
+                self._ck(rc)
+            capacity = n.value
+        cap = max(int(capacity), 1)
+        pix, tri = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        z, rgba = np.zeros(cap, dtype=np.float32), np.zeros((cap, 4), dtype=np.float32)
+        self._ck(self.L.lv_hull_get_fragments(self.h, _p(pix), _p(tri), _p(z), _p(rgba), int(capacity), C.byref(n)))
+        k = n.value
+        return pix[:k], tri[:k], z[:k], rgba[:k]
 
     def set_transfer_function(self, rgba, attr_min=0.0, attr_max=1.0):
         tf = np.ascontiguousarray(rgba, dtype=np.float32).reshape(-1, 4)

@@ -115,7 +115,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
             &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->visBuf, &ctx->deferredTf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
-            &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag,
+            &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag, &ctx->hullIdx, &ctx->hullVerts,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
             &ctx->bakeGbuf, &ctx->bakeSamples, &ctx->bakeOverflow, &ctx->mlatTrace, &ctx->buildArena, &ctx->partitionScratch, &ctx->firstHit,
@@ -310,6 +310,75 @@ int lv_set_tube_triangle_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uin
     ctx->triMeshFromTraj = false;
     ctx->triAccelValid = false;
     return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_set_tube_triangle_mesh(p, triangle_indices, num_triangles, vertices, num_vertices, line_points, num_line_points); });
+}
+
+int lv_set_hull_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uint32_t num_triangles, const float* positions, const float* normals,
+                     uint32_t num_vertices) {
+    if (!ctx) return LV_E_INVALID;
+    if (num_triangles && (!triangle_indices || !positions || !normals)) return lv_fail(ctx, LV_E_INVALID, "lv_set_hull_mesh: null input array");
+    for (uint64_t i = 0; i < 3ull * num_triangles; i++)
+        if (triangle_indices[i] >= num_vertices)
+            return lv_fail(ctx, LV_E_INVALID, "lv_set_hull_mesh: triangle %llu references vertex %u >= num_vertices %u",
+                           (unsigned long long)(i / 3), triangle_indices[i], num_vertices);
+    if (num_triangles == 0) num_vertices = 0;   // removes the mesh
+    for (uint64_t i = 0; i < 3ull * num_vertices; i++)
+        if (!std::isfinite(positions[i]) || !std::isfinite(normals[i]))
+            return lv_fail(ctx, LV_E_INVALID, "lv_set_hull_mesh: vertex %llu has a non-finite position or normal", (unsigned long long)(i / 3));
+    // HullTriangleVertexData, LineData.cpp:1177-1190
+    std::vector<lv_hull_vertex> verts(num_vertices);
+    for (uint32_t i = 0; i < num_vertices; i++) {
+        lv_hull_vertex& v = verts[i];
+        for (int k = 0; k < 3; k++) { v.vertexPosition[k] = positions[3 * size_t(i) + k]; v.vertexNormal[k] = normals[3 * size_t(i) + k]; }
+        v.padding0 = 0.0f; v.padding1 = 0.0f;
+    }
+    (void)hipSetDevice(ctx->device);
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));   // a frame in flight may still read the old mesh
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->hullIdx, size_t(num_triangles) * 12))) return rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->hullVerts, size_t(num_vertices) * sizeof(lv_hull_vertex)))) return rc;
+    if (num_triangles) {
+        LV_HIP(ctx, hipMemcpyAsync(ctx->hullIdx.ptr, triangle_indices, size_t(num_triangles) * 12, hipMemcpyHostToDevice, ctx->stream));
+        LV_HIP(ctx, hipMemcpyAsync(ctx->hullVerts.ptr, verts.data(), size_t(num_vertices) * sizeof(lv_hull_vertex), hipMemcpyHostToDevice,
+                                   ctx->stream));
+    }
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // host arrays are borrowed for the call only
+    ctx->hullNumTris = num_triangles;
+    ctx->hullNumVerts = num_vertices;
+    return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_set_hull_mesh(p, triangle_indices, num_triangles, positions, normals, num_vertices); });
+}
+
+int lv_get_hull_mesh(lv_ctx* ctx, uint32_t* out_triangle_indices, uint32_t max_triangles, float* out_positions, float* out_normals,
+                     uint32_t max_vertices, uint32_t* out_num_triangles, uint32_t* out_num_vertices) {
+    if (!ctx) return LV_E_INVALID;
+    if (out_num_triangles) *out_num_triangles = ctx->hullNumTris;
+    if (out_num_vertices) *out_num_vertices = ctx->hullNumVerts;
+    if (out_triangle_indices && max_triangles < ctx->hullNumTris)
+        return lv_fail(ctx, LV_E_CAPACITY, "lv_get_hull_mesh: the hull mesh has %u triangles", ctx->hullNumTris);
+    if ((out_positions || out_normals) && max_vertices < ctx->hullNumVerts)
+        return lv_fail(ctx, LV_E_CAPACITY, "lv_get_hull_mesh: the hull mesh has %u vertices", ctx->hullNumVerts);
+    (void)hipSetDevice(ctx->device);
+    std::vector<lv_hull_vertex> verts(ctx->hullNumVerts);
+    if (out_triangle_indices && ctx->hullNumTris)
+        LV_HIP(ctx, hipMemcpyAsync(out_triangle_indices, ctx->hullIdx.ptr, size_t(ctx->hullNumTris) * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if ((out_positions || out_normals) && ctx->hullNumVerts)
+        LV_HIP(ctx, hipMemcpyAsync(verts.data(), ctx->hullVerts.ptr, verts.size() * sizeof(lv_hull_vertex), hipMemcpyDeviceToHost, ctx->stream));
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < verts.size(); i++)
+        for (int k = 0; k < 3; k++) {
+            if (out_positions) out_positions[3 * i + k] = verts[i].vertexPosition[k];
+            if (out_normals) out_normals[3 * i + k] = verts[i].vertexNormal[k];
+        }
+    return LV_OK;
+}
+
+int lv_hull_get_fragments(lv_ctx* ctx, uint32_t* pixel, uint32_t* triangle, float* depth, float* rgba, uint64_t capacity, uint64_t* out_count) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out_count) return lv_fail(ctx, LV_E_INVALID, "lv_hull_get_fragments: out_count is null");
+    if (ctx->hullNumTris == 0) return lv_fail(ctx, LV_E_STATE, "lv_hull_get_fragments: lv_set_hull_mesh has not been called");
+    if (!ctx->cameraSet) return lv_fail(ctx, LV_E_STATE, "lv_hull_get_fragments: lv_set_camera has not been called");
+    if (!ctx->points.ptr && !ctx->trajSet) return lv_fail(ctx, LV_E_STATE, "lv_hull_get_fragments: lv_set_lines has not been called");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_hull_fragments(ctx, pixel, triangle, depth, rgba, capacity, out_count);
 }
 
 int lv_set_ao_parametrization(lv_ctx* ctx, const float* blending_weights, uint32_t num_line_vertices,
@@ -681,6 +750,29 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // DeferredRenderer.cpp:3003-3017: supersampling and the upscalers are not built
         if (!parseUint(value, u) || u != 1u)
             return lv_fail(ctx, LV_E_INVALID, "supersampling = '%s' is not built (1 only)", value);
+    } else if (k == "hull_opacity") {
+        // LineData.cpp:142-145: shallRenderSimulationMeshBoundary = hullOpacity > 0 once the setting has arrived
+        if (!parseFloat(value, f) || !(f >= 0.0f && f <= 1.0f)) return bad();
+        o.hullOpacity = f;
+        o.hullOpacitySet = true;
+    } else if (k == "hull_color") {
+        // three floats, linear RGB (the reference's GUI colour, LineData.cpp:321)
+        float c[3];
+        const char* p = value;
+        for (int i = 0; i < 3; i++) {
+            while (*p == ' ' || *p == ',' || *p == '\t') p++;
+            char* end = nullptr;
+            c[i] = strtof(p, &end);
+            if (end == p || !(c[i] >= 0.0f && c[i] <= 1.0f)) return bad();
+            p = end;
+        }
+        while (*p == ' ' || *p == '\t') p++;
+        if (*p != '\0') return bad();
+        for (int i = 0; i < 3; i++) o.hullColor[i] = c[i];
+    } else if (k == "hull_use_shading") {
+        if (strcmp(value, "true") == 0 || strcmp(value, "1") == 0) o.hullUseShading = true;
+        else if (strcmp(value, "false") == 0 || strcmp(value, "0") == 0) o.hullUseShading = false;
+        else return bad();
     } else if (k == "wboit_depth_weight") {
         // the depth weight of the WBOIT renderer (rendering mode 8): the line WBOITGather.glsl:23 runs, or the one it keeps as a comment
         if (strcmp(value, "reference") == 0) o.wboitOpenglWeight = false;
@@ -1048,7 +1140,7 @@ static int lv_get_stats_impl(lv_ctx* ctx, lv_stats* out, bool aggregate) {
         for (int k = 0; k < 3; k++) { s.ao_phase_iterations[k] = hc.aoPhaseIters[k]; s.ao_phase_lanes[k] = hc.aoPhaseLanes[k]; }
     }
     for (int k = 0; k < 8; k++) { s.ms_kernel_avg[k] = 0.0f; s.kernel_launches[k] = 0; }
-    for (int k = 0; k < lv_ctx::kNumKernels; k++) {
+    for (int k = 0; k < 8; k++) {   // (LV_KERNEL_HULL: lv_get_kernel_times)
         const uint64_t n = ctx->kernelLaunches[k];
         const uint64_t m = n < uint64_t(lv_ctx::kRing) ? n : uint64_t(lv_ctx::kRing);
         double sum = 0.0;

@@ -91,6 +91,13 @@ struct LvOptions {
     uint32_t peelMaxLayers = 2000;            // depth_peeling_max_layers: the cap of rendering mode 9's passes, 1 ... 2000 (DepthPeelingRenderer.cpp:288)
     uint32_t dcMaxColour = 0;                 // depth_complexity_max_colour: 0 = auto (numFragmentsMaxColor from the frame's maximum), else that value
     bool mboitStreamed = false;               // mboit_fragment_storage: false = "pool" (default), true = "streamed" (k_mboit_stream_pass: no fragment pool)
+    // the simulation-mesh hull (lv_hull.h): hull_opacity (0.3, LineData.hpp:474; hullOpacitySet: the key has been set -- the reference's
+    // shallRenderSimulationMeshBoundary is false until the setting arrives, LineData.cpp:142-145), hull_color (the linear value of sRGB
+    // 0.5, LineData.hpp:472-473), hull_use_shading (:475)
+    float hullOpacity = 0.3f;
+    bool hullOpacitySet = false;
+    float hullColor[3] = {0.214041144f, 0.214041144f, 0.214041144f};
+    bool hullUseShading = true;
     // EAW denoiser of the RTAO pass (ambient_occlusion_denoiser; AO defaults of createDenoiserObject, Denoiser.cpp:54-62)
     bool eawEnabled = false;
     uint32_t eawIterations = 3;               // eaw_denoiser_iterations (GUI range 0..5, EAWDenoiser.cpp:437)
@@ -155,6 +162,9 @@ struct lv_ctx {
     LvDeviceBuffer triIdx, triVerts, triPoints; // input order
     LvDeviceBuffer triNodes, tris;              // accel
     LvDeviceBuffer triPairFlag;                 // k_tri_pairs_check's verdict
+    // the simulation-mesh hull (lv_set_hull_mesh): 3 indices per triangle, 32-B HullTriangleVertexData; it does not belong to the lines
+    LvDeviceBuffer hullIdx, hullVerts;
+    uint32_t hullNumTris = 0, hullNumVerts = 0;
     bool triLeafPairs = false;                  // the leaves of the triangle LBVH as built hold 64-B pair records
     bool triMeshSet = false, triAccelValid = false;
     // lv_set_trajectories (lv_lines.hip): the trajectories themselves in HBM; `points` / `segIdx` are then written by the a2 kernels and
@@ -297,10 +307,10 @@ struct lv_ctx {
     bool evLinePointsValid = false, evTessValid = false; // ev[4], ev[6]: the a2 kernels of lv_set_trajectories; ev[8], ev[9]: the last device tessellation
     int lastMode = 0;
     // per-kernel launch timers: ring of event pairs per kernel id (LV_KERNEL_*)
-    static constexpr int kNumKernels = 8;
+    static constexpr int kNumKernels = 9;     // LV_KERNEL_HULL is the last; lv_stats reports the first eight
     static constexpr int kRing = 512;
     hipEvent_t evKernel[kNumKernels][2 * kRing];
-    uint64_t kernelLaunches[kNumKernels] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t kernelLaunches[kNumKernels] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 int lv_fail(lv_ctx* ctx, int code, const char* fmt, ...);
@@ -415,6 +425,8 @@ int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
                                uint8_t* out, float* outAccum, uint32_t* outLayers);
 int lv_frame_deferred_buffers(lv_ctx* ctx, uint32_t* outPrimitive, float* outDepth, uint64_t capacityPixels);
 int lv_frame_deferred_shade_only(lv_ctx* ctx, const uint32_t* primitive, const float* depth, uint32_t w, uint32_t h, uint32_t* out);
+int lv_frame_hull_fragments(lv_ctx* ctx, uint32_t* outPixel, uint32_t* outTriangle, float* outDepth, float* outRgba, uint64_t capacity,
+                            uint64_t* outCount);
 int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out);
 int lv_frame_al64_buffers(lv_ctx* ctx, uint64_t* outSlots, uint64_t* outTail, uint64_t capacityPixels);
 int lv_frame_al64_resolve_only(lv_ctx* ctx, const uint64_t* keys, uint64_t numKeys, const uint64_t* offsets, uint32_t w, uint32_t h,

@@ -27,6 +27,7 @@
 #include "lv_wboit.h"
 #include "lv_peel.h"
 #include "lv_deferred.h"
+#include "lv_hull.h"
 
 namespace {
 
@@ -4577,6 +4578,76 @@ int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloa
     return lv_read_back(ctx, {{out, ctx->scratchRays.ptr, size_t(pixels) * perPixel * 4}});
 }
 
+// ---- The simulation-mesh hull (lv_hull.h): one more launch between a mode's line pass and its resolve ----
+// LineData::shallRenderSimulationMeshBoundary: a mesh is set and hull_opacity has been set to a value > 0
+static bool lv_hull_drawn(const lv_ctx* ctx) {
+    return ctx->hullNumTris != 0u && ctx->opt.hullOpacitySet && ctx->opt.hullOpacity > 0.0f;
+}
+static LvHullDev lv_hull_dev(const lv_ctx* ctx) {
+    LvHullDev H;
+    H.idx = (const uint32_t*)ctx->hullIdx.ptr;
+    H.verts = (const lv_hull_vertex*)ctx->hullVerts.ptr;
+    H.numTris = ctx->hullNumTris;
+    for (int k = 0; k < 3; k++) H.color[k] = ctx->opt.hullColor[k];
+    H.opacity = ctx->opt.hullOpacity;
+    H.useShading = ctx->opt.hullUseShading ? 1u : 0u;
+    return H;
+}
+// The hull pass of a mode-5, mode-8 or mode-10 frame, if a hull is drawn: ONE launch of k_hull_pass<store> on the frame's requested-pixel
+// mask, ppllCount and the mode's buffer, timed as LV_KERNEL_HULL.  No memory beyond the mesh, no host synchronisation.
+static int lv_hull_pass(lv_ctx* ctx, int store, const LvUniforms& U, const LvSceneDev& S, bool allRequested, bool stats, LvDevCounters* dc,
+                        unsigned long long* buf, uint32_t arg) {
+    if (!lv_hull_drawn(ctx)) return LV_OK;
+    const LvHullList none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0ull};
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_HULL, lv_hull_launch(ctx->stream, store, uint32_t(ctx->numCUs), U, S.prism, lv_hull_dev(ctx),
+                                                        allRequested ? nullptr : (const uint32_t*)ctx->ppllStart.ptr,
+                                                        (uint32_t*)ctx->ppllCount.ptr, buf, arg, dc, stats, none));
+    return LV_OK;
+}
+
+// lv_hull_get_fragments: the LIST store over the whole viewport, twice -- the count, then (when the caller's capacity holds it) the
+// fragments into ctx->scratchRays, which no *_get_* call of the last frame keeps anything in
+int lv_frame_hull_fragments(lv_ctx* ctx, uint32_t* outPixel, uint32_t* outTriangle, float* outDepth, float* outRgba, uint64_t capacity,
+                            uint64_t* outCount) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    LvUniforms U;
+    lv_fill_uniforms(ctx, U);
+    LvPrismDev R;
+    lv_fill_prism(ctx, U, R);
+    const LvHullDev H = lv_hull_dev(ctx);
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, 8))) return rc;
+    LvHullList L = {(unsigned long long*)ctx->scratchRays.ptr, nullptr, nullptr, nullptr, nullptr, 0ull};
+    unsigned long long count = 0ull;
+    LV_HIP(ctx, hipMemsetAsync(L.counter, 0, 8, st));
+    lv_hull_launch(st, LV_HULL_STORE_LIST, uint32_t(ctx->numCUs), U, R, H, nullptr, nullptr, nullptr, 0u, nullptr, false, L);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(&count, L.counter, 8, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    *outCount = count;
+    if (capacity < count)
+        return lv_fail(ctx, LV_E_CAPACITY, "lv_hull_get_fragments: %llu fragments, capacity %llu", count, (unsigned long long)capacity);
+    if (count == 0ull || (!outPixel && !outTriangle && !outDepth && !outRgba)) return LV_OK;
+    // {counter, pad}, rgba (16 B), pixel, triangle, depth (4 B each) per fragment
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, 16 + size_t(count) * 28))) return rc;
+    char* base = (char*)ctx->scratchRays.ptr;
+    L.counter = (unsigned long long*)base;
+    L.rgba = (float4*)(base + 16);
+    L.pixel = (uint32_t*)(base + 16 + size_t(count) * 16);
+    L.triangle = L.pixel + size_t(count);
+    L.depth = (float*)(L.triangle + size_t(count));
+    L.capacity = count;
+    LV_HIP(ctx, hipMemsetAsync(L.counter, 0, 8, st));
+    lv_hull_launch(st, LV_HULL_STORE_LIST, uint32_t(ctx->numCUs), U, R, H, nullptr, nullptr, nullptr, 0u, nullptr, false, L);
+    LV_HIP(ctx, hipGetLastError());
+    if (outRgba) LV_HIP(ctx, hipMemcpyAsync(outRgba, L.rgba, size_t(count) * 16, hipMemcpyDeviceToHost, st));
+    if (outPixel) LV_HIP(ctx, hipMemcpyAsync(outPixel, L.pixel, size_t(count) * 4, hipMemcpyDeviceToHost, st));
+    if (outTriangle) LV_HIP(ctx, hipMemcpyAsync(outTriangle, L.triangle, size_t(count) * 4, hipMemcpyDeviceToHost, st));
+    if (outDepth) LV_HIP(ctx, hipMemcpyAsync(outDepth, L.depth, size_t(count) * 4, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    return LV_OK;
+}
+
 // The middle of a mode-8 or mode-10 frame, between the clear of the mode's buffer and the close: the phase mark and ONE launch of
 // k_stream_pass<MODE> on `buf` and `arg`.  LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in
 // modes 2, 3 and 6)
@@ -4613,6 +4684,7 @@ static int lv_al64_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTile
     lv_al64_clear(ctx, F.pixels * size_t(K + LV_AL64_TAIL), K);
     if ((rc = lv_stream_pass<LV_RENDERING_MODE_ATOMIC_LOOP_64>(ctx, U, S, T, gridTiles, stats, F, dc, (unsigned long long*)ctx->al64Buf.ptr, K)))
         return rc;
+    if ((rc = lv_hull_pass(ctx, LV_HULL_STORE_AL64, U, S, F.allRequested, stats, dc, (unsigned long long*)ctx->al64Buf.ptr, K))) return rc;
     uint32_t numGroups;
     if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_RESOLVE, (k_al64_resolve<<<numGroups, LV_WAVE, 0, ctx->stream>>>(
@@ -4654,6 +4726,8 @@ static int lv_wboit_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTil
     LV_HIP(ctx, hipMemsetAsync(ctx->wboitBuf.ptr, 0, F.pixels * size_t(LV_WBOIT_SUMS) * 8, ctx->stream));
     const uint32_t weightMode = ctx->opt.wboitOpenglWeight ? LV_WBOIT_WEIGHT_OPENGL : LV_WBOIT_WEIGHT_REFERENCE;
     if ((rc = lv_stream_pass<LV_RENDERING_MODE_WBOIT>(ctx, U, S, T, gridTiles, stats, F, dc, (unsigned long long*)ctx->wboitBuf.ptr, weightMode)))
+        return rc;
+    if ((rc = lv_hull_pass(ctx, LV_HULL_STORE_WBOIT, U, S, F.allRequested, stats, dc, (unsigned long long*)ctx->wboitBuf.ptr, weightMode)))
         return rc;
     uint32_t numGroups;
     if ((rc = lv_streamed_close(ctx, T, numGroups))) return rc;
@@ -4717,6 +4791,9 @@ static int lv_dc_count(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles&
                                                              allRequested ? 1u : 0u, leafList, stats ? 1u : 0u);
     }
     if ((rc = lv_segment_raster_end(ctx))) return rc;
+    // the hull's fragments are counted in front of the reduce: mode 5's maximum and statistics include them.  Mode 9 draws no hull
+    // (DepthPeelingRenderer.cpp:86)
+    if (!peel && (rc = lv_hull_pass(ctx, LV_HULL_STORE_COUNT, U, S, allRequested, stats, dc, nullptr, 0u))) return rc;
     const uint32_t pixels = U.width * U.height;
     const uint32_t reduceGrid = std::min<uint32_t>((pixels + LV_BLOCK - 1) / LV_BLOCK, uint32_t(ctx->numCUs) * 4u);
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_PPLL_GATHER, (k_dc_reduce<<<reduceGrid, LV_BLOCK, 0, st>>>(
@@ -4938,6 +5015,11 @@ static int lv_frame_check(lv_ctx* ctx, int mode) {
         return lv_fail(ctx, LV_E_INVALID, "rotating_helicity_bands and use_ribbons exclude each other (LineDataFlow.cpp:470,601-604)");
     if (ctx->opt.rtLss && ctx->opt.useRibbons && ctx->opt.ellipticTubes)
         return lv_fail(ctx, LV_E_INVALID, "Elliptic Tubes belong to the AABB geometry mode (VulkanRayTracer.cpp:198), not to Linear Swept Spheres");
+    // the simulation-mesh hull: modes 6 and 9 draw none (as the reference), the others are not built for it yet
+    if (lv_hull_drawn(ctx) && (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER || mode == LV_RENDERING_MODE_DEFERRED_SHADING ||
+                               mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mode == LV_RENDERING_MODE_MLAB))
+        return lv_fail(ctx, LV_E_INVALID, "mode %d does not draw the simulation-mesh hull yet: modes 5 (depth complexity), 8 (WBOIT) and 10 "
+                                          "(Atomic Loop 64) do; set hull_opacity = 0 or remove the mesh (lv_set_hull_mesh with 0 triangles)", mode);
     return LV_OK;
 }
 

@@ -112,7 +112,21 @@ bool loadTrajectoriesFromBinLines(const std::string& filename, BinLinesData& bin
                 if (!r.getArray(dirs.data(), sizeof(vec3) * dirs.size())) return false;
             }
         }
-        // numMeshOutlineTriangleIndices / Vertices / Normals and their arrays: not used by the line renderers
+        // the simulation grid outline mesh, BinLinesLoader.cpp:100-122 (files that end after the ribbon data: no mesh)
+        binLinesData.simulationMeshOutlineTriangleIndices.clear();
+        binLinesData.simulationMeshOutlineVertexPositions.clear();
+        binLinesData.simulationMeshOutlineVertexNormals.clear();
+        if (r.off + 12 <= r.n) {
+            const uint32_t numIndices = r.get<uint32_t>(), numVertices = r.get<uint32_t>(), numNormals = r.get<uint32_t>();
+            // truncated / corrupt: no allocation from a file-controlled length
+            if (size_t(numIndices) * 4 + (size_t(numVertices) + numNormals) * sizeof(vec3) > r.n - r.off) return false;
+            binLinesData.simulationMeshOutlineTriangleIndices.resize(numIndices);
+            binLinesData.simulationMeshOutlineVertexPositions.resize(numVertices);
+            binLinesData.simulationMeshOutlineVertexNormals.resize(numNormals);
+            if (numIndices && !r.getArray(binLinesData.simulationMeshOutlineTriangleIndices.data(), size_t(numIndices) * 4)) return false;
+            if (numVertices && !r.getArray(binLinesData.simulationMeshOutlineVertexPositions.data(), sizeof(vec3) * numVertices)) return false;
+            if (numNormals && !r.getArray(binLinesData.simulationMeshOutlineVertexNormals.data(), sizeof(vec3) * numNormals)) return false;
+        }
     }
     return true;
 }
@@ -123,11 +137,35 @@ bool loadTrajectoriesFromBinLines(const std::string& filename, Trajectories& tra
     return true;
 }
 
+void computeSmoothTriangleNormals(const std::vector<uint32_t>& triangleIndices, const std::vector<vec3>& vertexPositions,
+                                  std::vector<vec3>& vertexNormals) {
+    vertexNormals.assign(vertexPositions.size(), vec3(0.0f, 0.0f, 0.0f));
+    for (size_t t = 0; t + 2 < triangleIndices.size(); t += 3) {
+        const uint32_t i0 = triangleIndices[t], i1 = triangleIndices[t + 1], i2 = triangleIndices[t + 2];
+        if (i0 >= vertexPositions.size() || i1 >= vertexPositions.size() || i2 >= vertexPositions.size()) continue;
+        const vec3 p0 = vertexPositions[i0], p1 = vertexPositions[i1], p2 = vertexPositions[i2];
+        const vec3 a(p1.x - p0.x, p1.y - p0.y, p1.z - p0.z), b(p2.x - p0.x, p2.y - p0.y, p2.z - p0.z);
+        const vec3 fn(a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y);
+        for (uint32_t i : {i0, i1, i2}) {
+            vec3& n = vertexNormals[i];
+            n.x = n.x + fn.x; n.y = n.y + fn.y; n.z = n.z + fn.z;
+        }
+    }
+    for (vec3& n : vertexNormals) {
+        const float len = std::sqrt((n.x * n.x + n.y * n.y) + n.z * n.z);
+        if (len > 0.0f) { n.x = n.x / len; n.y = n.y / len; n.z = n.z / len; }
+        else n = vec3(0.0f, 0.0f, 0.0f);
+    }
+}
+
 bool saveTrajectoriesAsBinLines(const std::string& filename, const Trajectories& trajectories,
-                                const std::vector<std::vector<vec3>>& ribbonsDirections, bool verticesNormalized) {
+                                const std::vector<std::vector<vec3>>& ribbonsDirections, bool verticesNormalized,
+                                const std::vector<uint32_t>& meshOutlineTriangleIndices, const std::vector<vec3>& meshOutlineVertexPositions,
+                                const std::vector<vec3>& meshOutlineVertexNormals) {
     FILE* f = fopen(filename.c_str(), "wb");
     if (!f) return false;
-    const bool v2 = !ribbonsDirections.empty();
+    const bool hasRibbons = !ribbonsDirections.empty();
+    const bool v2 = hasRibbons || !meshOutlineTriangleIndices.empty();
     uint32_t hdr[3] = {v2 ? 2u : 1u, uint32_t(trajectories.size()),
                        trajectories.empty() ? 0u : uint32_t(trajectories[0].attributes.size())};
     fwrite(hdr, 4, 3, f);
@@ -137,13 +175,20 @@ bool saveTrajectoriesAsBinLines(const std::string& filename, const Trajectories&
         fwrite(t.positions.data(), sizeof(vec3), n, f);
         for (uint32_t a = 0; a < hdr[2]; a++) fwrite(t.attributes[a].data(), sizeof(float), n, f);
     }
-    if (v2) { // BinLinesLoader.cpp:196-247: verticesNormalized, hasAttributeNames = 0, hasRibbonData = 1, no outline mesh
-        const uint32_t trailer[3] = {verticesNormalized ? 1u : 0u, 0u, 1u};
+    if (v2) { // BinLinesLoader.cpp:196-247: verticesNormalized, hasAttributeNames = 0, hasRibbonData, the outline mesh
+        const uint32_t trailer[3] = {verticesNormalized ? 1u : 0u, 0u, hasRibbons ? 1u : 0u};
         fwrite(trailer, 4, 3, f);
-        for (size_t i = 0; i < trajectories.size(); i++)
+        for (size_t i = 0; hasRibbons && i < trajectories.size(); i++)
             fwrite(ribbonsDirections[i].data(), sizeof(vec3), trajectories[i].positions.size(), f);
-        const uint32_t mesh[3] = {0u, 0u, 0u};
+        const bool hasMesh = !meshOutlineTriangleIndices.empty();
+        const uint32_t mesh[3] = {uint32_t(meshOutlineTriangleIndices.size()), hasMesh ? uint32_t(meshOutlineVertexPositions.size()) : 0u,
+                                  hasMesh ? uint32_t(meshOutlineVertexNormals.size()) : 0u};
         fwrite(mesh, 4, 3, f);
+        if (hasMesh) {
+            fwrite(meshOutlineTriangleIndices.data(), 4, meshOutlineTriangleIndices.size(), f);
+            fwrite(meshOutlineVertexPositions.data(), sizeof(vec3), meshOutlineVertexPositions.size(), f);
+            fwrite(meshOutlineVertexNormals.data(), sizeof(vec3), meshOutlineVertexNormals.size(), f);
+        }
     }
     return fclose(f) == 0;
 }
@@ -264,8 +309,36 @@ static const char* const LINE_PRIMITIVE_MODE_DISPLAYNAMES[] = { // LineData.cpp:
         "Tube Ribbons (Programmable Pull)", "Tube Ribbons (Geometry Shader)", "Tube Ribbons (Triangle Mesh)",
         "Tube Ribbons (Mesh Shader)", "Tube Ribbons (Mesh Shader NV)"};
 
+void LineData::setSimulationMeshOutline(const std::vector<uint32_t>& triangleIndices, const std::vector<vec3>& vertexPositions,
+                                        const std::vector<vec3>& vertexNormals) {
+    simulationMeshOutlineTriangleIndices = triangleIndices;
+    simulationMeshOutlineVertexPositions = vertexPositions;
+    if (vertexNormals.size() == vertexPositions.size()) simulationMeshOutlineVertexNormals = vertexNormals;
+    else computeSmoothTriangleNormals(triangleIndices, vertexPositions, simulationMeshOutlineVertexNormals);
+    // LineDataFlow.cpp:445: a data set that comes with an outline mesh shows it
+    shallRenderSimulationMeshBoundary = !simulationMeshOutlineTriangleIndices.empty();
+    hullGeneration++;
+    dirty = true;
+}
+
 bool LineData::setNewSettings(const SettingsMap& settings) {
     bool shallReloadGatherShader = false;
+    // LineData.cpp:142-150; hull_color and hull_use_shading are GUI-only in the reference, settings keys here (linevis_hip.h)
+    if (!simulationMeshOutlineTriangleIndices.empty()) {
+        if (settings.getValueOpt("hull_opacity", hullOpacity)) {
+            shallRenderSimulationMeshBoundary = hullOpacity > 0.0f;
+            dirty = true;
+        }
+        std::string hullColorString;
+        if (settings.getValueOpt("hull_color", hullColorString)) {
+            float c[3];
+            if (sscanf(hullColorString.c_str(), "%f%*[ ,]%f%*[ ,]%f", &c[0], &c[1], &c[2]) == 3) {
+                for (int k = 0; k < 3; k++) hullColor[k] = c[k];
+                dirty = true;
+            }
+        }
+        if (settings.getValueOpt("hull_use_shading", hullUseShading)) dirty = true;
+    }
     std::string linePrimitiveModeName; // :107-140
     if (settings.getValueOpt("line_primitive_mode", linePrimitiveModeName)) {
         for (int i = 0; i < int(LINE_PRIMITIVES_COUNT); i++)
@@ -321,6 +394,9 @@ bool LineDataFlow::loadFromFile(const std::string& filename) {
         names = d.attributeNames;
         ribbons.swap(d.ribbonsDirections);
         alreadyNormalized = d.verticesNormalized; // version 2: StreamlineTracingRequester exports grid-normalised lines with the flag set
+        // the outline mesh is taken as stored (LineDataFlow.cpp:445-448: it is in the coordinates of the file's positions)
+        setSimulationMeshOutline(d.simulationMeshOutlineTriangleIndices, d.simulationMeshOutlineVertexPositions,
+                                 d.simulationMeshOutlineVertexNormals);
     } else if (!loadFlowTrajectoriesFromFile(filename, loaded, names)) {
         return false;
     }

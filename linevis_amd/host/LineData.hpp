@@ -40,13 +40,24 @@ struct BinLinesData {
     std::vector<std::string> attributeNames;
     std::vector<std::vector<vec3>> ribbonsDirections; // per trajectory, one direction per point; empty = no band data
     bool verticesNormalized = false;
+    /// the simulation grid outline mesh (BinLinesLoader.cpp:100-122): 3 indices per triangle, one position / normal per vertex
+    std::vector<uint32_t> simulationMeshOutlineTriangleIndices;
+    std::vector<vec3> simulationMeshOutlineVertexPositions, simulationMeshOutlineVertexNormals;
 };
+/// Per-vertex normals for a mesh that has none.  The reference takes sgl::computeSmoothTriangleNormals (LineData.cpp:701), which is
+/// not vendored: the definition is the build's own -- the face normals cross(p1 - p0, p2 - p0), whose length is twice
+/// the area, are added to their three vertices in triangle order, in float32, and the sums are normalised (a zero sum stays zero).
+void computeSmoothTriangleNormals(const std::vector<uint32_t>& triangleIndices, const std::vector<vec3>& vertexPositions,
+                                  std::vector<vec3>& vertexNormals);
 /// .binlines reader, versions 1 and 2 (BinLinesLoader.cpp:41-180)
 bool loadTrajectoriesFromBinLines(const std::string& filename, BinLinesData& binLinesData);
 bool loadTrajectoriesFromBinLines(const std::string& filename, Trajectories& trajectories);
-/// writer (BinLinesLoader.cpp:182-247): version 1 without, version 2 with ribbon directions
+/// writer (BinLinesLoader.cpp:182-247): version 1 without, version 2 with ribbon directions or an outline mesh
 bool saveTrajectoriesAsBinLines(const std::string& filename, const Trajectories& trajectories,
-                                const std::vector<std::vector<vec3>>& ribbonsDirections = {}, bool verticesNormalized = false);
+                                const std::vector<std::vector<vec3>>& ribbonsDirections = {}, bool verticesNormalized = false,
+                                const std::vector<uint32_t>& meshOutlineTriangleIndices = {},
+                                const std::vector<vec3>& meshOutlineVertexPositions = {},
+                                const std::vector<vec3>& meshOutlineVertexNormals = {});
 /// Wavefront-OBJ polylines as LineVis reads them (src/Loaders/ObjLoader.cpp:36-186): "v x y z" positions, "vt a0 a1 .."
 /// per-vertex attributes (same count on every line), "l i j k .." one trajectory per line statement (1-based indices),
 /// "a name0 name1 .." attribute names; positions with a component above 1e10 are dropped.
@@ -159,6 +170,20 @@ public:
     }
     uint64_t getDataGeneration() const { return dataGeneration; }
 
+    /// The simulation-mesh hull (LineData.hpp:471-479, LineData.cpp:142-145,1170-1206,1309-1311): the outline mesh the renderers of
+    /// modes 5, 8 and 10 upload (lv_set_hull_mesh), and its three settings.  Normals may be empty: computeSmoothTriangleNormals.
+    void setSimulationMeshOutline(const std::vector<uint32_t>& triangleIndices, const std::vector<vec3>& vertexPositions,
+                                  const std::vector<vec3>& vertexNormals = {});
+    bool hasSimulationMeshOutline() const { return !simulationMeshOutlineTriangleIndices.empty(); }
+    const std::vector<uint32_t>& getSimulationMeshOutlineTriangleIndices() const { return simulationMeshOutlineTriangleIndices; }
+    const std::vector<vec3>& getSimulationMeshOutlineVertexPositions() const { return simulationMeshOutlineVertexPositions; }
+    const std::vector<vec3>& getSimulationMeshOutlineVertexNormals() const { return simulationMeshOutlineVertexNormals; }
+    bool getShallRenderSimulationMeshBoundary() const { return shallRenderSimulationMeshBoundary; }
+    float getHullOpacity() const { return hullOpacity; }
+    const float* getHullColor() const { return hullColor; }
+    bool getHullUseShading() const { return hullUseShading; }
+    uint64_t getHullGeneration() const { return hullGeneration; }
+
     /// dataset-side settings keys: attribute, tube_num_subdivisions, use_capped_tubes, use_halos
     /// (src/LineData/LineData.cpp:87-181).  Returns true when renderers must re-fetch geometry/defines.
     virtual bool setNewSettings(const SettingsMap& settings);
@@ -182,6 +207,14 @@ protected:
     uint64_t dataGeneration = nextDataGeneration(); // renewed by new trajectories / another selected attribute
     bool cachedAabbDataValid = false;
     bool cachedTriangleDataValid = false;
+    // the simulation-mesh hull
+    bool shallRenderSimulationMeshBoundary = false;
+    float hullColor[3] = {0.214041144f, 0.214041144f, 0.214041144f};   // sRGBToLinearRGB(0.5), LineData.hpp:472-473
+    float hullOpacity = 0.3f;
+    bool hullUseShading = true;
+    std::vector<uint32_t> simulationMeshOutlineTriangleIndices;
+    std::vector<vec3> simulationMeshOutlineVertexPositions, simulationMeshOutlineVertexNormals;
+    uint64_t hullGeneration = 0;   // bumped with every new mesh
 };
 typedef std::shared_ptr<LineData> LineDataPtr;
 

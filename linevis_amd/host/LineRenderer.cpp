@@ -436,6 +436,27 @@ bool LineRenderer::uploadFrameState() {
         setOption("use_capped_tubes", lineData->getUseCappedTubesDefine(isRasterizer) ? "true" : "false");
         setOption("use_halos", lineData->getUseHalos() ? "true" : "false");
         setOption("tube_num_subdivisions", std::to_string(lineData->getTubeNumSubdivisions()));
+        if (drawsHull) {   // the simulation-mesh hull: the mesh once per data set, its settings with every change
+            if (uploadedHullData != lineData.get() || uploadedHullGeneration != lineData->getHullGeneration()) {
+                const std::vector<uint32_t>& idx = lineData->getSimulationMeshOutlineTriangleIndices();
+                const std::vector<vec3>& pos = lineData->getSimulationMeshOutlineVertexPositions();
+                const std::vector<vec3>& nrm = lineData->getSimulationMeshOutlineVertexNormals();
+                static_assert(sizeof(vec3) == 12, "vec3 is three packed floats");
+                if (!check(lv_set_hull_mesh(ctx, idx.data(), uint32_t(idx.size() / 3), pos.empty() ? nullptr : &pos[0].x,
+                                            nrm.empty() ? nullptr : &nrm[0].x, uint32_t(pos.size())), "lv_set_hull_mesh"))
+                    return false;
+                uploadedHullData = lineData.get();
+                uploadedHullGeneration = lineData->getHullGeneration();
+            }
+            // hull_opacity 0 = not drawn: LineData::shallRenderSimulationMeshBoundary decides (LineData.cpp:142-145)
+            snprintf(buf, sizeof(buf), "%.9g", lineData->getShallRenderSimulationMeshBoundary() ? double(lineData->getHullOpacity()) : 0.0);
+            setOption("hull_opacity", buf);
+            const float* hc = lineData->getHullColor();
+            char colour[96];
+            snprintf(colour, sizeof(colour), "%.9g %.9g %.9g", double(hc[0]), double(hc[1]), double(hc[2]));
+            setOption("hull_color", colour);
+            setOption("hull_use_shading", lineData->getHullUseShading() ? "true" : "false");
+        }
         // the trajectories themselves go to HBM (once per data set, with the ribbon directions and the helicity attribute when the data has
         // them) and the device writes the line points, the index pairs and -- whenever a frame needs them at another line width / band
         // setting -- the triangle tubes; use_device_geometry = false or more than 2^26-1 points: host-built render data.  After the
@@ -782,6 +803,7 @@ bool HipMBOITRenderer::setNewSettings(const SettingsMap& settings) {
 HipAtomicLoop64Renderer::HipAtomicLoop64Renderer(SceneData* sceneData, TransferFunctionWindow& tfw)
         : LineRenderer("Atomic Loop 64 Renderer", sceneData, tfw) {
     isRasterizer = true;
+    drawsHull = true;
 }
 
 void HipAtomicLoop64Renderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
@@ -824,6 +846,7 @@ void HipPerPixelLinkedListLineRenderer::computeStatistics(uint64_t& totalNumFrag
 HipWBOITRenderer::HipWBOITRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
         : LineRenderer("Weighted Blended OIT Renderer", sceneData, tfw) {
     isRasterizer = true;
+    drawsHull = true;
 }
 
 void HipWBOITRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {
@@ -941,6 +964,7 @@ bool HipDeferredRenderer::setNewSettings(const SettingsMap& settings) {
 HipDepthComplexityRenderer::HipDepthComplexityRenderer(SceneData* sceneData, TransferFunctionWindow& tfw)
         : LineRenderer("Depth Complexity Renderer", sceneData, tfw) {
     isRasterizer = true;
+    drawsHull = true;
 }
 
 void HipDepthComplexityRenderer::setLineData(LineDataPtr& newLineData, bool isNewData) {

@@ -253,6 +253,12 @@ protected:
     lv_ctx* ctx = nullptr;
     std::string lastError;
     bool isRasterizer = false;
+    /// LineRenderer::renderHull is a step of this renderer's frame AND the library draws it there (rendering modes 5, 8 and 10): the
+    /// renderer uploads the line data's outline mesh (lv_set_hull_mesh) and forwards hull_opacity / hull_color / hull_use_shading.  The
+    /// other renderers upload no mesh, so their frames are never refused for one.
+    bool drawsHull = false;
+    const LineData* uploadedHullData = nullptr;
+    uint64_t uploadedHullGeneration = 0;
     bool dirty = true, reRender = true, internalReRender = false;
     bool tfDirty = true, linesDirty = true, triangleMeshDirty = true;
     // device geometry (lv_set_trajectories_with_bands): on by default for flow lines; use_device_geometry = false keeps the host-built

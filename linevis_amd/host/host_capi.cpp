@@ -122,7 +122,39 @@ void lvh_flow_build_render_data_elliptic(void* hp, float bandWidth, uint32_t* ou
 int lvh_flow_load_binlines(void* hp, const char* path) { return static_cast<FlowHandle*>(hp)->flow()->loadFromFile(path) ? 0 : -1; }
 int lvh_flow_save_binlines(void* hp, const char* path) {
     LineDataFlow* fl = static_cast<FlowHandle*>(hp)->flow();
-    return saveTrajectoriesAsBinLines(path, fl->getTrajectories(), fl->getRibbonsDirections(), fl->getVerticesNormalized()) ? 0 : -1;
+    return saveTrajectoriesAsBinLines(path, fl->getTrajectories(), fl->getRibbonsDirections(), fl->getVerticesNormalized(),
+                                      fl->getSimulationMeshOutlineTriangleIndices(), fl->getSimulationMeshOutlineVertexPositions(),
+                                      fl->getSimulationMeshOutlineVertexNormals()) ? 0 : -1;
+}
+/// the simulation-mesh outline: 3 indices per triangle, 3 floats per vertex; normals NULL = computeSmoothTriangleNormals
+void lvh_flow_set_hull_mesh(void* hp, const uint32_t* indices, uint32_t nTriangles, const float* positions, const float* normals,
+                            uint32_t nVertices) {
+    std::vector<uint32_t> idx(indices, indices + 3 * size_t(nTriangles));
+    std::vector<vec3> pos(nVertices), nrm(normals ? nVertices : 0);
+    if (nVertices) memcpy(pos.data(), positions, size_t(nVertices) * 12);
+    if (normals && nVertices) memcpy(nrm.data(), normals, size_t(nVertices) * 12);
+    static_cast<FlowHandle*>(hp)->data->setSimulationMeshOutline(idx, pos, nrm);
+}
+/// NULL arrays: the counts only
+void lvh_flow_get_hull_mesh(void* hp, uint32_t* indices, float* positions, float* normals, uint32_t* outNumTriangles, uint32_t* outNumVertices) {
+    const LineData* d = static_cast<FlowHandle*>(hp)->data.get();
+    const std::vector<uint32_t>& idx = d->getSimulationMeshOutlineTriangleIndices();
+    const std::vector<vec3>& pos = d->getSimulationMeshOutlineVertexPositions();
+    const std::vector<vec3>& nrm = d->getSimulationMeshOutlineVertexNormals();
+    if (outNumTriangles) *outNumTriangles = uint32_t(idx.size() / 3);
+    if (outNumVertices) *outNumVertices = uint32_t(pos.size());
+    if (indices && !idx.empty()) memcpy(indices, idx.data(), idx.size() * 4);
+    if (positions && !pos.empty()) memcpy(positions, pos.data(), pos.size() * 12);
+    if (normals && !nrm.empty()) memcpy(normals, nrm.data(), nrm.size() * 12);
+}
+int lvh_flow_has_simulation_mesh_outline(void* hp) { return static_cast<FlowHandle*>(hp)->data->hasSimulationMeshOutline() ? 1 : 0; }
+int lvh_flow_shall_render_hull(void* hp) { return static_cast<FlowHandle*>(hp)->data->getShallRenderSimulationMeshBoundary() ? 1 : 0; }
+void lvh_compute_smooth_triangle_normals(const uint32_t* indices, uint32_t nTriangles, const float* positions, uint32_t nVertices, float* outNormals) {
+    std::vector<uint32_t> idx(indices, indices + 3 * size_t(nTriangles));
+    std::vector<vec3> pos(nVertices), nrm;
+    if (nVertices) memcpy(pos.data(), positions, size_t(nVertices) * 12);
+    computeSmoothTriangleNormals(idx, pos, nrm);
+    if (nVertices) memcpy(outNormals, nrm.data(), size_t(nVertices) * 12);
 }
 /// the verticesNormalized flag of version-2 .binlines files (read: honoured by loadFromFile; written from this state)
 void lvh_flow_set_vertices_normalized(void* hp, int flag) { static_cast<FlowHandle*>(hp)->flow()->setVerticesNormalized(flag != 0); }

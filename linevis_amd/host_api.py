@@ -42,6 +42,11 @@ def load():
         "lvh_flow_load_binlines": (i32, [vp, cp]),
         "lvh_flow_save_binlines": (i32, [vp, cp]),
         "lvh_flow_set_vertices_normalized": (None, [vp, i32]),
+        "lvh_flow_set_hull_mesh": (None, [vp, vp, u32, vp, vp, u32]),
+        "lvh_flow_get_hull_mesh": (None, [vp, vp, vp, vp, C.POINTER(u32), C.POINTER(u32)]),
+        "lvh_flow_has_simulation_mesh_outline": (i32, [vp]),
+        "lvh_flow_shall_render_hull": (i32, [vp]),
+        "lvh_compute_smooth_triangle_normals": (None, [vp, u32, vp, u32, vp]),
         "lvh_flow_vertices_normalized": (i32, [vp]),
         "lvh_flow_num_lines": (u64, [vp]),
         "lvh_flow_num_points": (u64, [vp]),
@@ -226,6 +231,33 @@ class LineDataFlow:
         if self.L.lvh_flow_load_binlines(self.h, path.encode()) != 0:
             raise IOError("loadTrajectoriesFromBinLines failed for %s" % path)
         return self
+
+    def set_hull_mesh(self, triangle_indices, positions, normals=None):
+        """The simulation-mesh outline (LineData::simulationMeshOutline*): triangle indices [n, 3], positions [m, 3], normals [m, 3] or
+        None = computeSmoothTriangleNormals.  The renderers of modes 5, 8 and 10 draw it (hull_opacity)."""
+        idx = np.ascontiguousarray(triangle_indices, dtype=np.uint32).reshape(-1, 3)
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        self.L.lvh_flow_set_hull_mesh(self.h, _p(idx), len(idx), _p(pos), None if nrm is None else _p(nrm), len(pos))
+        return self
+
+    def hull_mesh(self):
+        """(triangle indices [n, 3], positions [m, 3], normals [m, 3]) of the outline mesh; empty arrays without one"""
+        nt, nv = C.c_uint32(), C.c_uint32()
+        self.L.lvh_flow_get_hull_mesh(self.h, None, None, None, C.byref(nt), C.byref(nv))
+        idx = np.zeros((nt.value, 3), np.uint32)
+        pos, nrm = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32)
+        self.L.lvh_flow_get_hull_mesh(self.h, _p(idx), _p(pos), _p(nrm), None, None)
+        return idx, pos, nrm
+
+    @property
+    def has_simulation_mesh_outline(self):
+        return bool(self.L.lvh_flow_has_simulation_mesh_outline(self.h))
+
+    @property
+    def shall_render_hull(self):
+        """LineData::shallRenderSimulationMeshBoundary: a mesh is there and hull_opacity has not been set to 0"""
+        return bool(self.L.lvh_flow_shall_render_hull(self.h))
 
     def set_vertices_normalized(self, flag=True):
         """Declare the positions handed to set_trajectories as already normalised: saved as verticesNormalized in v2 files."""
@@ -695,3 +727,12 @@ class HeadlessLineRenderer:
         if rc != 0:
             raise capi.LineVisError(rc, "lv_get_stats")
         return s
+
+
+def compute_smooth_triangle_normals(triangle_indices, positions):
+    """The host layer's computeSmoothTriangleNormals (host/LineData.cpp): area-weighted, accumulated in triangle order in float32"""
+    idx = np.ascontiguousarray(triangle_indices, dtype=np.uint32).reshape(-1, 3)
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros_like(pos)
+    load().lvh_compute_smooth_triangle_normals(_p(idx), len(idx), _p(pos), len(pos), _p(out))
+    return out

@@ -12,12 +12,21 @@ import numpy as np
 
 
 @dataclass
+class HullMesh:
+    """The simulation-mesh outline of a version-2 .binlines file (BinLinesLoader.cpp:100-122): what lv_set_hull_mesh takes."""
+    triangle_indices: np.ndarray   # uint32 [T, 3]
+    positions: np.ndarray          # float32 [V, 3]
+    normals: np.ndarray            # float32 [V, 3]
+
+
+@dataclass
 class Trajectories:
     positions: np.ndarray      # float32 [P, 3]
     attributes: np.ndarray     # float32 [P]
     line_offsets: np.ndarray   # uint32 [L + 1]
     ribbon_directions: np.ndarray = None   # float32 [P, 3] or None: band data (LineDataFlow::ribbonsDirections)
     vertices_normalized: bool = False      # verticesNormalized of a version-2 .binlines file (TrajectoryFile.cpp:656 skips normalisation)
+    hull: HullMesh = None                  # the outline mesh of a version-2 .binlines file, as stored (normalize() leaves it alone)
 
     @property
     def num_lines(self):
@@ -53,7 +62,7 @@ def normalize(tr):
     scale3 = np.float32(0.5) / (mx - mn)
     scale = np.float32(scale3.min())
     out = ((p + translation) * scale).astype(np.float32)
-    return Trajectories(np.ascontiguousarray(out), tr.attributes, tr.line_offsets, tr.ribbon_directions)
+    return Trajectories(np.ascontiguousarray(out), tr.attributes, tr.line_offsets, tr.ribbon_directions, hull=tr.hull)
 
 
 def normalize_attributes(att):
@@ -237,8 +246,10 @@ def twisted_ribbons(tr, twist=6.0, seed=3):
 def write_binlines(path, tr, vertices_normalized=None):
     """Version 1: u32 version, u32 numTrajectories, u32 numAttributes, then per trajectory u32 numPoints, vec3[numPoints],
     float[numPoints] per attribute.  With band data version 2: the same, then u32 verticesNormalized, u32 hasAttributeNames (0),
-    u32 hasRibbonData (1), vec3[numPoints] ribbon directions per trajectory, three u32 zeros (no outline mesh)."""
-    v2 = tr.ribbon_directions is not None
+    u32 hasRibbonData, vec3[numPoints] ribbon directions per trajectory, then the outline mesh: u32 index count, u32 vertex count, u32
+    normal count, the three arrays (tr.hull; three zeros without one).  Version 2 is written for band data or an outline mesh."""
+    hull = getattr(tr, "hull", None)
+    v2 = tr.ribbon_directions is not None or hull is not None
     if vertices_normalized is None:
         vertices_normalized = bool(getattr(tr, "vertices_normalized", False))
     with open(path, "wb") as f:
@@ -249,13 +260,22 @@ def write_binlines(path, tr, vertices_normalized=None):
             f.write(np.ascontiguousarray(tr.positions[b:e], dtype="<f4").tobytes())
             f.write(np.ascontiguousarray(tr.attributes[b:e], dtype="<f4").tobytes())
         if v2:
-            f.write(struct.pack("<III", 1 if vertices_normalized else 0, 0, 1))   # verticesNormalized: the real state of the positions
-            f.write(np.ascontiguousarray(tr.ribbon_directions, dtype="<f4").tobytes())   # stored per trajectory = contiguous
-            f.write(struct.pack("<III", 0, 0, 0))
+            has_ribbons = tr.ribbon_directions is not None
+            f.write(struct.pack("<III", 1 if vertices_normalized else 0, 0, 1 if has_ribbons else 0))   # verticesNormalized: the real state of the positions
+            if has_ribbons:
+                f.write(np.ascontiguousarray(tr.ribbon_directions, dtype="<f4").tobytes())   # stored per trajectory = contiguous
+            if hull is None:
+                f.write(struct.pack("<III", 0, 0, 0))
+            else:
+                idx = np.ascontiguousarray(hull.triangle_indices, dtype="<u4").reshape(-1)
+                pos = np.ascontiguousarray(hull.positions, dtype="<f4").reshape(-1, 3)
+                nrm = np.ascontiguousarray(hull.normals, dtype="<f4").reshape(-1, 3)
+                f.write(struct.pack("<III", len(idx), len(pos), len(nrm)))
+                f.write(idx.tobytes() + pos.tobytes() + nrm.tobytes())
 
 
 def read_binlines(path, attribute_index=0):
-    """Reads v1 and v2 files (v2: ribbon directions kept, attribute names and the outline mesh skipped)."""
+    """Reads v1 and v2 files (v2: ribbon directions and the outline mesh (.hull) kept, attribute names skipped)."""
     with open(path, "rb") as f:
         data = f.read()
     (version,) = struct.unpack_from("<I", data, 0)
@@ -289,8 +309,18 @@ def read_binlines(path, attribute_index=0):
         off += 4
         if has_ribbons:
             rib = np.frombuffer(data, dtype="<f4", count=3 * tr.num_points, offset=off).reshape(-1, 3)
+            off += 12 * tr.num_points
             tr = Trajectories(tr.positions, tr.attributes, tr.line_offsets, np.array(rib, dtype=np.float32))
         tr.vertices_normalized = bool(_normalized)
+        n_idx, n_pos, n_nrm = struct.unpack_from("<III", data, off) if off + 12 <= len(data) else (0, 0, 0)
+        off += 12
+        if n_idx:
+            idx = np.frombuffer(data, dtype="<u4", count=n_idx, offset=off)
+            off += 4 * n_idx
+            pos = np.frombuffer(data, dtype="<f4", count=3 * n_pos, offset=off).reshape(-1, 3)
+            off += 12 * n_pos
+            nrm = np.frombuffer(data, dtype="<f4", count=3 * n_nrm, offset=off).reshape(-1, 3)
+            tr.hull = HullMesh(np.array(idx, dtype=np.uint32).reshape(-1, 3), np.array(pos, dtype=np.float32), np.array(nrm, dtype=np.float32))
     return tr
 
 
@@ -302,6 +332,59 @@ def load_flow_trajectories(path):
     out = normalize(tr)
     out.vertices_normalized = True
     return out
+
+
+# ------------------------------------------------------------------ the simulation-mesh hull
+def compute_smooth_triangle_normals(triangle_indices, positions):
+    """Per-vertex normals for a mesh that has none (the reference takes sgl::computeSmoothTriangleNormals, which is not vendored: the
+    definition is the build's, host/LineData.cpp states the same): the face normals cross(p1 - p0, p2 - p0) -- length = twice the
+    area, so the average is area-weighted -- are added to their three vertices in triangle order, in float32, and the sums are
+    normalised (a zero sum stays zero)."""
+    f = np.float32
+    idx = np.ascontiguousarray(triangle_indices, dtype=np.uint32).reshape(-1, 3)
+    pos = np.ascontiguousarray(positions, dtype=f).reshape(-1, 3)
+    a = pos[idx[:, 1]] - pos[idx[:, 0]]
+    b = pos[idx[:, 2]] - pos[idx[:, 0]]
+    fn = np.stack([a[:, 1] * b[:, 2] - b[:, 1] * a[:, 2], a[:, 2] * b[:, 0] - b[:, 2] * a[:, 0], a[:, 0] * b[:, 1] - b[:, 0] * a[:, 1]], 1).astype(f)
+    nrm = np.zeros_like(pos)
+    np.add.at(nrm, idx.reshape(-1), np.repeat(fn, 3, axis=0))   # unbuffered: element by element, in triangle order
+    ln = np.sqrt((nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]) + nrm[:, 2] * nrm[:, 2]).astype(f)
+    with np.errstate(all="ignore"):
+        return np.where(ln[:, None] > 0, nrm / ln[:, None], f(0.0)).astype(f)
+
+
+def box_hull(aabb, n, margin=0.0):
+    """A closed box around aabb = (min xyz, max xyz), `margin` wider on every side: n x n quads per face, 12 n^2 triangles wound
+    counter-clockwise seen from outside, 6 n^2 + 2 vertices shared along the box's edges, smooth normals."""
+    lo = np.asarray(aabb[0], dtype=np.float64) - margin
+    hi = np.asarray(aabb[1], dtype=np.float64) + margin
+    ids = {}
+    pos = []
+
+    def vid(i, j, k):
+        key = (i, j, k)
+        if key not in ids:
+            ids[key] = len(pos)
+            pos.append(lo + (hi - lo) * (np.array(key, dtype=np.float64) / n))
+        return ids[key]
+
+    tris = []
+    for axis in range(3):
+        u, v = (axis + 1) % 3, (axis + 2) % 3
+        for side in (0, n):
+            for a in range(n):
+                for b in range(n):
+                    def at(da, db):
+                        c = [0, 0, 0]
+                        c[axis], c[u], c[v] = side, a + da, b + db
+                        return vid(*c)
+                    q = [at(0, 0), at(1, 0), at(1, 1), at(0, 1)]       # counter-clockwise seen from +axis
+                    if side == 0:
+                        q = q[::-1]
+                    tris += [(q[0], q[1], q[2]), (q[0], q[2], q[3])]
+    idx = np.asarray(tris, dtype=np.uint32)
+    p = np.asarray(pos, dtype=np.float32)
+    return HullMesh(idx, p, compute_smooth_triangle_normals(idx, p))
 
 
 # ------------------------------------------------------------------ .obj polylines (ObjLoader.cpp:36-186)
