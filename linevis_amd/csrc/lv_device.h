@@ -87,6 +87,11 @@
 #ifndef LV_NODE_MIN_ACTIVE
 #define LV_NODE_MIN_ACTIVE 24  // node loop yields to the leaf loop when fewer lanes than this are descending
 #endif
+// k_ao_rays, measurement knob (EXPERIMENTS.md section 21).
+// LV_AO_SCALAR_STATE=0: a wave's queue chunk reaches its lanes through __shfl, which leaves the loop's wave-level state in vector registers.
+#ifndef LV_AO_SCALAR_STATE
+#define LV_AO_SCALAR_STATE 1
+#endif
 
 #ifndef LV_HANDOVER_MAX_BUSY
 #define LV_HANDOVER_MAX_BUSY 32 // cooperative closest hit: idle lanes take over stacked subtrees once at most this many lanes descend

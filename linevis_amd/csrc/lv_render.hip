@@ -503,6 +503,8 @@ __device__ __forceinline__ void lv_ao_generate_ray(const LvUniforms& U, float4 g
 // Scheduling inside a wave: test when >= 64 pairs wait; refill when >= LV_REFILL_THRESHOLD lanes are idle; otherwise
 // descend; flush partial batches only when nothing else can make progress.  Once the global queue is empty (drain) the
 // rays left in a wave are finished together: nobody retires early, idle lanes take over stacked subtrees of busy ones.
+// All wave-level state (queue chunk, s_gen window, FIFO head / tail, the decisions above) derives from ballots, kernel arguments
+// and readfirstlane, so the compiler keeps it in scalar registers and takes the decisions with scalar branches (LV_AO_SCALAR_STATE).
 // Resources: 31 KB LDS and <= 96 VGPRs -> 5 workgroups = 20 waves per CU; the kernel is VALU-issue-bound and needs that
 // occupancy to hide the dependent node fetches (12 -> 16 -> 20 waves per CU: -16 %, -7 %).
 // BAKE: the static prebaker's rays (VulkanAmbientOcclusionBaker.glsl:230-281).  G-buffer slot = parametrisation vertex *
@@ -563,7 +565,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
     bool hasRay = false, enq = false;
     unsigned long long r = 0;
     f3 inv = mk3(0, 0, 0), oi = mk3(0, 0, 0);
-    float best = 0.0f;
+    float tHi = 0.0f; // upper end of the node steps' slab interval: the ray's best hit (or aoRadius) + litSlack, summed where the hit changes
     unsigned cur = LV_INVALID, lastSeq = 0;
     unsigned owner = lane; // lane whose ray this lane descends for: its own, except in the drain phase (below)
     // queued (owner, leaf) pairs that start a test phase: a little less than a full wave -- the stint ends sooner for the lanes whose
@@ -639,7 +641,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             {
                 const lv_ao_key key = keyW[owner];
-                best = lv_ao_key_t(key); // shrinks the slab interval of the following node steps
+                tHi = lv_ao_key_t(key) + litSlack; // shrinks the slab interval of the following node steps
                 if (ANY_HIT && key != keyInit) { cur = LV_INVALID; st.clear(); }
             }
             continue;
@@ -674,7 +676,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                             const float2 r0 = rayW[3 * owner], r1 = rayW[3 * owner + 1], r2 = rayW[3 * owner + 2];
                             inv = lv_traversal_inv(mk3(r1.y, r2.x, r2.y));
                             oi = mk3(r0.x * inv.x, r0.y * inv.y, r1.x * inv.z);
-                            best = lv_ao_key_t(keyW[owner]);
+                            tHi = lv_ao_key_t(keyW[owner]) + litSlack;
                             st.clear();
                         }
                     }
@@ -689,7 +691,16 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                 if (chunkNext >= chunkEnd) {
                     unsigned long long base = 0;
                     if (lane == 0) base = atomicAdd(&dc->aoQueueHead, (unsigned long long)chunk);
+#if LV_AO_SCALAR_STATE
+                    // lane 0's value through readfirstlane, which the compiler knows to be wave-uniform: everything derived from it
+                    // (sourceDry, canRefill, drain, genCount, genPos, head, tail and the loop's decisions) then is provably uniform too --
+                    // scalar registers and scalar branches.  Through __shfl it counts as divergent, and with it the whole main loop:
+                    // counters in vector registers, decisions as lane masks, a dozen vector copies on every trip round the loop.
+                    chunkNext = (unsigned long long)__builtin_amdgcn_readfirstlane(unsigned(base)) |
+                                ((unsigned long long)__builtin_amdgcn_readfirstlane(unsigned(base >> 32)) << 32);
+#else
                     chunkNext = __shfl(base, 0, 64);
+#endif
                     chunkEnd = chunkNext + chunk;
                     if (chunkEnd > total) chunkEnd = total;
                     if (chunkNext >= total) { chunkNext = chunkEnd = total; sourceDry = true; }
@@ -752,7 +763,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                     keyW[lane] = keyInit;
                     inv = lv_traversal_inv(mk3(r1.y, r2.x, r2.y));
                     oi = mk3(r0.x * inv.x, r0.y * inv.y, r1.x * inv.z);
-                    best = U.aoRadius;
+                    tHi = U.aoRadius + litSlack;
                     r = genBase + gs;
                     owner = lane;
                     cur = 0;
@@ -774,7 +785,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             do {
                 if (STATS && lane == 0) { phIt[1]++; }
                 if (STATS && !(cur & LV_LEAF_BIT)) phLn[1]++;
-                if (!(cur & LV_LEAF_BIT)) cur = lv_node_step<STATS>(S, cur, oi, inv, 0.0f - litSlack, best + litSlack, st, cnt);
+                if (!(cur & LV_LEAF_BIT)) cur = lv_node_step<STATS>(S, cur, oi, inv, 0.0f - litSlack, tHi, st, cnt);
                 const bool isLeaf = cur != LV_INVALID && (cur & LV_LEAF_BIT);
                 const unsigned long long mL = __ballot(isLeaf);
                 if (mL) {

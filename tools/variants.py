@@ -31,6 +31,7 @@ PRESETS = {
     "spill12": "-DLV_STACK_SPILL_BLOCK=12",
     "ao_lds15": "-DLV_AO_STACK_LDS=15",
     "ao_lds16": "-DLV_AO_STACK_LDS=16",
+    "noscalar": "-DLV_AO_SCALAR_STATE=0",                          # k_ao_rays: queue chunk through __shfl, wave-level state in vector registers
 }
 
 
