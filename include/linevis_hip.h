@@ -396,6 +396,25 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   DepthPeelingRenderer.cpp:86 reset the pass) and none here: they render the same frame with or without a mesh.  Modes 1, 2, 3
  *   and 11 are not built for the hull yet: while a hull would be drawn lv_render returns LV_E_INVALID for them (the message names
  *   modes 5, 8 and 10; the context stays usable); with hull_opacity 0 or no mesh they render as without these keys, byte for byte.
+ *   line_primitive_mode: "Tube (Programmable Pull)" (default: the programmable-pull N-gon prism, today's frames byte for byte) |
+ *   "Quads (Programmable Pull)" (LineData::LinePrimitiveMode by its display name, LineData.cpp:56-74; LinePassQuads.glsl): two
+ *   camera-facing triangles per segment, shaded as a round tube from one interpolated coordinate.  Every other name of the reference's
+ *   list ("Quads (Geometry Shader)", "Tube (Geometry Shader)", "Tube (Triangle Mesh)", the mesh-shader and ribbon modes) is
+ *   LV_E_INVALID with a message that says the mode is not built, and the old value stays.  While quads are selected: rendering modes
+ *   5, 8 and 10 draw their line pass with quads (the hull pass, tile lists, shards and lv_create_multi handles as before; RTAO (Screen
+ *   Space) and depth cues are supported); modes 2, 3, 6 and 9 return LV_E_INVALID (the message names modes 5, 8 and 10; the context
+ *   stays usable); modes 1 and 11 ignore the option, as the reference, which never reads linePrimitiveMode there.  With quads,
+ *   LV_E_INVALID also for use_ribbons, rotating_helicity_bands, ambient_occlusion_mode = "RTAO (Prebaker)" (its lookup needs
+ *   phi = asin(x)), ppll_fragment_source = capsule_entry and ppll_prism_rasteriser = lbvh.  shading_numerics = fast: quads are shaded
+ *   by the exact path.  Build-owned definitions: line point i yields vertex 2 i (shiftSign -1) and 2 i + 1 (+1) at
+ *   linePoint + ((shiftSign * lineWidth) * 0.5) * offsetDirection, offsetDirection = normalize(cross(normalize(cameraPosition -
+ *   linePoint), normalize(tangent))), in float32 with the shading code's normalize; triangles (2a, 2b, 2b + 1), (2a, 2b + 1, 2a + 1);
+ *   coverage, fill rule, perspective-correct weights and the three kept rules are the prism's; a quad is front-facing by construction,
+ *   only the flipped triangle of a bow-tie is culled; a point whose tangent is parallel to its view direction gets a zero offset (the
+ *   shading code's normalize of a zero vector is zero, not NaN): a line seen exactly end-on draws nothing, and no colour is NaN.  Where GLSL
+ *   leaves asin / sin / cos to the driver the normal is xc = clamp(x, -1, 1), fragmentNormal = sqrt(fma(-xc, xc, 1)) *
+ *   normalize(normal0) + xc * normalize(normal1); EPSILON_WHITE = fwidth(|x|) comes from the 2 x 2 partners' rays on the same
+ *   triangle.  Timer: the quads pass is what LV_KERNEL_PPLL_RASTER times in these frames.
  *   deferred_rendering_mode: "Draw Indexed" (the reference's default, DeferredRenderer.hpp:297) only; draw_indexed_geometry_mode:
  *   "Precomputed Triangles" (:300) only; supersampling: 1 only.  The other values the reference knows ("Draw Indirect", "Task/Mesh
  *   Shader", "BVH Draw Indirect", "BVH Mesh Shader"; "Programmable Pulling"; 2, 4, 8 ...) are LV_E_INVALID with a message that says the
@@ -923,6 +942,20 @@ int lv_get_hull_mesh(lv_ctx* ctx, uint32_t* out_triangle_indices, uint32_t max_t
  * call of the last frame reads. */
 int lv_hull_get_fragments(lv_ctx* ctx, uint32_t* pixel, uint32_t* triangle, float* depth, float* rgba, uint64_t capacity,
                           uint64_t* out_count);
+/* Every kept line-quad fragment of the last frame, when that was a mode-5, mode-8 or mode-10 frame over the WHOLE viewport (lv_render,
+ * lv_render_device; not a tile list: such a frame fills the AO image for its tiles only) drawn with line_primitive_mode = "Quads
+ * (Programmable Pull)": unordered, evaluated again on the line data, the AO image and the depth range the frame left in the context --
+ * the inspection entry point of the quads' fragment stage, as lv_hull_get_fragments is the hull's.  pixel = y * width + x; segment: the
+ * index of the segment in the caller's order; triangle: 0 = (2a, 2b, 2b + 1), 1 = (2a, 2b + 1, 2a + 1); the window depth; the straight
+ * float32 colour (4 floats per fragment).  No alpha discard: that belongs to a mode.  *out_count is always the number of fragments; a
+ * smaller capacity returns LV_E_CAPACITY and writes nothing else.  Any output array may be NULL.  LV_E_STATE when the last frame was no
+ * such frame (a tube frame, a tile list, another mode, a refused call), and when what the pass reads is no longer the frame's: after
+ * lv_set_lines / lv_set_trajectories[_with_bands], a changed line_width, a viewport of another size (lv_set_camera), or a change of
+ * whether the lighting reads the AO image (ambient_occlusion_mode / _strength) -- render the frame again.  A camera pose, colour or
+ * strength changed since the frame changes the answer only: call it before changing them.  Touches nothing a *_get_* call of the last
+ * frame reads. */
+int lv_line_quads_get_fragments(lv_ctx* ctx, uint64_t capacity, uint32_t* pixel, uint32_t* segment, uint32_t* triangle, float* depth,
+                                float* rgba, uint64_t* out_count);
 /* Test entry point of the SVGF denoiser: one SVGFDenoiser::denoise() (SVGF.glsl Compute-Reproject, Compute-Filter-Moments,
  * svgf_denoiser_iterations x Compute-ATrous, the history copies of SVGF.cpp) on caller-supplied images of w x h pixels (1 ... 16384
  * each), row-major.  Inputs: noisy = 1 float per pixel (the raw AO), normal_depth = 4 floats {world normal xyz, depth}, flow_fwidth =

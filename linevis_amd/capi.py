@@ -115,7 +115,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
-           "lv_set_hull_mesh", "lv_get_hull_mesh", "lv_hull_get_fragments",
+           "lv_set_hull_mesh", "lv_get_hull_mesh", "lv_hull_get_fragments", "lv_line_quads_get_fragments",
            "lv_create_multi", "lv_multi_ranks", "lv_multi_rank_stats", "lv_multi_rebalance", "lv_multi_deal", "lv_tile_deal", "lv_make_tiles"]
 
 # function -> (LV_FN_* id, argument words, result words) of lv_selftest_eval
@@ -206,6 +206,7 @@ def load():
         ("lv_set_hull_mesh", [vp, vp, u32, vp, vp, u32]),
         ("lv_get_hull_mesh", [vp, vp, u32, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
         ("lv_hull_get_fragments", [vp, vp, vp, vp, vp, u64, C.POINTER(u64)]),
+        ("lv_line_quads_get_fragments", [vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
@@ -419,6 +420,23 @@ class Context:
         self._ck(self.L.lv_hull_get_fragments(self.h, _p(pix), _p(tri), _p(z), _p(rgba), int(capacity), C.byref(n)))
         k = n.value
         return pix[:k], tri[:k], z[:k], rgba[:k]
+
+    def line_quad_fragments(self, capacity=None):
+        """lv_line_quads_get_fragments: every kept line-quad fragment of the last whole-viewport mode-5, 8 or 10 frame drawn with line_primitive_mode =
+        "Quads (Programmable Pull)", unordered: (pixel = y * width + x, segment, triangle 0 | 1, window depth, straight rgba [n, 4]).
+        capacity None: as many as there are."""
+        n = C.c_uint64(0)
+        if capacity is None:
+            rc = self.L.lv_line_quads_get_fragments(self.h, 0, None, None, None, None, None, C.byref(n))
+            if rc not in (LV_OK, -4):
+                self._ck(rc)
+            capacity = n.value
+        cap = max(int(capacity), 1)
+        pix, seg, tri = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        z, rgba = np.zeros(cap, dtype=np.float32), np.zeros((cap, 4), dtype=np.float32)
+        self._ck(self.L.lv_line_quads_get_fragments(self.h, int(capacity), _p(pix), _p(seg), _p(tri), _p(z), _p(rgba), C.byref(n)))
+        k = n.value
+        return pix[:k], seg[:k], tri[:k], z[:k], rgba[:k]
 
     def set_transfer_function(self, rgba, attr_min=0.0, attr_max=1.0):
         tf = np.ascontiguousarray(rgba, dtype=np.float32).reshape(-1, 4)

@@ -381,6 +381,14 @@ int lv_hull_get_fragments(lv_ctx* ctx, uint32_t* pixel, uint32_t* triangle, floa
     return lv_frame_hull_fragments(ctx, pixel, triangle, depth, rgba, capacity, out_count);
 }
 
+int lv_line_quads_get_fragments(lv_ctx* ctx, uint64_t capacity, uint32_t* pixel, uint32_t* segment, uint32_t* triangle, float* depth,
+                                float* rgba, uint64_t* out_count) {
+    if (!ctx) return LV_E_INVALID;
+    if (!out_count) return lv_fail(ctx, LV_E_INVALID, "lv_line_quads_get_fragments: out_count is null");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_line_quads_fragments(ctx, pixel, segment, triangle, depth, rgba, capacity, out_count);
+}
+
 int lv_set_ao_parametrization(lv_ctx* ctx, const float* blending_weights, uint32_t num_line_vertices,
                               const float* sampling_locations, uint32_t num_parametrization_vertices) {
     if (!ctx) return LV_E_INVALID;
@@ -773,6 +781,22 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         if (strcmp(value, "true") == 0 || strcmp(value, "1") == 0) o.hullUseShading = true;
         else if (strcmp(value, "false") == 0 || strcmp(value, "0") == 0) o.hullUseShading = false;
         else return bad();
+    } else if (k == "line_primitive_mode") {
+        // LineData::LinePrimitiveMode by its display name (LineData.cpp:56-74): the programmable-pull prism (default) or the
+        // view-aligned line quads of modes 5, 8 and 10 (lv_linequad.h); the other names of the reference's list are not built
+        static const char* const notBuilt[] = {"Quads (Geometry Shader)", "Tube (Geometry Shader)", "Tube (Triangle Mesh)", "Tube (Mesh Shader)",
+                                               "Tube (Mesh Shader NV)", "Ribbon Quads (Geometry Shader)", "Tube Ribbons (Programmable Pull)",
+                                               "Tube Ribbons (Geometry Shader)", "Tube Ribbons (Triangle Mesh)", "Tube Ribbons (Mesh Shader)",
+                                               "Tube Ribbons (Mesh Shader NV)"};
+        if (strcmp(value, "Tube (Programmable Pull)") == 0) o.lineQuads = false;
+        else if (strcmp(value, "Quads (Programmable Pull)") == 0) o.lineQuads = true;
+        else {
+            for (const char* name : notBuilt)
+                if (strcmp(value, name) == 0)
+                    return lv_fail(ctx, LV_E_INVALID, "line_primitive_mode = '%s' is not built (\"Tube (Programmable Pull)\" and "
+                                                      "\"Quads (Programmable Pull)\" are)", value);
+            return bad();
+        }
     } else if (k == "wboit_depth_weight") {
         // the depth weight of the WBOIT renderer (rendering mode 8): the line WBOITGather.glsl:23 runs, or the one it keeps as a comment
         if (strcmp(value, "reference") == 0) o.wboitOpenglWeight = false;

@@ -91,6 +91,7 @@ struct LvOptions {
     uint32_t peelMaxLayers = 2000;            // depth_peeling_max_layers: the cap of rendering mode 9's passes, 1 ... 2000 (DepthPeelingRenderer.cpp:288)
     uint32_t dcMaxColour = 0;                 // depth_complexity_max_colour: 0 = auto (numFragmentsMaxColor from the frame's maximum), else that value
     bool mboitStreamed = false;               // mboit_fragment_storage: false = "pool" (default), true = "streamed" (k_mboit_stream_pass: no fragment pool)
+    bool lineQuads = false;                   // line_primitive_mode: false = "Tube (Programmable Pull)", true = "Quads (Programmable Pull)" (lv_linequad.h)
     // the simulation-mesh hull (lv_hull.h): hull_opacity (0.3, LineData.hpp:474; hullOpacitySet: the key has been set -- the reference's
     // shallRenderSimulationMeshBoundary is false until the setting arrives, LineData.cpp:142-145), hull_color (the linear value of sRGB
     // 0.5, LineData.hpp:472-473), hull_use_shading (:475)
@@ -273,6 +274,12 @@ struct lv_ctx {
         uint32_t w = 0, h = 0;                // its viewport
         uint32_t tile[2] = {0, 0};            // its ppll tile
         uint32_t param = 0;                   // mode 6: the moment count N; mode 10: the layer count K
+        // modes 5, 8, 10: the line pass drew line quads.  lv_line_quads_get_fragments evaluates the pass again on the context's resident
+        // line data and AO image, so it also asks that these are still the frame's: the segment count and whether the lighting read the
+        // AO image, as recorded here
+        bool quads = false;
+        uint32_t quadsSegs = 0;
+        bool quadsAo = false;
     } streamed;
     bool ppllArrays = false;                  // the last PPLL frame left per-pixel runs (raster_prism), not linked lists
     LvDeviceBuffer tilesDev, outDev, scratchRays, stackOverflow, mlatTrace;
@@ -425,6 +432,8 @@ int lv_frame_peel_resolve_only(lv_ctx* ctx, const uint32_t* entries, uint64_t nu
                                uint8_t* out, float* outAccum, uint32_t* outLayers);
 int lv_frame_deferred_buffers(lv_ctx* ctx, uint32_t* outPrimitive, float* outDepth, uint64_t capacityPixels);
 int lv_frame_deferred_shade_only(lv_ctx* ctx, const uint32_t* primitive, const float* depth, uint32_t w, uint32_t h, uint32_t* out);
+int lv_frame_line_quads_fragments(lv_ctx* ctx, uint32_t* outPixel, uint32_t* outSegment, uint32_t* outTriangle, float* outDepth, float* outRgba,
+                                  uint64_t capacity, uint64_t* outCount);
 int lv_frame_hull_fragments(lv_ctx* ctx, uint32_t* outPixel, uint32_t* outTriangle, float* outDepth, float* outRgba, uint64_t capacity,
                             uint64_t* outCount);
 int lv_frame_al64_num_layers(lv_ctx* ctx, uint32_t* out);

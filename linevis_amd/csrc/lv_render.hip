@@ -28,6 +28,7 @@
 #include "lv_peel.h"
 #include "lv_deferred.h"
 #include "lv_hull.h"
+#include "lv_linequad.h"
 
 namespace {
 
@@ -4464,6 +4465,10 @@ static int lv_streamed_close(lv_ctx* ctx, const LvTiles& T, uint32_t& numGroups)
 // it -- the last frame was a `mode` frame over the whole viewport, and the viewport is still that one
 static void lv_streamed_done(lv_ctx* ctx, const LvUniforms& U, int mode, uint32_t param = 0u) {
     ctx->streamed = {mode, ctx->tilesCoverViewport, U.width, U.height, {U.ppllTileW, U.ppllTileH}, param};
+    ctx->streamed.quads = ctx->opt.lineQuads && (mode == LV_RENDERING_MODE_DEPTH_COMPLEXITY || mode == LV_RENDERING_MODE_WBOIT ||
+                                                 mode == LV_RENDERING_MODE_ATOMIC_LOOP_64);
+    ctx->streamed.quadsSegs = ctx->numSegs;
+    ctx->streamed.quadsAo = U.useAmbientOcclusion && !U.aoPrebaked;
 }
 static bool lv_streamed_is(const lv_ctx* ctx, int mode) {
     const lv_ctx::StreamedFrame& r = ctx->streamed;
@@ -4659,6 +4664,66 @@ int lv_frame_hull_fragments(lv_ctx* ctx, uint32_t* outPixel, uint32_t* outTriang
     return LV_OK;
 }
 
+// ---- Line quads (lv_linequad.h): line_primitive_mode = "Quads (Programmable Pull)" replaces the prism pass of modes 5, 8 and 10 ----
+static LvLineQuadList lv_linequad_no_list() { return {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0ull}; }
+
+// lv_line_quads_get_fragments: the LIST store over the whole viewport, twice -- the count, then (when the caller's capacity holds it) the
+// fragments into ctx->scratchRays, as lv_frame_hull_fragments.  The pass reads what the frame read: the leaf-ordered segments, the AO
+// image and the depth range the frame left in the context, under the current camera and options
+int lv_frame_line_quads_fragments(lv_ctx* ctx, uint32_t* outPixel, uint32_t* outSegment, uint32_t* outTriangle, float* outDepth, float* outRgba,
+                                  uint64_t capacity, uint64_t* outCount) {
+    const lv_ctx::StreamedFrame& r = ctx->streamed;
+    if (!r.quads || !r.full)   // (lv_streamed_done; a tile-list frame filled the AO image for its tiles only)
+        return lv_fail(ctx, LV_E_STATE, "lv_line_quads_get_fragments: the last frame was not a mode-5, mode-8 or mode-10 frame over the whole "
+                                        "viewport drawn with line_primitive_mode = \"Quads (Programmable Pull)\"");
+    // The pass runs again on what the frame read, which has to be the frame's still: the viewport (the AO image has its size), the
+    // leaf-ordered segment records (lv_set_lines / lv_set_trajectories / a line-width or band switch end their validity) and the AO image
+    // (an AO mode switched on since would read an image no frame wrote).  Anything else -- camera pose, colours, strengths -- only
+    // changes the answer
+    LvUniforms U;
+    lv_fill_uniforms(ctx, U);
+    U.aoProjectLookup = 0u;
+    const bool aoNow = U.useAmbientOcclusion && !U.aoPrebaked;
+    if (r.w != ctx->width || r.h != ctx->height || !ctx->accelValid || ctx->accelLineWidth != lv_accel_width(ctx) ||
+        r.quadsSegs != ctx->numSegs || !ctx->segs.ptr || !ctx->prismFrames.ptr || !ctx->leafSeg.ptr || aoNow != r.quadsAo ||
+        (aoNow && (ctx->aoW != ctx->width || ctx->aoH != ctx->height || !(ctx->aoResult || ctx->ao.ptr))) || U.aoPrebaked ||
+        ctx->opt.useRibbons || ctx->opt.helicityBands)
+        return lv_fail(ctx, LV_E_STATE, "lv_line_quads_get_fragments: the viewport, the line data or the ambient occlusion mode changed since "
+                                        "the frame: render it again");
+    hipStream_t st = ctx->stream;
+    int rc;
+    LvSceneDev S = sceneDev(ctx);
+    lv_fill_prism(ctx, U, S.prism);
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, 8))) return rc;
+    LvLineQuadList L = lv_linequad_no_list();
+    L.counter = (unsigned long long*)ctx->scratchRays.ptr;
+    unsigned long long count = 0ull;
+    LV_HIP(ctx, hipMemsetAsync(L.counter, 0, 8, st));
+    lv_linequad_launch(st, LV_LINEQUAD_STORE_LIST, U, S, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, false, L);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(&count, L.counter, 8, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    *outCount = count;
+    if (capacity < count)
+        return lv_fail(ctx, LV_E_CAPACITY, "lv_line_quads_get_fragments: %llu fragments, capacity %llu", count, (unsigned long long)capacity);
+    if (count == 0ull || (!outPixel && !outSegment && !outTriangle && !outDepth && !outRgba)) return LV_OK;
+    // {counter, pad}, rgba (16 B), pixel, segment, triangle, depth (4 B each) per fragment
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, 16 + size_t(count) * 32))) return rc;
+    char* base = (char*)ctx->scratchRays.ptr;
+    L.counter = (unsigned long long*)base;
+    L.rgba = (float4*)(base + 16);
+    L.pixel = (uint32_t*)(base + 16 + size_t(count) * 16);
+    L.segment = L.pixel + size_t(count);
+    L.triangle = L.segment + size_t(count);
+    L.depth = (float*)(L.triangle + size_t(count));
+    L.capacity = count;
+    LV_HIP(ctx, hipMemsetAsync(L.counter, 0, 8, st));
+    lv_linequad_launch(st, LV_LINEQUAD_STORE_LIST, U, S, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, false, L);
+    return lv_read_back(ctx, {{outRgba, L.rgba, size_t(count) * 16}, {outPixel, L.pixel, size_t(count) * 4},
+                              {outSegment, L.segment, size_t(count) * 4}, {outTriangle, L.triangle, size_t(count) * 4},
+                              {outDepth, L.depth, size_t(count) * 4}});
+}
+
 // The middle of a mode-8 or mode-10 frame, between the clear of the mode's buffer and the close: the phase mark and ONE launch of
 // k_stream_pass<MODE> on `buf` and `arg`.  LV_KERNEL_PPLL_RASTER: the pass with what a sharded frame runs in front of it (as in
 // modes 2, 3 and 6)
@@ -4674,7 +4739,11 @@ static int lv_stream_pass(lv_ctx* ctx, const LvUniforms& U, const LvSceneDev& S,
 #define LV_LAUNCH_STREAM(NT, SH, FA)                                                                                            \
     k_stream_pass<MODE, NT, SH, FA><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr,                   \
             (uint32_t*)ctx->ppllCount.ptr, buf, dc, F.allRequested ? 1u : 0u, leafList, arg, stats ? 1u : 0u)
-    if (S.numSegs != 0) LV_SELECT_STREAM_PASS(LV_LAUNCH_STREAM);
+    if (ctx->opt.lineQuads)   // line_primitive_mode = "Quads (Programmable Pull)": the pass of lv_linequad.hip on the same buffers
+        lv_linequad_launch(st, MODE == LV_RENDERING_MODE_WBOIT ? LV_LINEQUAD_STORE_WBOIT : LV_LINEQUAD_STORE_AL64, U, S, leafList,
+                           F.allRequested ? nullptr : (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, buf, arg, dc, stats,
+                           lv_linequad_no_list());
+    else if (S.numSegs != 0) LV_SELECT_STREAM_PASS(LV_LAUNCH_STREAM);
 #undef LV_LAUNCH_STREAM
     return lv_segment_raster_end(ctx);
 }
@@ -4793,7 +4862,10 @@ static int lv_dc_count(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles&
     if (ctx->opt.timerMask >> 31) LV_HIP(ctx, hipEventRecord(ctx->ev[11], st));
     if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
     const uint32_t passGrid = uint32_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU;
-    if (S.numSegs != 0) {
+    if (!peel && ctx->opt.lineQuads) {   // line_primitive_mode = "Quads (Programmable Pull)" (mode 9 with quads: lv_frame_check)
+        lv_linequad_launch(st, LV_LINEQUAD_STORE_COUNT, U, S, leafList, allRequested ? nullptr : (const uint32_t*)ctx->ppllStart.ptr,
+                           (uint32_t*)ctx->ppllCount.ptr, nullptr, 0u, dc, stats, lv_linequad_no_list());
+    } else if (S.numSegs != 0) {
         if (S.prism.n == 6u)
             k_dc_count_pass<6><<<passGrid, LV_BLOCK, 0, st>>>(U, S, (const uint32_t*)ctx->ppllStart.ptr, (uint32_t*)ctx->ppllCount.ptr, dc,
                                                              allRequested ? 1u : 0u, leafList, stats ? 1u : 0u);
@@ -5031,6 +5103,22 @@ static int lv_frame_check(lv_ctx* ctx, int mode) {
                                mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mode == LV_RENDERING_MODE_MLAB))
         return lv_fail(ctx, LV_E_INVALID, "mode %d does not draw the simulation-mesh hull yet: modes 5 (depth complexity), 8 (WBOIT) and 10 "
                                           "(Atomic Loop 64) do; set hull_opacity = 0 or remove the mesh (lv_set_hull_mesh with 0 triangles)", mode);
+    // line_primitive_mode = "Quads (Programmable Pull)": drawn by modes 5, 8 and 10; modes 1 and 11 never read the primitive mode (as the
+    // reference); the others are not built for it, nor are the line data variants below (lv_linequad.h)
+    if (ctx->opt.lineQuads && fragments) {
+        if (mode != LV_RENDERING_MODE_DEPTH_COMPLEXITY && mode != LV_RENDERING_MODE_WBOIT && mode != LV_RENDERING_MODE_ATOMIC_LOOP_64)
+            return lv_fail(ctx, LV_E_INVALID, "mode %d does not draw line_primitive_mode = \"Quads (Programmable Pull)\": modes 5 (depth "
+                                              "complexity), 8 (WBOIT) and 10 (Atomic Loop 64) do; set it back to \"Tube (Programmable Pull)\"", mode);
+        if (ctx->opt.useRibbons)
+            return lv_fail(ctx, LV_E_INVALID, "line quads: use_ribbons (ribbon quads) is not built");
+        if (ctx->opt.helicityBands)
+            return lv_fail(ctx, LV_E_INVALID, "line quads: rotating_helicity_bands is not built");
+        if (ctx->opt.aoPrebaked)
+            return lv_fail(ctx, LV_E_INVALID, "line quads: ambient_occlusion_mode = \"RTAO (Prebaker)\" is not built (its lookup needs "
+                                              "phi = asin(x)); \"RTAO (Screen Space)\" is");
+        if (ctx->opt.ppllPrismLbvhWalk)
+            return lv_fail(ctx, LV_E_INVALID, "line quads: ppll_prism_rasteriser = lbvh is not supported");
+    }
     return LV_OK;
 }
 

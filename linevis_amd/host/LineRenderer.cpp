@@ -371,6 +371,11 @@ void LineRenderer::updateNewLineData(LineDataPtr& newLineData, bool isNewData) {
     reRender = true;
 }
 
+bool rendererDrawsLinePrimitiveMode(int renderingMode) {
+    return renderingMode == LV_RENDERING_MODE_DEPTH_COMPLEXITY || renderingMode == LV_RENDERING_MODE_WBOIT ||
+           renderingMode == LV_RENDERING_MODE_ATOMIC_LOOP_64;
+}
+
 // camera / clear colour / transfer function / geometry -> context (LineData::updateVulkanUniformBuffers,
 // LineData.cpp:1275-1319, and the buffer fetches of RayTracingRenderPass::setLineData, VulkanRayTracer.cpp:370-411)
 bool LineRenderer::uploadFrameState() {
@@ -457,6 +462,12 @@ bool LineRenderer::uploadFrameState() {
             setOption("hull_color", colour);
             setOption("hull_use_shading", lineData->getHullUseShading() ? "true" : "false");
         }
+        // LineData::linePrimitiveMode, for the renderers whose line pass draws it (rendering modes 5, 8 and 10): the view-aligned quads of
+        // "Quads (Programmable Pull)", else the programmable-pull prism every plugin draws.  The other plugins pass nothing on: they
+        // keep drawing the prism whatever the mode says.
+        if (rendererDrawsLinePrimitiveMode(int(getRenderingMode())))
+            setOption("line_primitive_mode", LineData::getLinePrimitiveMode() == LineData::LINE_PRIMITIVES_QUADS_PROGRAMMABLE_PULL
+                                                     ? "Quads (Programmable Pull)" : "Tube (Programmable Pull)");
         // the trajectories themselves go to HBM (once per data set, with the ribbon directions and the helicity attribute when the data has
         // them) and the device writes the line points, the index pairs and -- whenever a frame needs them at another line width / band
         // setting -- the triangle tubes; use_device_geometry = false or more than 2^26-1 points: host-built render data.  After the

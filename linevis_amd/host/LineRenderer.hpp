@@ -192,6 +192,11 @@ void computeAmbientOcclusionParametrization(const std::vector<std::vector<vec3>>
                                             std::vector<float>& samplingLocations);
 
 // ---------------------------------------------------------------- renderers
+/// The renderers whose line pass draws the line primitive LineData::getLinePrimitiveMode() selects, where the library builds it: rendering
+/// modes 5, 8 and 10 ("Quads (Programmable Pull)" besides the prism).  Their plugins forward line_primitive_mode; the other plugins
+/// forward nothing and keep drawing the prism.
+bool rendererDrawsLinePrimitiveMode(int renderingMode);
+
 class LineRenderer {
 public:
     LineRenderer(std::string windowName, SceneData* sceneData, TransferFunctionWindow& transferFunctionWindow);

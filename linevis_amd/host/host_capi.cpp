@@ -631,6 +631,10 @@ int lvh_renderer_ao_baker_state(void* r) {
     HipAmbientOcclusionBaker* hb = static_cast<HipAmbientOcclusionBaker*>(b);
     return (hb->getIsDataReady() ? 1 : 0) | (hb->getIsComputationRunning() ? 2 : 0);
 }
+/// LineData::getLinePrimitiveMode() (a static member, as in the reference) as its index in the reference's list of display names
+int lvh_line_primitive_mode_index() { return int(LineData::getLinePrimitiveMode()); }
+/// 1: the plugin of this rendering mode forwards LineData's line primitive mode to the library (line_primitive_mode), 0: it does not
+int lvh_rendering_mode_forwards_line_primitive_mode(int mode) { return rendererDrawsLinePrimitiveMode(mode) ? 1 : 0; }
 void* lvh_renderer_context(void* r) { return static_cast<HeadlessLineRenderer*>(r)->getLineRenderer()->getContext(); }
 
 } // extern "C"

@@ -112,6 +112,8 @@ def load():
         "lvh_renderer_needs_re_render": (i32, [vp]),
         "lvh_renderer_ao_baker_state": (i32, [vp]),
         "lvh_renderer_context": (vp, [vp]),
+        "lvh_rendering_mode_forwards_line_primitive_mode": (i32, [i32]),
+        "lvh_line_primitive_mode_index": (i32, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -180,6 +182,11 @@ class LineDataFlow:
         n = len(keys)
         self.L.lvh_flow_set_settings(self.h, (C.c_char_p * n)(*keys), (C.c_char_p * n)(*vals), n)
         return self
+
+    @property
+    def line_primitive_mode(self):
+        """LineData::getLinePrimitiveMode() by its display name (LineData.cpp:56-74); a static member, as in the reference"""
+        return LINE_PRIMITIVE_MODE_NAMES[self.L.lvh_line_primitive_mode_index()]
 
     @property
     def has_helicity(self):
@@ -564,6 +571,20 @@ def get_test_modes_deferred():
         L.lvh_test_mode_deferred(i, buf, n + 1)
         out.append(_parse_test_mode(buf.value.decode()))
     return out
+
+
+# LineData::LinePrimitiveMode by display name (LineData.cpp:56-74)
+LINE_PRIMITIVE_MODE_NAMES = ("Quads (Programmable Pull)", "Quads (Geometry Shader)", "Tube (Programmable Pull)", "Tube (Geometry Shader)",
+                             "Tube (Triangle Mesh)", "Tube (Mesh Shader)", "Tube (Mesh Shader NV)", "Ribbon Quads (Geometry Shader)",
+                             "Tube Ribbons (Programmable Pull)", "Tube Ribbons (Geometry Shader)", "Tube Ribbons (Triangle Mesh)",
+                             "Tube Ribbons (Mesh Shader)", "Tube Ribbons (Mesh Shader NV)")
+
+
+def forwards_line_primitive_mode(mode):
+    """Does the renderer plugin of this rendering mode pass LineData's line primitive mode on to the library (the option
+    line_primitive_mode)?  The plugins of modes 5, 8 and 10 do -- they draw "Quads (Programmable Pull)" besides the prism --, the others
+    keep drawing the prism whatever the mode says."""
+    return bool(load().lvh_rendering_mode_forwards_line_primitive_mode(int(mode)))
 
 
 class HeadlessLineRenderer:
