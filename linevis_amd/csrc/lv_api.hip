@@ -239,7 +239,7 @@ int lv_set_stream(lv_ctx* ctx, void* hip_stream) {
 int lv_set_lines(lv_ctx* ctx, const lv_line_point* points, uint32_t num_points, const uint32_t* seg, uint32_t num_segments) {
     if (!ctx) return LV_E_INVALID;
     if ((num_points && !points) || (num_segments && !seg)) return lv_fail(ctx, LV_E_INVALID, "null input array");
-    if (num_segments > 0x03FFFFFFu) return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 segments (leaf index field of the AO work queue)");
+    if (num_segments > LV_REF_MASK) return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 segments (leaf index field of the AO work queue)");
     for (uint64_t i = 0; i < 2ull * num_segments; i++)
         if (seg[i] >= num_points)
             return lv_fail(ctx, LV_E_INVALID, "segment %llu references point %u >= num_points %u",
@@ -277,7 +277,7 @@ int lv_set_tube_triangle_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uin
     if (!ctx) return LV_E_INVALID;
     if ((num_triangles && !triangle_indices) || (num_vertices && !vertices) || (num_line_points && !line_points))
         return lv_fail(ctx, LV_E_INVALID, "null input array");
-    if (num_triangles > 0x03FFFFFFu)
+    if (num_triangles > LV_REF_MASK)
         return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 triangles (leaf index field of the AO work queue)");
     for (uint64_t i = 0; i < 3ull * num_triangles; i++)
         if (triangle_indices[i] >= num_vertices)

@@ -14,6 +14,13 @@
 #define LV_BLOCK 256
 #define LV_LEAF_BIT 0x80000000u
 #define LV_INVALID 0xFFFFFFFFu
+// Node references and leaf indices are below 2^LV_REF_BITS: the leaf FIFOs pack (owner lane << LV_REF_BITS) | leaf into one word, and
+// lv_set_lines / lv_set_tube_triangle_mesh / the tessellators refuse more primitives than LV_REF_MASK (a 4-wide tree has fewer
+// inner nodes than leaves).  The byte offset of a 64-byte node or leaf record therefore fits 32 unsigned bits (LV_OFFSET32, lv_trace.h).
+#define LV_REF_BITS 26
+#define LV_REF_MASK ((1u << LV_REF_BITS) - 1u)
+static_assert(LV_REF_BITS + 6 <= 32, "byte offsets of 64-byte node and leaf records are formed in 32 bits (LV_OFFSET32)");
+static_assert(LV_WAVE <= (1u << (32 - LV_REF_BITS)), "the leaf FIFOs pack (owner lane, leaf) into one word");
 // per-thread traversal stack entries staged in LDS.  24 entries = 24 KB per workgroup: the tile kernels then need 40 KB
 // (k_ppll_gather 50 KB) and 4 (3) workgroups fit a CU instead of 3 (2) -- k_ao_primary -10 %, k_ppll_gather -11 % against 32 entries;
 // 14 entries fit one more but pay it back in overflow traffic (k_ppll_gather +5 %)

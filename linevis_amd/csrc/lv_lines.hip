@@ -573,7 +573,7 @@ int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const fl
             return lv_fail(ctx, LV_E_INVALID, "line_offsets must not decrease (line %u: %u -> %u)", l, line_offsets[l], line_offsets[l + 1]);
     const uint32_t numPoints = line_offsets[num_lines];
     if (numPoints && !positions) return lv_fail(ctx, LV_E_INVALID, "null positions");
-    if (numPoints > 0x03FFFFFFu) return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 points (leaf index field of the AO work queue)");
+    if (numPoints > LV_REF_MASK) return lv_fail(ctx, LV_E_CAPACITY, "at most 2^26-1 points (leaf index field of the AO work queue)");
     const float* ribbon = bands ? bands->ribbon_directions : nullptr;
     const float* helicity = bands ? bands->helicity : nullptr;
     const float givenMaxHelicity = bands ? bands->max_helicity : 0.0f;
@@ -727,7 +727,7 @@ static int lv_tessellate_tubes(lv_ctx* ctx) {
     LV_HIP(ctx, hipMemcpyAsync((void*)(ctx->pinned + 2), iOff + numLines, 8, hipMemcpyDeviceToHost, st));
     LV_HIP(ctx, hipStreamSynchronize(st));   // (also: the pageable table has been consumed)
     const uint64_t numVerts = *(volatile unsigned long long*)ctx->pinned, numIdx = *(volatile unsigned long long*)(ctx->pinned + 2);
-    if (numIdx / 3u > 0x03FFFFFFull || numVerts > 0xFFFFFFFFull)
+    if (numIdx / 3u > (unsigned long long)LV_REF_MASK || numVerts > 0xFFFFFFFFull)
         return lv_fail(ctx, LV_E_CAPACITY, "the tube mesh would have %llu triangles / %llu vertices: at most 2^26-1 triangles (leaf index field "
                                            "of the AO work queue)", (unsigned long long)(numIdx / 3u), (unsigned long long)numVerts);
     if ((rc = lv_buf_reserve(ctx, ctx->triIdx, size_t(numIdx) * 4))) return rc;

@@ -582,7 +582,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             if (mL) {
                 if (isLeaf) {
                     const unsigned idx = tail + unsigned(__popcll(mL & below));
-                    queueW[idx % LV_AO_QCAP] = (owner << 26) | (cur & 0x03FFFFFFu);
+                    queueW[idx % LV_AO_QCAP] = (owner << LV_REF_BITS) | (cur & LV_REF_MASK);
                     lastSeq = idx;
                     enq = true;
                     cur = lv_pop_or_done(st);
@@ -618,11 +618,11 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
             if (STATS && lane == 0) { phIt[2]++; phLn[2] += n; }
             if (lane < n) {
                 const unsigned e = queueW[(head + lane) % LV_AO_QCAP];
-                const unsigned owner = e >> 26, leaf = e & 0x03FFFFFFu;
+                const unsigned owner = e >> LV_REF_BITS, leaf = e & LV_REF_MASK;
                 const float2 r0 = rayW[3 * owner], r1 = rayW[3 * owner + 1], r2 = rayW[3 * owner + 2];
                 if (STATS) cnt.prims += PRIM == LV_PRIM_TRIANGLE ? S.triLeafSize : 1u; // primitives tested
                 float t; unsigned low;
-                if (lv_leaf_test<PRIM, LIT ? 1 : 0>(S, leaf, mk3(r0.x, r0.y, r1.x), mk3(r1.y, r2.x, r2.y), radius, capped, t, low, 0.0f,
+                if (lv_leaf_test<PRIM, LIT ? 1 : 0, !STATS>(S, leaf, mk3(r0.x, r0.y, r1.x), mk3(r1.y, r2.x, r2.y), radius, capped, t, low, 0.0f,
                                                     U.aoRadius)) {
                     if (t >= 0.0f && t <= U.aoRadius) { // traceAoRay: closest hit in [0, aoRadius], glsl:158-175
                         atomicMin(&keyW[owner], lv_ao_key_hit(t, low));
@@ -792,7 +792,7 @@ __global__ __launch_bounds__(LV_AO_BLOCK, LV_AO_MIN_WAVES) void k_ao_rays(const 
                 if (mL) {
                     if (isLeaf) {
                         const unsigned idx = tail + unsigned(__popcll(mL & below));
-                        queueW[idx % LV_AO_QCAP] = (owner << 26) | (cur & 0x03FFFFFFu);
+                        queueW[idx % LV_AO_QCAP] = (owner << LV_REF_BITS) | (cur & LV_REF_MASK);
                         lastSeq = idx;
                         enq = true;
                         cur = lv_pop_or_done(st);

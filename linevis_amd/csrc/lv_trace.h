@@ -399,6 +399,25 @@ __device__ __forceinline__ f3 lv_traversal_inv(f3 d) {
 #endif
 }
 
+// LV_OFFSET32=1: the byte offset of a node or of a leaf record is formed in 32 unsigned bits and added to the (wave-uniform) base
+// pointer -- one shift per lane and the scalar-base form of the load, in place of a 64-bit shift and a 64-bit add on a register pair.
+// Bound: references are below 2^LV_REF_BITS = 2^26 (lv_device.h; the setters refuse more), the widest record is 64 bytes: < 2^32.
+// Products that can pass 2^32 (48-byte records x triLeafSize, S.points, the sample rows) keep their 64-bit arithmetic.
+// LV_OFFSET32=0 (measurement knob) restores the 64-bit form.
+#ifndef LV_OFFSET32
+#define LV_OFFSET32 1
+#endif
+// record `index` of an array of (1 << SHIFT)-byte records
+template <int SHIFT, class T>
+__device__ __forceinline__ const T* lv_record_at(const T* base, unsigned index) {
+    static_assert(LV_REF_BITS + SHIFT <= 32, "index << SHIFT must fit 32 bits for every index the setters accept");
+#if LV_OFFSET32
+    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (index << SHIFT));
+#else
+    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t(index) << SHIFT));
+#endif
+}
+
 // ORDERED: 0 = children pushed as they come (all-hits), 1 = nearest hit child first, the rest as they come (closest hit:
 // measured as fast as a full sort, fewer instructions), 2 = all hit children in front-to-back order (MLAT: how early the
 // transmittance rule closes the ray interval depends on meeting the near layers first).
@@ -410,7 +429,7 @@ __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned n
     // k_render_rt_mlat keep their scratch and waves per SIMD with the early check, k_render_rt with the late one; tools/isa_report.py)
     constexpr bool RESERVE_EARLY = STACK::kLds != LV_STACK_LDS || ORDERED != 1;
     if (RESERVE_EARLY) st.reserve3();
-    const float4* p = S.nodes + 4 * size_t(node);
+    const float4* p = lv_record_at<6>(S.nodes, node);
     const float4 q0 = p[0], q1 = p[1], q2 = p[2], cf = p[3];
     if (STATS) cnt.nodes++;
     unsigned c0 = __float_as_uint(cf.x), c1 = __float_as_uint(cf.y), c2 = __float_as_uint(cf.z), c3 = __float_as_uint(cf.w);
@@ -622,22 +641,55 @@ __device__ __forceinline__ bool lv_tri_record_test(const LvSceneDev& S, unsigned
     return lv_ray_triangle(o, d, inv, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), S.triPad, t, u, v);
 }
 
+// LV_LEAF_FETCH_FIRST=1: a leaf test issues the loads of its leaf record before any of its arithmetic, and each 16-byte part of the
+// record as one load.  The records are the loads that miss the vector L1, and a test phase issues 64 of them at once; what runs first
+// otherwise is the three IEEE divisions of 1 / d (34 instructions per lane), and the compiler narrows and splits the parts it finds
+// partly used (six requests for a 64-byte pair record).  lv_load16 reads a part as one 4-vector; lv_after_loads is a compiler-only
+// fence that emits nothing: the loads before it cannot sink below it, and the direction handed through it cannot be divided above it.
+// The same bytes and the same float operations in the same order.  LV_LEAF_FETCH_FIRST=0 (measurement knob) restores the old order.
+#ifndef LV_LEAF_FETCH_FIRST
+#define LV_LEAF_FETCH_FIRST 1
+#endif
+typedef float lv_float4v __attribute__((ext_vector_type(4)));
+template <bool FIRST>
+__device__ __forceinline__ float4 lv_load16(const float4* p) {
+    if (!FIRST) return *p;
+    const lv_float4v v = *reinterpret_cast<const lv_float4v*>(p);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+template <bool FIRST>
+__device__ __forceinline__ void lv_after_loads(f3& d) {
+    if (FIRST) asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z) : : "memory");
+}
+// The second half of the fence: the record's words that the caller does not read (a kernel that ignores the primitive index, the
+// padding words) count as read here, after 1 / d.  Without it the register allocator hands those registers to the division's
+// temporaries, and the write-after-write hazard makes the division wait for the loads it was meant to overlap.
+template <bool FIRST>
+__device__ __forceinline__ void lv_loads_used(f3& inv, float w0, float w1, float w2, float w3) {
+    if (FIRST) asm volatile("" : "+v"(inv.x), "+v"(inv.y), "+v"(inv.z) : "v"(w0), "v"(w1), "v"(w2), "v"(w3));
+}
+
 // LIT: -1 = intersection form from S.literalIntersection at run time (tile kernels), 0 / 1 = fixed at compile time (k_ao_rays:
 // a run-time branch around both capsule tests costs the register that pushes the kernel over its 96-VGPR budget into scratch)
-template <int PRIM, int LIT = -1>
+// FETCH_FIRST = false: the record loads where the compiler puts them (the instrumented k_ao_rays: holding the record's registers
+// across the divisions costs it 8 bytes of scratch per lane, and nobody times it)
+template <int PRIM, int LIT = -1, bool FETCH_FIRST = true>
 __device__ __forceinline__ bool lv_leaf_test(const LvSceneDev& S, unsigned leaf, f3 o, f3 d, float radius, bool capped,
                                              float& t, unsigned& low, float tLo = -3.0e38f, float tHi = 3.0e38f) {
+    constexpr bool FF = FETCH_FIRST && LV_LEAF_FETCH_FIRST != 0;
     if (PRIM == LV_PRIM_TRIANGLE) {
         // closest of the leaf's triangles INSIDE the caller's ray interval [tLo, tHi] (a nearer hit outside it must not hide a
         // valid one of the same leaf); ties: lowest original index -- the merge key of the callers
-        const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
         bool any = false;
         t = 0.0f; low = 0u;
         if (S.triPairs) {
             // pair record: four 16-B loads for both triangles; the second triangle's operands are (q0, q2, q3) for a tube face (all
             // but the cap leaves) and are fetched again by address only by the waves that hold another code
-            const float4* rec = S.tris + 4 * size_t(leaf);
-            const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
+            const float4* rec = lv_record_at<6>(S.tris, leaf);
+            const float4 q0 = lv_load16<FF>(rec), q1 = lv_load16<FF>(rec + 1), q2 = lv_load16<FF>(rec + 2), q3 = lv_load16<FF>(rec + 3);
+            lv_after_loads<FF>(d);
+            f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+            lv_loads_used<FF>(inv, q0.w, q1.w, q2.w, q3.w);
             const unsigned idx0 = __float_as_uint(q0.w), code = __float_as_uint(q1.w);
             float tj, u, v;
             if (lv_ray_triangle(o, d, inv, mk3(q0.x, q0.y, q0.z), mk3(q1.x, q1.y, q1.z), mk3(q2.x, q2.y, q2.z), S.triPad, tj, u, v) &&
@@ -651,10 +703,20 @@ __device__ __forceinline__ bool lv_leaf_test(const LvSceneDev& S, unsigned leaf,
             }
             return any;
         }
+        // 48-byte records (a leaf whose triangles do not pair up): slot 0's record first, then 1 / d; 64-bit index arithmetic, the
+        // product with triLeafSize can pass 2^32
+        const float4* rec = S.tris + 3 * (size_t(leaf) * S.triLeafSize);
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
+        if (S.triLeafSize) { a = lv_load16<FF>(rec); b = lv_load16<FF>(rec + 1); c = lv_load16<FF>(rec + 2); }
+        lv_after_loads<FF>(d);
+        f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+        lv_loads_used<FF>(inv, a.w, b.w, c.w, c.w);
         for (uint32_t j = 0; j < S.triLeafSize; j++) {
-            float tj;
-            unsigned idx;
-            if (lv_tri_record_test(S, leaf, j, o, d, inv, tj, idx) && tj >= tLo && tj <= tHi) {
+            if (j) { a = rec[3 * size_t(j)]; b = rec[3 * size_t(j) + 1]; c = rec[3 * size_t(j) + 2]; }
+            const unsigned idx = __float_as_uint(a.w);
+            float tj, u, v;
+            if (lv_ray_triangle(o, d, inv, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), S.triPad, tj, u, v) &&
+                tj >= tLo && tj <= tHi) {
                 if (!any || tj < t || (tj == t && idx < low)) { t = tj; low = idx; }
                 any = true;
             }
@@ -665,16 +727,23 @@ __device__ __forceinline__ bool lv_leaf_test(const LvSceneDev& S, unsigned leaf,
         low = seg << 2;
         return lv_intersect_elliptic_tube(S, o, d, S.points[S.segIdx[2 * size_t(seg)]], S.points[S.segIdx[2 * size_t(seg) + 1]], t);
     } else {
-        const float4 a = S.segs[2 * size_t(leaf)], b = S.segs[2 * size_t(leaf) + 1];
+        // the segment's records (two end points, its axis for the closest-approach form, its original index) before any arithmetic
+        const float4* seg = lv_record_at<5>(S.segs, leaf);
+        const float4 a = lv_load16<FF>(seg), b = lv_load16<FF>(seg + 1);
+        const bool literal = LIT == 1 || (LIT == -1 && S.literalIntersection);
+        float4 ax = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!literal) ax = lv_load16<FF>(lv_record_at<4>(S.segAxis, leaf));
+        uint32_t segIndex = 0u;
+        if (FF) segIndex = *lv_record_at<2>(S.leafSeg, leaf);
+        lv_after_loads<FF>(d);
         int kind;
         bool hit;
-        if (LIT == 1 || (LIT == -1 && S.literalIntersection)) {
+        if (literal) {
             hit = lv_intersect_capsule_literal(o, d, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), radius, capped, t, kind);
         } else {
-            const float4 ax = S.segAxis[leaf];
             hit = lv_intersect_capsule_td(o, d, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(ax.x, ax.y, ax.z), radius, capped, t, kind);
         }
-        if (hit) low = (S.leafSeg[leaf] << 2) | unsigned(kind);
+        if (hit) low = ((FF ? segIndex : *lv_record_at<2>(S.leafSeg, leaf)) << 2) | unsigned(kind);
         return hit;
     }
 }

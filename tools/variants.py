@@ -31,6 +31,8 @@ PRESETS = {
     "spill12": "-DLV_STACK_SPILL_BLOCK=12",
     "ao_lds15": "-DLV_AO_STACK_LDS=15",
     "ao_lds16": "-DLV_AO_STACK_LDS=16",
+    "nofetchfirst": "-DLV_LEAF_FETCH_FIRST=0",                     # leaf tests: record loads where the compiler puts them (after 1 / d, narrowed and split)
+    "nooffset32": "-DLV_OFFSET32=0",                               # node and leaf-record addresses by 64-bit arithmetic per lane
     "noscalar": "-DLV_AO_SCALAR_STATE=0",                          # k_ao_rays: queue chunk through __shfl, wave-level state in vector registers
 }
 
