@@ -4,7 +4,7 @@
 that holds the node step (the innermost loop with the four global_load_dwordx4 of lv_node_step).
 
 Usage: python tools/isa_report.py [out.txt]   (cross-compiles with the library's flags; no GPU needed)
-       python tools/isa_report.py --compare OTHER_CSRC [a.hip ...] [OLD=NEW ...]   (two builds, function by function: see compare())
+       python tools/isa_report.py --compare OTHER_CSRC [a.hip ...] [OLD=NEW ...] [--other-flags=F,G]   (two builds, function by function: see compare())
 """
 import collections
 import concurrent.futures
@@ -29,9 +29,9 @@ def demangle(names, signature=False):
     return out if signature else [o.split("(")[0] for o in out]
 
 
-def compile_s(src, tmp):
+def compile_s(src, tmp, extra=()):
     s_path = os.path.join(tmp, os.path.basename(src) + ".s")
-    flags = [f for f in lv_build.FLAGS if f not in ("-fPIC",)]
+    flags = [f for f in lv_build.FLAGS if f not in ("-fPIC",)] + list(extra)
     r = subprocess.run([lv_build.hipcc()] + flags + ["-S", "--cuda-device-only", src, "-o", s_path,
                                                      "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
     if r.returncode != 0:
@@ -134,14 +134,17 @@ def compare(other_csrc, args):
     """python tools/isa_report.py --compare OTHER_CSRC [a.hip ...] [OLD=NEW ...]: compiles the named sources (default lv_render.hip
     and lv_peel.hip) of OTHER_CSRC (the csrc directory of another checkout) and of this tree, and lists every device function of the
     other build as identical to its counterpart here or as differing.  OLD=NEW renames a prefix of the other build's demangled names
-    first, e.g. 'k_al64_stream_pass<=k_stream_pass<10, '."""
+    first, e.g. 'k_al64_stream_pass<=k_stream_pass<10, '.  --other-flags=F,G appends compiler flags to the other build only (a parent
+    that was built with other flags)."""
+    other_flags = [f for a in args if a.startswith("--other-flags=") for f in a.split("=", 1)[1].split(",") if f]
+    args = [a for a in args if not a.startswith("--other-flags=")]
     renames = [a.split("=", 1) for a in args if "=" in a]
     sources = [a for a in args if "=" not in a] or ["lv_render.hip", "lv_peel.hip"]
     keys = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
     total = same = 0
     def compile_one(path):
         with tempfile.TemporaryDirectory() as tmp:
-            return compile_s(path, tmp)
+            return compile_s(path, tmp, other_flags if path.startswith(other_csrc) else ())
     with concurrent.futures.ThreadPoolExecutor(max_workers=4) as pool:   # (the threads only wait for hipcc)
         compiled = list(pool.map(compile_one, [os.path.join(c, s) for s in sources for c in (other_csrc, lv_build.CSRC)]))
     for i, src in enumerate(sources):

@@ -53,6 +53,10 @@ out = {
                    "~3.5-4.1 cycles.  bench.py therefore reports two VALU fractions: `frac` against the measured rate of the node "
                    "step's own instruction mix (what can actually bind) and `frac_vs_datasheet_issue` against 2 cycles per "
                    "instruction (the marketing peak, unreachable for unpackable code)"},
+    # what a packed fp32 pair costs against two plain ops, alone and with the v_mov_b32 that forms its register pair (E§23)
+    "packed_vs_plain_f32": {"rows": {k: {"ns_per_inst_per_simd": valu[k]["ns_per_inst_per_simd"]} for k in (
+        "v_mul_f32", "v_add_f32", "v_mov_b32", "v_fma_f32", "v_min3_f32", "v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32",
+        "v_pk_mul_f32+v_mov_b32", "v_pk_add_f32+v_mov_b32", "v_mul_f32+v_mul_f32", "v_mul_f32+v_add_f32") if k in valu}},
     "valu_all": valu, "tcp_all": tcp,
     "reading": "VALU: 'full' ops (fma, max, cvt, cmp, cndmask, bfe, dpp ...) issue at ~4.1 cycles per wave64 instruction, the simple "
                "ones (mul, add, and, shifts, mov) at ~2.3; an fma overlaps with a following cvt / cmp / cndmask / mul (pair ~5 "

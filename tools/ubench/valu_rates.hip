@@ -128,6 +128,29 @@ __global__ __launch_bounds__(256) void k_pk_mul(const float* p, float* out, unsi
     if (s == 123.456f) out[0] = s;
     if ((threadIdx.x & 63) == 0) atomicMax(cyc, t1 - t0);
 }
+// packed op + one plain v_mov_b32 on a chain of its own: what a packed pair costs when one of its operands has to be moved into an
+// aligned register pair first (the SLP vectoriser's cross and dot products in lv_ray_triangle), to be read against two plain ops
+#define PK_KERNEL(NAME, ASM)                                                                           \
+    __global__ __launch_bounds__(256) void NAME(const float* p, float* out, unsigned long long* cyc) { \
+        typedef float f2 __attribute__((ext_vector_type(2)));                                          \
+        f2 v[8]; float w[8]; f2 a = {p[threadIdx.x & 7], p[3]};                                        \
+        for (int k = 0; k < 8; k++) { v[k] = f2{p[(threadIdx.x + k) & 63] + a.x, p[k] + a.y}; w[k] = p[(threadIdx.x + 2 * k) & 63]; } \
+        unsigned long long t0 = __builtin_readcyclecounter();                                          \
+        for (int it = 0; it < NITER; it++) {                                                           \
+            _Pragma("unroll") for (int u = 0; u < 4; u++) {                                            \
+                _Pragma("unroll") for (int k = 0; k < 8; k++) asm volatile(ASM : "+v"(v[k]), "+v"(w[k]) : "v"(a), "v"(a.x)); \
+            }                                                                                          \
+        }                                                                                              \
+        unsigned long long t1 = __builtin_readcyclecounter();                                          \
+        float s = 0; for (int k = 0; k < 8; k++) s += v[k].x + v[k].y + w[k];                          \
+        if (s == 123.456f) out[0] = s;                                                                 \
+        if ((threadIdx.x & 63) == 0) atomicMax(cyc, t1 - t0);                                          \
+    }
+PK_KERNEL(k_pk_add, "v_pk_add_f32 %0, %0, %2")
+PK_KERNEL(k_pk_mul_mov, "v_pk_mul_f32 %0, %0, %2\n v_mov_b32 %1, %3")
+PK_KERNEL(k_pk_add_mov, "v_pk_add_f32 %0, %0, %2\n v_mov_b32 %1, %3")
+PK_KERNEL(k_mul_mul, "v_mul_f32 %1, %1, %3\n v_mul_f32 %1, %1, %3")
+PK_KERNEL(k_mul_add, "v_mul_f32 %1, %1, %3\n v_add_f32 %1, %1, %3")
 
 typedef void (*kern_t)(const float*, float*, unsigned long long*);
 struct Entry { const char* name; kern_t fn; int perStmt; };
@@ -158,6 +181,8 @@ int main(int argc, char** argv) {
         {"v_fma_f32+v_mul_f32", k_fma_mul, 2}, {"v_fma_f32+v_and_b32", k_fma_and, 2}, {"v_cvt_f32_ubyte1+v_max_f32", k_cvt_max, 2},
         {"v_max_f32+v_cmp(sgpr)", k_max_cmp, 2}, {"v_fma_f32+s_add_u32", k_fma_salu, 2},
         {"node-step mix: cvt,fma,cvt,fma,max3,min3,cmp,cndmask", k_nodemix, 8}, {"v_fmac_f32", k_fmac, 1}, {"v_pk_fma_f32", k_pk_fma, 1}, {"v_pk_mul_f32", k_pk_mul, 1},
+        {"v_pk_add_f32", k_pk_add, 1}, {"v_pk_mul_f32+v_mov_b32", k_pk_mul_mov, 2}, {"v_pk_add_f32+v_mov_b32", k_pk_add_mov, 2},
+        {"v_mul_f32+v_mul_f32", k_mul_mul, 2}, {"v_mul_f32+v_add_f32", k_mul_add, 2},
     };
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));

@@ -33,6 +33,7 @@ PRESETS = {
     "ao_lds16": "-DLV_AO_STACK_LDS=16",
     "nofetchfirst": "-DLV_LEAF_FETCH_FIRST=0",                     # leaf tests: record loads where the compiler puts them (after 1 / d, narrowed and split)
     "nooffset32": "-DLV_OFFSET32=0",                               # node and leaf-record addresses by 64-bit arithmetic per lane
+    "slp": "-fslp-vectorize",                                      # the SLP vectoriser back on (packed fp32 pairs in the intersection tests)
     "noscalar": "-DLV_AO_SCALAR_STATE=0",                          # k_ao_rays: queue chunk through __shfl, wave-level state in vector registers
 }
 
