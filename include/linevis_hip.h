@@ -156,6 +156,11 @@ typedef struct lv_stats {
 /* the simulation-mesh hull pass of modes 5, 8 and 10 (k_hull_pass).  lv_stats' two per-kernel arrays keep their eight entries: this
  * id is read with lv_get_kernel_times and selected with kernel_timers like the others */
 #define LV_KERNEL_HULL 8
+/* the passes of the spatial-hashing denoiser (ambient_occlusion_denoiser = "Spatial Hashing"), one record per RTAO iteration each:
+ * k_sh_write, k_sh_read, and the three a-trous passes of its tail together; read and selected like LV_KERNEL_HULL */
+#define LV_KERNEL_SH_WRITE 9
+#define LV_KERNEL_SH_READ 10
+#define LV_KERNEL_SH_TAIL 11
 
 typedef struct lv_ctx lv_ctx;
 
@@ -573,13 +578,24 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   race can leave in the first MAX_NUM_FRAGS nodes), so frames do not depend on that order; lv_ppll_get_buffers returns
  *   every list in ascending key order,
  *   ambient_occlusion_denoiser ("None" | "Edge-Avoiding A-Trous Wavelet Transform" (UTF-8 A-grave as in Denoiser.hpp:66; "EAW"
- *   is accepted too) | "SVGF")                                         (VulkanRayTracedAmbientOcclusion.cpp:683-696)
+ *   is accepted too) | "SVGF" | "Spatial Hashing")                     (VulkanRayTracedAmbientOcclusion.cpp:683-696)
  *   eaw_denoiser_iterations (0..5, default 3), eaw_denoiser_color_weights / _position_weights / _normal_weights,
  *   eaw_denoiser_phi_color / _phi_position / _phi_normal, eaw_denoiser_use_shared_memory   (EAWDenoiser.cpp:400-432)
  *   svgf_denoiser_iterations (0..5, default 5), svgf_denoiser_allowed_z_dist (0.002), svgf_denoiser_allowed_normal_dist
  *   (0.02): build-owned keys for parameters the reference exposes in its GUI only (SVGF.hpp:70-72,115).  SVGF is
  *   temporal: every lv_render* call advances its history (one step per RTAO iteration), always over the whole viewport;
  *   lv_set_lines resets the global frame counter, a change of the denoiser or of the viewport size clears the history,
+ *   "Spatial Hashing" (SpatialHashingDenoiser.cpp, SH_Denoise.glsl; the order-independent statement of linevis_amd/csrc/lv_sh.h): the
+ *   AO of every RTAO iteration is accumulated in world space, in a hash map of multi-resolution cells keyed by position and normal,
+ *   read back per hit and smoothed by three a-trous passes with fixed settings.  Like SVGF it takes the iteration's own AO image and
+ *   the global frame number, and runs over the whole viewport after every RTAO iteration.  Build-owned keys for what the reference
+ *   exposes in its GUI only: spatial_hashing_s_p (cell size in pixels, 0.1 ... 20, default 8), spatial_hashing_s_min_exp (smallest
+ *   cell 10^exp, -20 ... -1, default -17), spatial_hashing_s_nd (normal coarseness, 1 ... 10, default 3), spatial_hashing_num_cells
+ *   (>= 10, default 10000000; 16 B each, allocated while the denoiser is selected), spatial_hashing_atomics_mode ("Uint Quantized
+ *   Atomic Add"; "Float Atomic Add", "Uint Spinning Atomic Add" and "No Atomics" are refused: a float sum or a racing write depends
+ *   on the execution order).  The map survives camera and viewport changes; it is cleared when more than half of its cells are occupied, before a count
+ *   could reach 2^28, by lv_set_lines / lv_set_trajectories, a changed line_width, s_p, s_min_exp, s_nd or num_cells, and by
+ *   lv_spatial_hashing_reset.  A contribution that finds ten other keys in its probe window is dropped and counted (no eviction),
  *   band data (ribbons; the ray tracer's closest-hit paths: analytic geometry modes, or "Triangle Mesh" / rtao_geometry =
  *   triangle_tubes on the elliptic triangle tubes lv::LineDataFlow tessellates for such data; use_mlat over the same
  *   geometries; the PPLL gather over the analytic tubelets / capsules; the static prebaker: ray origins on the elliptic cross-
@@ -972,6 +988,27 @@ int lv_line_quads_get_fragments(lv_ctx* ctx, uint64_t capacity, uint32_t* pixel,
 int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_depth,
                             const float* flow_fwidth, float* color_history, float* moments_history, float* normal_depth_history,
                             float* out);
+/* Test entry point of the spatial-hashing denoiser: one Spatial_Hashing_Denoiser::denoise() (SH_Denoise.glsl Compute-Write and
+ * Compute-Read as stated in linevis_amd/csrc/lv_sh.h, then three EAWDenoise.Compute passes with useColorWeights = false, phiPosition =
+ * 0.3e-6, phiNormal = 0.1) on caller-supplied images of w x h pixels (1 ... 16384 each, fewer than 2^28 pixels), row-major.  Inputs:
+ * noisy = 1 float per pixel (the iteration's AO; clamped to [0, 1], NaN counts as 0), normal_world = 4 floats {world normal xyz,
+ * w}, position_world = 4 floats {world position xyz, w} (a pixel whose normal is (0, 0, 0) is a miss; finite values; all four
+ * components enter the a-trous distances), cam_pos = 3 floats.  Outputs, 1 float per pixel: out_read (may be NULL) = the read pass'
+ * image before the a-trous passes, 0 where nothing was read; out = the denoised image.  Cell sizes and the map size come from the
+ * spatial_hashing_* options.  The call accumulates into a map of its own (map 1) that persists across calls; the renderer's map (map
+ * 0) is not touched.  LV_E_INVALID for a null pointer or an extent outside the range. */
+int lv_spatial_hashing_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_world,
+                                       const float* position_world, const float* cam_pos, float* out_read, float* out);
+/* Empties map `which` (0 = the renderer's, 1 = lv_spatial_hashing_denoise_buffers') and zeroes its statistics. */
+int lv_spatial_hashing_reset(lv_ctx* ctx, int which);
+/* The occupied cells of map `which`, in no particular order: keys[i] = (checksum << 32) | hash, accumulators[i] = (sum << 28) | count
+ * with sum = the sum of floor(100 * occlusion + 0.5) and count = the number of contributions.  *count is always the number of
+ * occupied cells; a smaller capacity returns LV_E_CAPACITY and writes nothing else.  Both arrays NULL: only the count. */
+int lv_spatial_hashing_get_cells(lv_ctx* ctx, int which, uint64_t* keys, uint64_t* accumulators, uint64_t capacity, uint64_t* count);
+/* out[0 .. 3] = {occupied, stored, dropped, clears} of map `which`: cells in use, contributions stored in and dropped from the map
+ * since its last clear (stored + dropped = 4 x the hits written since then; the sum of all counts = stored), clears since the last
+ * reset (lv_spatial_hashing_reset, a new spatial_hashing_num_cells). */
+int lv_spatial_hashing_get_stats(lv_ctx* ctx, int which, uint64_t out[4]);
 /* LBVH export for structural tests: compressed 4-wide nodes of 16 uint32/float words (64 B) each -- words 0-2 grid
  * origin xyz, words 3-5 grid scale xyz (floats), words 6-8 qmin x/y/z and words 9-11 qmax x/y/z (byte k = child slot
  * k; decoded plane = origin + q * scale), words 12-15 child references (bit 31 = leaf, 0xFFFFFFFF = empty slot);

@@ -91,6 +91,8 @@ def streamline_settings(method="Runge-Kutta 4th Order", direction="Forward & Bac
 
 KERNEL_AO_PRIMARY, KERNEL_AO_RAYS, KERNEL_RENDER_RT, KERNEL_PPLL_GATHER, KERNEL_PPLL_RESOLVE, KERNEL_DEPTH_RANGE = range(6)
 KERNEL_HULL = 8        # LV_KERNEL_HULL: the simulation-mesh hull pass (kernel_times(); lv_stats' arrays keep the eight KERNEL_NAMES)
+# the passes of the spatial-hashing denoiser (LV_KERNEL_SH_*): k_sh_write, k_sh_read, the three a-trous passes of its tail together
+KERNEL_SH_WRITE, KERNEL_SH_READ, KERNEL_SH_TAIL = 9, 10, 11
 KERNEL_NAMES = ["k_ao_primary", "k_ao_rays", "k_render_rt", "k_ppll_gather", "k_ppll_resolve", "k_depth_minmax", "k_ppll_shade_prism",
                 "k_ppll_raster_prism"]
 
@@ -112,6 +114,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_render", "lv_render_device", "lv_render_tiles_device", "lv_get_stats", "lv_reset_timers", "lv_get_kernel_times", "lv_get_ao_tile_costs", "lv_get_dispatch_order", "lv_trace_rays",
            "lv_compute_depth_range", "lv_get_ao", "lv_ppll_get_buffers", "lv_ppll_resolve_buffers", "lv_mlab_resolve_buffers", "lv_mboit_resolve_buffers", "lv_mboit_get_moments", "lv_atomic_loop_get_num_layers", "lv_atomic_loop_get_buffers", "lv_atomic_loop_resolve_buffers", "lv_wboit_get_buffers", "lv_wboit_resolve_buffers",
            "lv_depth_complexity_get_buffers", "lv_depth_complexity_get_stats", "lv_depth_peeling_get_buffers", "lv_depth_peeling_resolve_buffers", "lv_deferred_get_buffers", "lv_deferred_shade_buffers", "lv_svgf_denoise_buffers", "lv_get_accel",
+           "lv_spatial_hashing_denoise_buffers", "lv_spatial_hashing_reset", "lv_spatial_hashing_get_cells", "lv_spatial_hashing_get_stats",
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
@@ -208,6 +211,10 @@ def load():
         ("lv_hull_get_fragments", [vp, vp, vp, vp, vp, u64, C.POINTER(u64)]),
         ("lv_line_quads_get_fragments", [vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]),
         ("lv_svgf_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        ("lv_spatial_hashing_denoise_buffers", [vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        ("lv_spatial_hashing_reset", [vp, i32]),
+        ("lv_spatial_hashing_get_cells", [vp, i32, vp, vp, u64, C.POINTER(u64)]),
+        ("lv_spatial_hashing_get_stats", [vp, i32, vp]),
         ("lv_get_accel", [vp, vp, u64, vp, u64]),
         ("lv_set_tube_triangle_mesh", [vp, vp, u32, vp, u32, vp, u32]),
         ("lv_set_trajectories", [vp, vp, vp, vp, u32]),
@@ -827,6 +834,43 @@ class Context:
         self._ck(self.L.lv_svgf_denoise_buffers(self.h, w, h, _p(a), _p(nd), _p(ff), _p(color_history), _p(moments_history),
                                                 _p(normal_depth_history), _p(out)))
         return out
+
+    def spatial_hashing_denoise(self, noisy, normal_world, position_world, cam_pos):
+        """One denoise() of the spatial-hashing denoiser on caller-supplied images (lv_spatial_hashing_denoise_buffers): noisy (h, w),
+        normal_world and position_world (h, w, 4), cam_pos (3,).  It accumulates into map 1, which persists across calls.  Returns
+        (read, out): the read pass' (h, w) image and the denoised one.  Cell sizes and the map size are the spatial_hashing_* options."""
+        a = np.ascontiguousarray(noisy, dtype=np.float32)
+        h, w = a.shape
+        nm = np.ascontiguousarray(normal_world, dtype=np.float32)
+        pm = np.ascontiguousarray(position_world, dtype=np.float32)
+        cam = np.ascontiguousarray(cam_pos, dtype=np.float32)
+        if nm.shape != (h, w, 4) or pm.shape != (h, w, 4) or cam.shape != (3,):
+            raise ValueError("normal_world and position_world must be (h, w, 4), cam_pos (3,)")
+        read = np.zeros((h, w), dtype=np.float32)
+        out = np.zeros((h, w), dtype=np.float32)
+        self._ck(self.L.lv_spatial_hashing_denoise_buffers(self.h, w, h, _p(a), _p(nm), _p(pm), _p(cam), _p(read), _p(out)))
+        return read, out
+
+    def spatial_hashing_reset(self, which=0):
+        """Empties map `which` (0 = the renderer's, 1 = spatial_hashing_denoise's) and zeroes its statistics."""
+        self._ck(self.L.lv_spatial_hashing_reset(self.h, int(which)))
+
+    def spatial_hashing_cells(self, which=0):
+        """The occupied cells of map `which` as (keys, sums, counts): uint64 key words (checksum << 32 | hash), the sums of
+        floor(100 * occlusion + 0.5) and the contribution counts, in no particular order."""
+        n = C.c_uint64(0)
+        self._ck(self.L.lv_spatial_hashing_get_cells(self.h, int(which), None, None, 0, C.byref(n)))
+        keys = np.zeros(max(n.value, 1), dtype=np.uint64)
+        acc = np.zeros(max(n.value, 1), dtype=np.uint64)
+        self._ck(self.L.lv_spatial_hashing_get_cells(self.h, int(which), _p(keys), _p(acc), keys.shape[0], C.byref(n)))
+        keys, acc = keys[:n.value], acc[:n.value]
+        return keys, acc >> np.uint64(28), acc & np.uint64(0x0FFFFFFF)
+
+    def spatial_hashing_stats(self, which=0):
+        """{occupied, stored, dropped, clears} of map `which` (lv_spatial_hashing_get_stats)."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._ck(self.L.lv_spatial_hashing_get_stats(self.h, int(which), _p(out)))
+        return dict(zip(("occupied", "stored", "dropped", "clears"), (int(v) for v in out)))
 
     def get_accel(self, num_nodes, num_leaves):
         nodes = np.zeros((max(num_nodes, 1), 16), dtype=np.uint32)

@@ -113,7 +113,8 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->depthMinMax, &ctx->ao, &ctx->aoAlt, &ctx->featNormal, &ctx->featNormalAlt, &ctx->featPosition, &ctx->featPositionAlt,
             &ctx->eawPing, &ctx->eawPong, &ctx->tilesHaloDev, &ctx->fullFrameTile, &ctx->svgf.normalDepth, &ctx->svgf.normalDepthHistory,
             &ctx->svgf.flowFwidth, &ctx->svgf.moments, &ctx->svgf.momentsHistory, &ctx->svgf.colorHistory, &ctx->svgf.tempAccum,
-            &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
+            &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven,
+            &ctx->shMapCells, &ctx->shMapCounters, &ctx->shGivenCells, &ctx->shGivenCounters, &ctx->shRead, &ctx->shNormal, &ctx->shPosition, &ctx->shPing, &ctx->shPong, &ctx->shGiven, &ctx->shCompact, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
             &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->visBuf, &ctx->deferredTf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
             &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag, &ctx->hullIdx, &ctx->hullVerts,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
@@ -268,6 +269,7 @@ int lv_set_lines(lv_ctx* ctx, const lv_line_point* points, uint32_t num_points, 
     // lastFrameViewProjectionMatrix = the current camera's
     ctx->aoGlobalFrameNumber = 0;
     ctx->lastFrameViewProjValid = false;
+    lv_sh_invalidate(ctx);
     return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_set_lines(p, points, num_points, seg, num_segments); });
 }
 
@@ -565,7 +567,7 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
     uint32_t u;
     if (k == "line_width") {
         if (!parseFloat(value, f) || !(f > 0.0f)) return bad();
-        if (f != o.lineWidth) lv_invalidate_bake(ctx);
+        if (f != o.lineWidth) { lv_invalidate_bake(ctx); lv_sh_invalidate(ctx); }
         o.lineWidth = f; // accel rebuilt lazily (setTriangleRepresentationDirty, LineRenderer.cpp:436-441)
     } else if (k == "depth_cue_strength") {
         if (!parseFloat(value, f)) return bad();
@@ -614,14 +616,20 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         o.aoJitterPrimary = parseBool(value);
     } else if (k == "ambient_occlusion_denoiser") {
         // DENOISER_NAMES, Denoiser.hpp:61-65,96-100 (VulkanRayTracedAmbientOcclusion.cpp:683-696)
-        const bool wasSvgf = o.svgfEnabled, wasEaw = o.eawEnabled;
-        if (strcmp(value, "None") == 0) { o.eawEnabled = false; o.svgfEnabled = false; }
-        else if (strcmp(value, "Edge-Avoiding \xC3\x80-Trous Wavelet Transform") == 0 || strcmp(value, "EAW") == 0) { o.eawEnabled = true; o.svgfEnabled = false; }
-        else if (strcmp(value, "SVGF") == 0) { o.eawEnabled = false; o.svgfEnabled = true; }
+        const bool wasSvgf = o.svgfEnabled, wasEaw = o.eawEnabled, wasSh = o.shEnabled;
+        if (strcmp(value, "None") == 0) { o.eawEnabled = false; o.svgfEnabled = false; o.shEnabled = false; }
+        else if (strcmp(value, "Edge-Avoiding \xC3\x80-Trous Wavelet Transform") == 0 || strcmp(value, "EAW") == 0) { o.eawEnabled = true; o.svgfEnabled = false; o.shEnabled = false; }
+        else if (strcmp(value, "SVGF") == 0) { o.eawEnabled = false; o.svgfEnabled = true; o.shEnabled = false; }
+        else if (strcmp(value, "Spatial Hashing") == 0) { o.eawEnabled = false; o.svgfEnabled = false; o.shEnabled = true; }
         else return lv_fail(ctx, LV_E_INVALID, "ambient_occlusion_denoiser '%s' is not provided (None | Edge-Avoiding \xC3\x80-Trous "
-                                               "Wavelet Transform | SVGF)", value);
+                                               "Wavelet Transform | SVGF | Spatial Hashing)", value);
         if (o.svgfEnabled != wasSvgf) ctx->svgf.historyValid = false; // createDenoiser(): fresh history
-        if (o.svgfEnabled != wasSvgf || o.eawEnabled != wasEaw) {
+        if (wasSh && !o.shEnabled) {   // createDenoiser() destroys the old one: the map (16 B x num_cells) leaves with it
+            (void)hipSetDevice(ctx->device);
+            const int rcSh = lv_sh_release(ctx, 0);
+            if (rcSh) return rcSh;
+        }
+        if (o.svgfEnabled != wasSvgf || o.eawEnabled != wasEaw || o.shEnabled != wasSh) {
             // any change of the denoiser: the image the colour pass samples (raw / EAW ping-pong / SVGF result) is stale, and a
             // running accumulation would mix feature maps that were never written -- setDenoiserType resets the frame number
             // (VulkanRayTracedAmbientOcclusion.cpp:683-696 -> onHasMoved): the accumulation restarts with the next frame
@@ -677,6 +685,25 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
     } else if (k == "svgf_denoiser_allowed_normal_dist") {       // SVGF.hpp:71
         if (!parseFloat(value, f) || !(f >= 0.0f)) return bad();
         o.svgfAllowedNormalDist = f;
+    } else if (k == "spatial_hashing_s_p") {                     // SpatialHashingDenoiser.cpp:184 (GUI only in the reference, like the next two)
+        if (!parseFloat(value, f) || !(f >= 0.1f) || !(f <= 20.0f)) return bad();
+        o.shSp = f;             // a changed keying option empties the maps at their next denoise (lv_sh.hip)
+    } else if (k == "spatial_hashing_s_min_exp") {               // :185
+        char* end = nullptr;
+        const long e = strtol(value, &end, 10);
+        if (end == value || *end != '\0' || e < -20 || e > -1) return bad();
+        o.shSMinExp = int(e);
+    } else if (k == "spatial_hashing_s_nd") {                    // :186
+        if (!parseFloat(value, f) || !(f >= 1.0f) || !(f <= 10.0f)) return bad();
+        o.shSNd = f;
+    } else if (k == "spatial_hashing_num_cells") {               // hm_cells, :42
+        if (!parseUint(value, u) || u < 10u) return bad();
+        o.shNumCells = u;
+    } else if (k == "spatial_hashing_atomics_mode") {            // SPATIAL_HASHING_ATOMICS_MODE_NAMES, SpatialHashingDenoiser.hpp:39-41
+        if (strcmp(value, "Float Atomic Add") == 0 || strcmp(value, "Uint Spinning Atomic Add") == 0 || strcmp(value, "No Atomics") == 0)
+            return lv_fail(ctx, LV_E_INVALID, "spatial_hashing_atomics_mode '%s' is not provided: a float sum or a racing write depends on the "
+                                              "execution order (Uint Quantized Atomic Add)", value);
+        if (strcmp(value, "Uint Quantized Atomic Add") != 0) return bad();
     } else if (k == "eaw_denoiser_iterations") {                 // EAWDenoiser.cpp:402-430
         if (!parseUint(value, u) || u > 5) return bad();
         o.eawIterations = u;
@@ -1734,6 +1761,43 @@ int lv_svgf_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* no
     if (w == 0 || h == 0 || w > 16384u || h > 16384u) return lv_fail(ctx, LV_E_INVALID, "extent %u x %u (1 ... 16384 each)", w, h);
     (void)hipSetDevice(ctx->device);
     return lv_svgf_denoise_given(ctx, w, h, noisy, normal_depth, flow_fwidth, color_history, moments_history, normal_depth_history, out);
+}
+
+int lv_spatial_hashing_denoise_buffers(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normal_world,
+                                       const float* position_world, const float* cam_pos, float* out_read, float* out) {
+    if (!ctx) return LV_E_INVALID;
+    if (!noisy || !normal_world || !position_world || !cam_pos || !out) return lv_fail(ctx, LV_E_INVALID, "null array");
+    if (w == 0 || h == 0 || w > 16384u || h > 16384u || uint64_t(w) * h >= (1ull << 28))
+        return lv_fail(ctx, LV_E_INVALID, "extent %u x %u (1 ... 16384 each, fewer than 2^28 pixels)", w, h);
+    (void)hipSetDevice(ctx->device);
+    return lv_sh_denoise_given(ctx, w, h, noisy, normal_world, position_world, cam_pos, out_read, out);
+}
+
+static int lv_sh_which(lv_ctx* ctx, int which) {
+    if (!ctx) return LV_E_INVALID;
+    if (which != 0 && which != 1) return lv_fail(ctx, LV_E_INVALID, "map %d (0 = the renderer's, 1 = lv_spatial_hashing_denoise_buffers')", which);
+    (void)hipSetDevice(ctx->device);
+    return LV_OK;
+}
+
+int lv_spatial_hashing_reset(lv_ctx* ctx, int which) {
+    int rc = lv_sh_which(ctx, which);
+    if (rc || (rc = lv_sh_reset(ctx, which))) return rc;
+    return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_spatial_hashing_reset(p, which); });
+}
+
+int lv_spatial_hashing_get_cells(lv_ctx* ctx, int which, uint64_t* keys, uint64_t* accumulators, uint64_t capacity, uint64_t* count) {
+    const int rc = lv_sh_which(ctx, which);
+    if (rc) return rc;
+    if (!count) return lv_fail(ctx, LV_E_INVALID, "null count");
+    return lv_sh_get_cells(ctx, which, keys, accumulators, capacity, count);
+}
+
+int lv_spatial_hashing_get_stats(lv_ctx* ctx, int which, uint64_t out[4]) {
+    const int rc = lv_sh_which(ctx, which);
+    if (rc) return rc;
+    if (!out) return lv_fail(ctx, LV_E_INVALID, "null array");
+    return lv_sh_get_stats(ctx, which, out);
 }
 
 int lv_get_accel(lv_ctx* ctx, void* out_nodes, uint64_t max_nodes, uint32_t* out_leaf_segment, uint64_t max_leaves) {

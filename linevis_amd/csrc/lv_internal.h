@@ -29,6 +29,16 @@ struct LvSvgfState {
     bool historyValid = false;                        // false: clear the history images before the next frame
 };
 
+// Host-side state of a hash map of the spatial-hashing denoiser (lv_sh.hip; semantics in lv_sh.h).  The map itself -- numCells x 16 B
+// {key word, accumulator}, vk_hash_map_buffer of SpatialHashingDenoiser.cpp:62-77 -- and its LvShCounters are device buffers of the context
+struct LvShState {
+    uint32_t numCells = 0;                            // cells of the allocated map; 0: none
+    bool clearPending = false;                        // the next denoise starts with a forced clear (lines / line width / keying options changed)
+    uint64_t pixelsSinceClear = 0;                    // bound on every cell's count since the last host-known clear (< 2^28)
+    float sp = 0.0f, sNd = 0.0f;                      // the options the cells were keyed with
+    int sMinExp = 0;
+};
+
 // Settings with the reference's defaults (file:line next to each value).
 struct LvOptions {
     float lineWidth = 0.002f;                 // src/Loaders/DataSetList.hpp:46
@@ -122,6 +132,13 @@ struct LvOptions {
     bool svgfEnabled = false;
     uint32_t svgfIterations = 5;              // maxNumIterations, SVGF.hpp:115 (GUI range 0..5)
     float svgfAllowedZDist = 0.002f, svgfAllowedNormalDist = 0.02f; // SVGF.hpp:70-71
+    // ambient_occlusion_denoiser = "Spatial Hashing" (Denoiser.hpp:64).  GUI-only in the reference (SpatialHashingDenoiser.cpp:89-92,
+    // 184-186, .hpp:101); the spatial_hashing_* keys are this build's.
+    bool shEnabled = false;
+    float shSp = 8.0f;                        // spatial_hashing_s_p: cell size in pixels, 0.1 ... 20
+    int shSMinExp = -17;                      // spatial_hashing_s_min_exp: s_min = 10^exp, -20 ... -1
+    float shSNd = 3.0f;                       // spatial_hashing_s_nd: normal coarseness, 1 ... 10
+    uint32_t shNumCells = 10000000u;          // spatial_hashing_num_cells (hm_cells, SpatialHashingDenoiser.cpp:42), >= 10
     // intersection_form: 0 = auto (default): the reference's literal roots whenever the RTAO pass traces the reference's
     // triangle tubes (rtao_geometry = triangle_tubes: the colour pass is then the only user of the capsule test and the
     // literal form is nearly free), closest approach otherwise; 1 = closest_approach; 2 = literal
@@ -231,7 +248,12 @@ struct lv_ctx {
     bool aoRestart = false;                   // the denoiser changed: a progressive RTAO accumulation may only continue from frame 0
     LvSvgfState svgf;
     LvDeviceBuffer svgfGiven;                 // every image of one lv_svgf_denoise_buffers call (lv_svgf_denoise_given)
-    LvDeviceBuffer fullFrameTile;             // one tile origin (0, 0): the SVGF chain always covers the viewport
+    LvDeviceBuffer fullFrameTile;             // one tile origin (0, 0): the SVGF and Spatial Hashing chains always cover the viewport
+    LvShState sh[2];                          // spatial hashing: [0] the renderer's map, [1] the map of lv_spatial_hashing_denoise_buffers
+    LvDeviceBuffer shMapCells, shMapCounters; // ... map 0: allocated while the denoiser is selected
+    LvDeviceBuffer shGivenCells, shGivenCounters; // ... map 1
+    LvDeviceBuffer shRead, shNormal, shPosition, shPing, shPong; // its read image, world-space maps {xyz, 0} and a-trous passes (full viewport)
+    LvDeviceBuffer shGiven, shCompact;        // every image of one lv_spatial_hashing_denoise_buffers call; lv_spatial_hashing_get_cells' copy
     uint32_t aoGlobalFrameNumber = 0;         // RTAO iterations since lv_set_lines (globalFrameNumber, ...AmbientOcclusion.cpp:582)
     float lastFrameViewProj[16] = {};         // projection * view at the previous RTAO iteration (:456,631)
     bool lastFrameViewProjValid = false;
@@ -314,10 +336,10 @@ struct lv_ctx {
     bool evLinePointsValid = false, evTessValid = false; // ev[4], ev[6]: the a2 kernels of lv_set_trajectories; ev[8], ev[9]: the last device tessellation
     int lastMode = 0;
     // per-kernel launch timers: ring of event pairs per kernel id (LV_KERNEL_*)
-    static constexpr int kNumKernels = 9;     // LV_KERNEL_HULL is the last; lv_stats reports the first eight
+    static constexpr int kNumKernels = 12;    // LV_KERNEL_SH_TAIL is the last; lv_stats reports the first eight
     static constexpr int kRing = 512;
     hipEvent_t evKernel[kNumKernels][2 * kRing];
-    uint64_t kernelLaunches[kNumKernels] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t kernelLaunches[kNumKernels] = {};
 };
 
 int lv_fail(lv_ctx* ctx, int code, const char* fmt, ...);
@@ -451,6 +473,21 @@ int lv_svgf_prepare(lv_ctx* ctx);
 int lv_svgf_denoise(lv_ctx* ctx, LvSvgfState& V, uint32_t width, uint32_t height, const float* noisy);
 int lv_svgf_denoise_given(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normalDepth, const float* flowFwidth,
                           float* colorHistory, float* momentsHistory, float* normalDepthHistory, float* out);
+// lv_sh.hip: the spatial-hashing denoiser; `which` = index into ctx->sh
+int lv_sh_denoise_frame(lv_ctx* ctx, const float camPos[3], const uint32_t* tileBase, uint32_t numGroups, uint32_t tileW, uint32_t tileH,
+                        uint32_t groupsX, uint32_t groupsPerTile, const uint32_t* hitCount, uint64_t maxPixels, const float** result);
+int lv_sh_denoise_given(lv_ctx* ctx, uint32_t w, uint32_t h, const float* noisy, const float* normalWorld, const float* positionWorld,
+                        const float camPos[3], float* outRead, float* out);
+int lv_sh_reset(lv_ctx* ctx, int which);
+int lv_sh_release(lv_ctx* ctx, int which);
+int lv_sh_get_stats(lv_ctx* ctx, int which, uint64_t out[4]);
+int lv_sh_get_cells(lv_ctx* ctx, int which, uint64_t* keys, uint64_t* accumulators, uint64_t capacity, uint64_t* outCount);
+// lv_render.hip: the a-trous tail of the spatial-hashing denoiser -- three passes of k_eaw_pass<true> over a w x h image with the
+// settings of SpatialHashingDenoiser.cpp:82-87; *result = the buffer that holds the last pass
+int lv_eaw_tail(lv_ctx* ctx, uint32_t w, uint32_t h, const float* src, const float4* normalMap, const float4* positionMap, float* ping,
+                float* pong, const float** result);
+// what the renderer's map was accumulated from has changed (lines, line width): the next denoise starts from an empty map
+inline void lv_sh_invalidate(lv_ctx* ctx) { ctx->sh[0].clearPending = true; }
 // lv_flow.hip
 int lv_flow_set_grid(lv_ctx* ctx, const float* vectorField, uint32_t xs, uint32_t ys, uint32_t zs, float dx, float dy,
                      float dz, const float* const* scalarFields, uint32_t numScalarFields);

@@ -636,6 +636,7 @@ int lv_set_trajectories_with_bands(lv_ctx* ctx, const float* positions, const fl
     ctx->trajSet = true;         // (the tube mesh is tessellated on demand: lv_ensure_tube_mesh)
     ctx->aoGlobalFrameNumber = 0;   // VulkanRayTracedAmbientOcclusionPass::setLineData (.cpp:437-460), as lv_set_lines
     ctx->lastFrameViewProjValid = false;
+    lv_sh_invalidate(ctx);
     return lv_forward_to_ranks(ctx, [&](lv_ctx* p) {
         return lv_set_trajectories_with_bands(p, positions, attribute, line_offsets, num_lines, bands);
     });

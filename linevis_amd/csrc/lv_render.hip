@@ -127,22 +127,7 @@ __global__ __launch_bounds__(LV_BLOCK, (STATS || PRIM == LV_PRIM_ELLIPTIC) ? 1 :
 }
 
 // ================================================================ RTAO
-// G-buffer layout: the segment of 64x64-pixel group g holds exactly the pixels of its tile that fall into the group (a 66 x 66 tile
-// -- 64 + a one-pixel AO halo -- is cut into 2 x 2 groups of 64 x 64, 2 x 64, 64 x 2 and 2 x 2 pixels): tile-major, then group rows,
-// then groups of a row.  The buffer then has numTiles * tileW * tileH slots, not groups * 4096 (4 x the memory with any halo).
-struct LvAoLayout { uint32_t tileW, tileH, groupsX, groupsPerTile; };
-__device__ __host__ __forceinline__ LvAoLayout lv_ao_layout(const LvTiles& T) {
-    LvAoLayout L;
-    L.tileW = T.tileW; L.tileH = T.tileH; L.groupsX = T.blocksX / 4u; L.groupsPerTile = (T.blocksX / 4u) * (T.blocksY / 4u);
-    return L;
-}
-__device__ __forceinline__ size_t lv_ao_group_base(const LvAoLayout& L, uint32_t group) {
-    const uint32_t tile = group / L.groupsPerTile, gi = group % L.groupsPerTile;
-    const uint32_t gxi = gi % L.groupsX, gyi = gi / L.groupsX;
-    const uint32_t hrow = min(64u, L.tileH - 64u * gyi);
-    return size_t(tile) * L.tileW * L.tileH + size_t(gyi) * 64u * L.tileW + size_t(gxi) * 64u * hrow;
-}
-
+// G-buffer layout: LvAoLayout, lv_tile.h
 // G-buffer entry of a pixel whose primary ray hit: 3 x float4
 //   g0 = {hit position, offsetFactor}, g1 = {surface tangent, pixel index bits}, g2 = {surface normal, 0}
 template <bool STATS, int PRIM>
@@ -419,19 +404,6 @@ __global__ __launch_bounds__(LV_BLOCK) void k_ao_tile_scan(const uint32_t* __res
     __syncthreads();
     uint32_t run = s_part[threadIdx.x];
     for (uint32_t i = b; i < e; i++) { tileBase[i] = run; run += tileCount[i]; }
-}
-
-// compacted-pixel ordinal -> G-buffer slot: group g with tileBase[g] <= ordinal < tileBase[g + 1] (binary search; the table
-// is a few KB and stays in L1), slot = first slot of the group's segment + (ordinal - tileBase[g]).  tileBase == nullptr: slot = ordinal.
-__device__ __forceinline__ size_t lv_ao_slot(const uint32_t* __restrict__ tileBase, uint32_t numTiles, const LvAoLayout& tileCapacity,
-                                             uint32_t ordinal) {
-    if (!tileBase) return ordinal;
-    uint32_t lo = 0, hi = numTiles; // invariant: tileBase[lo] <= ordinal < tileBase[hi]
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tileBase[mid] <= ordinal) lo = mid; else hi = mid;
-    }
-    return lv_ao_group_base(tileCapacity, lo) + (ordinal - tileBase[lo]);
 }
 
 // Best hit of an AO ray in LDS, merged with one atomicMin per hit.  The AO value is t / aoRadius or 0 / 1: it never reads which
@@ -3871,9 +3843,10 @@ static uint64_t lv_ao_grid(const lv_ctx* ctx, uint64_t maxRays) {
 // haloPx pixels: 1 when the colour rays are jittered (the AO lookup blends the four texels around the projected hit,
 // AmbientOcclusion.glsl:84-99), plus the 2 * (2^iterations - 1) pixels the EAW denoiser reads around every pixel it filters (a-trous
 // passes with step widths 1, 2, 4, ...).  SVGF is temporal -- its history is read at reprojected positions anywhere in the picture --
-// so with it the pass covers the whole viewport as one tile at the origin, no halo, whatever tiles the call renders.
+// so with it the pass covers the whole viewport as one tile at the origin, no halo, whatever tiles the call renders.  So does Spatial
+// Hashing: its map accumulates every hit of the viewport exactly once per iteration, whatever tiles, shards or ranks draw the frame.
 struct LvAoGeometry {
-    bool svgf;
+    bool wholeViewport;
     uint32_t haloPx, numTiles, tileW, tileH;
     uint64_t maxPixels;
     // workgroups of k_ao_primary, of k_ao_rays, and of k_primary_pair (the RTAO primaries' and the colour pass' in one launch)
@@ -3882,11 +3855,11 @@ struct LvAoGeometry {
 static LvAoGeometry lv_ao_geometry(const lv_ctx* ctx, const LvUniforms& U, const LvTiles& Tcolour) {
     LvAoGeometry G;
     const bool eaw = ctx->opt.eawEnabled && ctx->opt.eawIterations > 0u;
-    G.svgf = ctx->opt.svgfEnabled;
-    G.haloPx = G.svgf ? 0u : (U.aoProjectLookup ? 1u : 0u) + (eaw ? 2u * ((1u << ctx->opt.eawIterations) - 1u) : 0u);
-    G.numTiles = G.svgf ? 1u : Tcolour.numTiles;
-    G.tileW = G.svgf ? ctx->width : Tcolour.tileW + 2u * G.haloPx;
-    G.tileH = G.svgf ? ctx->height : Tcolour.tileH + 2u * G.haloPx;
+    G.wholeViewport = ctx->opt.svgfEnabled || ctx->opt.shEnabled;
+    G.haloPx = G.wholeViewport ? 0u : (U.aoProjectLookup ? 1u : 0u) + (eaw ? 2u * ((1u << ctx->opt.eawIterations) - 1u) : 0u);
+    G.numTiles = G.wholeViewport ? 1u : Tcolour.numTiles;
+    G.tileW = G.wholeViewport ? ctx->width : Tcolour.tileW + 2u * G.haloPx;
+    G.tileH = G.wholeViewport ? ctx->height : Tcolour.tileH + 2u * G.haloPx;
     const LvTiles T = lv_tiles(nullptr, G.numTiles, G.tileW, G.tileH);
     G.gridTiles = lv_tiles_grid(T);
     G.maxPixels = lv_tiles_pixels(T);
@@ -4045,6 +4018,47 @@ static int lv_group_order_sort(lv_ctx* ctx) {
     return LV_OK;
 }
 
+// the one-tile list of a pass over the whole viewport (SVGF, Spatial Hashing and its a-trous tail): origin (0, 0)
+static int lv_full_frame_tile(lv_ctx* ctx) {
+    if (ctx->fullFrameTile.ptr) return LV_OK;
+    int rc;
+    if ((rc = lv_buf_reserve(ctx, ctx->fullFrameTile, 8))) return rc;
+    LV_HIP(ctx, hipMemsetAsync(ctx->fullFrameTile.ptr, 0, 8, ctx->stream));
+    return LV_OK;
+}
+
+// EAWBlitPass(renderer, 3) of the spatial-hashing denoiser (SpatialHashingDenoiser.cpp:82-87): useColorWeights = false,
+// phiPositionScale = 1e-6 on the EAW defaults (phiPosition 0.3, phiNormal 0.1, EAWDenoiser.hpp:82-93), normal and position weights on
+int lv_eaw_tail(lv_ctx* ctx, uint32_t w, uint32_t h, const float* src, const float4* normalMap, const float4* positionMap, float* ping,
+                float* pong, const float** result) {
+    int rc;
+    if ((rc = lv_full_frame_tile(ctx))) return rc;
+    const LvTiles T = lv_tiles((const uint32_t*)ctx->fullFrameTile.ptr, 1u, w, h);
+    LvUniforms U;
+    memset(&U, 0, sizeof U);   // k_eaw_pass reads the extent only
+    U.width = w;
+    U.height = h;
+    LvEawParams E;
+    E.phiColor = 0.49f;
+    E.phiPosition = 0.3f * 0.000001f;
+    E.phiNormal = 0.1f * 1.0f;
+    E.useColor = 0u; E.usePosition = 1u; E.useNormal = 1u;
+    E.stepWidth = 1;
+    float* bufs[2] = {ping, pong};
+    const hipStream_t st = ctx->stream;
+    auto passes = [&]() {   // one timer record for the three
+        for (int i = 0; i < 3; i++) {
+            k_eaw_pass<true><<<nblocks(uint64_t(w) * h), LV_BLOCK, 0, st>>>(U, T, E, src, bufs[i & 1], normalMap, positionMap);
+            src = bufs[i & 1];
+            E.stepWidth *= 2;
+        }
+    };
+    LV_TIMED_LAUNCH(ctx, LV_KERNEL_SH_TAIL, passes());
+    LV_HIP(ctx, hipGetLastError());
+    *result = src;
+    return LV_OK;
+}
+
 // pairColour: the colour pass' scene view when its first-hit trace rides along with the RTAO primaries of the first iteration
 // (k_primary_pair; lv_frame_render decides) -- the hits land in ctx->firstHit, *paired says whether the launch happened
 static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& Tcolour, const LvSceneDev* pairColour = nullptr,
@@ -4058,17 +4072,14 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
     // why the running mean below reads the previous pass' image (ping-pong) instead of updating in place.  Or the whole viewport.
     const LvAoGeometry G = lv_ao_geometry(ctx, U, Tcolour);
     const bool eaw = ctx->opt.eawEnabled && ctx->opt.eawIterations > 0u;
-    const bool svgf = G.svgf, halo = G.haloPx != 0u;
+    const bool whole = G.wholeViewport, svgf = ctx->opt.svgfEnabled, sh = ctx->opt.shEnabled, halo = G.haloPx != 0u;
     const uint32_t haloPx = G.haloPx, gridTiles = uint32_t(G.gridTiles), gridTilesColour = uint32_t(lv_tiles_grid(Tcolour));
     const uint64_t maxPixelsColour = lv_tiles_pixels(Tcolour), maxPixels = G.maxPixels;
     LvTiles T = Tcolour;
-    if (svgf) {
-        if (!ctx->fullFrameTile.ptr) {
-            if ((rc = lv_buf_reserve(ctx, ctx->fullFrameTile, 8))) return rc;
-            LV_HIP(ctx, hipMemsetAsync(ctx->fullFrameTile.ptr, 0, 8, st));
-        }
+    if (whole) {
+        if ((rc = lv_full_frame_tile(ctx))) return rc;
         T = lv_tiles((const uint32_t*)ctx->fullFrameTile.ptr, G.numTiles, G.tileW, G.tileH);
-        if ((rc = lv_svgf_prepare(ctx))) return rc;
+        if (svgf && (rc = lv_svgf_prepare(ctx))) return rc;
     }
     if (halo) {
         const uint32_t n = Tcolour.numTiles;
@@ -4097,7 +4108,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
     const uint32_t numGroups = uint32_t(lv_tiles_groups(T));
     // dispatch order: the colour pass' (same launch geometry: both passes add to one cost array) or, on dilated tiles / the
     // whole viewport, one of its own
-    if ((svgf || halo) && (rc = lv_group_order_prepare(ctx, T, 1))) return rc;
+    if ((whole || halo) && (rc = lv_group_order_prepare(ctx, T, 1))) return rc;
     if ((rc = lv_group_order_sort(ctx))) return rc;
     const LvAoLayout tileCap = lv_ao_layout(T);   // segments sized by the pixels a group really holds
     if ((rc = lv_buf_reserve(ctx, ctx->aoGbuf, size_t(maxPixels) * 48))) return rc;
@@ -4105,7 +4116,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
     if ((rc = lv_buf_reserve(ctx, ctx->aoList, (2 * size_t(numGroups) + 1) * 4))) return rc; // per-group counts, then bases
     uint32_t* tileCount = (uint32_t*)ctx->aoList.ptr;
     uint32_t* tileBase = tileCount + numGroups;
-    ctx->aoNumGroups = svgf ? 0u : numGroups; // whole-viewport pass: no per-tile costs of the caller's tile list (lv_get_ao_tile_costs)
+    ctx->aoNumGroups = whole ? 0u : numGroups; // whole-viewport pass: no per-tile costs of the caller's tile list (lv_get_ao_tile_costs)
     ctx->aoGroupsPerTile = tileCap.groupsPerTile;
     const bool tri = lv_ao_triangle_tubes(ctx);
     // RTAO geometry: the capsules of the colour pass, or the reference's triangle tubes (own LBVH, own scene view)
@@ -4127,6 +4138,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
             return lv_fail(ctx, LV_E_STATE, "ambient_occlusion_denoiser changed: restart the accumulation with frame_number = 0");
         ctx->aoRestart = false;
     }
+    const float* shResult = nullptr;
     const uint32_t iterBegin = progressive ? ctx->opt.frameNumber : 0u;
     const uint32_t iterEnd = progressive ? std::min(ctx->opt.frameNumber + 1u, ctx->opt.aoIterations) : ctx->opt.aoIterations;
     for (uint32_t iter = iterBegin; iter < iterEnd; iter++) {
@@ -4135,10 +4147,13 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         LvSvgfFeat SF;
         SF.normalDepth = nullptr;
         SF.flowFwidth = nullptr;
-        if (svgf) {
-            // DISABLE_ACCUMULATION + useGlobalFrameNumber (SVGF.hpp:81-82; VulkanRayTracedAmbientOcclusion.cpp:415-421,576-581)
+        if (whole) {
+            // DISABLE_ACCUMULATION + useGlobalFrameNumber (SVGF.hpp:81-82, SpatialHashingDenoiser.hpp:83-84;
+            // VulkanRayTracedAmbientOcclusion.cpp:415-421,576-581)
             U.aoFrameNumber = 0;
             U.aoGlobalFrameNumber = ctx->aoGlobalFrameNumber;
+        }
+        if (svgf) {
             SF.normalDepth = (float4*)ctx->svgf.normalDepth.ptr;
             SF.flowFwidth = (float4*)ctx->svgf.flowFwidth.ptr;
             float vp[16];
@@ -4216,8 +4231,13 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         // temporal denoiser: denoise() belongs to every _render (VulkanRayTracedAmbientOcclusion.cpp:633-651), its history advances
         // with every RTAO iteration
         if (svgf && (rc = lv_svgf_denoise(ctx, ctx->svgf, ctx->width, ctx->height, (const float*)ctx->ao.ptr))) return rc;
+        // Spatial_Hashing_Denoiser::denoise() sits in the same place: the map takes every iteration's hits and AO
+        if (sh && (rc = lv_sh_denoise_frame(ctx, U.camPos, tileBase, numGroups, tileCap.tileW, tileCap.tileH, tileCap.groupsX,
+                                            tileCap.groupsPerTile, &dc->aoCount, maxPixels, &shResult)))
+            return rc;
     }
-    if (iterEnd > iterBegin || !ctx->aoResult) ctx->aoResult = svgf ? (const float*)ctx->svgf.result.ptr : (const float*)ctx->ao.ptr;
+    if (iterEnd > iterBegin || !ctx->aoResult)
+        ctx->aoResult = svgf ? (const float*)ctx->svgf.result.ptr : (sh && shResult) ? shResult : (const float*)ctx->ao.ptr;
     if (eaw && iterEnd > iterBegin) {
         // denoiser->denoise() after the RTAO pass (VulkanRayTracedAmbientOcclusion.cpp:633-651): the accumulation keeps running
         // on the raw image, the colour pass samples the denoised one
@@ -5509,7 +5529,7 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     const bool pairWanted = ctx->opt.overlapPrimaryPasses == 1 || (ctx->opt.overlapPrimaryPasses == 2 && gridTiles <= 16u * uint32_t(ctx->numCUs));
     const bool pairPrimaries = pairWanted && rayTracer && U.useAmbientOcclusion &&
                                !U.aoPrebaked && !ctx->opt.useMlat && !ctx->opt.rtTriangleMesh && !U.useEllipticTubes &&
-                               !ctx->opt.svgfEnabled && (U.useJitteredRays ? U.numSamplesPerFrame : 1u) == 1u && ctx->numSegs > 0u &&
+                               !ctx->opt.svgfEnabled && !ctx->opt.shEnabled && (U.useJitteredRays ? U.numSamplesPerFrame : 1u) == 1u && ctx->numSegs > 0u &&
                                (ctx->opt.numAccumulatedFrames <= 1u || ctx->opt.frameNumber < ctx->opt.aoIterations);
     // one reservation for every launch of this frame: no view built below can move the slab
     const size_t need = lv_frame_overflow_bytes(ctx, U, T, mode, pairPrimaries);

@@ -84,6 +84,36 @@ __device__ __forceinline__ void lv_group_cost_add(const LvTiles& T, const LvPixe
     }
 }
 
+// ---------------------------------------------------------------- G-buffer of the RTAO pass (lv_render.hip, lv_sh.hip)
+// G-buffer layout: the segment of 64x64-pixel group g holds exactly the pixels of its tile that fall into the group (a 66 x 66 tile
+// -- 64 + a one-pixel AO halo -- is cut into 2 x 2 groups of 64 x 64, 2 x 64, 64 x 2 and 2 x 2 pixels): tile-major, then group rows,
+// then groups of a row.  The buffer then has numTiles * tileW * tileH slots, not groups * 4096 (4 x the memory with any halo).
+struct LvAoLayout { uint32_t tileW, tileH, groupsX, groupsPerTile; };
+__device__ __host__ __forceinline__ LvAoLayout lv_ao_layout(const LvTiles& T) {
+    LvAoLayout L;
+    L.tileW = T.tileW; L.tileH = T.tileH; L.groupsX = T.blocksX / 4u; L.groupsPerTile = (T.blocksX / 4u) * (T.blocksY / 4u);
+    return L;
+}
+__device__ __forceinline__ size_t lv_ao_group_base(const LvAoLayout& L, uint32_t group) {
+    const uint32_t tile = group / L.groupsPerTile, gi = group % L.groupsPerTile;
+    const uint32_t gxi = gi % L.groupsX, gyi = gi / L.groupsX;
+    const uint32_t hrow = min(64u, L.tileH - 64u * gyi);
+    return size_t(tile) * L.tileW * L.tileH + size_t(gyi) * 64u * L.tileW + size_t(gxi) * 64u * hrow;
+}
+
+// compacted-pixel ordinal -> G-buffer slot: group g with tileBase[g] <= ordinal < tileBase[g + 1] (binary search; the table
+// is a few KB and stays in L1), slot = first slot of the group's segment + (ordinal - tileBase[g]).  tileBase == nullptr: slot = ordinal.
+__device__ __forceinline__ size_t lv_ao_slot(const uint32_t* __restrict__ tileBase, uint32_t numTiles, const LvAoLayout& tileCapacity,
+                                             uint32_t ordinal) {
+    if (!tileBase) return ordinal;
+    uint32_t lo = 0, hi = numTiles; // invariant: tileBase[lo] <= ordinal < tileBase[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tileBase[mid] <= ordinal) lo = mid; else hi = mid;
+    }
+    return lv_ao_group_base(tileCapacity, lo) + (ordinal - tileBase[lo]);
+}
+
 } // namespace
 
 #endif

@@ -41,10 +41,12 @@ bool HipRayTracedAmbientOcclusion::setNewSettings(const SettingsMap& settings) {
         optionChanged = true;
     }
     // the denoiser of the RTAO pass (VulkanRayTracedAmbientOcclusion::setNewSettings, .cpp:115-144,683-696) and its parameters
-    // (EAWDenoiser.cpp:400-432; the svgf_* keys are this build's): forwarded as they are, a change restarts the accumulation
+    // (EAWDenoiser.cpp:400-432; the svgf_* and spatial_hashing_* keys are this build's -- "SVGF" and "Spatial Hashing" have GUI sliders
+    // only in the reference): forwarded as they are, a change restarts the accumulation
     for (const auto& kv : settings.getMap()) {
         const std::string& k = kv.first;
-        if (k == "ambient_occlusion_denoiser" || k.rfind("eaw_denoiser_", 0) == 0 || k.rfind("svgf_denoiser_", 0) == 0) {
+        if (k == "ambient_occlusion_denoiser" || k.rfind("eaw_denoiser_", 0) == 0 || k.rfind("svgf_denoiser_", 0) == 0 ||
+            k.rfind("spatial_hashing_", 0) == 0) {
             lv_set_option(ctx, k.c_str(), kv.second.c_str());
             optionChanged = true;
         }
@@ -609,7 +611,7 @@ bool HipRayTracer::setNewSettings(const SettingsMap& settings) {
     for (const auto& kv : settings.getMap()) {
         const std::string& k = kv.first;
         if (k.rfind("ambient_occlusion_", 0) == 0 || k.rfind("eaw_denoiser_", 0) == 0 || k.rfind("svgf_denoiser_", 0) == 0 ||
-            k == "rtao_geometry" || k == "use_jittered_primary_rays")
+            k.rfind("spatial_hashing_", 0) == 0 || k == "rtao_geometry" || k == "use_jittered_primary_rays")
             accumulatedFramesCounter = 0;
     }
     std::string s;
