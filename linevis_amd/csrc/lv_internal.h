@@ -321,6 +321,7 @@ struct lv_ctx {
     uint64_t tilesGeneration = 0;             // bumped whenever tilesDev receives another list
     bool tilesCoverViewport = false;          // the uploaded tile list covers every pixel of the viewport (key: width, height, tile size)
     uint32_t tilesCoverKey[4] = {0, 0, 0, 0};
+    bool tilesOverlap = false;                // two tiles of the uploaded list share a pixel (same key): the RTAO running mean must not update in place
     std::vector<uint32_t> tilesHost;          // staging copy: caller's tile list is borrowed for the call only
     bool tilesUploaded = false;               // tilesDev holds tilesHost
     uint64_t ppllPoolNodes = 0;               // physical node slots of the pool (logical size + per-wave chunk slack)

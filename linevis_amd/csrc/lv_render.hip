@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <unordered_map>
 
 #include "lv_internal.h"
 #include "lv_trace.h"
@@ -811,8 +812,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_ao_reduce(const LvUniforms U, cons
     aoFactor /= float(spp);
     // screen space: the pixel of the compacted slot; prebaker: ambientOcclusionFactors[subdiv + N * vertex] = the slot
     const uint32_t pix = BAKE ? slot : __float_as_uint(gbuf[3 * lv_ao_slot(tileBase, numTiles, tileCapacity, slot) + 1].w);
-    // aoIn == ao except with a halo: the 1-pixel rings of neighbouring tiles overlap, a pixel may then be processed twice in
-    // one pass, and the running mean must read the PREVIOUS pass' image to stay idempotent (lv_run_ao)
+    // aoIn == ao except where tiles overlap (the 1-pixel rings of a halo, a tile listed twice): a pixel may then be processed twice
+    // in one pass, and the running mean must read the PREVIOUS pass' image to stay idempotent (lv_run_ao)
     if (U.aoFrameNumber != 0) aoFactor = mixf(aoIn[pix], aoFactor, 1.0f / float(U.aoFrameNumber + 1));
     ao[pix] = aoFactor;
 }
@@ -4094,8 +4095,12 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         }
         T = lv_tiles((const uint32_t*)ctx->tilesHaloDev.ptr, G.numTiles, G.tileW, G.tileH);
         if (lv_tiles_blocks(T) > 0x7FFFFFF0ull) return lv_fail(ctx, LV_E_INVALID, "tile list too large");
-        if ((rc = lv_buf_reserve(ctx, ctx->aoAlt, size_t(ctx->width) * ctx->height * 4))) return rc;
     }
+    // Tiles that share pixels -- the rings of a halo, a tile the caller lists twice -- compute those pixels once per tile.  The running
+    // mean of iteration > 0 reads the previous iteration's image: updated in place, the second copy of a pixel could read what the first
+    // had just written and blend the new factor in twice.  Such passes read one image and write the other.
+    const bool pingPong = halo || (!whole && ctx->tilesOverlap);
+    if (pingPong && (rc = lv_buf_reserve(ctx, ctx->aoAlt, size_t(ctx->width) * ctx->height * 4))) return rc;
     const size_t numPix = size_t(ctx->width) * ctx->height;
     if (eaw) {
         for (LvDeviceBuffer* b : {&ctx->featNormal, &ctx->featNormalAlt, &ctx->featPosition, &ctx->featPositionAlt})
@@ -4166,9 +4171,9 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         LV_HIP(ctx, hipMemsetAsync(tileCount, 0, size_t(numGroups) * 4, st));
         const uint32_t grid = uint32_t(G.gridRays);
         const float4* g = (const float4*)ctx->aoGbuf.ptr;
-        // halo: read the previous pass' image, write the other buffer, swap; otherwise update in place
+        // overlapping tiles: read the previous pass' image, write the other buffer, swap; otherwise update in place
         const float* aoIn = (const float*)ctx->ao.ptr;
-        float* ao = halo ? (float*)ctx->aoAlt.ptr : (float*)ctx->ao.ptr;
+        float* ao = pingPong ? (float*)ctx->aoAlt.ptr : (float*)ctx->ao.ptr;
         float* smp = (float*)ctx->aoSamples.ptr;
         // feature maps of the denoiser: same ping-pong as the AO image (the EAW halo makes the tiles overlap)
         const float4* fnIn = eaw ? (const float4*)ctx->featNormal.ptr : nullptr;
@@ -4226,7 +4231,7 @@ static int lv_run_ao(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles& T
         } else {
             k_ao_reduce<false><<<nblocks(maxPixels), LV_BLOCK, 0, st>>>(U, g, smp, aoIn, ao, dc, tileBase, numGroups, tileCap);
         }
-        if (halo) std::swap(ctx->ao, ctx->aoAlt);
+        if (pingPong) std::swap(ctx->ao, ctx->aoAlt);
         if (eaw) { std::swap(ctx->featNormal, ctx->featNormalAlt); std::swap(ctx->featPosition, ctx->featPositionAlt); }
         // temporal denoiser: denoise() belongs to every _render (VulkanRayTracedAmbientOcclusion.cpp:633-651), its history advances
         // with every RTAO iteration
@@ -5157,8 +5162,27 @@ static bool lv_tiles_cover(uint32_t width, uint32_t height, uint32_t tileW, uint
     return present == size_t(gx) * gy;
 }
 
-// The frame's tile list on the device (ctx->tilesDev, reserved by the caller) and ctx->tilesCoverViewport.  The tile list is usually
-// the same from frame to frame (a rank keeps its tiles): it is uploaded only when it changes, so that consecutive frames need no host
+// Do two tiles of the list share a pixel (a tile listed twice, tiles off the grid)?  Equal-sized tiles overlap iff |dx| < tileW and
+// |dy| < tileH; the grid cells of their origins are then the same or neighbours, and no cell holds the origins of two disjoint tiles.
+static bool lv_tiles_overlap(uint32_t tileW, uint32_t tileH, const uint32_t* tiles, uint32_t numTiles) {
+    std::unordered_map<uint64_t, uint32_t> cells;   // grid cell of an origin -> its tile
+    cells.reserve(numTiles);
+    for (uint32_t t = 0; t < numTiles; t++) {
+        const uint64_t tx = tiles[2 * t], ty = tiles[2 * t + 1], cx = tx / tileW, cy = ty / tileH;
+        for (uint64_t ny = cy ? cy - 1u : 0u; ny <= cy + 1u; ny++)
+            for (uint64_t nx = cx ? cx - 1u : 0u; nx <= cx + 1u; nx++) {
+                const auto it = cells.find(ny << 32 | nx);
+                if (it == cells.end()) continue;
+                const uint64_t ox = tiles[2 * it->second], oy = tiles[2 * it->second + 1];
+                if ((ox > tx ? ox - tx : tx - ox) < tileW && (oy > ty ? oy - ty : ty - oy) < tileH) return true;
+            }
+        cells[cy << 32 | cx] = t;
+    }
+    return false;
+}
+
+// The frame's tile list on the device (ctx->tilesDev, reserved by the caller), ctx->tilesCoverViewport and ctx->tilesOverlap.
+// The tile list is usually the same from frame to frame (a rank keeps its tiles): it is uploaded only when it changes, so that consecutive frames need no host
 // synchronisation and the CPU can enqueue frame k+1 while frame k runs.  The cover test runs again when the list, the viewport or the
 // tile size changed (ctx->tilesCoverKey).
 static int lv_frame_tiles(lv_ctx* ctx, const uint32_t* tilesXYHost, uint32_t numTiles, uint32_t tileW, uint32_t tileH) {
@@ -5177,6 +5201,7 @@ static int lv_frame_tiles(lv_ctx* ctx, const uint32_t* tilesXYHost, uint32_t num
     if (ctx->tilesCoverKey[0] != ctx->width || ctx->tilesCoverKey[1] != ctx->height || ctx->tilesCoverKey[2] != tileW ||
         ctx->tilesCoverKey[3] != tileH) {
         ctx->tilesCoverViewport = lv_tiles_cover(ctx->width, ctx->height, tileW, tileH, tilesXYHost, numTiles);
+        ctx->tilesOverlap = numTiles > 1u && lv_tiles_overlap(tileW, tileH, tilesXYHost, numTiles);
         ctx->tilesCoverKey[0] = ctx->width; ctx->tilesCoverKey[1] = ctx->height; ctx->tilesCoverKey[2] = tileW; ctx->tilesCoverKey[3] = tileH;
     }
     return LV_OK;
