@@ -399,8 +399,27 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   mode 5's counts, maximum and statistics, mode 8's sums and counts and mode 10's slots, tail and counts include it; memory added
  *   to a frame: none beyond the mesh; timer: LV_KERNEL_HULL.  Modes 6 and 9 draw no hull in the reference (MBOITRenderer.cpp:84 and
  *   DepthPeelingRenderer.cpp:86 reset the pass) and none here: they render the same frame with or without a mesh.  Modes 1, 2, 3
- *   and 11 are not built for the hull yet: while a hull would be drawn lv_render returns LV_E_INVALID for them (the message names
- *   modes 5, 8 and 10; the context stays usable); with hull_opacity 0 or no mesh they render as without these keys, byte for byte.
+ *   and -- unless hull_ray_tracing = on (below) -- 11 are not built for the hull: while a hull would be drawn lv_render returns
+ *   LV_E_INVALID for them (the message names modes 5, 8 and 10; the context stays usable); with hull_opacity 0 or no mesh they
+ *   render as without these keys, byte for byte.
+ *   hull_ray_tracing (build-owned switch): "off" (default: everything above, the refusal of mode 11 included) | "on": a mode-11
+ *   frame draws the hull while one is drawn by the rule of hull_opacity -- the reference puts a hull triangle BLAS into every TLAS of
+ *   the ray tracer (LineData.cpp:949-1162) and shades its hits in ClosestHitHull (TubeRayTracing.glsl:359-431) inside the transparency
+ *   loop of the lines.  Per step of that loop the nearer of the closest line hit and the closest hull hit is taken (a tie goes to the
+ *   line); the hull hit is the least t over the triangles the build's ray-triangle test accepts (Moeller-Trumbore without culling +
+ *   the own-box rule with pad = maxAbs * 1e-5 + 1e-6, maxAbs = the mesh's largest absolute coordinate; ties: lowest triangle index),
+ *   shaded with the interpolated normal NORMALISED (alpha = hull_opacity * (1 - |n . v|)), payload.hitT = |position - camera|; the
+ *   semantics are stated once in csrc/lv_hull_rt.h.  The colour pass is then k_render_rt_hull, for every geometry mode and band
+ *   variant of the colour pass (not under shading_numerics = fast, which is refused: see rt_record_hits); the hull's LBVH is built
+ *   by the first frame or lv_trace_rays_hull call that needs it, rebuilt after lv_set_hull_mesh and by nothing else.  With "on" and
+ *   no hull drawn the frame is the "off" frame byte for byte (the same kernels run).  use_mlat together with a drawn, ray-traced hull
+ *   returns LV_E_INVALID (the any-hit variant AnyHitHull is not built); modes 1, 2 and 3 keep refusing.
+ *   rt_record_hits (build-owned: "true" | "1" | "false" | "0", default false) / rt_hits_capacity (records, default 4 Mi, at most
+ *   64 Mi): a mode-11 frame without use_mlat runs k_render_rt_hull -- also when no hull is drawn -- and records every step of every
+ *   pixel's loop for lv_rt_get_hits.  A record numbers the steps of a loop in 16 bits: a recording frame with max_depth_complexity
+ *   above 65536 returns LV_E_INVALID.  k_render_rt_hull has no variant for shading_numerics = fast: a frame it would render -- a
+ *   recording frame, or a frame with a drawn, ray-traced hull -- returns LV_E_INVALID under that option instead of a frame with
+ *   other lighting than the non-recording one (the message names shading_numerics).
  *   line_primitive_mode: "Tube (Programmable Pull)" (default: the programmable-pull N-gon prism, today's frames byte for byte) |
  *   "Quads (Programmable Pull)" (LineData::LinePrimitiveMode by its display name, LineData.cpp:56-74; LinePassQuads.glsl): two
  *   camera-facing triangles per segment, shaded as a round tube from one interpolated coordinate.  Every other name of the reference's
@@ -753,6 +772,20 @@ int lv_trace_rays(lv_ctx* ctx, const float* origins, const float* dirs, float t_
  * index; out_uv (2 floats per ray, may be NULL) = barycentrics as rayQueryGetIntersectionBarycentricsEXT. */
 int lv_trace_rays_triangles(lv_ctx* ctx, const float* origins, const float* dirs, float t_min, float t_max, uint32_t n,
                             float* out_t, uint32_t* out_triangle, float* out_uv);
+/* Same against the simulation-mesh hull (lv_set_hull_mesh) with the hull's own pad (hull_ray_tracing above): the closest hull hit H of
+ * csrc/lv_hull_rt.h, t inside [t_min, t_max].  Works whatever hull_ray_tracing and hull_opacity say; builds the hull's LBVH if no frame
+ * has yet.  LV_E_STATE without a mesh. */
+int lv_trace_rays_hull(lv_ctx* ctx, const float* origins, const float* dirs, float t_min, float t_max, uint32_t n,
+                       float* out_t, uint32_t* out_triangle, float* out_uv);
+/* The steps of every pixel's transparency loop in the last whole-viewport mode-11 frame rendered with rt_record_hits (lv_render, or a
+ * tile list that covers the viewport without overlap; not with use_mlat): 9 uint32 per record {viewport pixel index y * W + x,
+ * sampleIdx << 16 | hitIdx, primitive, bits of t, bits of payload.hitT, bits of the hit's straight colour r, g, b, a}; primitive = bit
+ * 31 | hull triangle index for a hull hit, else original segment << 2 | kind (lv_trace_rays' kinds; original triangle << 2 in the
+ * Triangle Mesh geometry mode).  A miss is not recorded; records arrive in no particular order.  *out_count is always the number the
+ * frame produced; more than the rt_hits_capacity that frame ran with (raising the option afterwards does not help: render again), or
+ * than max_records with out_records given, returns LV_E_CAPACITY.  out_records may be
+ * NULL (query the count).  LV_E_STATE when the last frame recorded nothing. */
+int lv_rt_get_hits(lv_ctx* ctx, uint32_t* out_records, uint64_t max_records, uint64_t* out_count);
 /* LineRenderer::computeDepthRange (LineRenderer.cpp:410-431): min/max view depth of all line points. */
 int lv_compute_depth_range(lv_ctx* ctx, float out_min_max[2]);
 /* Full-viewport RTAO texture (.x channel of the RGBA32F accumulation image) after the last mode-11/2 render. */

@@ -5,7 +5,8 @@
 (src/Renderers/LineRenderer.cpp:433-498, VulkanRayTracer.cpp:226-278, ...), forwarded through
 LineRenderer::setNewSettings of the plugin classes in linevis_amd/host/ and LineData::setNewSettings of the data set -- among them
 hull_opacity, hull_color ("r g b") and hull_use_shading of the simulation-mesh hull, which the modes al64, wboit and "Depth Complexity
-Renderer" draw when the data has an outline mesh (a version-2 .binlines file, or --hull-box), and line_primitive_mode
+Renderer" draw when the data has an outline mesh (a version-2 .binlines file, or --hull-box) -- the mode rt ray-traces it with
+hull_ray_tracing=on --, and line_primitive_mode
 ("line_primitive_mode=Quads (Programmable Pull)": the same three modes draw view-aligned line quads instead of tubes).
 Needs an MI355X: there is no CPU fallback.
 """

@@ -118,7 +118,7 @@ SYMBOLS = ["lv_create", "lv_destroy", "lv_last_error", "lv_version", "lv_set_str
            "lv_set_tube_triangle_mesh", "lv_trace_rays_triangles", "lv_set_flow_grid", "lv_trace_streamlines", "lv_trace_streamlines_max_helicity_first",
            "lv_get_streamlines", "lv_get_streamline_seed_indices", "lv_set_ao_parametrization", "lv_get_baked_ao", "lv_bake_ao_start", "lv_bake_ao_poll", "lv_get_mlat_trace", "lv_selftest_rsqrt", "lv_selftest_eval", "lv_selftest_stack",
            "lv_set_trajectories", "lv_set_trajectories_with_bands", "lv_get_lines", "lv_get_tube_triangle_mesh",
-           "lv_set_hull_mesh", "lv_get_hull_mesh", "lv_hull_get_fragments", "lv_line_quads_get_fragments",
+           "lv_set_hull_mesh", "lv_get_hull_mesh", "lv_hull_get_fragments", "lv_trace_rays_hull", "lv_rt_get_hits", "lv_line_quads_get_fragments",
            "lv_create_multi", "lv_multi_ranks", "lv_multi_rank_stats", "lv_multi_rebalance", "lv_multi_deal", "lv_tile_deal", "lv_make_tiles"]
 
 # function -> (LV_FN_* id, argument words, result words) of lv_selftest_eval
@@ -231,6 +231,8 @@ def load():
         ("lv_set_ao_parametrization", [vp, vp, u32, vp, u32]),
         ("lv_get_baked_ao", [vp, vp, u64]),
         ("lv_get_mlat_trace", [vp, vp, u64, C.POINTER(u64)]),
+        ("lv_trace_rays_hull", [vp, vp, vp, f32, f32, u32, vp, vp, vp]),
+        ("lv_rt_get_hits", [vp, vp, u64, C.POINTER(u64)]),
         ("lv_selftest_rsqrt", [vp, C.POINTER(u64), C.POINTER(u32)]),
         ("lv_selftest_eval", [vp, u32, vp, u64, vp]),
         ("lv_selftest_stack", [vp, u32, u32, vp, u32, vp, vp, vp]),
@@ -525,6 +527,27 @@ class Context:
         uv = np.empty((n, 2), dtype=np.float32)
         self._ck(self.L.lv_trace_rays_triangles(self.h, _p(o), _p(d), t_min, t_max, n, _p(t), _p(tri), _p(uv)))
         return t, tri, uv
+
+    def trace_rays_hull(self, origins, dirs, t_min, t_max):
+        """lv_trace_rays_hull: the closest hit of every ray with the simulation-mesh hull -> (t, triangle or 0xFFFFFFFF, uv [n, 2])"""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        t = np.empty(n, dtype=np.float32)
+        tri = np.empty(n, dtype=np.uint32)
+        uv = np.empty((n, 2), dtype=np.float32)
+        self._ck(self.L.lv_trace_rays_hull(self.h, _p(o), _p(d), t_min, t_max, n, _p(t), _p(tri), _p(uv)))
+        return t, tri, uv
+
+    def rt_hits(self):
+        """lv_rt_get_hits: the steps of every pixel's loop in the last whole-viewport mode-11 frame rendered with rt_record_hits, as
+        (n, 9) uint32 records {pixel, sampleIdx << 16 | hitIdx, bit 31 | hull triangle or segment << 2 | kind, bits of t, of
+        payload.hitT and of the straight colour r, g, b, a}, in no particular order."""
+        cnt = C.c_uint64()
+        self._ck(self.L.lv_rt_get_hits(self.h, None, 0, C.byref(cnt)))
+        rec = np.zeros((max(int(cnt.value), 1), 9), dtype=np.uint32)
+        self._ck(self.L.lv_rt_get_hits(self.h, _p(rec), rec.shape[0], C.byref(cnt)))
+        return rec[:int(cnt.value)]
 
     def set_ao_parametrization(self, blending_weights, sampling_locations):
         bw = np.ascontiguousarray(blending_weights, dtype=np.float32)

@@ -116,7 +116,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven,
             &ctx->shMapCells, &ctx->shMapCounters, &ctx->shGivenCells, &ctx->shGivenCounters, &ctx->shRead, &ctx->shNormal, &ctx->shPosition, &ctx->shPing, &ctx->shPong, &ctx->shGiven, &ctx->shCompact, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
             &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->visBuf, &ctx->deferredTf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
-            &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag, &ctx->hullIdx, &ctx->hullVerts,
+            &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag, &ctx->hullIdx, &ctx->hullVerts, &ctx->hullNodes, &ctx->hullTris, &ctx->rtHits,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
             &ctx->bakeGbuf, &ctx->bakeSamples, &ctx->bakeOverflow, &ctx->mlatTrace, &ctx->buildArena, &ctx->partitionScratch, &ctx->firstHit,
@@ -346,6 +346,11 @@ int lv_set_hull_mesh(lv_ctx* ctx, const uint32_t* triangle_indices, uint32_t num
     LV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // host arrays are borrowed for the call only
     ctx->hullNumTris = num_triangles;
     ctx->hullNumVerts = num_vertices;
+    // the ray tracer's LBVH over the mesh is rebuilt by whoever walks it next (lv_bvh_build_hull); hullPad follows from the largest
+    // absolute coordinate
+    ctx->hullAccelValid = false;
+    ctx->hullMaxAbs = 0.0f;
+    for (uint64_t i = 0; i < 3ull * num_vertices; i++) ctx->hullMaxAbs = fmaxf(ctx->hullMaxAbs, fabsf(positions[i]));
     return lv_forward_to_ranks(ctx, [&](lv_ctx* p) { return lv_set_hull_mesh(p, triangle_indices, num_triangles, positions, normals, num_vertices); });
 }
 
@@ -859,6 +864,18 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
     } else if (k == "mlat_trace_capacity") {
         if (!parseUint(value, u) || u == 0 || u > (1u << 28)) return bad();
         o.mlatTraceCapacity = u;
+    } else if (k == "hull_ray_tracing") {
+        // mode 11 draws the simulation-mesh hull (lv_hull_rt.h); "off" keeps the refusal
+        if (strcmp(value, "on") == 0) o.hullRayTracing = true;
+        else if (strcmp(value, "off") == 0) o.hullRayTracing = false;
+        else return bad();
+    } else if (k == "rt_record_hits") {
+        if (strcmp(value, "true") == 0 || strcmp(value, "1") == 0) o.rtRecordHits = true;
+        else if (strcmp(value, "false") == 0 || strcmp(value, "0") == 0) o.rtRecordHits = false;
+        else return bad();
+    } else if (k == "rt_hits_capacity") {
+        if (!parseUint(value, u) || u == 0 || u > (1u << 26)) return bad();
+        o.rtHitsCapacity = u;
     } else if (k == "max_depth_complexity") {
         if (!parseUint(value, u) || u == 0) return bad();
         o.maxDepthComplexity = u;
@@ -1280,6 +1297,14 @@ int lv_trace_rays_triangles(lv_ctx* ctx, const float* origins, const float* dirs
     return lv_frame_trace_rays_triangles(ctx, origins, dirs, t_min, t_max, n, out_t, out_triangle, out_uv);
 }
 
+int lv_trace_rays_hull(lv_ctx* ctx, const float* origins, const float* dirs, float t_min, float t_max, uint32_t n, float* out_t,
+                       uint32_t* out_triangle, float* out_uv) {
+    if (!ctx) return LV_E_INVALID;
+    if (n && (!origins || !dirs || !out_t || !out_triangle)) return lv_fail(ctx, LV_E_INVALID, "null array");
+    (void)hipSetDevice(ctx->device);
+    return lv_frame_trace_rays_hull(ctx, origins, dirs, t_min, t_max, n, out_t, out_triangle, out_uv);
+}
+
 int lv_set_flow_grid(lv_ctx* ctx, const float* vector_field, uint32_t xs, uint32_t ys, uint32_t zs, float dx, float dy,
                      float dz, const float* const* scalar_fields, uint32_t num_scalar_fields) {
     if (!ctx) return LV_E_INVALID;
@@ -1641,6 +1666,27 @@ int lv_get_mlat_trace(lv_ctx* ctx, uint32_t* out_records, uint64_t max_records, 
                            hc.mlatTraceCount);
         if (hc.mlatTraceCount)
             LV_HIP(ctx, hipMemcpy(out_records, ctx->mlatTrace.ptr, size_t(hc.mlatTraceCount) * 16, hipMemcpyDeviceToHost));
+    }
+    return LV_OK;
+}
+
+int lv_rt_get_hits(lv_ctx* ctx, uint32_t* out_records, uint64_t max_records, uint64_t* out_count) {
+    if (!ctx) return LV_E_INVALID;
+    if (!ctx->rtHitsValid || !ctx->rtHits.ptr || !ctx->counters.ptr || ctx->lastMode != LV_RENDERING_MODE_VULKAN_RAY_TRACER)
+        return lv_fail(ctx, LV_E_STATE, "no hit records (render the whole viewport in mode 11 with rt_record_hits and without use_mlat first)");
+    (void)hipSetDevice(ctx->device);
+    LV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    LvDevCountersHost hc;
+    LV_HIP(ctx, hipMemcpy(&hc, ctx->counters.ptr, sizeof(hc), hipMemcpyDeviceToHost));
+    if (out_count) *out_count = hc.mlatTraceCount;
+    // (against the capacity the frame recorded with: the option may have been raised since, the buffer has not grown)
+    if (hc.mlatTraceCount > ctx->rtHitsFrameCapacity)
+        return lv_fail(ctx, LV_E_CAPACITY, "the frame produced %u hit records, rt_hits_capacity was %u", hc.mlatTraceCount, ctx->rtHitsFrameCapacity);
+    if (out_records) {
+        if (max_records < hc.mlatTraceCount)
+            return lv_fail(ctx, LV_E_CAPACITY, "out_records holds %llu records, %u stored", (unsigned long long)max_records, hc.mlatTraceCount);
+        if (hc.mlatTraceCount)
+            LV_HIP(ctx, hipMemcpy(out_records, ctx->rtHits.ptr, size_t(hc.mlatTraceCount) * 36, hipMemcpyDeviceToHost));
     }
     return LV_OK;
 }

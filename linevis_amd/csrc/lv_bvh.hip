@@ -133,7 +133,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_leaves(const lv_line_point* __rest
 // triangles of a tube face, then the next face, then the next segment: consecutive triangles are neighbours): box of group g =
 // union of the padded boxes of its triangles.  A tree over N / 4 leaves is one wide level lower and a quarter the size of a tree
 // over N (config 3: 12 M triangles, 0.26 GB of nodes that miss the caches); the closest hit does not depend on the topology.
-__global__ __launch_bounds__(LV_BLOCK) void k_tri_boxes(const lv_tube_vertex* __restrict__ verts,
+template <class VERTEX>   // lv_tube_vertex, or the hull's lv_hull_vertex (lv_bvh_build_hull): both 32 B with vertexPosition first
+__global__ __launch_bounds__(LV_BLOCK) void k_tri_boxes(const VERTEX* __restrict__ verts,
                                                         const uint32_t* __restrict__ triIdx, uint32_t nTri, uint32_t group,
                                                         uint32_t nLeaves, float pad, float* __restrict__ boxOrig,
                                                         uint32_t* __restrict__ boundsOrd) {
@@ -205,8 +206,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_tri_pairs_check(const uint32_t* __
 // 48-byte triangle records, `group` per leaf, leaves in Morton order: {v0.xyz, original triangle index}{v1.xyz, 0}{v2.xyz, 0};
 // the slots an incomplete last group leaves empty hold NaN vertices (the test rejects them: every comparison with NaN fails).
 // PAIRS: the 64-byte pair records above (group == 2, every pair encodable).
-template <bool PAIRS>
-__global__ __launch_bounds__(LV_BLOCK) void k_tri_leaves(const lv_tube_vertex* __restrict__ verts,
+template <bool PAIRS, class VERTEX>
+__global__ __launch_bounds__(LV_BLOCK) void k_tri_leaves(const VERTEX* __restrict__ verts,
                                                          const uint32_t* __restrict__ triIdx,
                                                          const float* __restrict__ boxOrig,
                                                          const uint32_t* __restrict__ sortedVals, uint32_t nTri, uint32_t group,
@@ -1821,5 +1822,39 @@ int lv_bvh_build_triangles(lv_ctx* ctx) {
     ctx->triAccelValid = true;
     ctx->triAccelLineWidth = ctx->opt.lineWidth;
     ctx->evTriBuildValid = true;
+    return LV_OK;
+}
+
+// LBVH over the simulation-mesh hull (the hull triangle BLAS of getRayTracingTube*AndHullTopLevelAS, LineData.cpp:949-1162): 48-B
+// triangle records, one triangle per leaf -- a caller's mesh has no tessellation order to group by.  hullPad (lv_hull_rt.h) depends on
+// the mesh alone: the tree outlives every option change and is rebuilt by lv_set_hull_mesh only.
+int lv_bvh_build_hull(lv_ctx* ctx) {
+    const uint32_t n = ctx->hullNumTris;
+    hipStream_t st = ctx->stream;
+    ctx->hullAccelValid = false;
+    ctx->hullBvhDepth = 0;
+    ctx->hullWideDepth = 0;
+    ctx->hullNumNodes = 0;
+    ctx->hullPad = ctx->hullMaxAbs * 1e-5f + 1e-6f;
+    if (n == 0) {
+        ctx->hullAccelValid = true;
+        return LV_OK;
+    }
+    int rc;
+    const lv_hull_vertex* verts = (const lv_hull_vertex*)ctx->hullVerts.ptr;
+    const uint32_t* triIdx = (const uint32_t*)ctx->hullIdx.ptr;
+    if ((rc = lv_buf_reserve(ctx, ctx->hullTris, size_t(n) * 48))) return rc;
+    const float pad = ctx->hullPad;
+    rc = lv_bvh_build_core(
+            ctx, n, ctx->hullNodes, ctx->hullNumNodes, ctx->hullBvhDepth, ctx->hullWideDepth, -1,
+            [&](float* boxOrig, uint32_t* bounds) {
+                k_tri_boxes<<<std::min(nblocks(n), 2048u), LV_BLOCK, 0, st>>>(verts, triIdx, n, 1u, n, pad, boxOrig, bounds);
+            },
+            [&](const uint32_t* sortedVals, const float* boxOrig, float* leafBox) {
+                k_tri_leaves<false><<<nblocks(n), LV_BLOCK, 0, st>>>(verts, triIdx, boxOrig, sortedVals, n, 1u, n, (float4*)ctx->hullTris.ptr,
+                                                                     leafBox);
+            });
+    if (rc) return rc;
+    ctx->hullAccelValid = true;
     return LV_OK;
 }

@@ -136,7 +136,9 @@ struct LvDevCounters {
     uint32_t maxNodesPerPixel;
     uint32_t fragAlloc;   // PPLL node-slot allocator (chunks); fragCounter stays the exact fragment count
     uint32_t prismDiscards;  // raster_prism: linked nodes the fragment stage turned into dead nodes (discarded fragments)
-    uint32_t mlatTraceCount; // records appended to the MLAT visiting-order trace (collect_stats)
+    uint32_t mlatTraceCount; // records appended to the MLAT visiting-order trace (collect_stats), or -- never in the same frame: use_mlat
+                             // has its own kernel -- by k_render_rt_hull to the hit records of rt_record_hits (lv_rt_get_hits).  One word for
+                             // both keeps the block at 224 bytes, a multiple of 32, for the frame's hipMemsetAsync
     uint32_t ppllOverflowPixels; // raster_prism: pixels with more kept fragments than the sort arrays (k_ppll_pixel_pass's list)
     uint32_t prismListCount;     // raster_prism on a tile list: segments k_ppll_cull_segments kept for this rank's tiles
     // k_ao_rays leaf-test diagnostics (collect_stats): tests that found a hit inside the interval, tests the conservative

@@ -153,6 +153,9 @@ struct LvOptions {
     bool ppllRayTracerColour = false;         // ppll_fragment_colour: false = "raster" (the reference's gather shader, default), true = "ray_tracer"
     bool mlatRecordTrace = false;             // with collect_stats: record every pixel's candidate visiting order
     uint32_t mlatTraceCapacity = 1u << 22;    // records (16 B each)
+    bool hullRayTracing = false;              // hull_ray_tracing: false = "off" (default: mode 11 refuses a drawn hull), true = "on" (lv_hull_rt.h)
+    bool rtRecordHits = false;                // rt_record_hits: a whole-viewport mode-11 frame records every step of every pixel's loop (lv_rt_get_hits)
+    uint32_t rtHitsCapacity = 1u << 22;       // rt_hits_capacity: records (36 B each)
 };
 
 struct LvMulti;
@@ -183,6 +186,15 @@ struct lv_ctx {
     // the simulation-mesh hull (lv_set_hull_mesh): 3 indices per triangle, 32-B HullTriangleVertexData; it does not belong to the lines
     LvDeviceBuffer hullIdx, hullVerts;
     uint32_t hullNumTris = 0, hullNumVerts = 0;
+    // its LBVH for the ray tracer (lv_bvh_build_hull; hull_ray_tracing, lv_trace_rays_hull): 48-B triangle records, one per leaf.  The
+    // pad of lv_ray_triangle's own-box rule depends on the mesh alone, so only lv_set_hull_mesh invalidates the tree
+    LvDeviceBuffer hullNodes, hullTris;
+    uint32_t hullNumNodes = 0, hullBvhDepth = 0, hullWideDepth = 0;
+    float hullMaxAbs = 0.0f, hullPad = 0.0f;  // largest |coordinate| of the mesh (lv_set_hull_mesh); hullPad of lv_hull_rt.h from it
+    bool hullAccelValid = false;
+    LvDeviceBuffer rtHits;                    // rt_record_hits: 9-word records of the last recording frame
+    bool rtHitsValid = false;                 // the last frame was a whole-viewport mode-11 frame that recorded
+    uint32_t rtHitsFrameCapacity = 0;         // ... into this many records (rt_hits_capacity may have changed since)
     bool triLeafPairs = false;                  // the leaves of the triangle LBVH as built hold 64-B pair records
     bool triMeshSet = false, triAccelValid = false;
     // lv_set_trajectories (lv_lines.hip): the trajectories themselves in HBM; `points` / `segIdx` are then written by the a2 kernels and
@@ -358,6 +370,14 @@ inline bool lv_literal_intersection(const lv_ctx* ctx) {
     if (ctx->opt.intersectionForm != 0) return ctx->opt.intersectionForm == 2;
     return !(ctx->opt.useAmbientOcclusion && !ctx->opt.aoPrebaked && !lv_ao_triangle_tubes(ctx));
 }
+// LineData::shallRenderSimulationMeshBoundary: a mesh is set and hull_opacity has been set to a value > 0
+inline bool lv_hull_drawn(const lv_ctx* ctx) {
+    return ctx->hullNumTris != 0u && ctx->opt.hullOpacitySet && ctx->opt.hullOpacity > 0.0f;
+}
+// a mode-11 frame's colour pass is k_render_rt_hull (lv_hull_rt.hip): hull_ray_tracing = on while a hull is drawn, or a recording frame
+inline bool lv_rt_hull_kernel(const lv_ctx* ctx) {
+    return !ctx->opt.useMlat && ((ctx->opt.hullRayTracing && lv_hull_drawn(ctx)) || ctx->opt.rtRecordHits);
+}
 inline float lv_accel_width(const lv_ctx* ctx) {
     return (ctx->opt.useRibbons && ctx->opt.ellipticTubes) ? ctx->opt.bandWidth : ctx->opt.lineWidth;
 }
@@ -389,6 +409,7 @@ void lv_buf_free(LvDeviceBuffer& b);
 // lv_bvh.hip
 int lv_bvh_build(lv_ctx* ctx);
 int lv_bvh_build_triangles(lv_ctx* ctx);
+int lv_bvh_build_hull(lv_ctx* ctx);
 // lv_lines.hip: (re)tessellates the tube mesh of lv_set_trajectories' lines if the line width / subdivision count / band settings
 // changed; no-op otherwise
 int lv_ensure_tube_mesh(lv_ctx* ctx);
@@ -431,6 +452,8 @@ int lv_frame_trace_rays(lv_ctx* ctx, const float* o, const float* d, float tMin,
                         uint32_t* outSeg, uint32_t* outKind);
 int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n,
                                   float* outT, uint32_t* outTri, float* outUV);
+int lv_frame_trace_rays_hull(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n, float* outT,
+                             uint32_t* outTri, float* outUV);
 // inFrame: called by lv_frame_render, which reserved the traversal-stack slab for the bake too (nothing inside a frame moves it)
 int lv_bake_ambient_occlusion(lv_ctx* ctx, bool async = false, bool inFrame = false);
 int lv_bake_poll(lv_ctx* ctx, bool wait);

@@ -29,6 +29,7 @@
 #include "lv_peel.h"
 #include "lv_deferred.h"
 #include "lv_hull.h"
+#include "lv_hull_rt.h"
 #include "lv_linequad.h"
 
 namespace {
@@ -3884,8 +3885,11 @@ static uint64_t lv_overflow_entries(uint64_t wideLevels, uint32_t ldsSlots) {
 // Bytes of the slab for one launch, one column per thread.  LvStackT addresses its column by 32-bit byte offsets from the slab's base:
 // a launch whose slab would not fit them is refused (lv_prepare_overflow, the asynchronous bake)
 static constexpr size_t LV_OVERFLOW_MAX_BYTES = 0xFFFFFFFFull;
-static size_t lv_overflow_bytes(const lv_ctx* ctx, uint64_t gridBlocks, uint32_t ldsSlots, bool triangles) {
-    return size_t(gridBlocks) * LV_BLOCK * lv_overflow_entries(triangles ? ctx->triWideDepth : ctx->wideDepth, ldsSlots) * 4;
+// tree: which LBVH the launch walks -- 0 (false) the capsules', 1 (true) the triangle tubes', LV_TREE_HULL the hull's
+#define LV_TREE_HULL 2
+static size_t lv_overflow_bytes(const lv_ctx* ctx, uint64_t gridBlocks, uint32_t ldsSlots, int tree) {
+    const uint32_t levels = tree == LV_TREE_HULL ? ctx->hullWideDepth : tree ? ctx->triWideDepth : ctx->wideDepth;
+    return size_t(gridBlocks) * LV_BLOCK * lv_overflow_entries(levels, ldsSlots) * 4;
 }
 // ... for every launch of a frame: lv_frame_render reserves ctx->stackOverflow once, BEFORE it builds a scene view, because a later,
 // larger request would free the slab under the views built before it.  Same geometries as the launches: lv_ao_geometry.
@@ -3894,6 +3898,8 @@ static size_t lv_frame_overflow_bytes(const lv_ctx* ctx, const LvUniforms& U, co
     size_t need = lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, false);
     if (ctx->opt.rtTriangleMesh && mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER)
         need = std::max(need, lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, true));
+    if (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER && lv_rt_hull_kernel(ctx) && lv_hull_drawn(ctx))   // k_render_rt_hull's second walk
+        need = std::max(need, lv_overflow_bytes(ctx, gridTiles, LV_STACK_LDS, LV_TREE_HULL));
     if (U.useAmbientOcclusion && !U.aoPrebaked) {
         const LvAoGeometry G = lv_ao_geometry(ctx, U, T);
         const bool tri = lv_ao_triangle_tubes(ctx);
@@ -3909,9 +3915,9 @@ static size_t lv_frame_overflow_bytes(const lv_ctx* ctx, const LvUniforms& U, co
 }
 // Points a scene view of a frame at the slab.  Nothing inside a frame moves it: a launch the reservation did not cover is an error.
 static int lv_prepare_overflow(lv_ctx* ctx, LvSceneDev& S, const char* launch, uint64_t gridBlocks, uint32_t ldsEntries = LV_STACK_LDS,
-                               bool triangles = false) {
+                               int tree = 0) {
     S.stackOverflow = nullptr;
-    const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, triangles);
+    const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, tree);
     if (bytes == 0) return LV_OK;
     if (bytes > LV_OVERFLOW_MAX_BYTES)
         return lv_fail(ctx, LV_E_CAPACITY, "%s: the traversal stacks would need %llu bytes; a launch addresses at most 4 GiB of them", launch,
@@ -3924,11 +3930,11 @@ static int lv_prepare_overflow(lv_ctx* ctx, LvSceneDev& S, const char* launch, u
 }
 // ... of an entry point outside a frame, which reserves for its one launch
 static int lv_reserve_overflow(lv_ctx* ctx, LvSceneDev& S, const char* launch, uint64_t gridBlocks, uint32_t ldsEntries = LV_STACK_LDS,
-                               bool triangles = false) {
-    const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, triangles);
+                               int tree = 0) {
+    const size_t bytes = lv_overflow_bytes(ctx, gridBlocks, ldsEntries, tree);
     int rc;
     if (bytes && (rc = lv_buf_reserve(ctx, ctx->stackOverflow, bytes))) return rc;
-    return lv_prepare_overflow(ctx, S, launch, gridBlocks, ldsEntries, triangles);
+    return lv_prepare_overflow(ctx, S, launch, gridBlocks, ldsEntries, tree);
 }
 
 // ---------------------------------------------------------------- dispatch order of the tile kernels
@@ -4620,10 +4626,6 @@ int lv_frame_mboit_stream_moments(lv_ctx* ctx, float* out, uint64_t capacityFloa
 }
 
 // ---- The simulation-mesh hull (lv_hull.h): one more launch between a mode's line pass and its resolve ----
-// LineData::shallRenderSimulationMeshBoundary: a mesh is set and hull_opacity has been set to a value > 0
-static bool lv_hull_drawn(const lv_ctx* ctx) {
-    return ctx->hullNumTris != 0u && ctx->opt.hullOpacitySet && ctx->opt.hullOpacity > 0.0f;
-}
 static LvHullDev lv_hull_dev(const lv_ctx* ctx) {
     LvHullDev H;
     H.idx = (const uint32_t*)ctx->hullIdx.ptr;
@@ -5095,6 +5097,7 @@ static int lv_frame_check(lv_ctx* ctx, int mode) {
         return lv_fail(ctx, LV_E_INVALID, "unsupported rendering mode %d (11 = ray tracer, 1 = deferred shading, 2 = PPLL, 3 = MLAB, "
                                           "5 = depth complexity, 6 = MBOIT, 8 = WBOIT, 9 = depth peeling, 10 = Atomic Loop 64)", mode);
     ctx->streamed = {};
+    ctx->rtHitsValid = false;   // (likewise the records of rt_record_hits: set again by a recording frame, lv_rt_frame)
     int rc;
     // the modes whose colour pass works on fragments (mode 1 works on the tube triangle mesh)
     const bool fragments = mode != LV_RENDERING_MODE_VULKAN_RAY_TRACER && mode != LV_RENDERING_MODE_DEFERRED_SHADING;
@@ -5123,8 +5126,23 @@ static int lv_frame_check(lv_ctx* ctx, int mode) {
         return lv_fail(ctx, LV_E_INVALID, "rotating_helicity_bands and use_ribbons exclude each other (LineDataFlow.cpp:470,601-604)");
     if (ctx->opt.rtLss && ctx->opt.useRibbons && ctx->opt.ellipticTubes)
         return lv_fail(ctx, LV_E_INVALID, "Elliptic Tubes belong to the AABB geometry mode (VulkanRayTracer.cpp:198), not to Linear Swept Spheres");
-    // the simulation-mesh hull: modes 6 and 9 draw none (as the reference), the others are not built for it yet
-    if (lv_hull_drawn(ctx) && (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER || mode == LV_RENDERING_MODE_DEFERRED_SHADING ||
+    // the simulation-mesh hull: modes 6 and 9 draw none (as the reference); mode 11 ray-traces it under hull_ray_tracing = on
+    // (lv_hull_rt.h), closest hits only; the others are not built for it yet
+    const bool hullRayTraced = mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER && ctx->opt.hullRayTracing;
+    if (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER && lv_rt_hull_kernel(ctx)) {
+        // k_render_rt_hull has no variant for the approximate lighting, and a record holds the step in 16 bits
+        if (ctx->opt.fastShading)
+            return lv_fail(ctx, LV_E_INVALID, "shading_numerics = fast is not built for the ray-traced hull and for rt_record_hits: set "
+                                              "shading_numerics = exact, or hull_ray_tracing = off and rt_record_hits = false");
+        if (ctx->opt.rtRecordHits && ctx->opt.maxDepthComplexity > 65536u)
+            return lv_fail(ctx, LV_E_INVALID, "rt_record_hits: a record numbers the steps of a loop in 16 bits, max_depth_complexity = %u "
+                                              "is more than 65536", ctx->opt.maxDepthComplexity);
+    }
+    if (lv_hull_drawn(ctx) && hullRayTraced && ctx->opt.useMlat)
+        return lv_fail(ctx, LV_E_INVALID, "hull_ray_tracing = on: use_mlat does not draw the simulation-mesh hull (the any-hit variant is not "
+                                          "built); set use_mlat = false, hull_opacity = 0 or remove the mesh");
+    if (lv_hull_drawn(ctx) && !hullRayTraced &&
+                              (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER || mode == LV_RENDERING_MODE_DEFERRED_SHADING ||
                                mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mode == LV_RENDERING_MODE_MLAB))
         return lv_fail(ctx, LV_E_INVALID, "mode %d does not draw the simulation-mesh hull yet: modes 5 (depth complexity), 8 (WBOIT) and 10 "
                                           "(Atomic Loop 64) do; set hull_opacity = 0 or remove the mesh (lv_set_hull_mesh with 0 triangles)", mode);
@@ -5235,6 +5253,29 @@ static int lv_rt_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTiles&
         return lv_mlat_render(ctx, U, SC, T, gridTiles, out, dc, tri);
     }
     if (tri && (rc = lv_prepare_overflow(ctx, SC, "colour pass (triangle mesh)", gridTiles, LV_STACK_LDS, true))) return rc;
+    if (lv_rt_hull_kernel(ctx)) {
+        // hull_ray_tracing = on with a drawn hull, or a recording frame: k_render_rt_hull (lv_hull_rt.hip).  Its two walks share one
+        // stack, so the launch gets the slab if either tree needs it (the frame reserved for the deeper one)
+        LvHullRtDev R;
+        R.nodes = (const float4*)ctx->hullNodes.ptr;
+        R.tris = (const float4*)ctx->hullTris.ptr;
+        R.pad = ctx->hullPad;
+        R.mesh = lv_hull_dev(ctx);
+        if (!lv_hull_drawn(ctx)) R.mesh.numTris = 0u;
+        else {
+            LvSceneDev SH = SC;
+            if ((rc = lv_prepare_overflow(ctx, SH, "colour pass (hull)", gridTiles, LV_STACK_LDS, LV_TREE_HULL))) return rc;
+            if (SH.stackOverflow) SC.stackOverflow = SH.stackOverflow;
+        }
+        uint32_t* rec = nullptr;
+        if (ctx->opt.rtRecordHits) {
+            if ((rc = lv_buf_reserve(ctx, ctx->rtHits, size_t(ctx->opt.rtHitsCapacity) * LV_RT_HIT_WORDS * 4))) return rc;
+            rec = (uint32_t*)ctx->rtHits.ptr;
+            ctx->rtHitsValid = ctx->tilesCoverViewport && !ctx->tilesOverlap;   // every pixel's loop exactly once
+            ctx->rtHitsFrameCapacity = ctx->opt.rtHitsCapacity;
+        }
+        return lv_hull_rt_render(ctx, U, SC, R, T, gridTiles, out, dc, tri, rec, ctx->opt.rtHitsCapacity);
+    }
 #define LV_LAUNCH_RT(ST, PR, BA) \
     LV_TIMED_LAUNCH(ctx, LV_KERNEL_RENDER_RT, (k_render_rt<ST, PR, BA><<<gridTiles, LV_BLOCK, 0, st>>>(U, SC, T, out, dc)))
 #define LV_LAUNCH_RT_PRE(ST, BA) \
@@ -5512,6 +5553,9 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
         if (!ctx->triAccelValid || ctx->triAccelLineWidth != ctx->opt.lineWidth)
             if ((rc = lv_bvh_build_triangles(ctx))) return rc;
     }
+    // hull_ray_tracing / rt_record_hits: the colour pass is k_render_rt_hull; the hull's LBVH is built by the first frame that walks it
+    const bool hullKernel = rayTracer && lv_rt_hull_kernel(ctx);
+    if (hullKernel && lv_hull_drawn(ctx) && !ctx->hullAccelValid && (rc = lv_bvh_build_hull(ctx))) return rc;
     if (mode == LV_RENDERING_MODE_DEFERRED_SHADING) {   // the mesh itself, no LBVH over it
         if ((rc = lv_ensure_tube_mesh(ctx))) return rc;
         if (!ctx->triMeshSet || ctx->numTris == 0u)
@@ -5552,7 +5596,8 @@ int lv_frame_render(lv_ctx* ctx, int mode, const uint32_t* tilesXYHost, uint32_t
     // "auto": while the colour pass' tile kernel is at most four rounds of workgroups (16 per CU; half a 1920 x 1080 frame) -- a frame
     // that fills the GPU several times over is throughput-bound in both passes and only pays the second shading (measured, EXPERIMENTS 13.2)
     const bool pairWanted = ctx->opt.overlapPrimaryPasses == 1 || (ctx->opt.overlapPrimaryPasses == 2 && gridTiles <= 16u * uint32_t(ctx->numCUs));
-    const bool pairPrimaries = pairWanted && rayTracer && U.useAmbientOcclusion &&
+    // (k_render_rt_hull traces every step itself: a frame does not depend on the option either way)
+    const bool pairPrimaries = pairWanted && rayTracer && !hullKernel && U.useAmbientOcclusion &&
                                !U.aoPrebaked && !ctx->opt.useMlat && !ctx->opt.rtTriangleMesh && !U.useEllipticTubes &&
                                !ctx->opt.svgfEnabled && !ctx->opt.shEnabled && (U.useJitteredRays ? U.numSamplesPerFrame : 1u) == 1u && ctx->numSegs > 0u &&
                                (ctx->opt.numAccumulatedFrames <= 1u || ctx->opt.frameNumber < ctx->opt.aoIterations);
@@ -6025,6 +6070,40 @@ int lv_frame_trace_rays_triangles(lv_ctx* ctx, const float* o, const float* d, f
     if ((rc = lv_reserve_overflow(ctx, S, "lv_trace_rays_triangles", nblocks(n), LV_STACK_LDS, true))) return rc;
     if (ctx->opt.traceRaysHardwareInv) k_trace_rays_tri<true><<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
     else k_trace_rays_tri<false><<<nblocks(n), LV_BLOCK, 0, st>>>(S, dO, dD, tMin, tMax, n, dT, dS, dUV);
+    LV_HIP(ctx, hipGetLastError());
+    LV_HIP(ctx, hipMemcpyAsync(outT, dT, size_t(n) * 4, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipMemcpyAsync(outTri, dS, size_t(n) * 4, hipMemcpyDeviceToHost, st));
+    if (outUV) LV_HIP(ctx, hipMemcpyAsync(outUV, dUV, size_t(n) * 8, hipMemcpyDeviceToHost, st));
+    LV_HIP(ctx, hipStreamSynchronize(st));
+    return LV_OK;
+}
+
+// lv_trace_rays_hull: the closest hull hit of arbitrary rays (H of lv_hull_rt.h), whatever hull_ray_tracing says
+int lv_frame_trace_rays_hull(lv_ctx* ctx, const float* o, const float* d, float tMin, float tMax, uint32_t n, float* outT, uint32_t* outTri,
+                             float* outUV) {
+    int rc;
+    if (ctx->hullNumTris == 0u) return lv_fail(ctx, LV_E_STATE, "lv_trace_rays_hull: lv_set_hull_mesh has not been called");
+    if (!ctx->hullAccelValid && (rc = lv_bvh_build_hull(ctx))) return rc;
+    if (n == 0) return LV_OK;
+    hipStream_t st = ctx->stream;
+    const size_t rb = size_t(n) * 12;
+    if ((rc = lv_buf_reserve(ctx, ctx->scratchRays, 2 * rb + size_t(n) * 16))) return rc;
+    char* base = (char*)ctx->scratchRays.ptr;
+    float* dO = (float*)base;
+    float* dD = (float*)(base + rb);
+    float* dT = (float*)(base + 2 * rb);
+    uint32_t* dS = (uint32_t*)(base + 2 * rb + size_t(n) * 4);
+    float* dUV = (float*)(base + 2 * rb + size_t(n) * 8);
+    LV_HIP(ctx, hipMemcpyAsync(dO, o, rb, hipMemcpyHostToDevice, st));
+    LV_HIP(ctx, hipMemcpyAsync(dD, d, rb, hipMemcpyHostToDevice, st));
+    LvSceneDev S = sceneDev(ctx);
+    if ((rc = lv_reserve_overflow(ctx, S, "lv_trace_rays_hull", nblocks(n), LV_STACK_LDS, LV_TREE_HULL))) return rc;
+    LvHullRtDev R;
+    R.nodes = (const float4*)ctx->hullNodes.ptr;
+    R.tris = (const float4*)ctx->hullTris.ptr;
+    R.pad = ctx->hullPad;
+    R.mesh = lv_hull_dev(ctx);
+    lv_hull_rt_trace_rays(st, S, R, dO, dD, tMin, tMax, n, dT, dS, dUV);
     LV_HIP(ctx, hipGetLastError());
     LV_HIP(ctx, hipMemcpyAsync(outT, dT, size_t(n) * 4, hipMemcpyDeviceToHost, st));
     LV_HIP(ctx, hipMemcpyAsync(outTri, dS, size_t(n) * 4, hipMemcpyDeviceToHost, st));

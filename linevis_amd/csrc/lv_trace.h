@@ -421,7 +421,12 @@ __device__ __forceinline__ const T* lv_record_at(const T* base, unsigned index) 
 // ORDERED: 0 = children pushed as they come (all-hits), 1 = nearest hit child first, the rest as they come (closest hit:
 // measured as fast as a full sort, fewer instructions), 2 = all hit children in front-to-back order (MLAT: how early the
 // transmittance rule closes the ray interval depends on meeting the near layers first).
-template <bool STATS, int ORDERED = 1, class STACK>
+// GUARD_EMPTY: an empty slot that passes the slab test counts as missed.  Its inverted box fails the test on every axis the ray moves
+// along by the node's extent there -- unless that extent is below the test's tolerance (tf * 1e-5 + 4e-7) and the other axes do not
+// take part (direction components of exactly +-0: their planes are NaN).  Segment and tube boxes are never that thin; the nodes over a
+// planar part of the simulation-mesh hull are, and a slot that slipped through would come back as LV_INVALID = "finished" with
+// references still stacked.  The hull walks (lv_hull_rt.hip) set it; every other walk keeps its code.
+template <bool STATS, int ORDERED = 1, bool GUARD_EMPTY = false, class STACK>
 __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned node, f3 oi, f3 inv, float tMin, float tMax,
                                                  STACK& st, LvCounters& cnt) {
     // Room for the three pushes is made before the node is fetched in k_ao_rays and in the all-hits / ordered walks, and after the
@@ -443,16 +448,20 @@ __device__ __forceinline__ unsigned lv_node_step(const LvSceneDev& S, unsigned n
     const uint32_t nearY = sy ? qxy : qny, farY = sy ? qny : qxy;
     const uint32_t nearZ = sz ? qxz : qnz, farZ = sz ? qnz : qxz;
     float k0, k1, k2, k3;
-    // empty slots carry an inverted box (lv_write_wide_node) and fail the slab test by themselves; should one slip through,
-    // its reference is LV_INVALID and it is neither descended nor pushed
+    // empty slots carry an inverted box (lv_write_wide_node) and fail the slab test by themselves.  One that slipped through would come
+    // back or be pushed as LV_INVALID, which reads as "finished": see GUARD_EMPTY above for when that can happen and who guards
     const bool h0 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 0, A, B, tMin, tMax, k0);
     const bool h1 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 1, A, B, tMin, tMax, k1);
     const bool h2 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 2, A, B, tMin, tMax, k2);
     const bool h3 = lv_slab_q(nearX, nearY, nearZ, farX, farY, farZ, 3, A, B, tMin, tMax, k3);
     const float INF = __builtin_inff();
     // a missed child keeps its reference and gets the key +inf: the key travels with the reference through the network and
-    // decides below whether the reference is pushed / descended (empty slots never hit: inverted boxes, lv_write_wide_node)
+    // decides below whether the reference is pushed / descended (empty slots: inverted boxes, lv_write_wide_node; GUARD_EMPTY above)
     k0 = h0 ? k0 : INF; k1 = h1 ? k1 : INF; k2 = h2 ? k2 : INF; k3 = h3 ? k3 : INF;
+    if (GUARD_EMPTY) {
+        k0 = c0 == LV_INVALID ? INF : k0; k1 = c1 == LV_INVALID ? INF : k1;
+        k2 = c2 == LV_INVALID ? INF : k2; k3 = c3 == LV_INVALID ? INF : k3;
+    }
     if (ORDERED == 2) { // 5-comparator sorting network, misses (key = +inf) sink to the end
         lv_cswap(k0, c0, k1, c1);
         lv_cswap(k2, c2, k3, c3);
@@ -803,7 +812,7 @@ struct LvHitQueue {
 // at a time by the lanes that already finished.  ANY_HIT: gl_RayFlagsTerminateOnFirstHitEXT.
 // FAST_INV: the node steps use lv_traversal_inv (the ray-trace entry points under traversal_reciprocal = hardware: arbitrary rays
 // through the reciprocals k_ao_rays descends with); the frame kernels keep the division.
-template <bool STATS, bool ANY_HIT, int PRIM = LV_PRIM_CAPSULE, bool FAST_INV = false>
+template <bool STATS, bool ANY_HIT, int PRIM = LV_PRIM_CAPSULE, bool FAST_INV = false, bool GUARD_EMPTY = false>
 __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float radius, bool capped, bool active, f3 o, f3 d,
                                                   float tMin, float tMax, const LvStackMem& sm, const LvCoopMem& cm,
                                                   LvCounters& cnt) {
@@ -907,7 +916,7 @@ __device__ __forceinline__ LvHit lv_trace_closest(const LvSceneDev& S, float rad
         }
         int nNow;
         do { // tight descend loop
-            if (!(cur & LV_LEAF_BIT)) cur = lv_node_step<STATS>(S, cur, oi, inv, tMin - slack, best + slack, st, cnt);
+            if (!(cur & LV_LEAF_BIT)) cur = lv_node_step<STATS, 1, GUARD_EMPTY>(S, cur, oi, inv, tMin - slack, best + slack, st, cnt);
             const bool lf = cur != LV_INVALID && (cur & LV_LEAF_BIT);
             const unsigned long long m = __ballot(lf);
             if (m) {

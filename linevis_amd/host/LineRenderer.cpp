@@ -654,6 +654,15 @@ bool HipRayTracer::setNewSettings(const SettingsMap& settings) {
     }
     if (settings.getValueOpt("max_depth_complexity", maxDepthComplexity))
         setOption("max_depth_complexity", std::to_string(maxDepthComplexity));
+    // hull_ray_tracing (build-owned, linevis_hip.h): with "on" this plugin draws the hull -- it uploads the data set's outline mesh and
+    // forwards the three hull_* settings with the next frame state; without the key it uploads no mesh, as before
+    std::string hullRayTracing;
+    if (settings.getValueOpt("hull_ray_tracing", hullRayTracing) && setOption("hull_ray_tracing", hullRayTracing)) {
+        drawsHull = hullRayTracing == "on";
+        if (!drawsHull) setOption("hull_opacity", "0");   // (a mesh uploaded under "on" stays; nothing draws it)
+        linesDirty = true;
+        accumulatedFramesCounter = 0;
+    }
     return shallReloadGatherShader;
 }
 

@@ -260,7 +260,8 @@ protected:
     bool isRasterizer = false;
     /// LineRenderer::renderHull is a step of this renderer's frame AND the library draws it there (rendering modes 5, 8 and 10): the
     /// renderer uploads the line data's outline mesh (lv_set_hull_mesh) and forwards hull_opacity / hull_color / hull_use_shading.  The
-    /// other renderers upload no mesh, so their frames are never refused for one.
+    /// other renderers upload no mesh, so their frames are never refused for one; the ray tracer's plugin sets it under the settings
+    /// key hull_ray_tracing = "on".
     bool drawsHull = false;
     const LineData* uploadedHullData = nullptr;
     uint64_t uploadedHullGeneration = 0;
