@@ -399,9 +399,9 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   mode 5's counts, maximum and statistics, mode 8's sums and counts and mode 10's slots, tail and counts include it; memory added
  *   to a frame: none beyond the mesh; timer: LV_KERNEL_HULL.  Modes 6 and 9 draw no hull in the reference (MBOITRenderer.cpp:84 and
  *   DepthPeelingRenderer.cpp:86 reset the pass) and none here: they render the same frame with or without a mesh.  Modes 1, 2, 3
- *   and -- unless hull_ray_tracing = on (below) -- 11 are not built for the hull: while a hull would be drawn lv_render returns
- *   LV_E_INVALID for them (the message names modes 5, 8 and 10; the context stays usable); with hull_opacity 0 or no mesh they
- *   render as without these keys, byte for byte.
+ *   and 11 are not built for the hull: while a hull would be drawn lv_render returns LV_E_INVALID for them (the message names modes
+ *   5, 8 and 10; the context stays usable); with hull_opacity 0 or no mesh they render as without these keys, byte for byte.  Two
+ *   build-owned switches, below, lift the refusal: hull_fragment_pool = on for modes 2 and 3, hull_ray_tracing = on for mode 11.
  *   hull_ray_tracing (build-owned switch): "off" (default: everything above, the refusal of mode 11 included) | "on": a mode-11
  *   frame draws the hull while one is drawn by the rule of hull_opacity -- the reference puts a hull triangle BLAS into every TLAS of
  *   the ray tracer (LineData.cpp:949-1162) and shades its hits in ClosestHitHull (TubeRayTracing.glsl:359-431) inside the transparency
@@ -414,6 +414,25 @@ int lv_set_background(lv_ctx* ctx, const float rgba[4]);
  *   by the first frame or lv_trace_rays_hull call that needs it, rebuilt after lv_set_hull_mesh and by nothing else.  With "on" and
  *   no hull drawn the frame is the "off" frame byte for byte (the same kernels run).  use_mlat together with a drawn, ray-traced hull
  *   returns LV_E_INVALID (the any-hit variant AnyHitHull is not built); modes 1, 2 and 3 keep refusing.
+ *   hull_fragment_pool (build-owned switch): "off" (default: everything above, the refusal of modes 2 and 3 and its message
+ *   included) | "on": a mode-2 or mode-3 frame draws the hull while one is drawn by the rule of hull_opacity -- the reference draws
+ *   it inside the gather of its pooled renderers (PerPixelLinkedListLineRenderer.cpp:448-461), after the lines, through the same
+ *   gatherFragment.  The hull fragment is the one above (coverage, 0 <= z < 1, position, normal, colour); alpha < 0.001 is
+ *   discarded by both gathers.  Mode 2: the node {packed straight colour, bits of |position - camera|} is sorted and blended with
+ *   the line nodes, takes a slot of the same pool (dropped like a line fragment where the pool is full) and is exported by
+ *   lv_ppll_get_buffers like any node.  The hull's slots are taken BEFORE the lines' (its ranks come first in every run), so a
+ *   mode-2 frame whose pool runs full drops line fragments first -- the reference draws the hull last and would drop hull fragments
+ *   first; either frame is one its pool cannot hold, raise ppll_expected_avg_depth_complexity.  Mode 3: the entry {packUnorm4x8(rgb
+ *   * a, 1 - a), window depth, key} with key = (segments << 6) + hull triangle folds after every line fragment of its pixel, in
+ *   triangle order (the reference's ordered interlock: the hull is drawn after the lines); (segments << 6) + hull triangles >
+ *   0xFFFFFFFE returns LV_E_INVALID.  Both: a stored hull fragment counts in the pixel's 16-bit count (a pixel holds at most 65535
+ *   fragments, lines and hull together: mode 2 drops the rest, mode 3 returns LV_E_CAPACITY), a kept one in lv_stats.fragments;
+ *   tile lists, shards and lv_create_multi handles as for the lines.  Memory added: 4 bytes per pixel of the padded viewport, and
+ *   pool slack for the hull launch's waves; no host synchronisation added; timer: LV_KERNEL_HULL (two launches per frame).  While a
+ *   hull is drawn under "on", ppll_prism_rasteriser = lbvh, ppll_fragment_source = capsule_entry and line_primitive_mode = "Quads
+ *   (Programmable Pull)" return LV_E_INVALID at render time: the hull is stored in the segment rasteriser's pool only.  Pooled mode
+ *   6 draws no hull, modes 1 and 11 are untouched by this switch; with "on" and no hull drawn every frame is the "off" frame byte
+ *   for byte.  The semantics are stated once in csrc/lv_hull_pool.h.
  *   rt_record_hits (build-owned: "true" | "1" | "false" | "0", default false) / rt_hits_capacity (records, default 4 Mi, at most
  *   64 Mi): a mode-11 frame without use_mlat runs k_render_rt_hull -- also when no hull is drawn -- and records every step of every
  *   pixel's loop for lv_rt_get_hits.  A record numbers the steps of a loop in 16 bits: a recording frame with max_depth_complexity

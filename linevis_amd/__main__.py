@@ -6,7 +6,7 @@
 LineRenderer::setNewSettings of the plugin classes in linevis_amd/host/ and LineData::setNewSettings of the data set -- among them
 hull_opacity, hull_color ("r g b") and hull_use_shading of the simulation-mesh hull, which the modes al64, wboit and "Depth Complexity
 Renderer" draw when the data has an outline mesh (a version-2 .binlines file, or --hull-box) -- the mode rt ray-traces it with
-hull_ray_tracing=on --, and line_primitive_mode
+hull_ray_tracing=on, the modes ppll and mlab store it in their fragment pool with hull_fragment_pool=on --, and line_primitive_mode
 ("line_primitive_mode=Quads (Programmable Pull)": the same three modes draw view-aligned line quads instead of tubes).
 Needs an MI355X: there is no CPU fallback.
 """

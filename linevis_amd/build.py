@@ -16,7 +16,7 @@ LIB = os.path.join(OUT_DIR, "liblinevis_hip.so")
 SOURCES = [("lv_api.hip", "lv_api.o", []), ("lv_bvh.hip", "lv_bvh.o", []), ("lv_render.hip", "lv_render.o", []), ("lv_peel.hip", "lv_peel.o", []),
            ("lv_deferred.hip", "lv_deferred.o", []), ("lv_hull.hip", "lv_hull.o", []), ("lv_hull_rt.hip", "lv_hull_rt.o", []), ("lv_linequad.hip", "lv_linequad.o", []), ("lv_flow.hip", "lv_flow.o", []), ("lv_lines.hip", "lv_lines.o", []), ("lv_svgf.hip", "lv_svgf.o", []), ("lv_sh.hip", "lv_sh.o", []), ("lv_multi.hip", "lv_multi.o", [])] + \
           [("lv_mlat.hip", "lv_mlat_%d.o" % p, ["-DLV_MLAT_PART=%d" % p]) for p in range(4)]
-HEADERS = ["lv_device.h", "lv_trace.h", "lv_prism.h", "lv_tile.h", "lv_mboit.h", "lv_al64.h", "lv_wboit.h", "lv_peel.h", "lv_deferred.h", "lv_hull.h", "lv_hull_rt.h", "lv_linequad.h", "lv_sh.h", "lv_internal.h", os.path.join("..", "..", "include", "linevis_hip.h")]
+HEADERS = ["lv_device.h", "lv_trace.h", "lv_prism.h", "lv_tile.h", "lv_mboit.h", "lv_al64.h", "lv_wboit.h", "lv_peel.h", "lv_deferred.h", "lv_hull.h", "lv_hull_pool.h", "lv_hull_rt.h", "lv_linequad.h", "lv_sh.h", "lv_internal.h", os.path.join("..", "..", "include", "linevis_hip.h")]
 # -fno-slp-vectorize: the SLP vectoriser fuses the cross and dot products of the intersection tests into v_pk_mul / v_pk_add / v_pk_fma_f32
 # and pays for their aligned register pairs with v_mov_b32 -- a packed pair plus one move costs more than the two plain operations
 # (tools/ubench/valu_rates.hip), and the pairs push the tile kernels into scratch.  Same float operations, same results (EXPERIMENTS.md 23).

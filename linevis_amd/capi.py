@@ -393,7 +393,8 @@ class Context:
 
     def set_hull_mesh(self, triangle_indices, positions, normals):
         """lv_set_hull_mesh: the simulation-mesh hull, triangle indices [n, 3], positions and normals [m, 3] (normals are used as given).
-        No triangles (None or empty) removes the mesh.  Drawn by modes 5, 8 and 10 once hull_opacity has been set to a value > 0."""
+        No triangles (None or empty) removes the mesh.  Drawn by modes 5, 8 and 10 once hull_opacity has been set to a value > 0 (mode 11 under hull_ray_tracing = on, modes 2 and 3 under
+        hull_fragment_pool = on)."""
         idx = np.ascontiguousarray(triangle_indices if triangle_indices is not None else [], dtype=np.uint32).reshape(-1, 3)
         if len(idx) == 0:
             self._ck(self.L.lv_set_hull_mesh(self.h, None, 0, None, None, 0))

@@ -116,7 +116,7 @@ static std::vector<LvDeviceBuffer*> lv_all_buffers(lv_ctx* ctx) {
             &ctx->svgf.tempAccumFiltered, &ctx->svgf.ping, &ctx->svgf.pong, &ctx->svgf.result, &ctx->svgfGiven,
             &ctx->shMapCells, &ctx->shMapCounters, &ctx->shGivenCells, &ctx->shGivenCounters, &ctx->shRead, &ctx->shNormal, &ctx->shPosition, &ctx->shPing, &ctx->shPong, &ctx->shGiven, &ctx->shCompact, &ctx->aoGbuf, &ctx->aoList, &ctx->aoSamples,
             &ctx->counters, &ctx->ppllNodes, &ctx->ppllStart, &ctx->ppllCount, &ctx->ppllScratch, &ctx->prismRecords, &ctx->scanTemp, &ctx->ppllOverflow, &ctx->mlabLong, &ctx->mlabStatsSnap, &ctx->mboitAccum, &ctx->al64Buf, &ctx->wboitBuf, &ctx->peelBuf, &ctx->dcStatsDev, &ctx->visBuf, &ctx->deferredTf, &ctx->ppllCoarse, &ctx->prismLeafList, &ctx->flowOccupancy, &ctx->flowPoints, &ctx->flowPointsNext, &ctx->flowSelfGrid, &ctx->twistTex, &ctx->tilesDev, &ctx->outDev,
-            &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag, &ctx->hullIdx, &ctx->hullVerts, &ctx->hullNodes, &ctx->hullTris, &ctx->rtHits,
+            &ctx->scratchRays, &ctx->stackOverflow, &ctx->trajPos, &ctx->trajAttr, &ctx->trajOff, &ctx->trajLineValid, &ctx->trajLineRef, &ctx->trajRecLine, &ctx->trajTess, &ctx->trajRibbon, &ctx->trajHelicity, &ctx->trajMaxHelicity, &ctx->trajRecPoint, &ctx->trajMeshRot, &ctx->triIdx, &ctx->triVerts, &ctx->triPoints, &ctx->triNodes, &ctx->tris, &ctx->triPairFlag, &ctx->hullIdx, &ctx->hullVerts, &ctx->hullNodes, &ctx->hullTris, &ctx->rtHits, &ctx->hullRanks,
             &ctx->flowVectors, &ctx->flowScalars, &ctx->flowMisc, &ctx->flowSeeds, &ctx->flowOutPos, &ctx->flowOutAtt, &ctx->flowCounts,
             &ctx->bakeBlendingWeights, &ctx->bakeSamplingLocations, &ctx->bakedAo, &ctx->bakeLcgSkip, &ctx->bakedAoPending, &ctx->bakeCounters,
             &ctx->bakeGbuf, &ctx->bakeSamples, &ctx->bakeOverflow, &ctx->mlatTrace, &ctx->buildArena, &ctx->partitionScratch, &ctx->firstHit,
@@ -868,6 +868,11 @@ int lv_set_option(lv_ctx* ctx, const char* key, const char* value) {
         // mode 11 draws the simulation-mesh hull (lv_hull_rt.h); "off" keeps the refusal
         if (strcmp(value, "on") == 0) o.hullRayTracing = true;
         else if (strcmp(value, "off") == 0) o.hullRayTracing = false;
+        else return bad();
+    } else if (k == "hull_fragment_pool") {
+        // modes 2 and 3 draw the simulation-mesh hull into their fragment pool (lv_hull_pool.h); "off" keeps the refusal
+        if (strcmp(value, "on") == 0) o.hullFragmentPool = true;
+        else if (strcmp(value, "off") == 0) o.hullFragmentPool = false;
         else return bad();
     } else if (k == "rt_record_hits") {
         if (strcmp(value, "true") == 0 || strcmp(value, "1") == 0) o.rtRecordHits = true;

@@ -251,6 +251,16 @@ struct LvSvgfFeat {
 // the same formula), the camera's right axis (column 0 of inverse(viewMatrix)) that spans the ray-space basis, row 2 of the view
 // matrix + the clip distances (depth clipping of the fragments)
 #define LV_SCAN_ITEMS 4096u      // pixel addresses per workgroup of k_ppll_scan (run offsets are relative to these blocks)
+// start of a pixel's run in the fragment array (k_ppll_scan: offsets relative to the pixel's block of LV_SCAN_ITEMS addresses + the block's base)
+__device__ __forceinline__ uint32_t lv_run_start(const uint32_t* __restrict__ startOffset, const uint32_t* __restrict__ blockBase,
+                                                 uint32_t addr) {
+    return startOffset[addr] + blockBase[addr / LV_SCAN_ITEMS];
+}
+// the entry formats of the pooled fragment stages (k_ppll_shade_prism, k_hull_shade_records) and the key of a discarded mode-3 entry
+#define LV_ENTRY_PPLL 0
+#define LV_ENTRY_MLAB 1
+#define LV_ENTRY_MBOIT 2
+#define LV_MLAB_NO_KEY 0xFFFFFFFFu
 #define LV_PRISM_MAX_SUBDIV 16
 struct LvPrismDev {
     float c[LV_PRISM_MAX_SUBDIV], s[LV_PRISM_MAX_SUBDIV];

@@ -21,7 +21,9 @@
 // The gather is the mode's own, as for a line fragment: mode 10 discards alpha < 0.001 (AtomicLoop64Gather.glsl:56-59) and inserts
 // (bits(z) << 32) | packUnorm4x8(colour); mode 8 discards nothing and adds lv_wboit_add's terms under lv_wboit_weight(alpha, z); mode 5
 // counts.  Every store adds 1 to the pixel's count and to the frame's fragment counter.
-// Not built: the hull in modes 1, 2, 3 and 11 (refused while a hull would be drawn); modes 6 and 9 draw none in the reference.
+// Modes 2 and 3 store it in their fragment pool behind hull_fragment_pool = on (lv_hull_pool.h: the RECORD store of k_hull_pass and a
+// fragment stage of its own), mode 11 ray-traces it behind hull_ray_tracing = on (lv_hull_rt.h); by default both refuse a frame while a
+// hull would be drawn.  Not built: the hull in mode 1; modes 6 and 9 draw none in the reference.
 #pragma once
 #include "lv_device.h"
 #include "lv_trace.h"
@@ -35,6 +37,7 @@
 #define LV_HULL_STORE_WBOIT 1   // mode 8: lv_wboit_add
 #define LV_HULL_STORE_AL64 2    // mode 10: lv_al64_insert
 #define LV_HULL_STORE_LIST 3    // lv_hull_get_fragments: the fragment appended to a list
+// (4: LV_HULL_STORE_RECORD of lv_hull_pool.h, modes 2 and 3)
 #ifndef LV_HULL_SMALL
 #define LV_HULL_SMALL 64u       // as LV_VIS_SMALL: a lane walks a pixel rectangle of at most this many pixels itself
 #endif

@@ -156,6 +156,7 @@ struct LvOptions {
     bool hullRayTracing = false;              // hull_ray_tracing: false = "off" (default: mode 11 refuses a drawn hull), true = "on" (lv_hull_rt.h)
     bool rtRecordHits = false;                // rt_record_hits: a whole-viewport mode-11 frame records every step of every pixel's loop (lv_rt_get_hits)
     uint32_t rtHitsCapacity = 1u << 22;       // rt_hits_capacity: records (36 B each)
+    bool hullFragmentPool = false;            // hull_fragment_pool: false = "off" (default: modes 2 and 3 refuse a drawn hull), true = "on" (lv_hull_pool.h)
 };
 
 struct LvMulti;
@@ -288,6 +289,7 @@ struct lv_ctx {
     LvDeviceBuffer flowSelfGrid;              // loop check "Grid": one bit per cell and line of a batch
     LvDeviceBuffer prismLeafList;             // raster_prism, sharded frames: segments that can touch the frame's tile list (k_ppll_cull_segments)
     LvDeviceBuffer ppllCoarse;                // raster_prism, sharded frames: 32 x 32-pixel cells that hold requested pixels (k_ppll_mark_tiles)
+    LvDeviceBuffer hullRanks;                 // hull_fragment_pool: per padded pixel, the hull entries k_hull_shade_records has placed so far
     LvDeviceBuffer ppllOverflow;              // raster_prism: pixel addresses with more kept fragments than ppllMaxNumFrags (k_ppll_pixel_pass)
     LvDeviceBuffer mlabLong;                  // mode 3: {pixel address, output index} of the pixels k_mlab_resolve_long folds
     LvDeviceBuffer mlabStatsSnap;             // mode 3 with collect_stats: the statistics counters before the front end (pool regrowth)

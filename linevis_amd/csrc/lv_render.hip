@@ -29,6 +29,7 @@
 #include "lv_peel.h"
 #include "lv_deferred.h"
 #include "lv_hull.h"
+#include "lv_hull_pool.h"
 #include "lv_hull_rt.h"
 #include "lv_linequad.h"
 
@@ -1163,12 +1164,7 @@ __global__ __launch_bounds__(LV_BLOCK, PRIM == LV_PRIM_PRISM ? LV_PRISM_MIN_WAVE
     if (STATS) lv_flush_counters(cnt, dc);
 }
 
-// start of a pixel's run in the fragment array (k_ppll_scan: offsets relative to the pixel's block of LV_SCAN_ITEMS addresses + the block's base)
-__device__ __forceinline__ uint32_t lv_run_start(const uint32_t* __restrict__ startOffset, const uint32_t* __restrict__ blockBase,
-                                                 uint32_t addr) {
-    return startOffset[addr] + blockBase[addr / LV_SCAN_ITEMS];
-}
-
+// (lv_run_start, the start of a pixel's run in the fragment array: lv_device.h)
 // Fragment stage of ppll_fragment_source = raster_prism: one lane per record of the coverage kernel (k_ppll_gather<LV_PRIM_PRISM>),
 // grid-stride over the record pool -- LinePassGeometryShaderTubes.glsl:732-1129 on the perspective-correct inputs (lv_shade_prism) +
 // the store of gatherFragment (LinkedListGather.glsl:33-72): {colour, depth} goes to slot pixelOffset[pixel] + rank of the fragment
@@ -1178,7 +1174,7 @@ __device__ __forceinline__ uint32_t lv_run_start(const uint32_t* __restrict__ st
 // MLAB (rendering mode 3, MLABGather.glsl:63-91): the entry is 12 B {packUnorm4x8(rgb * a, 1 - a), window depth, primitive key}
 // instead, the key = leafSeg[leaf] << 6 | triangle orders the pixel's fragments as the reference's ordered interlock folds them
 // (index-buffer order: segment by segment, triangles 2k, 2k + 1 of a segment); a discarded fragment is {0, LV_PPLL_DEAD, LV_MLAB_NO_KEY}.
-#define LV_MLAB_NO_KEY 0xFFFFFFFFu
+// (LV_MLAB_NO_KEY and the LV_ENTRY_* formats: lv_device.h -- the hull's fragment stage in lv_hull.hip writes the same entries)
 // window depth gl_FragCoord.z = clip.z / clip.w of a world position: rows z and w of proj * view in lv_clip_rows' order
 __device__ __forceinline__ float lv_window_depth(const LvUniforms& U, f3 p) {
     float mz[4], mw[4];
@@ -1216,9 +1212,6 @@ __device__ __forceinline__ f3 lv_prism_frag_pos(const LvSceneDev& S, const LvUni
 // receives (16 B, entry dst of the colour array) and the view depth -screenSpacePosition.z (4 B, entry dst of the depth array that
 // starts poolSlots colour entries in); only the `kept` rules discard (the alpha < 0.001 discard lives in the gather shaders of modes
 // 2 and 3, not in MBOIT's); a discarded fragment's depth word is LV_PPLL_DEAD.
-#define LV_ENTRY_PPLL 0
-#define LV_ENTRY_MLAB 1
-#define LV_ENTRY_MBOIT 2
 // view depth of a world position: row z of the view matrix in one fixed float32 order, negated
 __device__ __forceinline__ float lv_view_depth(const LvUniforms& U, f3 p) {
     return -(((U.view[2] * p.x + U.view[6] * p.y) + U.view[10] * p.z) + U.view[14]);
@@ -5087,6 +5080,12 @@ static const char* lv_prism_mode_name(int mode) {
          : mode == LV_RENDERING_MODE_MBOIT ? "MBOIT" : "MLAB";
 }
 
+// a mode-2 or mode-3 frame draws the hull into its fragment pool (lv_hull_pool.h): hull_fragment_pool = on while a hull is drawn
+static bool lv_hull_pooled(const lv_ctx* ctx, int mode) {
+    return ctx->opt.hullFragmentPool && lv_hull_drawn(ctx) &&
+           (mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mode == LV_RENDERING_MODE_MLAB);
+}
+
 // What a frame call is refused for before anything is built or enqueued: the mode, the options that exclude each other, the state
 // the caller has not set.  A call of a supported mode ends the record of the last frame (ctx->streamed: set again at the end of a
 // streamed mode-6, a mode-5, 8, 9 or 10 frame, lv_streamed_done), refused or not.
@@ -5141,7 +5140,25 @@ static int lv_frame_check(lv_ctx* ctx, int mode) {
     if (lv_hull_drawn(ctx) && hullRayTraced && ctx->opt.useMlat)
         return lv_fail(ctx, LV_E_INVALID, "hull_ray_tracing = on: use_mlat does not draw the simulation-mesh hull (the any-hit variant is not "
                                           "built); set use_mlat = false, hull_opacity = 0 or remove the mesh");
-    if (lv_hull_drawn(ctx) && !hullRayTraced &&
+    if (lv_hull_pooled(ctx, mode)) {
+        // hull_fragment_pool = on (lv_hull_pool.h): the hull store fills the segment rasteriser's record pool only
+        if (ctx->opt.lineQuads)
+            return lv_fail(ctx, LV_E_INVALID, "hull_fragment_pool = on: mode %d stores the simulation-mesh hull in the segment rasteriser's "
+                                              "record pool, which line_primitive_mode = \"Quads (Programmable Pull)\" does not fill; set it back "
+                                              "to \"Tube (Programmable Pull)\", hull_opacity = 0 or remove the mesh", mode);
+        if (!lv_ppll_prism_source(ctx))
+            return lv_fail(ctx, LV_E_INVALID, "hull_fragment_pool = on: mode %d stores the simulation-mesh hull in the segment rasteriser's "
+                                              "record pool, which ppll_fragment_source = capsule_entry does not fill; set it to auto or raster_prism, "
+                                              "hull_opacity = 0 or remove the mesh", mode);
+        if (ctx->opt.ppllPrismLbvhWalk)
+            return lv_fail(ctx, LV_E_INVALID, "hull_fragment_pool = on: mode %d stores the simulation-mesh hull in the segment rasteriser's "
+                                              "record pool, which ppll_prism_rasteriser = lbvh does not fill; set it to segments, hull_opacity "
+                                              "= 0 or remove the mesh", mode);
+        if (mode == LV_RENDERING_MODE_MLAB && !lv_hull_pool_keys_fit(ctx->numSegs, ctx->hullNumTris))
+            return lv_fail(ctx, LV_E_INVALID, "hull_fragment_pool = on: mode 3 keys a hull fragment (segments << 6) + triangle; %llu segments "
+                                              "and %u hull triangles do not fit 32 bits", (unsigned long long)ctx->numSegs, ctx->hullNumTris);
+    }
+    if (lv_hull_drawn(ctx) && !hullRayTraced && !lv_hull_pooled(ctx, mode) &&
                               (mode == LV_RENDERING_MODE_VULKAN_RAY_TRACER || mode == LV_RENDERING_MODE_DEFERRED_SHADING ||
                                mode == LV_RENDERING_MODE_PER_PIXEL_LINKED_LIST || mode == LV_RENDERING_MODE_MLAB))
         return lv_fail(ctx, LV_E_INVALID, "mode %d does not draw the simulation-mesh hull yet: modes 5 (depth complexity), 8 (WBOIT) and 10 "
@@ -5354,6 +5371,17 @@ static int lv_pool_front(lv_ctx* ctx, const LvUniforms& U, const LvSceneDev& S, 
             allRequested ? 1u : 0u, leafList)
         uint32_t* leafList;
         if ((rc = lv_segment_raster_front(ctx, U, S, T, gridTiles, stats, allRequested, dc, leafList))) return rc;
+        if (lv_hull_pooled(ctx, mode)) {
+            // the hull's records (lv_hull_pool.h), BEFORE the lines': the hull then holds ranks [0, h) of every pixel's run, which
+            // its fragment stage hands out again from the counters zeroed here
+            if ((rc = lv_buf_reserve(ctx, ctx->hullRanks, padded4 * 16))) return rc;
+            LV_HIP(ctx, hipMemsetAsync(ctx->hullRanks.ptr, 0, padded4 * 16, st));
+            const LvHullList none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0ull};
+            LV_TIMED_LAUNCH(ctx, LV_KERNEL_HULL, lv_hull_launch(st, LV_HULL_STORE_RECORD, uint32_t(ctx->numCUs), U, S.prism, lv_hull_dev(ctx),
+                                                                allRequested ? nullptr : (const uint32_t*)ctx->ppllStart.ptr,
+                                                                (uint32_t*)ctx->ppllCount.ptr, (unsigned long long*)gatherPool, poolSlots,
+                                                                dc, stats, none));
+        }
         if (S.numSegs != 0) {
             if (S.prism.n == 6u) { if (stats) LV_LAUNCH_RASTER(true, 6); else LV_LAUNCH_RASTER(false, 6); }
             else { if (stats) LV_LAUNCH_RASTER(true, 0); else LV_LAUNCH_RASTER(false, 0); }
@@ -5418,8 +5446,11 @@ static int lv_pool_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTile
     // physical pool = the reference's linkedListSize + the tail every wave of the gather may leave unused in its last
     // chunk of node slots (k_ppll_gather / k_ppll_raster_prism), so that the effective capacity is never below the reference's
     const bool segmentRaster = prismSource && !ctx->opt.ppllPrismLbvhWalk;
-    const uint64_t chunkSlack = segmentRaster ? uint64_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU * (LV_BLOCK / LV_WAVE) * LV_PRISM_RASTER_CHUNK
+    uint64_t chunkSlack = segmentRaster ? uint64_t(ctx->numCUs) * LV_PRISM_RASTER_BLOCKS_PER_CU * (LV_BLOCK / LV_WAVE) * LV_PRISM_RASTER_CHUNK
                                               : uint64_t(gridTiles) * numSlices * (LV_BLOCK / LV_WAVE) * LV_PPLL_CHUNK;
+    // (+ the tails of the hull launch's waves when, and only when, the hull is drawn into the pool)
+    const bool hullPooled = lv_hull_pooled(ctx, mode);
+    if (hullPooled) chunkSlack += uint64_t(lv_hull_launch_waves(uint32_t(ctx->numCUs), ctx->hullNumTris, U.height)) * LV_HULL_CHUNK;
     uint64_t poolSlots64 = uint64_t(U.ppllLinkedListSize) + chunkSlack;
     // MLAB drops no fragment (the reference's MLAB has no pool): it starts from the linkedListSize of the options (no chunk slack:
     // a frame that needs more slots grows the pool below) or from what the largest mode-3 frame so far needed
@@ -5483,6 +5514,13 @@ static int lv_pool_frame(lv_ctx* ctx, LvUniforms& U, LvSceneDev& S, const LvTile
 #undef LV_LAUNCH_SHADE3
 #undef LV_LAUNCH_SHADE2
 #undef LV_LAUNCH_SHADE
+        // the fragment stage of the hull's records (lv_hull_pool.h): other slots of the pool, other entries of the runs
+        if (hullPooled)
+            LV_TIMED_LAUNCH(ctx, LV_KERNEL_HULL, lv_hull_shade_launch(st, mlab ? LV_ENTRY_MLAB : LV_ENTRY_PPLL, uint32_t(ctx->numCUs), U, S.prism,
+                                                                      lv_hull_dev(ctx), (const uint32_t*)ctx->prismRecords.ptr,
+                                                                      (uint32_t*)ctx->ppllNodes.ptr, (const uint32_t*)ctx->ppllStart.ptr,
+                                                                      blockBase, (uint32_t*)ctx->ppllCount.ptr, (uint32_t*)ctx->hullRanks.ptr,
+                                                                      dc, poolSlots, ctx->numSegs << 6));   // (lv_frame_check: the keys fit 32 bits)
         // the listed pixels: their nearest ppllMaxNumFrags fragments to the front of the run
         if (!mlab) k_ppll_select_nearest<<<uint32_t(ctx->numCUs) * 16u, LV_WAVE, 0, st>>>(
                 U, (uint2*)ctx->ppllNodes.ptr, (uint2*)ctx->prismRecords.ptr, (const uint32_t*)ctx->ppllStart.ptr, blockBase,

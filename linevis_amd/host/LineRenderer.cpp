@@ -656,14 +656,19 @@ bool HipRayTracer::setNewSettings(const SettingsMap& settings) {
         setOption("max_depth_complexity", std::to_string(maxDepthComplexity));
     // hull_ray_tracing (build-owned, linevis_hip.h): with "on" this plugin draws the hull -- it uploads the data set's outline mesh and
     // forwards the three hull_* settings with the next frame state; without the key it uploads no mesh, as before
-    std::string hullRayTracing;
-    if (settings.getValueOpt("hull_ray_tracing", hullRayTracing) && setOption("hull_ray_tracing", hullRayTracing)) {
-        drawsHull = hullRayTracing == "on";
-        if (!drawsHull) setOption("hull_opacity", "0");   // (a mesh uploaded under "on" stays; nothing draws it)
-        linesDirty = true;
-        accumulatedFramesCounter = 0;
-    }
+    if (setHullSwitch(settings, "hull_ray_tracing")) accumulatedFramesCounter = 0;
     return shallReloadGatherShader;
+}
+
+// The opt-in switches under which a renderer that refuses a drawn hull by default draws it (hull_ray_tracing: mode 11;
+// hull_fragment_pool: modes 2 and 3).  true: the key was given and the library took its value.
+bool LineRenderer::setHullSwitch(const SettingsMap& settings, const char* key) {
+    std::string value;
+    if (!settings.getValueOpt(key, value) || !setOption(key, value)) return false;
+    drawsHull = value == "on";
+    if (!drawsHull) setOption("hull_opacity", "0");   // (a mesh uploaded under "on" stays; nothing draws it)
+    linesDirty = true;
+    return true;
 }
 
 // VulkanRayTracer::setNewState, VulkanRayTracer.cpp:280-330: the camelCase keys the canned benchmark states carry
@@ -720,6 +725,8 @@ bool HipPerPixelLinkedListLineRenderer::setNewSettings(const SettingsMap& settin
         std::string s;
         if (settings.getValueOpt(key, s)) setOption(key, s);
     }
+    // hull_fragment_pool (build-owned, linevis_hip.h): with "on" this plugin draws the hull, as the ray tracer's under hull_ray_tracing
+    setHullSwitch(settings, "hull_fragment_pool");
     return r;
 }
 
@@ -756,6 +763,7 @@ bool HipMLABRenderer::setNewSettings(const SettingsMap& settings) {
         std::string s;
         if (settings.getValueOpt(key, s)) setOption(key, s);
     }
+    setHullSwitch(settings, "hull_fragment_pool");   // (as HipPerPixelLinkedListLineRenderer)
     return r;
 }
 

@@ -261,8 +261,9 @@ protected:
     /// LineRenderer::renderHull is a step of this renderer's frame AND the library draws it there (rendering modes 5, 8 and 10): the
     /// renderer uploads the line data's outline mesh (lv_set_hull_mesh) and forwards hull_opacity / hull_color / hull_use_shading.  The
     /// other renderers upload no mesh, so their frames are never refused for one; the ray tracer's plugin sets it under the settings
-    /// key hull_ray_tracing = "on".
+    /// key hull_ray_tracing = "on", the plugins of modes 2 and 3 under hull_fragment_pool = "on" (setHullSwitch).
     bool drawsHull = false;
+    bool setHullSwitch(const SettingsMap& settings, const char* key);
     const LineData* uploadedHullData = nullptr;
     uint64_t uploadedHullGeneration = 0;
     bool dirty = true, reRender = true, internalReRender = false;

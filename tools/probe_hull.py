@@ -1,16 +1,20 @@
-"""The simulation-mesh hull in rendering modes 5, 8 and 10 (K = 8) on the config-4 scene: the 1M-segment tornado streamlines at
+"""The simulation-mesh hull in rendering modes 5, 8 and 10 (K = 8) and -- hull_fragment_pool = on -- in the pooled modes 2 and 3 on the
+config-4 scene: the 1M-segment tornado streamlines at
 1920 x 1080 with config 4's settings and the transparent transfer function, scenes.box_hull around the data with n = 8 (768
 triangles) and n = 64 (49 152 triangles).  Per mode, in ONE process: the frame without a hull mesh, then with each box -- warm-up
 frames, then 5 timed frames (lv_render_device into a device image, wall clock per frame with the stream synchronised; the median is the
 figure) and the per-kernel timers of lv_get_kernel_times (LV_KERNEL_PPLL_RASTER = the line pass, LV_KERNEL_HULL = the hull pass,
-LV_KERNEL_PPLL_RESOLVE = the resolve).  Three such processes run one after the other.
+LV_KERNEL_PPLL_RESOLVE = the resolve; modes 2 and 3: LV_KERNEL_HULL holds two launches per frame, the record pass and the hull's fragment
+stage, and the figure is their sum; LV_KERNEL_PPLL_SHADE = the lines' fragment stage).  Three such processes run one after the other.
+Without --modes the three pool-free modes are measured, as before; --modes picks others (--modes mode2,mode3,mode8 --out
+profiles/hull_pool_c4.json is the pooled hull's measurement).
 
 The timing gate is the parent commit, not this code: with --parent-tree DIR (a checkout of the parent commit with its library built)
 the no-hull frames of the three modes are measured in three processes of the parent too, interleaved with this build's, and the
 result records both and whether this build's medians stay within the parent's own spread above the parent's slowest process.
 Reads nothing outside the repository and the given tree.  Writes profiles/hull_c4.json.
 
-    python tools/probe_hull.py [--frames 5] [--warmup 2] [--processes 3] [--parent-tree DIR]
+    python tools/probe_hull.py [--frames 5] [--warmup 2] [--processes 3] [--parent-tree DIR] [--modes mode5,mode8,...] [--out FILE]
 """
 import argparse
 import json
@@ -22,8 +26,10 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = {"gather": 3, "resolve": 4, "raster": 7, "hull": 8}   # LV_KERNEL_PPLL_GATHER, _RESOLVE, _RASTER, LV_KERNEL_HULL
-MODES = [("mode5", 5, {}), ("mode8", 8, {}), ("mode10_k8", 10, {"atomic_loop_num_layers": 8})]
+KERNELS = {"gather": 3, "resolve": 4, "shade": 6, "raster": 7, "hull": 8}   # LV_KERNEL_PPLL_GATHER, _RESOLVE, _SHADE, _RASTER, LV_KERNEL_HULL
+MODES = [("mode5", 5, {}), ("mode8", 8, {}), ("mode10_k8", 10, {"atomic_loop_num_layers": 8}),
+         ("mode2", 2, {"hull_fragment_pool": "on"}), ("mode3", 3, {"hull_fragment_pool": "on"})]   # (the pooled modes: behind the switch)
+DEFAULT_MODES = "mode5,mode8,mode10_k8"   # without --modes: the three of profiles/hull_c4.json; the pooled modes on request
 BOXES = [8, 64]
 W, H = 1920, 1080
 
@@ -57,7 +63,13 @@ def measure(args, tree):
             if hull:
                 ctx.set_option("hull_opacity", 0.3)
         for name, mode, settings in MODES:
-            ctx.set_options(settings)
+            if name not in args.selected:
+                continue
+            try:
+                ctx.set_options(settings)
+            except capi.LineVisError:      # (a parent tree without the switch: its pooled modes are measured without a hull only)
+                if hull is not None:
+                    continue
             for _ in range(args.warmup):
                 ctx.render_device(image.data_ptr(), mode=mode)
             torch.cuda.synchronize()
@@ -70,6 +82,10 @@ def measure(args, tree):
                 wall.append((time.perf_counter() - t0) * 1e3)
             st = ctx.stats()
             times = {k: np.asarray(ctx.kernel_times(i), dtype=np.float64) for k, i in kernels.items()}
+            if mode in (2, 3) and len(times.get("hull", ())):   # two launches per frame: the frame's sum (a mode-3 frame that regrows
+                # its pool has three: the warm-up frames absorb it, --warmup >= 1; another count is reported as it is, not summed)
+                if len(times["hull"]) == 2 * args.frames:
+                    times["hull"] = times["hull"].reshape(args.frames, 2).sum(1)
             run = {"mode": mode, "hull": hull_name, "hull_triangles": 0 if hull is None else int(len(hull.triangle_indices)),
                    "frame_ms_median": float(np.median(wall)), "frame_ms_all": [float(x) for x in wall], "gpu_frame_ms": float(st.ms_total),
                    "fragments": int(st.fragments), "max_depth_complexity": int(st.max_depth_complexity),
@@ -81,7 +97,7 @@ def measure(args, tree):
 
 def child(args, tree):
     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", tree, "--frames", str(args.frames), "--warmup",
-                          str(args.warmup)], capture_output=True, text=True, timeout=900, cwd=tree)
+                          str(args.warmup), "--modes", ",".join(args.selected)], capture_output=True, text=True, timeout=900, cwd=tree)
     line = [x for x in out.stdout.splitlines() if x.startswith("RESULT ")]
     if out.returncode != 0 or not line:
         raise SystemExit("the process on %s failed (exit status %d):\n%s" % (tree, out.returncode, out.stderr[-3000:]))
@@ -95,8 +111,13 @@ def main():
     ap.add_argument("--processes", type=int, default=3)
     ap.add_argument("--parent-tree", default="")
     ap.add_argument("--child", default="")
+    ap.add_argument("--modes", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hull_c4.json"))
     args = ap.parse_args()
+    args.selected = [m for m in (args.modes or DEFAULT_MODES).split(",") if m]
+    unknown = [m for m in args.selected if m not in [name for name, _, _ in MODES]]
+    if unknown:
+        ap.error("unknown modes %s (known: %s)" % (unknown, ", ".join(name for name, _, _ in MODES)))
     if args.child:
         print("RESULT " + json.dumps(measure(args, args.child)), flush=True)
         return
@@ -114,12 +135,15 @@ def main():
         summary[key] = {"frame_ms_median_per_process": med(this, key), "fragments": this[0]["runs"][key]["fragments"],
                         "kernel_ms_median_first_process": k}
     result = {"workload": "config-4 scene (tornado, 1M segments, 1920 x 1080, config 4's settings, transparent transfer function); "
-                          "modes 5, 8 and 10 (K = 8) without a hull mesh and with box_hull n = 8 / n = 64, hull_opacity 0.3",
+                          "%s (mode 10: K = 8; modes 2 and 3: hull_fragment_pool = on) without a hull mesh and with box_hull n = 8 / n = 64, "
+                          "hull_opacity 0.3" % ", ".join(args.selected),
               "frames": args.frames, "warmup": args.warmup, "summary": summary, "processes": this}
     if parent:
         gate = {}
         for name, _, _ in MODES:
             key = name + "_no_hull"
+            if key not in this[0]["runs"] or key not in parent[0]["runs"]:
+                continue
             p, t = med(parent, key), med(this, key)
             spread = max(p) - min(p)
             gate[key] = {"parent_ms": p, "this_ms": t, "parent_spread_ms": spread, "this_median_ms": float(np.median(t)),
